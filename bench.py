@@ -25,6 +25,7 @@ import argparse
 import hashlib
 import json
 import os
+import re
 import sys
 import time
 
@@ -47,6 +48,16 @@ WORKLOADS = {
     "opq_train": ("device part of Opq::train_iteration (rotate, k-means update, quantize->reconstruct, X^T.R), {rows} x d={d} per GPU, M={m}, K={k}", (300, 15, 256), 10_000_000),
     "kmeans": ("kmeans_iteration on all {m} subquantizers (training step; SURVEY 8f rank 1), {rows} x d={d} per GPU, K={k}", (300, 15, 256), 10_000_000),
 }
+
+# the default one-GPU run: the other single-GPU BASELINE configs (key, workload, rows) ...
+SUB_CONFIGS = (("configs[2]", "opq_encode", 10_000_000),
+               ("configs[3]", "reconstruct", 100_000_000),
+               ("configs[4]_one_gpu_shard", "encode_d768", 12_500_000))
+# ... and the reference's OWN shapes (not BASELINE configs): its criterion bench (benches/pq.rs:9-10) and its statistical
+# test (pq.rs:431-440), 10 M rows each, same record form.  (Third: M = d / 2 two-float sub-vectors at the headline dimension
+# -- the shape finalfusion's own quantizer front end is remembered to default to; nothing in the reference's sources pins it.)
+REFERENCE_SHAPES = (("benches_pq_rs_d128_M16_K16", (128, 16, 16)), ("pq_rs_test_d20_M10_K128", (20, 10, 128)),
+                    ("half_dim_d300_M150_K256", (300, 150, 256)))
 
 
 def parse():
@@ -78,6 +89,9 @@ def parse():
                     help="opq_train workload: X^T.R as a plain split-K product (context option cross_product_exact = 0: float tolerance, no per-block partials)")
     ap.add_argument("--dry-run", action="store_true",
                     help="exercise sharding/reduction/printing only (CPU, gloo); no GPU work")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what every timed path of the run computed in its last step to DIR/<name>.npy "
+                         "(float32, at most 64 MB in all; larger outputs are sampled: see dump_sample)")
     return ap.parse_args()
 
 
@@ -139,6 +153,39 @@ def source_hash():
             h.update(name.encode())
             h.update(open(os.path.join(base, name), "rb").read())
     return h.hexdigest()[:16]
+
+
+DUMP_BYTES = 60_000_000           # --dump-outputs: array bytes of all files together (64 MB with room for the .npy headers)
+OUTPUT_NAMES = {"encode": "codes", "encode_d768": "codes", "opq_encode": "codes", "reconstruct": "reconstruction",
+                "opq_reconstruct": "reconstruction", "lookup": "reconstruction", "adc_scan": "distances"}
+
+
+def dump_sample(t, budget, axis=0):
+    """float32 host copy of the tensor / array t, or, when that exceeds `budget` bytes, of a fixed sample of its rows along
+    `axis`: the first and last 256 (ragged last tiles live there) and a draw of numpy's default_rng(0) from the rest, in row
+    order.  The sample depends on the shape alone, so two runs with the same arguments dump the same rows."""
+    import numpy as np
+    n = t.shape[axis]
+    keep = max(1, budget // max(1, 4 * (int(np.prod(t.shape)) // max(1, n))))
+    if n > keep:
+        e = min(256, keep // 4)
+        rest = np.random.default_rng(0).choice(n - 2 * e, keep - 2 * e, replace=False) + e
+        idx = np.sort(np.concatenate([np.arange(e), rest, np.arange(n - e, n)]))
+        if hasattr(t, "index_select"):           # torch tensor: sampled on its device, only the sample is copied
+            import torch
+            t = t.index_select(axis, torch.from_numpy(idx).to(t.device))
+        else:
+            t = np.take(t, idx, axis=axis)
+    if hasattr(t, "cpu"):
+        t = t.cpu().numpy()
+    return np.ascontiguousarray(t, dtype=np.float32)
+
+
+def write_outputs(path, outputs):
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def load_pmc_traffic(workload, rows, d, m, k, suffix=""):
@@ -204,7 +251,8 @@ class Bench:
             src[r0:r0 + (1 << 20)].normal_(generator=g)
         return src
 
-    def run(self, workload, rows, d, m, k, steps, warmup, cpu=True):
+    def run(self, workload, rows, d, m, k, steps, warmup, cpu=True, dump=0):
+        """dump > 0: the record carries "outputs", what the last timed step computed, in at most `dump` bytes (dump_sample)."""
         import numpy as np
         import synth
         torch, args = self.torch, self.args
@@ -265,10 +313,11 @@ class Bench:
             # instances; the K timed steps are ONE library call with n_iterations = K, exactly how
             # pq.rs:176 drives it (centroids carried from step to step)
             from reductive_amd.pq import kmeans_iterations
+            state = {}
 
             def run_steps(n_it):
                 if n_it > 0:
-                    kmeans_iterations(q0, src, n_iterations=n_it, want_loss=False, ctx=self.ctx)
+                    state["q"] = kmeans_iterations(q0, src, n_iterations=n_it, want_loss=False, ctx=self.ctx)[0]
             run_steps(warmup)
             torch.cuda.synchronize()
             self.barrier()
@@ -289,6 +338,13 @@ class Bench:
         extra["kernels_launched_per_step"] = kernel
         if workload in ("encode", "encode_d768", "opq_encode", "opq_train"):
             extra["encode_kernel"] = pq.last_encode_kernel()
+        outputs = {}                              # taken before the CPU baseline and the store-ceiling fill below overwrite dst
+        if dump and workload in ("opq_train", "kmeans"):
+            outputs = {"quantizers": dump_sample(state["q"], dump // 2)}
+            if workload == "opq_train":
+                outputs["cross"] = dump_sample(state["cross"], dump // 2)
+        elif dump:
+            outputs = {OUTPUT_NAMES[workload]: dump_sample(dst, dump, axis=dst.dim() - 1 if workload == "adc_scan" else 0)}
 
         sec = kernel_ms * 1e-3
         suffix = ""
@@ -373,7 +429,7 @@ class Bench:
         pq.close()
         torch.cuda.empty_cache()
         return {"elapsed": elapsed, "rows": rows, "steps": steps, "warmup": warmup, "extra": extra,
-                "roofline": roof, "cpu_baseline": cpu_rec, "shape": (d, m, k)}
+                "roofline": roof, "cpu_baseline": cpu_rec, "shape": (d, m, k), "outputs": outputs}
 
 
 METRIC_NAMES = {"encode": "vectors/sec PQ encode", "encode_d768": "vectors/sec PQ encode",
@@ -434,12 +490,20 @@ def main():
         print(json.dumps(in_process(args, d, m, k, rows)), flush=True)
         return
 
+    # the default one-GPU run also times SUB_CONFIGS and REFERENCE_SHAPES after the headline, in the same process;
+    # --dump-outputs shares its byte budget equally between the timed paths of the run (or of all ranks)
+    default_headline = (args.workload == "encode" and (d, m, k) == (300, 15, 256) and rows == 10_000_000)
+    with_subs = use_gpu and world == 1 and default_headline and not args.no_sub_configs
+    n_paths = 1 + len(SUB_CONFIGS) + len(REFERENCE_SHAPES) if with_subs else world
+    dump = DUMP_BYTES // n_paths if args.dump_outputs else 0
+    outputs = {}
     if use_gpu:
         if args.single_device:
             local_rank = 0
         b = Bench(args, rank, world, local_rank, barrier)
-        main_r = b.run(args.workload, rows, d, m, k, args.steps, args.warmup)
+        main_r = b.run(args.workload, rows, d, m, k, args.steps, args.warmup, dump=dump)
         elapsed = main_r["elapsed"]
+        outputs.update((("rank%d." % rank if world > 1 else "") + n, a) for n, a in main_r.pop("outputs").items())
     else:
         main_r = None
         barrier()
@@ -464,35 +528,31 @@ def main():
         if not use_gpu:
             rec.pop("roofline", None)
         # the other single-GPU BASELINE configs, each with its own roofline / cpu_baseline / parity record
-        default_headline = (args.workload == "encode" and (d, m, k) == (300, 15, 256) and rows == 10_000_000)
-        if use_gpu and world == 1 and default_headline and not args.no_sub_configs:
+        if with_subs:
             subs = {}
-            for key, wl, srows in (("configs[2]", "opq_encode", 10_000_000),
-                                   ("configs[3]", "reconstruct", 100_000_000),
-                                   ("configs[4]_one_gpu_shard", "encode_d768", 12_500_000)):
+            for key, wl, srows in SUB_CONFIGS:
                 sd, sm, sk = WORKLOADS[wl][1]
                 try:
-                    r = b.run(wl, srows, sd, sm, sk, max(1, min(args.steps, args.sub_steps)), min(2, max(1, args.warmup)))
+                    r = b.run(wl, srows, sd, sm, sk, max(1, min(args.steps, args.sub_steps)), min(2, max(1, args.warmup)), dump=dump)
                     subs[key] = record(wl, r, 1)
+                    outputs.update((re.sub(r"\W", "", key) + "." + n, a) for n, a in r["outputs"].items())
                 except Exception as e:            # a sub-config must never take the headline line down
                     subs[key] = {"error": "%s: %s" % (type(e).__name__, e)}
             rec["configs"] = subs
-            # the reference's OWN shapes (not BASELINE configs): its criterion bench (benches/pq.rs:9-10) and its statistical
-            # test (pq.rs:431-440), 10 M rows each, same record form
             refs = {}
-            # (third: M = d / 2 two-float sub-vectors at the headline dimension -- the shape finalfusion's own quantizer front end
-            # is remembered to default to; nothing in /root/reference pins it)
-            for key, (sd, sm, sk) in (("benches_pq_rs_d128_M16_K16", (128, 16, 16)), ("pq_rs_test_d20_M10_K128", (20, 10, 128)),
-                                      ("half_dim_d300_M150_K256", (300, 150, 256))):
+            for key, (sd, sm, sk) in REFERENCE_SHAPES:
                 try:
-                    r = b.run("encode", 10_000_000, sd, sm, sk, max(1, min(args.steps, args.sub_steps)), min(2, max(1, args.warmup)))
+                    r = b.run("encode", 10_000_000, sd, sm, sk, max(1, min(args.steps, args.sub_steps)), min(2, max(1, args.warmup)), dump=dump)
                     refs[key] = record("encode", r, 1)
+                    outputs.update((key + "." + n, a) for n, a in r["outputs"].items())
                 except Exception as e:
                     refs[key] = {"error": "%s: %s" % (type(e).__name__, e)}
             rec["reference_shapes"] = refs
         if use_gpu:
             rec["summary"] = summarize(rec)       # LAST key: the tail of the line always shows every BASELINE config
         print(json.dumps(rec), flush=True)
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, outputs)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
@@ -554,6 +614,8 @@ def in_process(args, d, m, k, rows):
     for _ in range(args.steps):
         pq.quantize_batch_into(x, out)
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, {"codes": dump_sample(out, DUMP_BYTES)})
     per = (rows + n_slots - 1) // n_slots
     rec = {"metric": "vectors/sec PQ encode, host-resident batch through the library's device sharder (d=%d, M=%d, K=%d)" % (d, m, k),
            "value": rows * args.steps / elapsed, "unit": "vectors/s", "n_gpus": n_slots, "steps": args.steps,

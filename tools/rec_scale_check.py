@@ -1,5 +1,6 @@
-import sys, torch
-sys.path.insert(0, '/root/repo'); sys.path.insert(0, '/root/repo/tests')
+import os, sys, torch
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np, synth, reductive_amd
 M, K, dsub = 15, 256, 20
 q = synth.normalish(43, (M, K, dsub))
