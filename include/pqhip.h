@@ -268,7 +268,8 @@ int32_t pqhip_at_dot_b_f32_dev(pqhip_ctx *ctx, int32_t device_slot, const float 
  * about the host path / deployment); every other switch is an explicit call below.
  *
  * pqhip_set_encode_variant: force an encode kernel family on one codebook (PQHIP_EUNSUPPORTED from the next
- * quantize call when the family has no instantiation for the shape):
+ * quantize call when the family has no instantiation for the shape).  Codebooks with sub-vectors of more than 128 floats or
+ * K > 256 have one matrix-core form, through 64-bit keys: every variant other than 1 and 8 takes it where it applies.
  *   0  auto
  *   1  scalar anchor kernel (exact by construction, any shape)
  *   2  MFMA 32x32x2 with a lane-local (VALU) argmin          auto for sub-vectors of <= 2 floats

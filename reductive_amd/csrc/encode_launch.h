@@ -31,6 +31,20 @@ PQHIP_DECL_LAUNCH(0, 1) PQHIP_DECL_LAUNCH(0, 2) PQHIP_DECL_LAUNCH(0, 4) PQHIP_DE
 PQHIP_DECL_LAUNCH(2, 1) PQHIP_DECL_LAUNCH(2, 2) PQHIP_DECL_LAUNCH(2, 4) PQHIP_DECL_LAUNCH(2, 8)
 #undef PQHIP_DECL_LAUNCH
 
+// true when launch_encode_mfma has an instantiation for (kind, T, DP, vec, code_bytes); code_bytes 8: the 64-bit keys of
+// grouped codebooks (KIND 2, T = 8).  KIND 3 also needs rows_per_item <= 32 * kMfma16MaxTiles.
+constexpr bool mfma_has(int kind, int T, int DP, bool vec, int code_bytes)
+{
+    if (T != 1 && T != 2 && T != 4 && T != 8) return false;
+    const bool codes = code_bytes == 1 || code_bytes == 4 || (code_bytes == 8 && kind == 2 && T == 8);
+    if (DP > 32)
+        return kind == 2 && codes && (DP == 40 || DP == 48 || DP == 56 || DP == 64 || DP == 80 || DP == 96 || DP == 112 || DP == 128);
+    if (DP < 2 || DP % 2 != 0) return false;
+    if (kind == 0) return code_bytes == 1;
+    if (kind == 2) return codes;
+    return kind == 3 && T >= 2 && DP % 4 == 0 && vec && (code_bytes == 1 || code_bytes == 4);
+}
+
 // lds_pad: extra dynamic LDS per workgroup (occupancy experiments of diagnostic builds; 0 in the default build)
 inline bool launch_encode_mfma(int kind, int T, int DP, bool vec, int code_bytes, const EncodeArgs& a,
                                dim3 grid, hipStream_t st, unsigned lds_pad = 0)

@@ -6,6 +6,7 @@
 #include "kernels_mfma.hip.h"     // kBigNorm
 #include "kernels_prep.hip.h"
 #include "smallk_launch.h"        // smallk_has / smallk_kp
+#include "vor2_launch.h"         // vor2_has_lds
 #include "vor2_prep.h"
 
 using namespace pqhip;
@@ -286,7 +287,7 @@ int32_t codebook_create_impl(pqhip_ctx* ctx, const float* quantizers, int64_t M,
     Vor2Tables vor2;
     // (context option "candidate_tables" = 0 skips them: the host build takes 2.4 s for M = 150, K = 256 on 8 cores)
     if (dsub <= 2 && K <= 256 && only_slot < 0 && T != 0 && ctx->opt.candidate_tables.load(std::memory_order_relaxed) != 0 &&
-        vor2_build(quantizers, M, K, dsub, vor2)) {
+        vor2_build(quantizers, M, K, dsub, vor2) && vor2_has_lds(vor2.max_region_words, (int)K)) {
         cb->vor2 = true;
         cb->vor2_max_region_words = vor2.max_region_words;
     }
@@ -376,9 +377,7 @@ int64_t pqhip_codebook_reconstructed_len(const pqhip_codebook* cb) { return cb ?
 int64_t pqhip_codebook_n_centroids(const pqhip_codebook* cb) { return cb ? cb->K : 0; }
 int32_t pqhip_codebook_has_projection(const pqhip_codebook* cb) { return cb && cb->has_proj; }
 
-// variants: 0 auto; 1 scalar anchor; 2 VALU-argmin MFMA kernel; 4 k_encode_mfma_lds3; 6 small-codebook VALU kernel;
-// 7 pair kernel; 8 fused OPQ kernel; 9 k_encode_mfma16.  (3 and 5 were the retired register-resident LDS-argmin kernel
-// and the first-generation fused OPQ kernel: refused since round 4.)
+// the variants: include/pqhip.h; the rule that applies them: plan_encode (pqhip_encode.hip)
 int32_t pqhip_set_encode_variant(pqhip_codebook* cb, int32_t variant)
 {
     if (!cb || variant < 0 || variant > 11 || variant == 3 || variant == 5) return PQHIP_EINVAL;

@@ -4,9 +4,9 @@
 // concern:
 //     pqhip_ctx.hip       contexts, device slots, staging sets, options, launch log, status strings
 //     pqhip_codebook.hip  codebook handles: upload, preparation kernels, scratch leases, error-flag slots
-//     pqhip_encode.hip    PQ encode dispatch (every encode kernel family)
+//     pqhip_encode.hip    PQ encode dispatch: the plan (plan_encode) and the launch of every encode kernel family
 //     pqhip_rotate.hip    x.P / r.P^T dispatch (rotation kernels v8 / v9, slab fallback)
-//     pqhip_opq.hip       quantize / reconstruct / lookup on device-resident rows (fused OPQ, gather)
+//     pqhip_opq.hip       quantize / reconstruct / lookup on device-resident rows (two-kernel OPQ paths, gather)
 //     pqhip_adc.hip       asymmetric-distance tables and scans
 //     pqhip_train.hip     k-means iterations, X^T.R, the OPQ training step, resident matrices
 //     pqhip_host.hip      host-resident entry points: row sharding over devices, pinned double-buffered staging
@@ -299,7 +299,7 @@ struct pqhip_codebook {
     bool wide = false;      // 128 < dsub <= 1,024: groups of 32 T <= 128 centroids through k_encode_mfma_wide / _wide2 (kernels_mfma_wide.hip.h)
     int KP = 0;             // small codebooks (K <= 64, instantiated dsub): padded centroid count of the VALU kernel
     bool pair16 = false;    // K <= 16 and dsub in {2, 4, 8, 16}: the two-subquantizers-per-tile kernel applies
-    bool vor2 = false;      // dsub == 2, K <= 256, immutable centroids within range: the candidate-list kernel applies
+    bool vor2 = false;      // dsub <= 2, K <= 256, immutable centroids within range, tables within LDS: the candidate-list kernel applies
     uint32_t vor2_max_region_words = 0;
     int groups = 1;         // K > 256: groups of 256 centroids (8 tiles each) merged through 64-bit keys
     bool norms_ok = false;  // all ||c||^2 finite and < 2^100
@@ -391,6 +391,43 @@ struct ErrFlag {
 };
 
 // ---- pqhip_encode.hip ----------------------------------------------------------------------------------------
+// The encode dispatch.  plan_encode() decides which kernel serves a call -- no HIP call, no allocation -- and the launch
+// helpers only launch what it decided.  Families in priority order: the fused OPQ kernel (the caller's unrotated rows),
+// the 64-bit-key forms of wide sub-vectors and K > 256 (every variant but 1 where they fit: their codebooks have no other
+// matrix-core kernel), then the families of pqhip_set_encode_variant (include/pqhip.h).  Each has `fits` (an instantiation
+// exists and its preconditions hold) and `auto` (the measured rule): variant 0 takes the first family whose `auto` and `fits`
+// hold, else the scalar anchor; a forced variant takes its family where it fits and is PQHIP_EUNSUPPORTED elsewhere.
+enum class EncodeFamily { none, opq_fused, rotated, wide, grouped, vor2, pair16, small16, smallk, mfma, anchor };
+struct EncodeCall {
+    int64_t n = 0;
+    int code_bytes = 1;           // 1 or 4 (2- and 8-byte codes are converted around the call)
+    bool rows_aligned = false;    // rows start on 16 bytes and the row stride is a multiple of 4 floats
+    bool word_codes = false;      // codes can be stored as 32-bit words (4-byte aligned base, row stride a multiple of 4)
+    bool bad_flag = false;        // the kernel consults the device's finite-norm flag (captured k-means iterations)
+    bool beside_update = false;   // the k-means assignment step, whose update kernels run beside it on a second stream
+    bool opq_rows = false;        // the caller's unrotated rows of an OPQ handle
+    int n_cus = 256;              // compute units of the device
+};
+struct EncodePlan {
+    int32_t status = PQHIP_OK;
+    EncodeFamily family = EncodeFamily::none;   // rotated: x.P into scratch first, then a plan of its own for those rows
+    int kind = 0;                 // mfma: 0 VALU argmin, 2 LDS-atomic argmin, 3 the same on 16x16x4 (encode_launch.h)
+    bool vec = false;             // mfma: every one of the DP floats of a sub-vector is real (dsub == DP), else the last is padding
+    int grp = 0;                  // mfma: 4 when DP % 4 == 0, else 2
+    const char* kernel = "";      // what pqhip_last_encode_kernel and the launch log report
+};
+EncodePlan plan_encode(const pqhip_codebook& cb, const EncodeCall& call, const Options& opt);
+// Encode rows as `plan` decided (every family but `rotated`): the buffers of the call.
+struct EncodeIo {
+    const float* x;
+    int64_t x_rs;
+    void* codes;
+    int64_t o_rs;
+    hipStream_t st;
+    const int* bad_flag;
+};
+int32_t encode_planned(pqhip_codebook* cb, int slot, const EncodePlan& plan, const EncodeCall& call, const EncodeIo& io);
+EncodeCall encode_call(const pqhip_codebook* cb, int slot, const EncodeIo& io, int64_t n, int code_bytes);
 // PQ encode of device-resident, already rotated rows.  bad_flag != nullptr: the matrix-core kernel is launched whatever
 // the host last knew about the centroid norms and consults the device flag itself (captured k-means iterations).
 int32_t encode_plain_dev(pqhip_codebook* cb, int slot, const float* d_x, int64_t n, int64_t x_rs, void* d_codes, int code_bytes,

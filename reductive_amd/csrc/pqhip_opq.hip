@@ -1,11 +1,10 @@
-// pqhip_opq.hip -- quantize / reconstruct / lookup on device-resident rows: the fused OPQ encode, the two-kernel
+// pqhip_opq.hip -- quantize / reconstruct / lookup on device-resident rows: the two-kernel
 // OPQ paths through a leased scratch buffer, the codebook gather and its rotation-fused form, and the device entry
 // points of include/pqhip.h (pq.rs:268-283, pq.rs:309-327, primitives.rs:110-173).
 #include "pqhip_internal.h"
 
 #include "kernels_gather.hip.h"
 #include "kernels_gather_cg.hip.h"
-#include "opq_fused2_launch.h"
 
 using namespace pqhip;
 
@@ -264,58 +263,20 @@ static int64_t opq_chunk_rows(pqhip_codebook* cb, int slot, int64_t n)
 int32_t quantize_dev_impl(pqhip_codebook* cb, int slot, const float* d_x, int64_t n, int64_t x_rs,
                           void* d_codes, int code_bytes, int64_t o_rs, hipStream_t st)
 {
-    if (!cb->has_proj) return encode_plain_dev(cb, slot, d_x, n, x_rs, d_codes, code_bytes, o_rs, st);
     if (n == 0) return PQHIP_OK;
-    CodebookDev& cd = cb->dev[slot];
-    // OPQ (pq.rs:276) in ONE kernel where kernels_opq_fused2.hip.h is instantiated (P block AND codebook fragments in LDS,
-    // x straight from global memory, the rotated rows never leave the register file: no scratch buffer, no chunk loop).
-    // Needs u8 codes from a codebook with finite norms and 16-byte aligned rows.  Encode variant 8 forces it; the context
-    // option "opq_fused" = 0 (or PQHIP_FUSED2_OPQ=0) keeps the two-kernel path.
-    {
-        const int DP = (int)cb->dsub;
-        // (same-box A/B, 10 M x 300: 29.95 vs 30.57 ms in steady state, and the HBM traffic of a step drops from 3.5x to
-        // ~1x the algorithmic bytes)
-        const bool fused2_off = cb->ctx->opt.opq_fused.load(std::memory_order_relaxed) == 0;   // option "opq_fused" / PQHIP_FUSED2_OPQ=0
-        const bool want2 = cb->variant == 8 || (cb->variant == 0 && !fused2_off);
-        const bool vec = (cb->d % 4 == 0) && (x_rs % 4 == 0) && ((reinterpret_cast<uintptr_t>(d_x) & 15) == 0);
-        if (want2 && code_bytes == 1 && cb->groups == 1 && cb->T != 0 && cb->norms_ok && cb->dsub % 2 == 0 && cb->dsub <= 32 && vec &&
-            opq_fused2_has(DP, cb->T, (int)cb->d)) {
-            OpqFusedArgs a;
-            a.x = d_x; a.n = n; a.x_rs = x_rs; a.P = cd.P; a.d = (int)cb->d;
-            a.frags = cd.frags; a.cc = cd.cc; a.cb = cd.cb;
-            a.out = (uint8_t*)d_codes; a.o_rs = o_rs;
-            a.M = (int)cb->M; a.K = (int)cb->K; a.k_pad = cb->k_pad;
-            const int nm = opq_fused2_slots(DP, cb->T, (int)cb->d) / DP;      // sub-vectors per column block (64 or 32 slots)
-            a.ncb = (int)((cb->M + nm - 1) / nm);
-            // tiles of 32 rows per wave: as many as leave ~8 rounds of workgroups (one per CU) for the whole launch, 4 .. 96
-            // (10 M x 300, one box: 12 tiles 29.84 ms, 24: 29.57, 48: 29.40, 96: 29.24, 160: 30.6, 192 (4 rounds): 38.8 --
-            // the P block and three fragment sets, 138 KB, are staged once per workgroup)
-            const int f2_tiles_env = diag().fused2_tiles;
-            const int64_t want_rg = std::max<int64_t>(1, 8ll * cb->ctx->devs[slot]->n_cus / a.ncb);
-            const int f2_tiles = f2_tiles_env ? f2_tiles_env : (int)std::max<int64_t>(4, std::min<int64_t>(96, (n / want_rg + 255) / 256));
-            a.rows_per_wg = 8 * 32 * f2_tiles;              // 8 waves x f2_tiles tiles of 32 rows
-            const int64_t n_rg = (n + a.rows_per_wg - 1) / a.rows_per_wg;
-            a.rg_per_xcd = (n_rg + 7) / 8;
-            const dim3 grid((unsigned)(a.rg_per_xcd * a.ncb * 8));
-            StampRun stamps;      // (diagnostic builds: in-kernel s_memtime summary of the launch)
-            PQCHK(stamps.begin(diag().fused_stamp, (size_t)grid.x * 8 * 5, st));
-            a.stamps = stamps.ptr();
-            const int e = launch_opq_fused2(DP, cb->T, a, grid, st);
-            if (e != 0) { g_hip_err = std::string("k_opq_encode_fused2: ") + (e > 0 ? hipGetErrorString((hipError_t)e) : "no instantiation"); return PQHIP_EHIP; }
-            PQCHK(stamps.report5(st, "fused2", "rotation", "encode"));
-            note_kernel("k_opq_encode_fused2");
-            cb->last_kernel = "k_opq_encode_fused2";
-            return PQHIP_OK;
-        }
-        if (cb->variant == 8) return PQHIP_EUNSUPPORTED;
-    }
+    // OPQ (pq.rs:276): the fused rotation + encode kernel where the plan takes it (plan_encode, its first family)
+    const EncodeIo io{d_x, x_rs, d_codes, o_rs, st, nullptr};
+    EncodeCall c = encode_call(cb, slot, io, n, code_bytes);
+    c.opq_rows = cb->has_proj;
+    const EncodePlan plan = plan_encode(*cb, c, cb->ctx->opt);
+    if (plan.family != EncodeFamily::rotated) return encode_planned(cb, slot, plan, c, io);
     // otherwise: rx = x.dot(P) into a leased scratch buffer, chunked, then PQ encode of rx
     const int64_t chunk = opq_chunk_rows(cb, slot, n);
     ScratchLease rx(cb, slot, st);
     PQCHK(rx.acquire((size_t)chunk * cb->d * sizeof(float)));
     for (int64_t r0 = 0; r0 < n; r0 += chunk) {
         const int64_t rows = std::min<int64_t>(chunk, n - r0);
-        PQCHK(rotate_dev(d_x + r0 * x_rs, rows, x_rs, cd.P, (int)cb->d, (float*)rx.ptr(), cb->d, st));
+        PQCHK(rotate_dev(d_x + r0 * x_rs, rows, x_rs, cb->dev[slot].P, (int)cb->d, (float*)rx.ptr(), cb->d, st));
         PQCHK(encode_plain_dev(cb, slot, (const float*)rx.ptr(), rows, cb->d,
                                (char*)d_codes + r0 * o_rs * code_bytes, code_bytes, o_rs, st));
     }

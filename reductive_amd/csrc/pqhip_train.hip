@@ -170,9 +170,12 @@ static int32_t kmeans_run_dev(pqhip_codebook* cb, int slot, const float* d_x, in
     // Small training sets are launch-bound (a dozen short kernels and a host sync per iteration):
     // all iterations but the last are one captured hipGraph replayed on the internal stream.  The
     // finite-norm decision stays on the device inside the graph (bad_flag).  Any failure to capture
-    // or instantiate falls back to the eager loop below, which has not run anything yet.
+    // or instantiate falls back to the eager loop below, which has not run anything yet.  The graph needs an assignment kernel
+    // that reads the device flag: the one the plan picks for such a call must be the matrix-core kernel.
     int it0 = 0;
-    const bool try_graph = nwin == 1 && cb->groups == 1 && !cb->wide && cb->T != 0 && cb->variant != 1 && n_iterations >= 3 &&
+    EncodeCall gc = encode_call(cb, slot, EncodeIo{d_x, x_rs, codes.p, M, st, cd.err + 1}, n, code_bytes);
+    gc.beside_update = true;
+    const bool try_graph = nwin == 1 && plan_encode(*cb, gc, cb->ctx->opt).family == EncodeFamily::mfma && n_iterations >= 3 &&
                            n <= (1 << 20) && cb->ctx->opt.kmeans_no_graph.load(std::memory_order_relaxed) == 0;
     if (try_graph) {
         HIPCHK(hipEventRecord(aux.done, st));            // the instances and the codebook are ready on st

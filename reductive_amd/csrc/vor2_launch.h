@@ -12,6 +12,12 @@ struct Vor2Launch {
     uint32_t max_region_words;
     int n_cus;
 };
-// false: the tables of one subquantizer do not fit LDS
+// The kernel stages the tables, centroids and norms of whole subquantizers in LDS: one subquantizer's must fit 150 KB.  This
+// depends on the handle only (codebook_create_impl settles it).
+inline size_t vor2_lds_per_m(uint32_t max_region_words, int K) { return ((size_t)max_region_words + 4 + (size_t)K * 4) * 4; }
+inline bool vor2_has_lds(uint32_t max_region_words, int K) { return vor2_lds_per_m(max_region_words, K) <= 150 * 1024; }
+// ... and the launch's workgroups must fit a one-dimensional grid (2^31 - 1), which depends on the row count
+bool vor2_has_grid(int M, int K, int dsub, uint32_t max_region_words, int64_t n, int n_cus);
+// false: no instantiation (vor2_has_lds / vor2_has_grid)
 bool launch_vor2(const Vor2Launch& l, hipStream_t st);
 }  // namespace pqhip

@@ -6,11 +6,20 @@
 
 namespace pqhip {
 
-bool launch_vor2(const Vor2Launch& l, hipStream_t st)
+namespace {
+struct Geometry {
+    Vor2Args a;
+    size_t lds;
+    int nt;
+    int64_t n_wg;
+};
+
+Geometry geometry(const Vor2Launch& l)
 {
+    Geometry g;
+    Vor2Args& a = g.a;
     // subquantizers per workgroup: as many as keep the group's tables, centroids and norms within 64 KB (two workgroups per CU)
-    const size_t per_m = ((size_t)l.max_region_words + 4 + (size_t)l.K * 4) * 4;
-    if (per_m > 150 * 1024) return false;
+    const size_t per_m = vor2_lds_per_m(l.max_region_words, l.K);
     // (smaller groups for more workgroups per CU lose: every group is one more pass over the rows' cache lines -- d = 300, M = 150,
     // K = 256 with 64 / 48 / 36 / 24 / 16 KB per workgroup: 16.5 / 19.7 / 28.6 / 38.4 / 53.1 ms per 10 M rows)
     int mg = (int)std::max<size_t>(1, (64 * 1024) / per_m);
@@ -19,7 +28,6 @@ bool launch_vor2(const Vor2Launch& l, hipStream_t st)
     mg = (l.M + n_groups - 1) / n_groups;                          // even groups
     const size_t lds = per_m * (size_t)mg;
     const int nt = n_groups >= 8 ? 512 : 256;                      // threads per workgroup (kernels_vor2.hip.h)
-    Vor2Args a;
     a.x = l.x; a.n = l.n; a.x_rs = l.x_rs; a.out = l.out; a.o_rs = l.o_rs; a.cb = l.cb; a.cc = l.cc; a.tab = l.tab; a.off = l.off;
     a.M = l.M; a.K = l.K; a.k_pad = l.k_pad; a.dsub = l.dsub; a.mg = mg;
     // rows per thread: the tables are staged once per workgroup, so as many as leave about four rounds of workgroups per group,
@@ -41,9 +49,28 @@ bool launch_vor2(const Vor2Launch& l, hipStream_t st)
     // a one-dimensional grid: the kernel maps workgroup ids to (row block, group) so that the groups of a row block share an XCD
     a.n_groups = n_groups;
     a.n_row_blocks = (l.n + rows_per_wg - 1) / rows_per_wg;
-    const int64_t n_wg = ((a.n_row_blocks + 7) / 8) * 8 * n_groups;
-    if (n_wg > 0x7fffffffll) return false;
-    const dim3 grid((unsigned)n_wg);
+    g.lds = lds;
+    g.nt = nt;
+    g.n_wg = ((a.n_row_blocks + 7) / 8) * 8 * n_groups;
+    return g;
+}
+}  // namespace
+
+bool vor2_has_grid(int M, int K, int dsub, uint32_t max_region_words, int64_t n, int n_cus)
+{
+    Vor2Launch l{};
+    l.n = n; l.M = M; l.K = K; l.dsub = dsub; l.max_region_words = max_region_words; l.n_cus = n_cus;
+    return geometry(l).n_wg <= 0x7fffffffll;
+}
+
+bool launch_vor2(const Vor2Launch& l, hipStream_t st)
+{
+    const Geometry g = geometry(l);
+    if (!vor2_has_lds(l.max_region_words, l.K) || g.n_wg > 0x7fffffffll) return false;
+    const Vor2Args& a = g.a;
+    const size_t lds = g.lds;
+    const int nt = g.nt, mg = a.mg;
+    const dim3 grid((unsigned)g.n_wg);
 #define PQHIP_VOR2_NT(MGT, NTT)                                                                                          \
     do {                                                                                                                 \
         if (lds > 48 * 1024 &&                                                                                           \

@@ -508,8 +508,8 @@ class Pq:
             pass
 
     def set_encode_variant(self, variant):
-        """test/bench knob (include/pqhip.h: pqhip_set_encode_variant): 0 auto, 1 scalar anchor kernel, 2 / 4 MFMA kernels,
-        6 small-codebook VALU kernel, 7 pair kernel (K <= 16), 8 fused OPQ kernel, 9 16x16x4 MFMA kernel."""
+        """test/bench knob: force an encode kernel family on this handle (0 = auto); the variants are described at
+        pqhip_set_encode_variant in include/pqhip.h."""
         rc = _lib.lib().pqhip_set_encode_variant(self._cb(), variant)
         if rc != _lib.OK:
             raise _lib.PqHipError(rc)

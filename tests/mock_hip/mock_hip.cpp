@@ -3,7 +3,8 @@
 // scratch-lease pool, flag tables, handle lifetimes) under AddressSanitizer + UBSan / ThreadSanitizer on a
 // machine without a GPU.  "Device" memory is malloc'd host memory, copies are memcpy, streams and events
 // complete immediately, kernel launches do nothing (results are garbage; the sanitizers watch the memory
-// traffic around them).  Test infrastructure only -- the product never links this.
+// traffic around them) but are recorded with their geometry (mock_hip_launch_trace: the encode dispatch trace of
+// san_driver.cpp).  Test infrastructure only -- the product never links this.
 //
 // Round 4 ("multi-device code has only ever met one ordinal"): the mock reports
 // MOCK_HIP_DEVICES devices (default 2, the multi-GPU driver sets 8) and TAGS every allocation, stream and
@@ -15,12 +16,15 @@
 // not judged.  Destroying / freeing is allowed from any device, as in the real runtime.
 #include <hip/hip_runtime.h>
 
+#include <cxxabi.h>
+
 #include <atomic>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <map>
 #include <mutex>
+#include <string>
 
 namespace {
 
@@ -78,6 +82,27 @@ void check_ptr_on(const char* what, const void* p, int want_dev)
     if (d >= 0 && d != want_dev) violation(what, d, want_dev);
 }
 
+// launch trace (see hipLaunchKernel)
+struct CallConfig { dim3 grid, block; size_t shmem = 0; hipStream_t stream = nullptr; };
+thread_local CallConfig g_cfg;
+thread_local std::string g_trace;
+std::map<const void*, std::string>& kernel_names()     // host stub -> device symbol (filled before main by the fat binaries)
+{
+    static std::map<const void*, std::string> m;
+    return m;
+}
+std::string demangled(const char* sym)
+{
+    int status = 0;
+    char* d = abi::__cxa_demangle(sym, nullptr, nullptr, &status);
+    std::string s = (status == 0 && d) ? d : sym;
+    std::free(d);
+    for (const char* prefix : {"void ", "pqhip::"})
+        if (s.compare(0, std::strlen(prefix), prefix) == 0) s.erase(0, std::strlen(prefix));
+    const size_t paren = s.find('(');                   // drop the parameter list
+    if (paren != std::string::npos) s.erase(paren);
+    return s;
+}
 }  // namespace
 
 extern "C" {
@@ -126,7 +151,11 @@ hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t, unsigned)
     check_stream_current("hipStreamWaitEvent(stream)", s);     // (waiting for an event of another device is legal)
     return hipSuccess;
 }
-hipError_t hipStreamBeginCapture(hipStream_t, hipStreamCaptureMode) { return hipErrorNotSupported; }   // eager k-means loop
+hipError_t hipStreamBeginCapture(hipStream_t, hipStreamCaptureMode)   // eager k-means loop (the attempt is in the launch trace)
+{
+    g_trace += "hipStreamBeginCapture\n";
+    return hipErrorNotSupported;
+}
 hipError_t hipStreamEndCapture(hipStream_t, hipGraph_t* g) { *g = nullptr; return hipErrorNotSupported; }
 hipError_t hipGraphInstantiate(hipGraphExec_t*, hipGraph_t, hipGraphNode_t*, char*, size_t) { return hipErrorNotSupported; }
 hipError_t hipGraphLaunch(hipGraphExec_t, hipStream_t) { return hipErrorNotSupported; }
@@ -230,21 +259,37 @@ hipError_t hipHostUnregister(void* p)
 
 hipError_t hipFuncSetAttribute(const void*, hipFuncAttribute, int) { return hipSuccess; }
 hipError_t hipOccupancyMaxActiveBlocksPerMultiprocessor(int* n, const void*, int, size_t) { *n = 1; return hipSuccess; }
-// nothing runs; the launch must target a stream of the CURRENT device (the library sets the device per entry point)
-static thread_local hipStream_t g_cfg_stream = nullptr;
-hipError_t hipLaunchKernel(const void*, dim3, dim3, void**, size_t, hipStream_t s)
+// Nothing runs; the launch must target a stream of the CURRENT device (the library sets the device per entry point).
+// Every launch is appended to the calling thread's launch trace as "<kernel> <grid> <block> <dynamic LDS>" (the dispatch
+// mode of san_driver.cpp prints it): the kernel by its device symbol, demangled, as __hipRegisterFunction recorded it.
+hipError_t hipLaunchKernel(const void* f, dim3 grid, dim3 block, void**, size_t shmem, hipStream_t s)
 {
     check_stream_current("hipLaunchKernel(stream)", s);
+    std::string name;
+    {
+        std::lock_guard<std::mutex> g(g_mu);
+        auto it = kernel_names().find(f);
+        name = it == kernel_names().end() ? "?" : it->second;
+    }
+    char geo[128];
+    std::snprintf(geo, sizeof geo, " %ux%ux%u %ux%ux%u %zu\n", grid.x, grid.y, grid.z, block.x, block.y, block.z, shmem);
+    g_trace += name + geo;
     return hipSuccess;
 }
-hipError_t __hipPushCallConfiguration(dim3, dim3, size_t, hipStream_t s) { g_cfg_stream = s; return hipSuccess; }
+hipError_t __hipPushCallConfiguration(dim3 g, dim3 b, size_t m, hipStream_t s) { g_cfg = CallConfig{g, b, m, s}; return hipSuccess; }
 hipError_t __hipPopCallConfiguration(dim3* g, dim3* b, size_t* m, hipStream_t* s)
 {
-    *g = dim3(1); *b = dim3(1); *m = 0; *s = g_cfg_stream;
+    *g = g_cfg.grid; *b = g_cfg.block; *m = g_cfg.shmem; *s = g_cfg.stream;
     return hipSuccess;
 }
 void** __hipRegisterFatBinary(const void*) { static void* h[1]; return h; }
-void __hipRegisterFunction(void**, const void*, char*, const char*, unsigned, void*, void*, void*, void*, int*) {}
+void __hipRegisterFunction(void**, const void* host_stub, char*, const char* device_name, unsigned, void*, void*, void*, void*, int*)
+{
+    std::lock_guard<std::mutex> g(g_mu);
+    kernel_names()[host_stub] = demangled(device_name);
+}
+const char* mock_hip_launch_trace(void) { return g_trace.c_str(); }
+void mock_hip_launch_trace_reset(void) { g_trace.clear(); }
 void __hipRegisterVar(void**, void*, char*, const char*, int, size_t, int, int) {}
 void __hipUnregisterFatBinary(void**) {}
 

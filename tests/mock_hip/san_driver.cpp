@@ -4,6 +4,7 @@
 // leases from several host threads), range errors, handle lifetimes.  Nothing is computed (kernel launches
 // are no-ops in the mock): the pass criterion is "no AddressSanitizer / UBSan report and the status codes
 // the C ABI promises".
+#include <array>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -13,6 +14,7 @@
 #include "pqhip.h"
 
 #define CHECK(c) do { if (!(c)) { std::printf("FAIL %s:%d %s\n", __FILE__, __LINE__, #c); return 1; } } while (0)
+#define PQCHK_RUN(c) do { if ((c) != 0) return 1; } while (0)
 
 // PQHIP_TEST_SCRATCH_ROWS=<n> (read by THIS driver, not by the library): n-row OPQ scratch chunks through the context
 // option, so that every OPQ call walks many chunks and a remainder through one lease
@@ -163,8 +165,189 @@ static int threads_mode()
     return 0;
 }
 
+extern "C" const char* mock_hip_launch_trace(void);
+extern "C" void mock_hip_launch_trace_reset(void);
+
+// "dispatch" mode: which encode kernel serves a call, with which template arguments and launch geometry, for a fixed list of
+// calls that covers every border of the encode dispatch (K, sub-vector length, the M-dependent rules, every variant, index
+// width, row alignment and strides, OPQ with and without the fused kernel, the candidate tables, the k-means iteration).
+// Printed per call: the status, pqhip_last_encode_kernel (quoted), the library's launch log (bracketed) and, indented, the
+// mock's launch trace ("<kernel> <grid> <block> <dynamic LDS>"); tests/test_encode_dispatch.py compares the output with
+// tests/golden/encode_dispatch.txt.  Kernels do not run, so the rows are never read on the host: the calls with a huge row
+// count pass a small buffer.
+namespace dispatch {
+
+struct Call {
+    int64_t M, K, dsub;
+    int variant = 0, code_bytes = 1;
+    int64_t n = 4096;
+    bool opq = false;
+    int64_t x_pad = 0, x_off = 0;      // row stride d + x_pad floats; rows start x_off floats into the buffer
+    int64_t o_pad = 0, c_off = 0;      // code row stride M + o_pad elements; codes start c_off bytes into the buffer
+    int fused = 1, tables = 1;         // context options "opq_fused" and "candidate_tables"
+    bool big_n = false;                // n rows over a small buffer (see above)
+};
+
+static std::vector<float> centroids(int64_t M, int64_t K, int64_t dsub)
+{
+    std::vector<float> q((size_t)(M * K * dsub));
+    for (size_t i = 0; i < q.size(); ++i) q[i] = (float)((i * 2654435761ull >> 8) & 0xffff) / 65536.0f;   // distinct centroids
+    return q;
+}
+
+static void print_trace()
+{
+    const std::string t = mock_hip_launch_trace();
+    size_t b = 0;
+    for (size_t e; (e = t.find('\n', b)) != std::string::npos; b = e + 1) std::printf("    %s\n", t.substr(b, e - b).c_str());
+}
+
+static int run(pqhip_ctx* ctx, const Call& c)
+{
+    const int64_t d = c.M * c.dsub, x_rs = d + c.x_pad, o_rs = c.M + c.o_pad;
+    CHECK(pqhip_ctx_set_option(ctx, "candidate_tables", c.tables) == PQHIP_OK);
+    CHECK(pqhip_ctx_set_option(ctx, "opq_fused", c.fused) == PQHIP_OK);
+    const std::vector<float> q = centroids(c.M, c.K, c.dsub);
+    std::vector<float> P;
+    if (c.opq) { P.assign((size_t)(d * d), 0.f); for (int64_t i = 0; i < d; ++i) P[(size_t)(i * d + i)] = 1.f; }
+    pqhip_codebook* cb = nullptr;
+    CHECK(pqhip_codebook_create(ctx, q.data(), c.M, c.K, c.dsub, c.opq ? P.data() : nullptr, &cb) == PQHIP_OK);
+    CHECK(pqhip_set_encode_variant(cb, c.variant) == PQHIP_OK);
+    const int64_t rows = c.big_n ? 1 : c.n;
+    std::vector<float> x((size_t)(rows * x_rs + c.x_off + 4));
+    std::vector<uint8_t> codes((size_t)((rows * o_rs + 1) * c.code_bytes + c.c_off));
+    mock_hip_launch_trace_reset();
+    pqhip_launch_log_reset();
+    const int32_t rc = pqhip_quantize_batch_f32_dev(cb, 0, x.data() + c.x_off, c.n, x_rs, codes.data() + c.c_off, c.code_bytes, o_rs,
+                                                    nullptr);
+    std::string extra;                 // (the fields that differ from the defaults)
+    auto add = [&](const char* what, long long v) { extra += " " + std::string(what) + std::to_string(v); };
+    if (c.x_pad) add("x_rs=d+", c.x_pad);
+    if (c.x_off) add("x_off=", c.x_off);
+    if (c.o_pad) add("o_rs=M+", c.o_pad);
+    if (c.c_off) add("c_off=", c.c_off);
+    if (!c.tables) add("candidate_tables=", 0);
+    std::printf("%s M=%lld K=%lld dsub=%lld v=%d cb=%d n=%lld%s: %d \"%s\" [%s]\n", c.opq ? (c.fused ? "opq" : "opq(opq_fused=0)") : "pq",
+                (long long)c.M, (long long)c.K, (long long)c.dsub, c.variant, c.code_bytes, (long long)c.n, extra.c_str(), rc,
+                pqhip_last_encode_kernel(cb), pqhip_launch_log());
+    print_trace();
+    pqhip_codebook_destroy(cb);
+    return 0;
+}
+
+static int kmeans(pqhip_ctx* ctx, int64_t M, int64_t K, int64_t dsub, int64_t n, int iterations, int no_graph)
+{
+    CHECK(pqhip_ctx_set_option(ctx, "kmeans_no_graph", no_graph) == PQHIP_OK);
+    const int64_t d = M * dsub;
+    std::vector<float> q = centroids(M, K, dsub), x((size_t)(n * d)), loss((size_t)M);
+    mock_hip_launch_trace_reset();
+    pqhip_launch_log_reset();
+    const int32_t rc = pqhip_kmeans_iterations_f32_dev(ctx, 0, q.data(), M, K, dsub, x.data(), n, d, iterations, loss.data(), nullptr);
+    std::printf("kmeans M=%lld K=%lld dsub=%lld n=%lld iterations=%d kmeans_no_graph=%d: %d [%s]\n", (long long)M,
+                (long long)K, (long long)dsub, (long long)n, iterations, no_graph, rc, pqhip_launch_log());
+    print_trace();
+    CHECK(pqhip_ctx_set_option(ctx, "kmeans_no_graph", 0) == PQHIP_OK);
+    return 0;
+}
+
+static int dispatch_mode()
+{
+    pqhip_ctx* ctx = nullptr;
+    CHECK(pqhip_ctx_create(nullptr, 0, &ctx) == PQHIP_OK);
+    for (int v = -1; v <= 12; ++v) {
+        pqhip_codebook* cb = nullptr;
+        const std::vector<float> q = centroids(1, 4, 2);
+        CHECK(pqhip_codebook_create(ctx, q.data(), 1, 4, 2, nullptr, &cb) == PQHIP_OK);
+        std::printf("pqhip_set_encode_variant(%d): status %d\n", v, pqhip_set_encode_variant(cb, v));
+        pqhip_codebook_destroy(cb);
+    }
+    // every sub-vector length against every centroid count of the rules, default variant
+    const int64_t dsubs[] = {1, 2, 3, 4, 6, 7, 8, 12, 16, 20, 24, 28, 32, 40, 64, 100, 128, 130, 256, 300, 1024, 1100};
+    const int64_t Ks[] = {1, 16, 17, 32, 33, 64, 128, 129, 256, 257, 1000};
+    for (int64_t dsub : dsubs)
+        for (int64_t K : Ks) PQCHK_RUN(run(ctx, Call{2, K, dsub, 0, K <= 256 ? 1 : 4}));
+    // every variant, u8 and u32 codes, on a shape of each family
+    const int64_t shapes[][3] = {{10, 128, 2}, {10, 16, 2}, {64, 16, 2}, {16, 256, 1}, {16, 16, 8}, {32, 16, 4}, {48, 16, 4},
+                                 {15, 16, 20}, {15, 32, 20}, {16, 64, 8}, {8, 64, 12}, {15, 256, 20}, {16, 256, 16}, {8, 256, 32},
+                                 {10, 128, 7}, {10, 200, 6}, {5, 256, 48}, {3, 256, 100}, {2, 256, 130}, {2, 100, 300},
+                                 {3, 1000, 8}, {2, 1000, 200}, {2, 16, 1100}, {4, 33, 3}};
+    for (const auto& s : shapes)
+        for (int v : {0, 1, 2, 4, 6, 7, 8, 9, 10, 11})
+            for (int bytes : {1, 4})
+                if (bytes == 4 || s[1] <= 256) PQCHK_RUN(run(ctx, Call{s[0], s[1], s[2], v, bytes}));
+    // the M-dependent rules: pair kernel from 48 subquantizers on (4 floats), the LDS caps of the 16x16x4 small-codebook kernel
+    // (96 KB) and of the pair kernel (160 KB), candidate-list workgroups of 512 threads from eight groups of subquantizers on;
+    // the template flag of the small-codebook kernel (M a multiple of the subquantizers per row block)
+    for (int64_t M : {47, 48}) PQCHK_RUN(run(ctx, Call{M, 16, 4}));
+    for (int64_t M : {23, 24}) PQCHK_RUN(run(ctx, Call{M, 32, 32}));
+    for (int64_t M : {60, 61}) for (int v : {0, 7}) PQCHK_RUN(run(ctx, Call{M, 16, 16, v}));
+    for (int64_t M : {32, 56, 64, 72}) PQCHK_RUN(run(ctx, Call{M, 64, 2}));
+    for (int64_t M : {20, 40, 41}) PQCHK_RUN(run(ctx, Call{M, 64, 1}));
+    for (int64_t M : {3, 4, 6, 7}) PQCHK_RUN(run(ctx, Call{M, 16, 12}));
+    // the 2- and 8-byte index widths (through converted codes)
+    for (const auto& s : shapes)
+        for (int bytes : {2, 8}) PQCHK_RUN(run(ctx, Call{s[0], s[1], s[2], 0, bytes}));
+    // row alignment and strides: misaligned rows, odd row strides, odd code strides, misaligned codes
+    for (const auto& s : {std::array<int64_t, 3>{16, 16, 8}, {15, 32, 20}, {32, 16, 4}, {15, 256, 20}, {10, 128, 2}, {16, 16, 2}})
+        for (int v : {0, 10}) {
+            Call c{s[0], s[1], s[2], v};
+            PQCHK_RUN(run(ctx, c));
+            c.x_off = 1; PQCHK_RUN(run(ctx, c));
+            c.x_off = 0; c.x_pad = 1; PQCHK_RUN(run(ctx, c));
+            c.x_pad = 4; PQCHK_RUN(run(ctx, c));
+            c.x_pad = 0; c.o_pad = 1; PQCHK_RUN(run(ctx, c));
+            c.o_pad = 4; PQCHK_RUN(run(ctx, c));
+            c.c_off = 1; PQCHK_RUN(run(ctx, c));
+        }
+    // OPQ: the fused kernel's instantiations (d = 300, 256, 768), shapes without one; opq_fused 0 / 1; alignment; variants
+    for (const auto& s : {std::array<int64_t, 3>{15, 256, 20}, {16, 256, 16}, {48, 256, 16}, {10, 128, 2}, {16, 16, 8}, {3, 1000, 8}})
+        for (int fused : {1, 0})
+            for (int v : {0, 1, 4, 8, 9, 11})
+                for (int bytes : {1, 2, 4}) {
+                    Call c{s[0], s[1], s[2], v, bytes};
+                    c.opq = true; c.fused = fused; c.n = 1000;
+                    if (bytes == 1 && s[1] > 256) continue;
+                    PQCHK_RUN(run(ctx, c));
+                    if (v == 0 && bytes == 1) {
+                        c.x_off = 1; PQCHK_RUN(run(ctx, c));
+                        c.x_off = 0; c.x_pad = 1; PQCHK_RUN(run(ctx, c));
+                    }
+                }
+    // Pq handles without the candidate tables
+    for (const auto& s : {std::array<int64_t, 3>{10, 128, 2}, {16, 256, 1}, {10, 16, 2}})
+        for (int v : {0, 11}) {
+            Call c{s[0], s[1], s[2], v};
+            c.tables = 0;
+            PQCHK_RUN(run(ctx, c));
+        }
+    // row counts: none, one, a few, a large batch; 2^46 rows exceed the candidate-list kernel's 2^31 workgroups
+    for (const auto& s : {std::array<int64_t, 3>{15, 256, 20}, {16, 256, 16}, {16, 16, 8}, {10, 128, 2}, {3, 1000, 8}, {2, 256, 200}})
+        for (int64_t n : {0ll, 1ll, 100ll, 3000000ll}) {
+            Call c{s[0], s[1], s[2], 0, s[1] <= 256 ? 1 : 4};
+            c.n = n; c.big_n = n > 4096;
+            PQCHK_RUN(run(ctx, c));
+        }
+    for (int64_t M : {4, 64}) {
+        Call c{M, 64, 2};
+        c.n = 1ll << 46; c.big_n = true;
+        PQCHK_RUN(run(ctx, c));
+    }
+    // k-means iterations: the captured-graph attempt, the assignment kernels beside the update, K > 256, wide sub-vectors
+    for (const auto& s : {std::array<int64_t, 3>{15, 256, 20}, {8, 256, 16}, {4, 16, 2}, {4, 16, 8}, {3, 1000, 8}, {2, 256, 200},
+                          {2, 8, 1100}})
+        for (int it : {1, 3}) PQCHK_RUN(kmeans(ctx, s[0], s[1], s[2], 5000, it, 0));
+    PQCHK_RUN(kmeans(ctx, 15, 256, 20, 5000, 3, 1));
+    PQCHK_RUN(kmeans(ctx, 2, 16, 4, (1 << 20) + 1, 3, 0));
+    pqhip_ctx_destroy(ctx);
+    CHECK(mock_hip_violations() == 0);
+    return 0;
+}
+
+}  // namespace dispatch
+
 int main(int argc, char** argv)
 {
+    if (argc > 1 && std::string(argv[1]) == "dispatch") return dispatch::dispatch_mode();
     if (argc > 1 && std::string(argv[1]) == "threads") return threads_mode();
     if (argc > 1 && std::string(argv[1]) == "devices") return devices_mode();
     int32_t nd = 0;
