@@ -8,6 +8,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <string>
 #include <thread>
 #include <vector>
@@ -343,11 +344,26 @@ static int dispatch_mode()
     return 0;
 }
 
+// "centroids M K dsub" mode: the bits of centroids(M, K, dsub) as hex, one per line, so that the GPU replay of the golden
+// file (tests/dispatch_golden.py) can check that it builds the very codebooks the dispatch above was decided on
+static int centroids_mode(int argc, char** argv)
+{
+    if (argc != 5) { std::fprintf(stderr, "usage: san_driver centroids M K dsub\n"); return 2; }
+    const std::vector<float> q = centroids(std::atoll(argv[2]), std::atoll(argv[3]), std::atoll(argv[4]));
+    for (float f : q) {
+        uint32_t b;
+        std::memcpy(&b, &f, sizeof b);
+        std::printf("%08x\n", b);
+    }
+    return 0;
+}
+
 }  // namespace dispatch
 
 int main(int argc, char** argv)
 {
     if (argc > 1 && std::string(argv[1]) == "dispatch") return dispatch::dispatch_mode();
+    if (argc > 1 && std::string(argv[1]) == "centroids") return dispatch::centroids_mode(argc, argv);
     if (argc > 1 && std::string(argv[1]) == "threads") return threads_mode();
     if (argc > 1 && std::string(argv[1]) == "devices") return devices_mode();
     int32_t nd = 0;
