@@ -168,6 +168,28 @@ int32_t pqhip_adc_scan_f32_dev(pqhip_codebook *cb, int32_t device_slot, const fl
                                int64_t n_queries, const void *d_codes, int32_t code_bytes, int64_t n_codes,
                                int64_t codes_row_stride, float *d_out, int64_t out_row_stride, void *stream);
 
+/*
+ * ADC search: the k nearest rows of every query, without the [n_queries][n_codes] distance matrix.  For query q,
+ * dist_q[i] is exactly what pqhip_adc_scan_f32_dev writes for row i (the same sequential f32 sum over m from +0), and
+ * rows are ordered by (key(dist_q[i]), i) ascending: key is the first-minimum order of cluster_assignments
+ * (src/kmeans.rs:133-159) -- -0 == +0, all NaNs equal and above +Inf -- and equal distances go to the smaller row
+ * index.  Row q of d_dist [n_queries][dist_row_stride] f32 and d_idx [n_queries][idx_row_stride] int64 receives the
+ * first min(k, n_codes) rows in that order, sorted, so d_idx[q][0] is the first minimum of the scan's row q; a NaN
+ * distance is returned as the canonical quiet NaN.  When k > n_codes, slots n_codes .. k-1 hold index -1 and +Inf.
+ * The order is strict, so the selection is exact and the results do not depend on the grid, the row ranges of the
+ * workgroups or the number of queries served per pass over the codes.  Indices are local to the code matrix passed
+ * in: a caller that shards the codes adds each shard's offset.
+ * 1 <= k <= 1024 (k < 1: PQHIP_EINVAL, k > 1024: PQHIP_EUNSUPPORTED); code_bytes 1 or 4; codes_row_stride < M or a
+ * row stride of an output < k: PQHIP_ESHAPE.  n_queries == 0 launches nothing; n_codes == 0 writes the padding only.
+ * A code >= K reads entry 0 and raises the stream's range flag (pqhip_check_codes_dev -> PQHIP_ECODE_RANGE).
+ * Asynchronous on `stream`; per-workgroup partial lists live in the codebook's scratch, the caller allocates only the
+ * outputs.
+ */
+int32_t pqhip_adc_search_f32_dev(pqhip_codebook *cb, int32_t device_slot, const float *d_tables, int64_t n_queries,
+                                 const void *d_codes, int32_t code_bytes, int64_t n_codes, int64_t codes_row_stride,
+                                 int32_t k, float *d_dist, int64_t dist_row_stride,
+                                 int64_t *d_idx, int64_t idx_row_stride, void *stream);
+
 /* Reconstruct's range check is asynchronous on the device path: returns PQHIP_ECODE_RANGE if any
  * device call since the last query saw a code >= K (synchronises `stream`). */
 int32_t pqhip_check_codes_dev(pqhip_codebook *cb, int32_t device_slot, void *stream);

@@ -75,6 +75,89 @@ constexpr int kAdcMaxValueWords = 25;   // M <= 100 on the fast path
 typedef unsigned u32x4_u __attribute__((ext_vector_type(4), aligned(4)));
 typedef unsigned u32x2_u __attribute__((ext_vector_type(2), aligned(4)));
 
+// The NW aligned dwords that cover the code row at byte address `a` (its first byte is byte a & 3 of w[0]): wide loads
+// when the window lies inside [lo, hi) -- the code matrix -- and byte loads of the row's own M bytes otherwise.
+template <int NW>
+__device__ __forceinline__ void adc_fetch_row(uintptr_t a, uintptr_t lo, uintptr_t hi, int M, unsigned (&w)[NW])
+{
+    const uintptr_t a0 = a & ~(uintptr_t)3;
+    if (a0 >= lo && a0 + 4 * NW <= hi) {
+        const unsigned* p = reinterpret_cast<const unsigned*>(a0);
+        constexpr int N4 = (NW / 4) * 4, N2 = N4 + ((NW - N4) / 2) * 2;
+#pragma unroll
+        for (int k = 0; k < N4; k += 4) {
+            const u32x4_u v = *reinterpret_cast<const u32x4_u*>(p + k);
+            w[k] = v[0]; w[k + 1] = v[1]; w[k + 2] = v[2]; w[k + 3] = v[3];
+        }
+        if (N2 > N4) {
+            const u32x2_u v = *reinterpret_cast<const u32x2_u*>(p + N4);
+            w[N4] = v[0]; w[N4 + 1] = v[1];
+        }
+        if (NW > N2) w[N2] = p[N2];
+    } else {
+#pragma unroll
+        for (int k = 0; k < NW; ++k) {
+            unsigned v = 0;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const uintptr_t b = a0 + 4 * k + e;
+                if (b >= a && b < a + (uintptr_t)M) v |= (unsigned)*reinterpret_cast<const uint8_t*>(b) << (8 * e);
+            }
+            w[k] = v;
+        }
+    }
+}
+
+// sum over m = 0 .. M-1, in order, from +0, of lut[m][code m] for the row fetched by adc_fetch_row (shift sh = a & 3);
+// lut is [M][K] in LDS.  A code >= K sets `bad` and reads entry 0.
+template <int NV>
+__device__ __forceinline__ float adc_row_sum(const unsigned (&w)[NV + 1], unsigned sh, const float* lm, int M, int K, bool& bad)
+{
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+        const unsigned v = __builtin_amdgcn_alignbyte(w[k + 1], w[k], sh);   // bytes 4k .. 4k+3 of the row
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            if (4 * k + e < M) {
+                unsigned c = (v >> (8 * e)) & 0xffu;
+                if (c >= (unsigned)K) { bad = true; c = 0; }
+                s = fadd(s, lm[c]);
+                lm += K;
+            }
+        }
+    }
+    return s;
+}
+
+// The same sum for 4 NH queries at once over the interleaved image lut[NH][M][K][4] (MK = M K), added onto s (the
+// caller's +0): s[hq][0] holds queries 4 hq, 4 hq + 1 and s[hq][1] queries 4 hq + 2, 4 hq + 3, each its own sequential
+// f32 chain over m.  (k_adc_scan_u8_mq keeps its own copy of this loop and of the fetch: routed through these functions,
+// its register allocation changes at NV >= 24, and the scan's code objects are meant to stay as they are.)
+template <int NV, int NH>
+__device__ __forceinline__ void adc_row_sum_mq(const unsigned (&w)[NV + 1], unsigned sh, const float* lm, int M, int K, int MK,
+                                               bool& bad, f32x2 (&s)[NH][2])
+{
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+        const unsigned v = __builtin_amdgcn_alignbyte(w[k + 1], w[k], sh);   // bytes 4k .. 4k+3 of the row
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            if (4 * k + e < M) {
+                unsigned c = (v >> (8 * e)) & 0xffu;
+                if (c >= (unsigned)K) { bad = true; c = 0; }
+#pragma unroll
+                for (int hq = 0; hq < NH; ++hq) {
+                    const f32x4 t = *reinterpret_cast<const f32x4*>(lm + (size_t)hq * MK * 4 + 4 * c);
+                    s[hq][0] = pk_add(s[hq][0], (f32x2){t[0], t[1]});
+                    s[hq][1] = pk_add(s[hq][1], (f32x2){t[2], t[3]});
+                }
+                lm += 4 * K;
+            }
+        }
+    }
+}
+
 // NV = ceil(M / 4) dwords of code bytes per row; the window fetched is NV + 1 aligned dwords.
 template <int NV>
 __global__ __launch_bounds__(256) void k_adc_scan_u8(const uint8_t* __restrict__ codes, int64_t n, int64_t c_rs,
@@ -94,50 +177,10 @@ __global__ __launch_bounds__(256) void k_adc_scan_u8(const uint8_t* __restrict__
     bool bad = false;
     for (int64_t row = row_begin + threadIdx.x; row < row_end; row += 256) {
         const uintptr_t a = lo + (uintptr_t)(row * c_rs);
-        const uintptr_t a0 = a & ~(uintptr_t)3;
         unsigned w[NW];
-        if (a0 >= lo && a0 + 4 * NW <= hi) {
-            const unsigned* p = reinterpret_cast<const unsigned*>(a0);
-            constexpr int N4 = (NW / 4) * 4, N2 = N4 + ((NW - N4) / 2) * 2;
-#pragma unroll
-            for (int k = 0; k < N4; k += 4) {
-                const u32x4_u v = *reinterpret_cast<const u32x4_u*>(p + k);
-                w[k] = v[0]; w[k + 1] = v[1]; w[k + 2] = v[2]; w[k + 3] = v[3];
-            }
-            if (N2 > N4) {
-                const u32x2_u v = *reinterpret_cast<const u32x2_u*>(p + N4);
-                w[N4] = v[0]; w[N4 + 1] = v[1];
-            }
-            if (NW > N2) w[N2] = p[N2];
-        } else {
-#pragma unroll
-            for (int k = 0; k < NW; ++k) {
-                unsigned v = 0;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const uintptr_t b = a0 + 4 * k + e;
-                    if (b >= a && b < a + (uintptr_t)M) v |= (unsigned)*reinterpret_cast<const uint8_t*>(b) << (8 * e);
-                }
-                w[k] = v;
-            }
-        }
+        adc_fetch_row<NW>(a, lo, hi, M, w);
         const unsigned sh = (unsigned)(a & 3);
-        float s = 0.f;
-        const float* lm = lut_s;
-#pragma unroll
-        for (int k = 0; k < NV; ++k) {
-            const unsigned v = __builtin_amdgcn_alignbyte(w[k + 1], w[k], sh);   // bytes 4k .. 4k+3 of the row
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                if (4 * k + e < M) {
-                    unsigned c = (v >> (8 * e)) & 0xffu;
-                    if (c >= (unsigned)K) { bad = true; c = 0; }
-                    s = fadd(s, lm[c]);
-                    lm += K;
-                }
-            }
-        }
-        out[row] = s;
+        out[row] = adc_row_sum<NV>(w, sh, lut_s, M, K, bad);
     }
     if (bad) atomicOr(err, 1);
 }

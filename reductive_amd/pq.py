@@ -874,3 +874,40 @@ class Pq:
             if rc != _lib.OK:
                 raise _lib.PqHipError(rc, "pqhip_check_codes_dev")
         return out
+
+    def adc_search_device(self, codes, tables, k, stream=None, check=False):
+        """The k nearest rows per query without the distance matrix: codes and tables as for adc_scan_device ->
+        (dist, idx), CUDA float32 and int64 [nq, k] ([k] for 2-D tables).  dist[q, j] is the scan's distance of row
+        idx[q, j]; rows are ordered by distance -- NaN above +Inf -- then by index (pqhip_adc_search_f32_dev).  Past
+        the last row: index -1, distance +Inf."""
+        import torch
+        assert codes.is_cuda and codes.dtype in (torch.uint8, torch.int32) and codes.dim() == 2
+        assert tables.is_cuda and tables.dtype == torch.float32 and tables.is_contiguous()
+        M, K = self.quantized_len(), self.n_quantizer_centroids()
+        if codes.shape[1] != M:
+            raise PanicError("Quantization length does not match number of subquantizers")
+        single = tables.dim() == 2
+        if tuple(tables.shape[-2:]) != (M, K):
+            raise PanicError("lookup tables must be [.., %d, %d]" % (M, K))
+        nq = 1 if single else tables.shape[0]
+        if codes.stride(1) != 1:
+            codes = codes.contiguous()
+        n = codes.shape[0]
+        dist = torch.empty((nq, k), dtype=torch.float32, device=codes.device)
+        idx = torch.empty((nq, k), dtype=torch.int64, device=codes.device)
+        cb = self._cb()
+        if stream is None:
+            stream = torch.cuda.current_stream(codes.device).cuda_stream
+        slot = self._slot_for(codes)
+        rc = _lib.lib().pqhip_adc_search_f32_dev(cb, slot, tables.data_ptr(), nq, codes.data_ptr(), codes.element_size(), n,
+                                                codes.stride(0) if n > 1 else max(codes.stride(0), M), k,
+                                                dist.data_ptr(), k, idx.data_ptr(), k, ctypes.c_void_p(stream))
+        if rc != _lib.OK:
+            raise _lib.PqHipError(rc, "pqhip_adc_search_f32_dev")
+        if check:
+            rc = _lib.lib().pqhip_check_codes_dev(cb, slot, ctypes.c_void_p(stream))
+            if rc == _lib.ECODE_RANGE:
+                raise PanicError("ndarray: index out of bounds")
+            if rc != _lib.OK:
+                raise _lib.PqHipError(rc, "pqhip_check_codes_dev")
+        return (dist[0], idx[0]) if single else (dist, idx)
