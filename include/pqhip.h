@@ -299,7 +299,8 @@ int32_t pqhip_at_dot_b_f32_dev(pqhip_ctx *ctx, int32_t device_slot, const float 
  *   6  VALU kernel for small codebooks (K <= 64, u8 codes)   auto for K <= 16, sub-vectors of <= 8 floats where 10 does not fit
  *   7  two subquantizers per matrix tile (K <= 16)           auto for 2 floats, and 4 floats from 48 subquantizers on
  *   8  OPQ only: rotation + encode in one kernel             auto where instantiated (opq_fused2_launch.h)
- *   9  MFMA 16x16x4, LDS-atomic argmin, four waves per SIMD  auto for K > 128 and sub-vectors of 12 .. 24 floats
+ *   9  MFMA 16x16x4, LDS-atomic argmin, four waves per SIMD  auto for K > 128 and sub-vectors of 12 .. 24 floats;
+ *      256 centroids of 20 floats: a bf16 16x16x32 screen, undecided rows resolved exactly (same codes)
  *  10  MFMA 16x16x4 for small codebooks (K <= 32, 4 / 8 / 12 / 16 / 20 / 24 / 32 floats, u8 codes, 16-byte aligned rows)   auto wherever it fits
  *  11  1- and 2-float sub-vectors, K <= 256: per-cell candidate lists (Pq handles with finite, in-range centroids)
  *      auto for K > 16, and for every K at 1 float

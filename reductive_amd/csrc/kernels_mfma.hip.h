@@ -45,9 +45,20 @@ struct EncodeArgs {
     // every row takes the exact path.  Lets a captured k-means iteration (hipGraph) stay correct
     // without the host looking at the flag between iterations.  nullptr: the host has checked.
     const int* bad_flag;
-    // diagnostics only (PQHIP_DEBUG_ENC_STAMP): per wave {tiles, step-loop cycles, seam cycles, wave cycles, realtime ticks}
+    // diagnostics only (PQHIP_DEBUG_ENC_STAMP): per wave {tiles, step-loop cycles, seam cycles (k_encode_mfma16: row counts),
+    // wave cycles, realtime ticks}
     unsigned long long* stamps = nullptr;
 };
+
+// value of lane groups 0..3 (same i16) in every lane
+__device__ __forceinline__ void gather_groups(float v, float (&o)[4])
+{
+    const unsigned u = __float_as_uint(v);
+    const auto r = __builtin_amdgcn_permlane16_swap(u, u, false, false);       // [0]: even group of the pair, [1]: odd group
+    const auto e = __builtin_amdgcn_permlane32_swap(r[0], r[0], false, false); // [0]: lower half, [1]: upper half
+    const auto d = __builtin_amdgcn_permlane32_swap(r[1], r[1], false, false);
+    o[0] = __uint_as_float(e[0]); o[1] = __uint_as_float(d[0]); o[2] = __uint_as_float(e[1]); o[3] = __uint_as_float(d[1]);
+}
 
 // Order-preserving map of an f32 distance onto u32 under ordered-float's total order
 // (kmeans.rs:149-156): NaN greatest, -0 == +0.  Smaller key <=> smaller distance.
@@ -72,11 +83,14 @@ __device__ __forceinline__ unsigned ord_key(float d)
 // 10 M rows).  groups > 0 selects the 64-bit key output of grouped codebooks (mv = virtual m).
 __device__ __forceinline__ bool of_equal(float a, float b) { return (a != a && b != b) || a == b; }
 
-template <typename IdxT>
+// DSUB > 0: dsub is that compile-time constant (the loads of a row and a centroid are then issued together instead of
+// one load latency per chain step; same operations, same results)
+template <typename IdxT, int DSUB = 0>
 __device__ __noinline__ void encode_rows_slow_v(const float* x, int64_t x_rs, void* out, int64_t o_rs,
-                                                const float* cb, const float* cc, int K, int dsub,
+                                                const float* cb, const float* cc, int K, int dsub_arg,
                                                 int k_pad, int groups, int mv, int64_t row0, unsigned need)
 {
+    const int dsub = DSUB > 0 ? DSUB : dsub_arg;
     const int lane = threadIdx.x & 63;
     const int m = groups > 0 ? mv / groups : mv;
     const float* cbm = cb + (int64_t)m * K * dsub;

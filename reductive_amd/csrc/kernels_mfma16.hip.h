@@ -29,21 +29,13 @@
 // k_encode_mfma_lds3.  Results are bit-identical to it (tests/test_gpu_parity.py runs every shape through both).
 #pragma once
 #include "kernels_mfma.hip.h"
+#include "kernels_mfma16_screen.hip.h"
 
 namespace pqhip {
 
-// value of lane groups 0..3 (same i16) in every lane
-__device__ __forceinline__ void gather_groups(float v, float (&o)[4])
-{
-    const unsigned u = __float_as_uint(v);
-    const auto r = __builtin_amdgcn_permlane16_swap(u, u, false, false);       // [0]: even group of the pair, [1]: odd group
-    const auto e = __builtin_amdgcn_permlane32_swap(r[0], r[0], false, false); // [0]: lower half, [1]: upper half
-    const auto d = __builtin_amdgcn_permlane32_swap(r[1], r[1], false, false);
-    o[0] = __uint_as_float(e[0]); o[1] = __uint_as_float(d[0]); o[2] = __uint_as_float(e[1]); o[3] = __uint_as_float(d[1]);
-}
-
+// the FP32 body: every instantiation but those of mfma16_screens()
 template <int T, int DP, typename IdxT>
-__global__ __launch_bounds__(256, 4) void k_encode_mfma16(EncodeArgs a)
+__device__ __forceinline__ void encode_mfma16_f32(const EncodeArgs& a)
 {
     static_assert(T >= 2 && DP % 4 == 0 && DP >= 4 && DP <= 32, "no such instantiation");
     constexpr int S = DP / 4;                 // matrix instructions per chain
@@ -342,6 +334,13 @@ __global__ __launch_bounds__(256, 4) void k_encode_mfma16(EncodeArgs a)
         o[0] = st_tiles; o[1] = st_steps; o[2] = 0;
         o[3] = __builtin_amdgcn_s_memtime() - st_t0; o[4] = __builtin_amdgcn_s_memrealtime() - st_r0;
     }
+}
+
+template <int T, int DP, typename IdxT>
+__global__ __launch_bounds__(256, 4) void k_encode_mfma16(EncodeArgs a)
+{
+    if constexpr (mfma16_screens<T, DP>()) encode_mfma16_screen<IdxT>(a);
+    else encode_mfma16_f32<T, DP, IdxT>(a);
 }
 
 }  // namespace pqhip

@@ -349,7 +349,8 @@ struct StampRun {
         return PQHIP_OK;
     }
     // the five-word-per-wave layout of the encode / fused kernels: {tiles, phase A cycles, phase B cycles, wave life, real time}
-    int32_t report5(hipStream_t st, const char* what, const char* a_name, const char* b_name);
+    // (b_counts: word 2 holds {low 32 bits, high 32 bits} row counts, printed as totals of the launch)
+    int32_t report5(hipStream_t st, const char* what, const char* a_name, const char* b_name, bool b_counts = false);
 };
 
 // ---- pqhip_ctx.hip -------------------------------------------------------------------------------------------
