@@ -20,6 +20,10 @@ namespace pqhip {
 // equals fl(t - fl(dp + dp)) only while dp + dp cannot overflow; |dp| <= sqrt(xx * cc) keeps
 // that true with a wide margin below 2^100.
 constexpr float kBigNorm = 1.2676506e30f;  // 2^100
+// k_encode_mfma16 instantiations that take the bf16 screen body (kernels_mfma16_screen.hip.h); their diagnostic stamps
+// carry a sixth word per wave, the cycles of the codebook-image staging
+constexpr bool mfma16_screen_shape(int T, int DP) { return T == 8 && DP == 20; }
+constexpr int kScreenStampWords = 6;
 constexpr int kMfma16MaxTiles = 64;        // k_encode_mfma16: row tiles per wave (rows_per_item <= 2048), one bit each in a 64-bit mask
 
 struct EncodeArgs {

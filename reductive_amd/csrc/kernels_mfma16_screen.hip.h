@@ -19,10 +19,13 @@
 //
 // Layout (16x16x32 bf16): lane (i16, q) supplies A[i16][k = 8q .. 8q + 7] and B[k = 8q .. 8q + 7][i16] per 32-k
 // half h and receives D[4q + v][i16].  A = 16 centroids (block cb), B = 16 rows (block rb).  The split codebook
-// image (256 rows of 64 bf16, padded to 144 B) is built by the workgroup from cb / cc -- the padding does not make the
-// ds_read_b128 conflict-free: SQ_LDS_BANK_CONFLICT measures 128 cycles per 32-row tile (profiles/r5_*_counters.txt);
-// the B operand of a lane is two 8-element windows of its row's k layout, x[(8q + j) mod 20] and x[(12 + 8q + j)
-// mod 20], loaded as four 4-float chunks and split in registers.
+// image (256 rows of 64 bf16 = 128 B, no padding) is built by the workgroup from cb / cc; chunk j (16 B) of row r is
+// stored at chunk j ^ ((r >> 1) & 7), which puts the 16 lanes of every ds_read_b128 lane group on 16 different 16-B
+// bank slots.  The B operand of a lane is two 8-element windows of its row's k layout,
+// x[(8q + j) mod 20] and x[(12 + 8q + j) mod 20], loaded as four 4-float chunks and split in registers.
+// Schedule: the 16 centroid blocks are software-pipelined -- block cb + 1's four matrix instructions are issued before
+// the selection on block cb's accumulators, A fragments are read two blocks ahead, the next tile's rows are split
+// into bf16 operands in the middle of the current tile, and its first block is issued before the lane-group merge.
 #pragma once
 #include "kernels_mfma.hip.h"
 
@@ -35,7 +38,7 @@ constexpr float kScreenAbs = 0x1p-100f;   // flushed subnormal products and oper
 constexpr float kScreenTiny = 0x1p-100f;  // keeps the index bits of M out of the subnormal range
 
 // instantiations that take the screen body (the others keep the FP32 body of k_encode_mfma16)
-template <int T, int DP> constexpr bool mfma16_screens() { return T == 8 && DP == 20; }
+template <int T, int DP> constexpr bool mfma16_screens() { return mfma16_screen_shape(T, DP); }
 
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
@@ -52,18 +55,24 @@ __device__ __forceinline__ float bf16_hi(unsigned p) { return __uint_as_float(p 
 // canonicalize them before fminf / fmaxf
 __device__ __forceinline__ float vmin(float a, float b) { float r; asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 __device__ __forceinline__ float vmax(float a, float b) { float r; asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ float vmed3(float a, float b, float c)
+// two keys k1, k2 into the running (smallest m, second smallest s), m and s updated in place (tied operands, so the
+// unrolled blocks need no register copies): the second smallest of {m, s, k1, k2} is min(s, med3(m, k1, k2)) when
+// m <= s, and the smallest is min3(m, k1, k2) -- five instructions per two keys with the two that build them, against
+// three per key one at a time.  The keys of a lane are distinct (index bits), and for the rows the screen decides they
+// are finite, so m and s are exactly the two smallest keys either way.
+__device__ __forceinline__ void keep2(float& m, float& s, float k1, float k2)
 {
-    float r;
-    asm("v_med3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    return r;
+    float t;
+    asm("v_med3_f32 %0, %1, %2, %3" : "=v"(t) : "v"(m), "v"(k1), "v"(k2));
+    asm("v_min_f32 %0, %0, %1" : "+v"(s) : "v"(t));
+    asm("v_min3_f32 %0, %0, %1, %2" : "+v"(m) : "v"(k1), "v"(k2));
 }
 
 template <typename IdxT>
 __device__ __forceinline__ void encode_mfma16_screen(const EncodeArgs& a)
 {
     constexpr int DP = 20;
-    constexpr int kRow = 72;  // bf16 per image row: 64 + 8 pad
+    constexpr int kRow = 64;  // bf16 per image row, eight 16-B chunks, chunk j of row r at j ^ ((r >> 1) & 7)
     __shared__ __attribute__((aligned(16))) unsigned short img_s[256 * kRow];
     __shared__ unsigned need_s[4][kMfma16MaxTiles];
     __shared__ unsigned maxcc_s;
@@ -82,6 +91,7 @@ __device__ __forceinline__ void encode_mfma16_screen(const EncodeArgs& a)
     const int64_t group = g_local * 8 + xcd;
     const bool wg_active = (g_local < a.chunks_per_xcd) && (group < a.n_chunks);
 
+    const unsigned long long st_s0 = a.stamps ? __builtin_amdgcn_s_memtime() : 0;
     if (wg_active && threadIdx.x == 0) maxcc_s = 0u;
     __syncthreads();
     if (wg_active) {
@@ -113,10 +123,12 @@ __device__ __forceinline__ void encode_mfma16_screen(const EncodeArgs& a)
         }
         w[31] = 0u;
         u32x4_t* dst = reinterpret_cast<u32x4_t*>(&img_s[c * kRow]);
+        const int swz = (c >> 1) & 7;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) dst[j] = (u32x4_t){w[4 * j], w[4 * j + 1], w[4 * j + 2], w[4 * j + 3]};
+        for (int j = 0; j < 8; ++j) dst[j ^ swz] = (u32x4_t){w[4 * j], w[4 * j + 1], w[4 * j + 2], w[4 * j + 3]};
     }
     __syncthreads();
+    const unsigned long long st_stage = a.stamps ? __builtin_amdgcn_s_memtime() - st_s0 : 0;   // image staging
     const int64_t row_begin = (group * 4 + wave) * a.rows_per_item;
     if (!wg_active || row_begin >= a.n) return;
     int64_t row_end = row_begin + a.rows_per_item;
@@ -174,34 +186,60 @@ __device__ __forceinline__ void encode_mfma16_screen(const EncodeArgs& a)
     unsigned long long flagged = 0;                                     // wave-uniform: tiles with rows for the exact path
     unsigned long long st_tiles = 0, st_steps = 0, st_rows = 0;   // st_rows: {exact-path rows, resolved rows}
     const unsigned long long st_t0 = a.stamps ? __builtin_amdgcn_s_memtime() : 0, st_r0 = a.stamps ? __builtin_amdgcn_s_memrealtime() : 0;
-    const unsigned short* const arow = &img_s[i16 * kRow + 8 * q];
+    // A fragments of block cb: rows 16 cb + i16, chunks q and 4 + q (k = 8q .. 8q + 7 of each 32-k half), swizzled
+    const int swz = (i16 >> 1) & 7;
+    const unsigned short* const arow0 = &img_s[i16 * kRow + 8 * (q ^ swz)];
+    const unsigned short* const arow1 = &img_s[i16 * kRow + 8 * ((4 + q) ^ swz)];
+    auto load_a = [&](int cb, u32x4_t (&af)[2]) {
+        af[0] = *reinterpret_cast<const u32x4_t*>(arow0 + cb * 16 * kRow);
+        af[1] = *reinterpret_cast<const u32x4_t*>(arow1 + cb * 16 * kRow);
+    };
+    auto screen = [&](const u32x4_t (&af)[2], const u32x4_t (&bop)[2][2], f32x4 (&acc)[2]) {
+#pragma unroll
+        for (int rb = 0; rb < 2; ++rb) {
+            acc[rb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, af[0]), __builtin_bit_cast(bf16x8_t, bop[rb][0]),
+                                                              (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+            acc[rb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, af[1]), __builtin_bit_cast(bf16x8_t, bop[rb][1]), acc[rb], 0, 0, 0);
+        }
+    };
+
+    // prologue: the first tile's operands, A fragments of blocks 0 and 1, block 0
     float xv[2][16];
+    u32x4_t bop[2][2];
+    float xx[2];
     load_tile(xv, row_begin);
-    int tile_idx = 0;
-    for (int64_t row0 = row_begin; row0 < row_end; row0 += 32, ++tile_idx) {
+    split(xv, bop, xx);
+    u32x4_t af[2][2];
+    f32x4 acc[2][2];
+    load_a(0, af[0]);
+    load_a(1, af[1]);
+    screen(af[0], bop, acc[0]);
+    // one 32-row tile; bop / xx hold its split rows, bnext / xxn receive the next tile's.  The loop below alternates two
+    // operand sets, so no operand is copied at the seam.
+    auto tile = [&](int64_t row0, int tile_idx, const u32x4_t (&bop)[2][2], const float (&xx)[2], u32x4_t (&bnext)[2][2], float (&xxn)[2]) {
         const unsigned long long st_a = a.stamps ? __builtin_amdgcn_s_memtime() : 0;
-        u32x4_t bop[2][2];
-        float xx[2];
-        split(xv, bop, xx);
-        if (row0 + 32 < row_end) load_tile(xv, row0 + 32);             // in flight during the matrix work
+        // row0 stays a scalar: the per-lane row addresses are formed where they are used instead of being carried
+        // from tile to tile in vector registers
+        asm("" : "+s"(row0));
+        // the next tile's rows (past row_end the loads are clamped like a short tile's, and their result is never used)
+        load_tile(xv, row0 + 32);
         float mk[2] = {__builtin_inff(), __builtin_inff()}, sk[2] = {__builtin_inff(), __builtin_inff()};
+        // step cb: issue block cb + 1, read the A fragments of block cb + 2 (mod 16: the next tile's blocks 0, 1),
+        // then select on block cb
 #pragma unroll
         for (int cb = 0; cb < 16; ++cb) {
-            const u32x4_t a0 = *reinterpret_cast<const u32x4_t*>(arow + cb * 16 * kRow);
-            const u32x4_t a1 = *reinterpret_cast<const u32x4_t*>(arow + cb * 16 * kRow + 32);
+            if (cb < 15) screen(af[(cb + 1) & 1], bop, acc[(cb + 1) & 1]);
+            load_a((cb + 2) & 15, af[cb & 1]);
+            if (cb == 8) split(xv, bnext, xxn);                          // the loads have landed by now
+            auto key = [&](int rb, int v) { return __uint_as_float((__float_as_uint(acc[cb & 1][rb][v]) & kKeyMask) | (unsigned)(4 * cb + v)); };
 #pragma unroll
             for (int rb = 0; rb < 2; ++rb) {
-                f32x4 acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a0), __builtin_bit_cast(bf16x8_t, bop[rb][0]),
-                                                                   (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a1), __builtin_bit_cast(bf16x8_t, bop[rb][1]), acc, 0, 0, 0);
-#pragma unroll
-                for (int v = 0; v < 4; ++v) {
-                    const float k = __uint_as_float((__float_as_uint(acc[v]) & kKeyMask) | (unsigned)(4 * cb + v));
-                    sk[rb] = vmed3(mk[rb], k, sk[rb]);
-                    mk[rb] = vmin(mk[rb], k);
-                }
+                keep2(mk[rb], sk[rb], key(rb, 0), key(rb, 1));
+                keep2(mk[rb], sk[rb], key(rb, 2), key(rb, 3));
             }
         }
+        // the next tile's block 0 runs under the merge
+        screen(af[0], bnext, acc[0]);
         // ---- merge the four lane groups of each row; store the decided rows, resolve the few-candidate rows, record the
         // others
         unsigned need = 0, few_rows = 0;
@@ -260,6 +298,14 @@ __device__ __forceinline__ void encode_mfma16_screen(const EncodeArgs& a)
         }
         if (a.stamps) st_rows += (unsigned long long)__builtin_popcount(few_rows) | ((unsigned long long)__builtin_popcount(need) << 32);
         if (a.stamps) { st_tiles += 1; st_steps += __builtin_amdgcn_s_memtime() - st_a; }
+    };
+    u32x4_t bop2[2][2];
+    float xx2[2];
+    for (int64_t row0 = row_begin, tile_idx = 0;; row0 += 64, tile_idx += 2) {
+        if (row0 >= row_end) break;
+        tile(row0, (int)tile_idx, bop, xx, bop2, xx2);
+        if (row0 + 32 >= row_end) break;
+        tile(row0 + 32, (int)tile_idx + 1, bop2, xx2, bop, xx);
     }
     // ---- rows for the exact path: nothing is live here
     while (flagged) {                                                   // wave-uniform
@@ -269,9 +315,9 @@ __device__ __forceinline__ void encode_mfma16_screen(const EncodeArgs& a)
         encode_rows_slow_v<IdxT, DP>(a.x, a.x_rs, a.out, a.o_rs, a.cb, a.cc, a.K, DP, a.k_pad, 0, m, row_begin + 32 * (int64_t)ti, nd);
     }
     if (a.stamps && lane == 0) {
-        unsigned long long* o = a.stamps + ((size_t)blockIdx.x * 4 + wave) * 5;
+        unsigned long long* o = a.stamps + ((size_t)blockIdx.x * 4 + wave) * kScreenStampWords;
         o[0] = st_tiles; o[1] = st_steps; o[2] = st_rows;
-        o[3] = __builtin_amdgcn_s_memtime() - st_t0; o[4] = __builtin_amdgcn_s_memrealtime() - st_r0;
+        o[3] = __builtin_amdgcn_s_memtime() - st_t0; o[4] = __builtin_amdgcn_s_memrealtime() - st_r0; o[5] = st_stage;
     }
 }
 

@@ -305,12 +305,14 @@ static int32_t launch_mfma(pqhip_codebook* cb, int slot, const EncodePlan& p, co
     }
     // (row alignment does not matter: the loads are dword-aligned wide loads)
     StampRun stamps;      // (diagnostic builds: in-kernel s_memtime summary of the launch)
-    PQCHK(stamps.begin(diag().enc_stamp && p.kind >= 2, (size_t)grid.x * 4 * 5, io.st));
+    const int stamp_words = (p.kind == 3 && mfma16_screen_shape(cb->T, cb->DP)) ? kScreenStampWords : 5;
+    PQCHK(stamps.begin(diag().enc_stamp && p.kind >= 2, (size_t)grid.x * 4 * stamp_words, io.st));
     a.stamps = stamps.ptr();
     if (!launch_encode_mfma(p.kind, cb->T, cb->DP, p.vec, c.code_bytes, a, grid, io.st, diag().lds_pad)) return no_instantiation(p.kernel);
     // k_encode_mfma16 (kind 3) leaves row counts in word 2: rows resolved among a few candidates in the loop, rows on
-    // the exact path (both zero in its FP32 body); kinds 0 and 2 leave the seam cycles there
-    if (p.kind == 3) return stamps.report5(io.st, "encode", "steps", "resolved / exact-path", true);
+    // the exact path (both zero in its FP32 body); kinds 0 and 2 leave the seam cycles there.  The screen body adds the
+    // image-staging cycles as a sixth word.
+    if (p.kind == 3) return stamps.report5(io.st, "encode", "steps", "resolved / exact-path", true, stamp_words);
     return stamps.report5(io.st, "encode", "steps", "seam");
 }
 

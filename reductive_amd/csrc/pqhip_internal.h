@@ -349,8 +349,9 @@ struct StampRun {
         return PQHIP_OK;
     }
     // the five-word-per-wave layout of the encode / fused kernels: {tiles, phase A cycles, phase B cycles, wave life, real time}
-    // (b_counts: word 2 holds {low 32 bits, high 32 bits} row counts, printed as totals of the launch)
-    int32_t report5(hipStream_t st, const char* what, const char* a_name, const char* b_name, bool b_counts = false);
+    // (b_counts: word 2 holds {low 32 bits, high 32 bits} row counts, printed as totals of the launch; words = 6: a sixth
+    // word per wave holds set-up cycles before the first tile, printed per wave)
+    int32_t report5(hipStream_t st, const char* what, const char* a_name, const char* b_name, bool b_counts = false, int words = 5);
 };
 
 // ---- pqhip_ctx.hip -------------------------------------------------------------------------------------------
