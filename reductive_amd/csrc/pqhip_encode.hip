@@ -309,10 +309,11 @@ static int32_t launch_mfma(pqhip_codebook* cb, int slot, const EncodePlan& p, co
     PQCHK(stamps.begin(diag().enc_stamp && p.kind >= 2, (size_t)grid.x * 4 * stamp_words, io.st));
     a.stamps = stamps.ptr();
     if (!launch_encode_mfma(p.kind, cb->T, cb->DP, p.vec, c.code_bytes, a, grid, io.st, diag().lds_pad)) return no_instantiation(p.kernel);
-    // k_encode_mfma16 (kind 3) leaves row counts in word 2: rows resolved among a few candidates in the loop, rows on
-    // the exact path (both zero in its FP32 body); kinds 0 and 2 leave the seam cycles there.  The screen body adds the
+    // k_encode_mfma16 (kind 3) leaves row counts in word 2: of the rows the screen does not decide, those with two to four
+    // candidates, one per lane group (round 6 resolved them in the loop), and all others (both zero in its FP32 body);
+    // kinds 0 and 2 leave the seam cycles there.  The screen body adds the
     // image-staging cycles as a sixth word.
-    if (p.kind == 3) return stamps.report5(io.st, "encode", "steps", "resolved / exact-path", true, stamp_words);
+    if (p.kind == 3) return stamps.report5(io.st, "encode", "steps", "2-4-candidate / other off-screen", true, stamp_words);
     return stamps.report5(io.st, "encode", "steps", "seam");
 }
 
