@@ -11,13 +11,17 @@ in HBM -> u8 codes in HBM.  With N > 1 every rank owns an independent row shard 
 exchange step: no collective on the data path, "weak" scaling); the only collectives are the
 barrier and the max-reduction of the elapsed time.  Rank 0 prints ONE JSON line.
 
-The default single-GPU run times the headline (BASELINE.json configs[1]) exactly as the contract
-says and then, in the same process and the same JSON line (key "configs"), the other single-GPU
-BASELINE configs with their own roofline / cpu_baseline / parity records:
+A plain run times the headline (BASELINE.json configs[1]) and prints its line, with the roofline
+figures of its own timed steps; nothing else runs.  `--full` adds what takes work of its own: the
+CPU baseline and oracle parity check of every timed path, the store-ceiling runs of the reconstruct
+and lookup workloads and, in the default single-GPU run, in the same process and the same JSON
+line (key "configs"), the other single-GPU BASELINE configs with their own roofline / cpu_baseline
+/ parity records, and after them the reference's own shapes (key "reference_shapes").  The configs:
     configs[2]  Opq rotate+encode 10 M x 300          (--workload opq_encode)
     configs[3]  Pq::reconstruct_batch 100 M codes      (--workload reconstruct --rows 100000000)
     configs[4]  one GPU's shard (12.5 M rows) of the 100 M x 768, M=48 encode  (--workload encode_d768)
-`--no-sub-configs` skips them; `--workload X` runs X alone as the top-level record.
+`--no-sub-configs` skips them; `--workload X` runs X alone as the top-level record.  `--dump-outputs`
+writes the outputs of every timed path of the default run, so it times the other configs as well.
 `--in-process N` instead drives the LIBRARY's own sharder (pqhip_ctx_create(devices) +
 pqhip_quantize_batch_f32 over one host batch, codes concatenated host-side: north_star's form).
 """
@@ -72,9 +76,12 @@ def parse():
     ap.add_argument("--k", type=int, default=None, help="centroids per subquantizer (u8 codes up to 256, 32-bit codes beyond)")
     ap.add_argument("--variant", type=int, default=0, help="0 auto, 1 anchor kernel, 2 MFMA kernel")
     ap.add_argument("--cpu-rows", type=int, default=2_000_000, help="rows of the CPU-baseline sample")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline figure: CPU baselines and oracle parity checks, store-ceiling runs, and the "
+                         "configs[2..4] and reference-shape records of the default run")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines, parity checks and store ceilings")
     ap.add_argument("--no-sub-configs", action="store_true",
-                    help="headline only: skip the configs[2..4] sub-records of the default run")
+                    help="headline only: skip the configs[2..4] and reference-shape records of a --full or --dump-outputs run")
     ap.add_argument("--sub-steps", type=int, default=10, help="timed steps of every sub-config (after 2 warm-up steps)")
     ap.add_argument("--in-process", type=int, default=0, metavar="N",
                     help="drive the library's own row sharder over N device slots from ONE process and one host batch")
@@ -398,7 +405,8 @@ class Bench:
         else:
             roof["traffic_note"] = why
 
-        if cpu and self.world == 1 and not args.no_cpu_baseline:
+        checks = args.full and not args.no_cpu_baseline
+        if cpu and self.world == 1 and checks:
             if workload in ("encode", "opq_encode", "encode_d768"):
                 cpu_rec = cpu_baseline(args, q, P, src, dst, pq, full=(workload == "encode"))
             elif workload == "reconstruct":
@@ -409,7 +417,7 @@ class Bench:
                 cpu_rec = cpu_baseline_kmeans(args, q0, src, self.ctx)
             elif workload == "adc_scan":
                 cpu_rec = cpu_baseline_adc(q, query, src, dst, lut)
-        if workload in ("reconstruct", "lookup") and not args.no_cpu_baseline:
+        if workload in ("reconstruct", "lookup") and checks:
             # what plain streaming stores reach on THIS output allocation of THIS box (torch fill_, no reads): the
             # write rate moves 5-9 % with the physical placement of the buffer for every store pattern
             # (tools/store_patterns.hip), so the kernel is also quoted against it.  After the parity
@@ -490,10 +498,12 @@ def main():
         print(json.dumps(in_process(args, d, m, k, rows)), flush=True)
         return
 
-    # the default one-GPU run also times SUB_CONFIGS and REFERENCE_SHAPES after the headline, in the same process;
-    # --dump-outputs shares its byte budget equally between the timed paths of the run (or of all ranks)
+    # with --full the default one-GPU run also times SUB_CONFIGS and REFERENCE_SHAPES after the headline, in the same
+    # process; so does --dump-outputs, whose files are what every one of these paths computed.  The dump shares its byte
+    # budget equally between the timed paths of the run (or of all ranks)
     default_headline = (args.workload == "encode" and (d, m, k) == (300, 15, 256) and rows == 10_000_000)
-    with_subs = use_gpu and world == 1 and default_headline and not args.no_sub_configs
+    with_subs = (use_gpu and world == 1 and default_headline and not args.no_sub_configs
+                 and (args.full or bool(args.dump_outputs)))
     n_paths = 1 + len(SUB_CONFIGS) + len(REFERENCE_SHAPES) if with_subs else world
     dump = DUMP_BYTES // n_paths if args.dump_outputs else 0
     outputs = {}
@@ -626,7 +636,7 @@ def in_process(args, d, m, k, rows):
                       "shards": [[i * per, min(rows, (i + 1) * per)] for i in range(n_slots)],
                       "placement": "inputs and outputs in pageable host memory"},
            "host_gbs": rows * (4 * d + m) * args.steps / elapsed / 1e9}
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         from oracle import pq_oracle as orc
         n_s = min(rows, 200_000)
         tail = slice(rows - n_s, rows)
