@@ -190,6 +190,32 @@ int32_t pqhip_adc_search_f32_dev(pqhip_codebook *cb, int32_t device_slot, const 
                                  int32_t k, float *d_dist, int64_t dist_row_stride,
                                  int64_t *d_idx, int64_t idx_row_stride, void *stream);
 
+/*
+ * ADC similarity search: the k rows of largest inner product with every query.
+ *   ip_tables[q][m][j] = unrolled_dot(quantizers[m][j], y_q[m*dsub .. (m+1)*dsub)), y_q as for pqhip_adc_tables_f32_dev
+ *                        (query_q.dot(projection) first for an OPQ quantizer, the same sequential dot).  This is the dp
+ *                        term of the distance table, so bit for bit tables == fl(fl(yy + cc) - fl(ip + ip)); in real
+ *                        arithmetic sum_m ip_tables[q][m][codes[i][m]] = <query_q, reconstruct(codes[i])>, OPQ included.
+ *   score[q][i]        = fl(s[q][i] * scales[i]), s[q][i] the scan's row sum over the IP tables (sequential f32 over m
+ *                        from +0); without d_scales (NULL) the score is s itself.  pqhip_adc_scan_f32_dev over IP
+ *                        tables already yields the unscaled scores of every row; no separate entry point is needed.
+ * Rows are ordered by (key(-score), i) ascending, key as for pqhip_adc_search_f32_dev: the largest score first, -0 == +0,
+ * every NaN after every number (-Inf included), equal scores to the smaller row index; the order is strict, so the
+ * result does not depend on the grid or the merge order.  Row q of d_score / d_idx receives the first min(k, n_codes)
+ * rows in that order; slots past the last row hold index -1 and -Inf.  A returned score is the row's score bit for bit,
+ * except that a zero comes back as +0 and a NaN as the canonical quiet NaN (the key keeps neither distinction).
+ * d_scales [n_codes] f32 or NULL.  Limits, status codes and their precedence are those of pqhip_adc_search_f32_dev
+ * (EINVAL, ENODEV, EUNSUPPORTED, ESHAPE; 1 <= k <= 1024; code_bytes 1 or 4); n_queries == 0 launches nothing,
+ * n_codes == 0 writes the padding only; a code >= K reads entry 0 and raises the stream's range flag.  The table call
+ * checks its arguments as pqhip_adc_tables_f32_dev does.  Both calls are asynchronous on `stream`.
+ */
+int32_t pqhip_adc_ip_tables_f32_dev(pqhip_codebook *cb, int32_t device_slot, const float *d_queries,
+                                    int64_t n_queries, int64_t q_row_stride, float *d_tables, void *stream);
+int32_t pqhip_adc_ip_search_f32_dev(pqhip_codebook *cb, int32_t device_slot, const float *d_tables, int64_t n_queries,
+                                    const void *d_codes, int32_t code_bytes, int64_t n_codes, int64_t codes_row_stride,
+                                    const float *d_scales, int32_t k, float *d_score, int64_t score_row_stride,
+                                    int64_t *d_idx, int64_t idx_row_stride, void *stream);
+
 /* Reconstruct's range check is asynchronous on the device path: returns PQHIP_ECODE_RANGE if any
  * device call since the last query saw a code >= K (synchronises `stream`). */
 int32_t pqhip_check_codes_dev(pqhip_codebook *cb, int32_t device_slot, void *stream);

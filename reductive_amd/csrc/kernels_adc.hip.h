@@ -57,6 +57,21 @@ __global__ void k_adc_tables(const float* __restrict__ y, int64_t y_rs, int nq, 
     tables[idx] = fsub(fadd(yy, cc[(int64_t)m * k_pad + j]), fadd(dp, dp));
 }
 
+// Inner-product tables of the similarity search: ip_tables[q][m][j] = dp = c_j . y_m, the dp term of k_adc_tables
+// alone (the same unrolled dot, the same operand order), so that k_adc_tables' entry is fl(fl(yy + cc_j) - fl(dp + dp)).
+__global__ void k_adc_ip_tables(const float* __restrict__ y, int64_t y_rs, int nq, const float* __restrict__ cb,
+                                int M, int K, int dsub, float* __restrict__ tables)
+{
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t per_q = (int64_t)M * K;
+    if (idx >= nq * per_q) return;
+    const int q = (int)(idx / per_q);
+    const int r = (int)(idx - q * per_q);
+    const int m = r / K, j = r - m * K;
+    const float* ym = y + q * y_rs + (int64_t)m * dsub;
+    tables[idx] = dot_unrolled_global(cb + ((int64_t)m * K + j) * dsub, ym, dsub);
+}
+
 // ---------------------------------------------------------------------------------------------
 // Table-sum scan: out[i] = sum_{m = 0..M-1, in order, from +0} lut[m][codes[i][m]]   (u8 codes)
 //

@@ -17,6 +17,7 @@
 // no harm.  After the row loop the 16 waves' lists are merged in a tree through LDS (the table image is dead by then)
 // and the workgroup writes one sorted list per query to scratch.  k_adc_search_merge merges the workgroups' lists of
 // one query and writes the first k entries (index -1 and +Inf past the last row).
+// The similarity search (k_adc_ip_search_*, at the end) offers the key of -score to the same selection.
 #pragma once
 #include "kernels_adc.hip.h"
 
@@ -387,6 +388,177 @@ __global__ __launch_bounds__(512) void k_adc_search_merge(const unsigned* __rest
             if (e < kk) {
                 const bool pad = lst.i[r] == ~0ull;
                 dist[(int64_t)q * d_rs + e] = pad ? __uint_as_float(0x7f800000u) : adc_key_value(lst.k[r]);
+                idx[(int64_t)q * i_rs + e] = pad ? (int64_t)-1 : (int64_t)lst.i[r];
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Similarity search (pqhip_adc_ip_search_f32_dev): the same producers and merge with one change per row -- the value
+// offered to the unchanged SearchState is -fl(s * scale), s the row sum over inner-product tables and scale = scales[i]
+// (1 without scales: exact), loaded once per row for all NQ queries; negation is exact, so the smallest key is the
+// largest score.  The loops are restated here rather than shared through a template flag so that the distance kernels
+// above keep their code objects instruction for instruction (a shared body changed their register allocation).
+// ---------------------------------------------------------------------------------------------
+template <int NV, int NQ, int L>
+__global__ __launch_bounds__(1024) void k_adc_ip_search_u8(const uint8_t* __restrict__ codes, int64_t n, int64_t c_rs,
+                                                           const float* __restrict__ lut /* [NQ][M][K] */,
+                                                           const float* __restrict__ scales /* [n] or null */, int M, int K,
+                                                           int kk, int64_t rows_per_wg, unsigned* __restrict__ part_k,
+                                                           uint64_t* __restrict__ part_i, int* __restrict__ err)
+{
+    static_assert(NQ == 1 || NQ == 4 || NQ == 8, "queries per pass");
+    constexpr int NW = NV + 1, NH = NQ / 4;
+    extern __shared__ __attribute__((aligned(16))) float lds_s[];
+    const int MK = M * K;
+    if (NQ == 1) {
+        for (int i = threadIdx.x; i < MK; i += 1024) lds_s[i] = lut[i];
+    } else {
+        for (int i = threadIdx.x; i < NQ * MK; i += 1024) {
+            const int q = i / MK, r = i - q * MK;
+            lds_s[((q >> 2) * MK + r) * 4 + (q & 3)] = lut[i];
+        }
+    }
+    unsigned* qk = reinterpret_cast<unsigned*>(lds_s + NQ * MK);   // [16][NQ][kSearchQueue]
+    unsigned* qi = qk + kSearchWaves * NQ * kSearchQueue;
+    __syncthreads();
+    const int wave = threadIdx.x >> 6;
+    SearchState<L> st[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) st[q].init();
+    const int64_t row_begin = (int64_t)blockIdx.x * rows_per_wg;
+    int64_t row_end = row_begin + rows_per_wg;
+    if (row_end > n) row_end = n;
+    const uintptr_t lo = reinterpret_cast<uintptr_t>(codes);
+    const uintptr_t hi = lo + (uintptr_t)((n - 1) * c_rs + M);      // one past the last code byte
+    bool bad = false;
+    for (int64_t base = row_begin; base < row_end; base += 1024) {  // wave-uniform trip count: the selection is wave-wide
+        const int64_t row = base + threadIdx.x;
+        const bool valid = row < row_end;
+        float neg[NQ];                                              // -score per query
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) neg[q] = 0.f;
+        if (valid) {
+            const float sc = scales ? scales[row] : 1.f;
+            const uintptr_t a = lo + (uintptr_t)(row * c_rs);
+            unsigned w[NW];
+            adc_fetch_row<NW>(a, lo, hi, M, w);
+            const unsigned sh = (unsigned)(a & 3);
+            if constexpr (NQ == 1) {
+                neg[0] = -fmul(adc_row_sum<NV>(w, sh, lds_s, M, K, bad), sc);
+            } else {
+                f32x2 s[NH][2];
+#pragma unroll
+                for (int hq = 0; hq < NH; ++hq) { s[hq][0] = (f32x2){0.f, 0.f}; s[hq][1] = (f32x2){0.f, 0.f}; }
+                adc_row_sum_mq<NV, NH>(w, sh, lds_s, M, K, MK, bad, s);
+#pragma unroll
+                for (int hq = 0; hq < NH; ++hq) {
+                    neg[4 * hq + 0] = -fmul(s[hq][0][0], sc);
+                    neg[4 * hq + 1] = -fmul(s[hq][0][1], sc);
+                    neg[4 * hq + 2] = -fmul(s[hq][1][0], sc);
+                    neg[4 * hq + 3] = -fmul(s[hq][1][1], sc);
+                }
+            }
+        }
+        const unsigned off = (unsigned)(row - row_begin);
+#pragma unroll
+        for (int q = 0; q < NQ; ++q)
+            st[q].offer(neg[q], off, valid, qk + (wave * NQ + q) * kSearchQueue, qi + (wave * NQ + q) * kSearchQueue, kk);
+    }
+    if (bad) atomicOr(err, 1);
+    search_finish<NQ, L>(st, qk, qi, reinterpret_cast<unsigned*>(lds_s), row_begin, part_k, part_i);
+}
+
+// k_adc_search_any in similarity form: any code width, the table in LDS when TAB_LDS, else read through L2
+template <typename IdxT, int L, bool TAB_LDS>
+__global__ __launch_bounds__(1024) void k_adc_ip_search_any(const IdxT* __restrict__ codes, int64_t n, int64_t c_rs,
+                                                            const float* __restrict__ lut,
+                                                            const float* __restrict__ scales /* [n] or null */, int M, int K,
+                                                            int kk, int64_t rows_per_wg, unsigned* __restrict__ part_k,
+                                                            uint64_t* __restrict__ part_i, int* __restrict__ err)
+{
+    extern __shared__ __attribute__((aligned(16))) float lds_a[];
+    const int MK = M * K;
+    const float* tab = lut;
+    unsigned* qk = reinterpret_cast<unsigned*>(lds_a);
+    if (TAB_LDS) {
+        for (int i = threadIdx.x; i < MK; i += 1024) lds_a[i] = lut[i];
+        tab = lds_a;
+        qk = reinterpret_cast<unsigned*>(lds_a + MK);
+    }
+    unsigned* qi = qk + kSearchWaves * kSearchQueue;
+    __syncthreads();
+    const int wave = threadIdx.x >> 6;
+    SearchState<L> st[1];
+    st[0].init();
+    const int64_t row_begin = (int64_t)blockIdx.x * rows_per_wg;
+    int64_t row_end = row_begin + rows_per_wg;
+    if (row_end > n) row_end = n;
+    bool bad = false;
+    for (int64_t base = row_begin; base < row_end; base += 1024) {
+        const int64_t row = base + threadIdx.x;
+        const bool valid = row < row_end;
+        float neg = 0.f;
+        if (valid) {
+            const IdxT* cr = codes + row * c_rs;
+            float s = 0.f;
+            for (int m = 0; m < M; ++m) {
+                uint64_t c = (uint64_t)cr[m];
+                if (c >= (uint64_t)K) { bad = true; c = 0; }
+                s = fadd(s, tab[(int64_t)m * K + (int64_t)c]);
+            }
+            neg = -fmul(s, scales ? scales[row] : 1.f);
+        }
+        st[0].offer(neg, (unsigned)(row - row_begin), valid, qk + wave * kSearchQueue, qi + wave * kSearchQueue, kk);
+    }
+    if (bad) atomicOr(err, 1);
+    search_finish<1, L>(st, qk, qi, reinterpret_cast<unsigned*>(lds_a), row_begin, part_k, part_i);
+}
+
+// the score a similarity key stands for (the key is that of -score): a zero comes back as +0 (0 - (+0)), a NaN as the
+// canonical quiet NaN, every other score bit for bit (0 - v = -v exactly)
+__device__ __forceinline__ float adc_ip_key_score(unsigned key)
+{
+    if (key == 0xffffffffu) return __uint_as_float(0x7fc00000u);
+    return fsub(0.f, adc_key_value(key));
+}
+
+// k_adc_search_merge in similarity form: the same list merge; writes the scores of the first kk entries, and past the
+// last row index -1 and -Inf.
+template <int L>
+__global__ __launch_bounds__(512) void k_adc_ip_search_merge(const unsigned* __restrict__ part_k,
+                                                             const uint64_t* __restrict__ part_i, int n_lists, int kk,
+                                                             float* __restrict__ score, int64_t s_rs,
+                                                             int64_t* __restrict__ idx, int64_t i_rs)
+{
+    constexpr int LK = 64 * L;
+    extern __shared__ __attribute__((aligned(16))) unsigned lds_m[];
+    unsigned* ck = lds_m;                                                    // [8][LK]
+    uint64_t* ci = reinterpret_cast<uint64_t*>(lds_m + kSearchMergeWaves * LK);   // [8][LK]
+    const int q = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    WaveList<L, uint64_t> lst;
+    lst.clear();
+    for (int g = wave; g < n_lists; g += kSearchMergeWaves) {
+        const size_t base = ((size_t)q * n_lists + g) * LK;
+        lst.merge_sorted(part_k + base, part_i + base);
+    }
+    lst.store(ck + wave * LK, ci + wave * LK);
+    __syncthreads();
+    for (int h = kSearchMergeWaves / 2; h >= 1; h >>= 1) {
+        if (wave < h) {
+            lst.merge_sorted(ck + (wave + h) * LK, ci + (wave + h) * LK);
+            lst.store(ck + wave * LK, ci + wave * LK);
+        }
+        __syncthreads();
+    }
+    if (wave == 0) {
+#pragma unroll
+        for (int r = 0; r < L; ++r) {
+            const int e = r * 64 + lane;
+            if (e < kk) {
+                const bool pad = lst.i[r] == ~0ull;
+                score[(int64_t)q * s_rs + e] = pad ? __uint_as_float(0xff800000u) : adc_ip_key_score(lst.k[r]);
                 idx[(int64_t)q * i_rs + e] = pad ? (int64_t)-1 : (int64_t)lst.i[r];
             }
         }

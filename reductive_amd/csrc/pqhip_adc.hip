@@ -67,6 +67,7 @@ struct SearchLaunch {
     int64_t n, c_rs, rows_per_wg;
     unsigned grid;
     int M, K, k;
+    const float* scales;     // IP: [n] row scales or null; unused by the distance search
     unsigned* part_k;
     uint64_t* part_i;
     int* err;
@@ -81,112 +82,129 @@ inline size_t search_lds(size_t table_bytes, int nq, int L)
     return std::max(table_bytes + queues, comb);
 }
 
-template <int NV, int NQ, int L>
+// IP = false: the distance search (k_adc_search_*); IP = true: the similarity search (k_adc_ip_search_*)
+template <bool IP, int NV, int NQ, int L>
 int32_t launch_search_u8(const SearchLaunch& a, const uint8_t* codes, const float* lut, size_t lds)
 {
     if constexpr (NQ * L > 16) {
         return PQHIP_EUNSUPPORTED;
     } else {
-        const void* kern = (const void*)k_adc_search_u8<NV, NQ, L>;
+        const void* kern = IP ? (const void*)k_adc_ip_search_u8<NV, NQ, L> : (const void*)k_adc_search_u8<NV, NQ, L>;
         HIPCHK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        hipLaunchKernelGGL((k_adc_search_u8<NV, NQ, L>), dim3(a.grid), dim3(1024), lds, a.st, codes, a.n, a.c_rs, lut, a.M, a.K,
-                           a.k, a.rows_per_wg, a.part_k, a.part_i, a.err);
-        note_kernel(NQ == 8 ? "k_adc_search_u8_mq<8 queries>" : NQ == 4 ? "k_adc_search_u8_mq<4 queries>" : "k_adc_search_u8");
+        if constexpr (IP) {
+            hipLaunchKernelGGL((k_adc_ip_search_u8<NV, NQ, L>), dim3(a.grid), dim3(1024), lds, a.st, codes, a.n, a.c_rs, lut,
+                               a.scales, a.M, a.K, a.k, a.rows_per_wg, a.part_k, a.part_i, a.err);
+            note_kernel(NQ == 8 ? "k_adc_ip_search_u8_mq<8 queries>" : NQ == 4 ? "k_adc_ip_search_u8_mq<4 queries>" : "k_adc_ip_search_u8");
+        } else {
+            hipLaunchKernelGGL((k_adc_search_u8<NV, NQ, L>), dim3(a.grid), dim3(1024), lds, a.st, codes, a.n, a.c_rs, lut, a.M, a.K,
+                               a.k, a.rows_per_wg, a.part_k, a.part_i, a.err);
+            note_kernel(NQ == 8 ? "k_adc_search_u8_mq<8 queries>" : NQ == 4 ? "k_adc_search_u8_mq<4 queries>" : "k_adc_search_u8");
+        }
         return PQHIP_OK;
     }
 }
 
-template <int NQ, int L>
+template <bool IP, int NQ, int L>
 int32_t launch_search_u8_nv(int nvb, const SearchLaunch& a, const uint8_t* codes, const float* lut, size_t lds)
 {
     switch (nvb) {
-    case 1: return launch_search_u8<1, NQ, L>(a, codes, lut, lds);
-    case 2: return launch_search_u8<2, NQ, L>(a, codes, lut, lds);
-    case 4: return launch_search_u8<4, NQ, L>(a, codes, lut, lds);
-    case 8: return launch_search_u8<8, NQ, L>(a, codes, lut, lds);
-    case 13: return launch_search_u8<13, NQ, L>(a, codes, lut, lds);
-    case kAdcMaxValueWords: return launch_search_u8<kAdcMaxValueWords, NQ, L>(a, codes, lut, lds);
+    case 1: return launch_search_u8<IP, 1, NQ, L>(a, codes, lut, lds);
+    case 2: return launch_search_u8<IP, 2, NQ, L>(a, codes, lut, lds);
+    case 4: return launch_search_u8<IP, 4, NQ, L>(a, codes, lut, lds);
+    case 8: return launch_search_u8<IP, 8, NQ, L>(a, codes, lut, lds);
+    case 13: return launch_search_u8<IP, 13, NQ, L>(a, codes, lut, lds);
+    case kAdcMaxValueWords: return launch_search_u8<IP, kAdcMaxValueWords, NQ, L>(a, codes, lut, lds);
     default: return PQHIP_EUNSUPPORTED;
     }
 }
 
-template <int NQ>
+template <bool IP, int NQ>
 int32_t launch_search_u8_l(int L, int nvb, const SearchLaunch& a, const uint8_t* codes, const float* lut, size_t lds)
 {
     switch (L) {
-    case 1: return launch_search_u8_nv<NQ, 1>(nvb, a, codes, lut, lds);
-    case 2: return launch_search_u8_nv<NQ, 2>(nvb, a, codes, lut, lds);
-    case 4: return launch_search_u8_nv<NQ, 4>(nvb, a, codes, lut, lds);
-    case 8: return launch_search_u8_nv<NQ, 8>(nvb, a, codes, lut, lds);
-    case 16: return launch_search_u8_nv<NQ, 16>(nvb, a, codes, lut, lds);
+    case 1: return launch_search_u8_nv<IP, NQ, 1>(nvb, a, codes, lut, lds);
+    case 2: return launch_search_u8_nv<IP, NQ, 2>(nvb, a, codes, lut, lds);
+    case 4: return launch_search_u8_nv<IP, NQ, 4>(nvb, a, codes, lut, lds);
+    case 8: return launch_search_u8_nv<IP, NQ, 8>(nvb, a, codes, lut, lds);
+    case 16: return launch_search_u8_nv<IP, NQ, 16>(nvb, a, codes, lut, lds);
     default: return PQHIP_EUNSUPPORTED;
     }
 }
 
-template <typename IdxT, int L>
+template <bool IP, typename IdxT, int L, bool TAB_LDS>
+void launch_search_any_t(const SearchLaunch& a, const IdxT* codes, const float* lut, size_t lds)
+{
+    if constexpr (IP)
+        hipLaunchKernelGGL((k_adc_ip_search_any<IdxT, L, TAB_LDS>), dim3(a.grid), dim3(1024), lds, a.st, codes, a.n, a.c_rs,
+                           lut, a.scales, a.M, a.K, a.k, a.rows_per_wg, a.part_k, a.part_i, a.err);
+    else
+        hipLaunchKernelGGL((k_adc_search_any<IdxT, L, TAB_LDS>), dim3(a.grid), dim3(1024), lds, a.st, codes, a.n, a.c_rs, lut,
+                           a.M, a.K, a.k, a.rows_per_wg, a.part_k, a.part_i, a.err);
+}
+
+template <bool IP, typename IdxT, int L>
 int32_t launch_search_any(const SearchLaunch& a, const IdxT* codes, const float* lut, bool tab_lds)
 {
     const size_t table = tab_lds ? (size_t)a.M * a.K * sizeof(float) : 0;
     const size_t lds = search_lds(table, 1, L);
-    const void* kern = tab_lds ? (const void*)k_adc_search_any<IdxT, L, true> : (const void*)k_adc_search_any<IdxT, L, false>;
+    const void* kern = IP ? (tab_lds ? (const void*)k_adc_ip_search_any<IdxT, L, true> : (const void*)k_adc_ip_search_any<IdxT, L, false>)
+                          : (tab_lds ? (const void*)k_adc_search_any<IdxT, L, true> : (const void*)k_adc_search_any<IdxT, L, false>);
     HIPCHK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    if (tab_lds)
-        hipLaunchKernelGGL((k_adc_search_any<IdxT, L, true>), dim3(a.grid), dim3(1024), lds, a.st, codes, a.n, a.c_rs, lut,
-                           a.M, a.K, a.k, a.rows_per_wg, a.part_k, a.part_i, a.err);
-    else
-        hipLaunchKernelGGL((k_adc_search_any<IdxT, L, false>), dim3(a.grid), dim3(1024), lds, a.st, codes, a.n, a.c_rs, lut,
-                           a.M, a.K, a.k, a.rows_per_wg, a.part_k, a.part_i, a.err);
-    note_kernel(tab_lds ? "k_adc_search_wide" : "k_adc_search_any");
+    if (tab_lds) launch_search_any_t<IP, IdxT, L, true>(a, codes, lut, lds);
+    else launch_search_any_t<IP, IdxT, L, false>(a, codes, lut, lds);
+    if (IP) note_kernel(tab_lds ? "k_adc_ip_search_wide" : "k_adc_ip_search_any");
+    else note_kernel(tab_lds ? "k_adc_search_wide" : "k_adc_search_any");
     return PQHIP_OK;
 }
 
-template <typename IdxT>
+template <bool IP, typename IdxT>
 int32_t launch_search_any_l(int L, const SearchLaunch& a, const IdxT* codes, const float* lut, bool tab_lds)
 {
     switch (L) {
-    case 1: return launch_search_any<IdxT, 1>(a, codes, lut, tab_lds);
-    case 2: return launch_search_any<IdxT, 2>(a, codes, lut, tab_lds);
-    case 4: return launch_search_any<IdxT, 4>(a, codes, lut, tab_lds);
-    case 8: return launch_search_any<IdxT, 8>(a, codes, lut, tab_lds);
-    case 16: return launch_search_any<IdxT, 16>(a, codes, lut, tab_lds);
+    case 1: return launch_search_any<IP, IdxT, 1>(a, codes, lut, tab_lds);
+    case 2: return launch_search_any<IP, IdxT, 2>(a, codes, lut, tab_lds);
+    case 4: return launch_search_any<IP, IdxT, 4>(a, codes, lut, tab_lds);
+    case 8: return launch_search_any<IP, IdxT, 8>(a, codes, lut, tab_lds);
+    case 16: return launch_search_any<IP, IdxT, 16>(a, codes, lut, tab_lds);
     default: return PQHIP_EUNSUPPORTED;
     }
 }
 
-template <int L>
+template <bool IP, int L>
 int32_t launch_search_merge_t(int nq, int n_lists, int k, const unsigned* part_k, const uint64_t* part_i, float* dist, int64_t d_rs,
                               int64_t* idx, int64_t i_rs, hipStream_t st)
 {
     const size_t lds = (size_t)kSearchMergeWaves * 64 * L * (sizeof(unsigned) + sizeof(uint64_t));
-    HIPCHK(hipFuncSetAttribute((const void*)k_adc_search_merge<L>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    hipLaunchKernelGGL((k_adc_search_merge<L>), dim3((unsigned)nq), dim3(64 * kSearchMergeWaves), lds, st, part_k, part_i,
-                       n_lists, k, dist, d_rs, idx, i_rs);
-    note_kernel("k_adc_search_merge");
+    const void* kern = IP ? (const void*)k_adc_ip_search_merge<L> : (const void*)k_adc_search_merge<L>;
+    HIPCHK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    if constexpr (IP)
+        hipLaunchKernelGGL((k_adc_ip_search_merge<L>), dim3((unsigned)nq), dim3(64 * kSearchMergeWaves), lds, st, part_k, part_i,
+                           n_lists, k, dist, d_rs, idx, i_rs);
+    else
+        hipLaunchKernelGGL((k_adc_search_merge<L>), dim3((unsigned)nq), dim3(64 * kSearchMergeWaves), lds, st, part_k, part_i,
+                           n_lists, k, dist, d_rs, idx, i_rs);
+    note_kernel(IP ? "k_adc_ip_search_merge" : "k_adc_search_merge");
     return PQHIP_OK;
 }
 
+template <bool IP>
 int32_t launch_search_merge(int L, int nq, int n_lists, int k, const unsigned* part_k, const uint64_t* part_i, float* dist,
                             int64_t d_rs, int64_t* idx, int64_t i_rs, hipStream_t st)
 {
     switch (L) {
-    case 1: return launch_search_merge_t<1>(nq, n_lists, k, part_k, part_i, dist, d_rs, idx, i_rs, st);
-    case 2: return launch_search_merge_t<2>(nq, n_lists, k, part_k, part_i, dist, d_rs, idx, i_rs, st);
-    case 4: return launch_search_merge_t<4>(nq, n_lists, k, part_k, part_i, dist, d_rs, idx, i_rs, st);
-    case 8: return launch_search_merge_t<8>(nq, n_lists, k, part_k, part_i, dist, d_rs, idx, i_rs, st);
-    case 16: return launch_search_merge_t<16>(nq, n_lists, k, part_k, part_i, dist, d_rs, idx, i_rs, st);
+    case 1: return launch_search_merge_t<IP, 1>(nq, n_lists, k, part_k, part_i, dist, d_rs, idx, i_rs, st);
+    case 2: return launch_search_merge_t<IP, 2>(nq, n_lists, k, part_k, part_i, dist, d_rs, idx, i_rs, st);
+    case 4: return launch_search_merge_t<IP, 4>(nq, n_lists, k, part_k, part_i, dist, d_rs, idx, i_rs, st);
+    case 8: return launch_search_merge_t<IP, 8>(nq, n_lists, k, part_k, part_i, dist, d_rs, idx, i_rs, st);
+    case 16: return launch_search_merge_t<IP, 16>(nq, n_lists, k, part_k, part_i, dist, d_rs, idx, i_rs, st);
     default: return PQHIP_EUNSUPPORTED;
     }
 }
 
-}  // namespace pqh
-
-using namespace pqh;
-
-extern "C" {
-
-// ---- "next" row: asymmetric distance computation over a resident code matrix ----------------------
-int32_t pqhip_adc_tables_f32_dev(pqhip_codebook* cb, int32_t slot, const float* d_q, int64_t nq, int64_t q_rs,
-                                 float* d_tables, void* stream)
+// Lookup tables for both searches: the query is rotated first for an OPQ codebook (pq.rs:293), then one thread per
+// (q, m, j) writes the squared distance (k_adc_tables) or, IP, the inner product alone (k_adc_ip_tables).
+int32_t adc_tables(bool ip, pqhip_codebook* cb, int32_t slot, const float* d_q, int64_t nq, int64_t q_rs, float* d_tables,
+                   void* stream)
 {
     if (!cb || nq < 0) return PQHIP_EINVAL;
     if (slot < 0 || slot >= (int)cb->dev.size()) return PQHIP_ENODEV;
@@ -210,13 +228,117 @@ int32_t pqhip_adc_tables_f32_dev(pqhip_codebook* cb, int32_t slot, const float* 
         y_rs = cb->d;
     }
     const int64_t total = nq * cb->M * cb->K;
-    hipLaunchKernelGGL(k_adc_tables, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, y, y_rs, (int)nq, cd.cb,
-                       cd.cc, (int)cb->M, (int)cb->K, (int)cb->dsub, cb->k_pad, d_tables);
+    if (ip) {
+        hipLaunchKernelGGL(k_adc_ip_tables, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, y, y_rs, (int)nq, cd.cb,
+                           (int)cb->M, (int)cb->K, (int)cb->dsub, d_tables);
+    } else {
+        hipLaunchKernelGGL(k_adc_tables, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, y, y_rs, (int)nq, cd.cb,
+                           cd.cc, (int)cb->M, (int)cb->K, (int)cb->dsub, cb->k_pad, d_tables);
+    }
     HIPCHK(hipGetLastError());
-    note_kernel("k_adc_tables");
+    note_kernel(ip ? "k_adc_ip_tables" : "k_adc_tables");
     return PQHIP_OK;
 }
 
+// The fused scan + exact top-k of both searches, one policy: argument checks, queries per pass (NQ L <= 16 and the
+// 160 KB of LDS, option "adc_single_query"), the u8 fast path or the generic kernel, the partial lists in the
+// codebook's scratch, one merge per pass.  IP: similarity (k_adc_ip_search_*, d_scales may be null); else distance.
+template <bool IP>
+int32_t adc_search(pqhip_codebook* cb, int32_t slot, const float* d_tables, int64_t nq, const void* d_codes, int32_t code_bytes,
+                   int64_t n, int64_t c_rs, const float* d_scales, int32_t k, float* d_dist, int64_t d_rs, int64_t* d_idx,
+                   int64_t i_rs, void* stream)
+{
+    if (!cb || nq < 0 || n < 0 || k < 1) return PQHIP_EINVAL;
+    if (slot < 0 || slot >= (int)cb->dev.size()) return PQHIP_ENODEV;
+    if (code_bytes != 1 && code_bytes != 4) return PQHIP_EUNSUPPORTED;
+    if (k > kSearchMaxK) return PQHIP_EUNSUPPORTED;
+    if (nq == 0) return PQHIP_OK;
+    if (!d_dist || !d_idx || (n > 0 && (!d_tables || !d_codes))) return PQHIP_EINVAL;
+    if ((n > 0 && c_rs < cb->M) || d_rs < k || i_rs < k) return PQHIP_ESHAPE;
+    SET_DEVICE(cb->ctx->devs[slot]->ordinal);
+    hipStream_t st = (hipStream_t)stream;
+    const int L = search_list_regs(k);
+    if (n == 0) {      // padding only
+        for (int64_t q = 0; q < nq; q += 65535) {
+            const int nqp = (int)std::min<int64_t>(nq - q, 65535);
+            PQCHK(launch_search_merge<IP>(L, nqp, 0, k, nullptr, nullptr, d_dist + q * d_rs, d_rs, d_idx + q * i_rs, i_rs, st));
+            HIPCHK(hipGetLastError());
+        }
+        return PQHIP_OK;
+    }
+    ErrFlag ef(cb, slot, st);
+    const int M = (int)cb->M, K = (int)cb->K;
+    const size_t table = (size_t)M * K * sizeof(float);
+    const int nv = (M + 3) / 4;
+    const int nvb = search_nv_bucket(nv);
+    const bool fast = code_bytes == 1 && nvb != 0 && search_lds(table, 1, L) <= 160 * 1024;
+    // Queries per pass on the fast path: every query of a pass keeps a list of 64 L entries (2 L VGPRs) per wave, so
+    // NQ L <= 16 (at most 32 list VGPRs beside the row sum; 1,024-thread workgroups leave 128 VGPRs per lane): 8 queries
+    // up to k = 128, 4 up to k = 256, one beyond -- and only while NQ table images plus the queues fit the 160 KB of LDS.
+    // Option "adc_single_query" = 1 keeps one query per pass, as for the scan.
+    const bool mq_on = cb->ctx->opt.adc_single_query.load(std::memory_order_relaxed) == 0;
+    int nqp_first = 1;
+    if (fast && mq_on) {
+        for (int c : {8, 4}) {
+            if (c * L <= 16 && search_lds(table * c, c, L) <= 160 * 1024 && nq >= c) { nqp_first = c; break; }
+        }
+    }
+    const int n_cus = cb->ctx->devs[slot]->n_cus;
+    // one 1,024-thread workgroup per CU, a contiguous row range each (offsets within it are 32-bit: < 2^31 rows)
+    int64_t rows_per_wg = round_up((n + n_cus - 1) / n_cus, 1024);
+    rows_per_wg = std::max<int64_t>(rows_per_wg, 4096);
+    rows_per_wg = std::min<int64_t>(rows_per_wg, (int64_t)1 << 30);
+    const int64_t grid = (n + rows_per_wg - 1) / rows_per_wg;
+    const size_t list_entries = (size_t)nqp_first * grid * 64 * L;
+    ScratchLease part(cb, slot, st);
+    PQCHK(part.acquire(list_entries * (sizeof(unsigned) + sizeof(uint64_t))));
+    uint64_t* part_i = (uint64_t*)part.ptr();
+    unsigned* part_k = (unsigned*)(part_i + list_entries);
+    SearchLaunch a{n, c_rs, rows_per_wg, (unsigned)grid, M, K, k, d_scales, part_k, part_i, ef.flag, st};
+    const bool adc_any = diag().adc_any;
+    int64_t q = 0;
+    for (int nqp : {8, 4, 1}) {
+        if (nqp > nqp_first) continue;
+        if (nqp == 4 && !(fast && mq_on && 4 * L <= 16 && search_lds(table * 4, 4, L) <= 160 * 1024)) continue;
+        for (; q + nqp <= nq; q += nqp) {
+            const float* lut = d_tables + q * (int64_t)M * K;
+            if (fast) {
+                const size_t lds = search_lds(table * nqp, nqp, L);
+                if (nqp == 8) PQCHK((launch_search_u8_l<IP, 8>(L, nvb, a, (const uint8_t*)d_codes, lut, lds)));
+                else if (nqp == 4) PQCHK((launch_search_u8_l<IP, 4>(L, nvb, a, (const uint8_t*)d_codes, lut, lds)));
+                else PQCHK((launch_search_u8_l<IP, 1>(L, nvb, a, (const uint8_t*)d_codes, lut, lds)));
+            } else {
+                const bool tab_lds = !adc_any && search_lds(table, 1, L) <= 160 * 1024;
+                if (code_bytes == 1) PQCHK((launch_search_any_l<IP, uint8_t>(L, a, (const uint8_t*)d_codes, lut, tab_lds)));
+                else PQCHK((launch_search_any_l<IP, uint32_t>(L, a, (const uint32_t*)d_codes, lut, tab_lds)));
+            }
+            HIPCHK(hipGetLastError());
+            PQCHK(launch_search_merge<IP>(L, nqp, (int)grid, k, part_k, part_i, d_dist + q * d_rs, d_rs, d_idx + q * i_rs, i_rs, st));
+            HIPCHK(hipGetLastError());
+        }
+    }
+    return PQHIP_OK;
+}
+
+}  // namespace pqh
+
+using namespace pqh;
+
+extern "C" {
+
+// ---- "next" row: asymmetric distance computation over a resident code matrix ----------------------
+int32_t pqhip_adc_tables_f32_dev(pqhip_codebook* cb, int32_t slot, const float* d_q, int64_t nq, int64_t q_rs,
+                                 float* d_tables, void* stream)
+{
+    return adc_tables(false, cb, slot, d_q, nq, q_rs, d_tables, stream);
+}
+
+// similarity search: the inner-product tables (the dp term of the distance tables)
+int32_t pqhip_adc_ip_tables_f32_dev(pqhip_codebook* cb, int32_t slot, const float* d_q, int64_t nq, int64_t q_rs,
+                                    float* d_tables, void* stream)
+{
+    return adc_tables(true, cb, slot, d_q, nq, q_rs, d_tables, stream);
+}
 
 int32_t pqhip_adc_scan_f32_dev(pqhip_codebook* cb, int32_t slot, const float* d_tables, int64_t nq, const void* d_codes,
                                int32_t code_bytes, int64_t n, int64_t c_rs, float* d_out, int64_t o_rs, void* stream)
@@ -284,76 +406,14 @@ int32_t pqhip_adc_search_f32_dev(pqhip_codebook* cb, int32_t slot, const float* 
                                  int32_t code_bytes, int64_t n, int64_t c_rs, int32_t k, float* d_dist, int64_t d_rs,
                                  int64_t* d_idx, int64_t i_rs, void* stream)
 {
-    if (!cb || nq < 0 || n < 0 || k < 1) return PQHIP_EINVAL;
-    if (slot < 0 || slot >= (int)cb->dev.size()) return PQHIP_ENODEV;
-    if (code_bytes != 1 && code_bytes != 4) return PQHIP_EUNSUPPORTED;
-    if (k > kSearchMaxK) return PQHIP_EUNSUPPORTED;
-    if (nq == 0) return PQHIP_OK;
-    if (!d_dist || !d_idx || (n > 0 && (!d_tables || !d_codes))) return PQHIP_EINVAL;
-    if ((n > 0 && c_rs < cb->M) || d_rs < k || i_rs < k) return PQHIP_ESHAPE;
-    SET_DEVICE(cb->ctx->devs[slot]->ordinal);
-    hipStream_t st = (hipStream_t)stream;
-    const int L = search_list_regs(k);
-    if (n == 0) {      // padding only
-        for (int64_t q = 0; q < nq; q += 65535) {
-            const int nqp = (int)std::min<int64_t>(nq - q, 65535);
-            PQCHK(launch_search_merge(L, nqp, 0, k, nullptr, nullptr, d_dist + q * d_rs, d_rs, d_idx + q * i_rs, i_rs, st));
-            HIPCHK(hipGetLastError());
-        }
-        return PQHIP_OK;
-    }
-    ErrFlag ef(cb, slot, st);
-    const int M = (int)cb->M, K = (int)cb->K;
-    const size_t table = (size_t)M * K * sizeof(float);
-    const int nv = (M + 3) / 4;
-    const int nvb = search_nv_bucket(nv);
-    const bool fast = code_bytes == 1 && nvb != 0 && search_lds(table, 1, L) <= 160 * 1024;
-    // Queries per pass on the fast path: every query of a pass keeps a list of 64 L entries (2 L VGPRs) per wave, so
-    // NQ L <= 16 (at most 32 list VGPRs beside the row sum; 1,024-thread workgroups leave 128 VGPRs per lane): 8 queries
-    // up to k = 128, 4 up to k = 256, one beyond -- and only while NQ table images plus the queues fit the 160 KB of LDS.
-    // Option "adc_single_query" = 1 keeps one query per pass, as for the scan.
-    const bool mq_on = cb->ctx->opt.adc_single_query.load(std::memory_order_relaxed) == 0;
-    int nqp_first = 1;
-    if (fast && mq_on) {
-        for (int c : {8, 4}) {
-            if (c * L <= 16 && search_lds(table * c, c, L) <= 160 * 1024 && nq >= c) { nqp_first = c; break; }
-        }
-    }
-    const int n_cus = cb->ctx->devs[slot]->n_cus;
-    // one 1,024-thread workgroup per CU, a contiguous row range each (offsets within it are 32-bit: < 2^31 rows)
-    int64_t rows_per_wg = round_up((n + n_cus - 1) / n_cus, 1024);
-    rows_per_wg = std::max<int64_t>(rows_per_wg, 4096);
-    rows_per_wg = std::min<int64_t>(rows_per_wg, (int64_t)1 << 30);
-    const int64_t grid = (n + rows_per_wg - 1) / rows_per_wg;
-    const size_t list_entries = (size_t)nqp_first * grid * 64 * L;
-    ScratchLease part(cb, slot, st);
-    PQCHK(part.acquire(list_entries * (sizeof(unsigned) + sizeof(uint64_t))));
-    uint64_t* part_i = (uint64_t*)part.ptr();
-    unsigned* part_k = (unsigned*)(part_i + list_entries);
-    SearchLaunch a{n, c_rs, rows_per_wg, (unsigned)grid, M, K, k, part_k, part_i, ef.flag, st};
-    const bool adc_any = diag().adc_any;
-    int64_t q = 0;
-    for (int nqp : {8, 4, 1}) {
-        if (nqp > nqp_first) continue;
-        if (nqp == 4 && !(fast && mq_on && 4 * L <= 16 && search_lds(table * 4, 4, L) <= 160 * 1024)) continue;
-        for (; q + nqp <= nq; q += nqp) {
-            const float* lut = d_tables + q * (int64_t)M * K;
-            if (fast) {
-                const size_t lds = search_lds(table * nqp, nqp, L);
-                if (nqp == 8) PQCHK(launch_search_u8_l<8>(L, nvb, a, (const uint8_t*)d_codes, lut, lds));
-                else if (nqp == 4) PQCHK(launch_search_u8_l<4>(L, nvb, a, (const uint8_t*)d_codes, lut, lds));
-                else PQCHK(launch_search_u8_l<1>(L, nvb, a, (const uint8_t*)d_codes, lut, lds));
-            } else {
-                const bool tab_lds = !adc_any && search_lds(table, 1, L) <= 160 * 1024;
-                if (code_bytes == 1) PQCHK(launch_search_any_l<uint8_t>(L, a, (const uint8_t*)d_codes, lut, tab_lds));
-                else PQCHK(launch_search_any_l<uint32_t>(L, a, (const uint32_t*)d_codes, lut, tab_lds));
-            }
-            HIPCHK(hipGetLastError());
-            PQCHK(launch_search_merge(L, nqp, (int)grid, k, part_k, part_i, d_dist + q * d_rs, d_rs, d_idx + q * i_rs, i_rs, st));
-            HIPCHK(hipGetLastError());
-        }
-    }
-    return PQHIP_OK;
+    return adc_search<false>(cb, slot, d_tables, nq, d_codes, code_bytes, n, c_rs, nullptr, k, d_dist, d_rs, d_idx, i_rs, stream);
+}
+
+int32_t pqhip_adc_ip_search_f32_dev(pqhip_codebook* cb, int32_t slot, const float* d_tables, int64_t nq, const void* d_codes,
+                                    int32_t code_bytes, int64_t n, int64_t c_rs, const float* d_scales, int32_t k,
+                                    float* d_score, int64_t s_rs, int64_t* d_idx, int64_t i_rs, void* stream)
+{
+    return adc_search<true>(cb, slot, d_tables, nq, d_codes, code_bytes, n, c_rs, d_scales, k, d_score, s_rs, d_idx, i_rs, stream);
 }
 
 }  // extern "C"

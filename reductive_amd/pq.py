@@ -911,3 +911,71 @@ class Pq:
             if rc != _lib.OK:
                 raise _lib.PqHipError(rc, "pqhip_check_codes_dev")
         return (dist[0], idx[0]) if single else (dist, idx)
+
+    # ---- ADC similarity search: inner products over resident codes --------------------------------------------------
+    def adc_ip_tables_device(self, queries, stream=None):
+        """queries: CUDA float32 [d] or [nq, d] -> inner-product tables [M, K] or [nq, M, K]:
+        tables[q, m, j] = unrolled_dot(quantizers[m, j], y_q[m]), the dp term of adc_tables_device (y = query.dot(projection)
+        first for OPQ).  sum_m tables[q, m, codes[i, m]] is <query_q, reconstruct(codes[i])> (pqhip_adc_ip_tables_f32_dev)."""
+        import torch
+        assert queries.is_cuda and queries.dtype == torch.float32 and queries.dim() in (1, 2)
+        single = queries.dim() == 1
+        q2 = queries[None] if single else queries
+        if q2.shape[1] != self.reconstructed_len():
+            raise PanicError("Quantizer and vector length mismatch")
+        if q2.stride(1) != 1:
+            q2 = q2.contiguous()
+        M, K = self.quantized_len(), self.n_quantizer_centroids()
+        out = torch.empty((q2.shape[0], M, K), dtype=torch.float32, device=queries.device)
+        cb = self._cb()
+        if stream is None:
+            stream = torch.cuda.current_stream(queries.device).cuda_stream
+        rc = _lib.lib().pqhip_adc_ip_tables_f32_dev(cb, self._slot_for(queries), q2.data_ptr(), q2.shape[0],
+                                                   q2.stride(0) if q2.shape[0] > 1 else max(q2.stride(0), q2.shape[1]),
+                                                   out.data_ptr(), ctypes.c_void_p(stream))
+        if rc != _lib.OK:
+            raise _lib.PqHipError(rc, "pqhip_adc_ip_tables_f32_dev")
+        return out[0] if single else out
+
+    def adc_ip_search_device(self, codes, tables, k, scales=None, stream=None, check=False):
+        """The k most similar rows per query: codes as for adc_scan_device, tables from adc_ip_tables_device, scales None
+        or CUDA float32 [n] -> (score, idx), CUDA float32 and int64 [nq, k] ([k] for 2-D tables).  score[q, j] =
+        fl(scan[q, i] * scales[i]) of row i = idx[q, j] (the scan's sum alone without scales); rows are ordered by
+        descending score -- NaN after -Inf -- then by index (pqhip_adc_ip_search_f32_dev).  A zero score comes back as
+        +0, a NaN as the canonical NaN.  Past the last row: index -1, score -Inf."""
+        import torch
+        assert codes.is_cuda and codes.dtype in (torch.uint8, torch.int32) and codes.dim() == 2
+        assert tables.is_cuda and tables.dtype == torch.float32 and tables.is_contiguous()
+        M, K = self.quantized_len(), self.n_quantizer_centroids()
+        if codes.shape[1] != M:
+            raise PanicError("Quantization length does not match number of subquantizers")
+        single = tables.dim() == 2
+        if tuple(tables.shape[-2:]) != (M, K):
+            raise PanicError("lookup tables must be [.., %d, %d]" % (M, K))
+        nq = 1 if single else tables.shape[0]
+        if codes.stride(1) != 1:
+            codes = codes.contiguous()
+        n = codes.shape[0]
+        if scales is not None:
+            assert scales.is_cuda and scales.dtype == torch.float32 and scales.is_contiguous()
+            if tuple(scales.shape) != (n,):
+                raise PanicError("scales must hold one value per code row")
+        score = torch.empty((nq, k), dtype=torch.float32, device=codes.device)
+        idx = torch.empty((nq, k), dtype=torch.int64, device=codes.device)
+        cb = self._cb()
+        if stream is None:
+            stream = torch.cuda.current_stream(codes.device).cuda_stream
+        slot = self._slot_for(codes)
+        rc = _lib.lib().pqhip_adc_ip_search_f32_dev(cb, slot, tables.data_ptr(), nq, codes.data_ptr(), codes.element_size(),
+                                                   n, codes.stride(0) if n > 1 else max(codes.stride(0), M),
+                                                   scales.data_ptr() if scales is not None else None, k,
+                                                   score.data_ptr(), k, idx.data_ptr(), k, ctypes.c_void_p(stream))
+        if rc != _lib.OK:
+            raise _lib.PqHipError(rc, "pqhip_adc_ip_search_f32_dev")
+        if check:
+            rc = _lib.lib().pqhip_check_codes_dev(cb, slot, ctypes.c_void_p(stream))
+            if rc == _lib.ECODE_RANGE:
+                raise PanicError("ndarray: index out of bounds")
+            if rc != _lib.OK:
+                raise _lib.PqHipError(rc, "pqhip_check_codes_dev")
+        return (score[0], idx[0]) if single else (score, idx)

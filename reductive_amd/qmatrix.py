@@ -101,7 +101,7 @@ def read_chunk(f, stream_offset=None, ctx=None):
 
 
 class QuantizedMatrix:
-    """Codes (+ norms) resident in HBM next to the device codebook: the lookup and scan consumer."""
+    """Codes (+ norms) resident in HBM next to the device codebook: the lookup, scan and similarity-search consumer."""
 
     def __init__(self, pq, codes, norms=None, device="cuda:0"):
         import torch
@@ -134,6 +134,20 @@ class QuantizedMatrix:
     def distances(self, queries):
         """asymmetric squared distances of the query vector(s) to every (un-normalised) code row."""
         return self.pq.adc_scan_device(self.codes, self.pq.adc_tables_device(queries))
+
+    def inner_products(self, queries, use_norms=True):
+        """inner products of the query vector(s) with every row: the scan over the inner-product tables, times the
+        stored norms when use_norms (and the matrix has them) -> [n] or [nq, n]."""
+        ip = self.pq.adc_scan_device(self.codes, self.pq.adc_ip_tables_device(queries))
+        if use_norms and self.norms is not None:
+            ip = ip * self.norms
+        return ip
+
+    def most_similar(self, queries, k, use_norms=True):
+        """the k rows of largest inner product with what embeddings() returns (the stored vectors, unscaled, with
+        use_norms=False or without norms), largest first, ties to the smaller row -> (score, idx) [k] or [nq, k]."""
+        scales = self.norms if use_norms else None
+        return self.pq.adc_ip_search_device(self.codes, self.pq.adc_ip_tables_device(queries), k, scales=scales)
 
 
 def dumps(pq, codes, norms=None):
