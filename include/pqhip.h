@@ -216,6 +216,46 @@ int32_t pqhip_adc_ip_search_f32_dev(pqhip_codebook *cb, int32_t device_slot, con
                                     const float *d_scales, int32_t k, float *d_score, int64_t score_row_stride,
                                     int64_t *d_idx, int64_t idx_row_stride, void *stream);
 
+/*
+ * ADC search over a partitioned code matrix (IVFADC without residual encoding): both searches above restricted, per
+ * query, to the rows of the lists the query probes.  d_list_off [n_lists + 1] int64: list l is rows
+ * [list_off[l], list_off[l + 1]) of d_codes.  d_probes [n_queries][probes_row_stride] int64: the first n_probe entries
+ * of row q are list ids; -1 is padding and is skipped; any other value outside [0, n_lists) is skipped and raises the
+ * stream's range flag.  A list named twice in one row is a caller error: its rows may be returned twice.
+ * S_q = the rows of the lists named by probe row q.  Row q of the outputs receives the first min(k, |S_q|) rows of S_q
+ * ordered by (key(dist), position) ascending -- the similarity search: (key(-score), position) -- with dist, score and
+ * key exactly as for pqhip_adc_search_f32_dev / pqhip_adc_ip_search_f32_dev and position the row's index in d_codes;
+ * index -1 and +Inf (similarity: -Inf) after them.  Returned indices are positions in d_codes; returned values follow
+ * the rules of the exhaustive searches (NaN canonical, a similarity zero as +0).
+ * Hence: the result equals that of pqhip_adc_search_f32_dev / pqhip_adc_ip_search_f32_dev on the same matrix with
+ * every row outside S_q removed, indices mapped back.  The codes are those of the vectors themselves, so approximation
+ * comes only from which lists are probed; with every list probed the result is the exhaustive search's.  The order is
+ * strict: the result does not depend on the number of workgroups that share a query (chosen on the host from n_codes,
+ * n_lists, n_probe, n_queries and the CU count; option "adc_lists_wgs_per_query" forces it).
+ * No byte outside the code matrix is read whatever the offsets and probes hold: a range is clamped to [0, n_codes] and
+ * an inverted range is empty; both raise the range flag (pqhip_check_codes_dev -> PQHIP_ECODE_RANGE), as does a
+ * code >= K, which reads entry 0.
+ * Status codes and their precedence as for pqhip_adc_search_f32_dev (EINVAL, ENODEV, EUNSUPPORTED, ESHAPE), plus:
+ * n_lists < 0, n_probe < 1, or a null d_list_off / d_probes with n_queries > 0: PQHIP_EINVAL; probes_row_stride <
+ * n_probe: PQHIP_ESHAPE; code_bytes != 1, M > 100, a table that does not fit the 160 KB of LDS beside the queues,
+ * n_codes > 2^32 - 2 (positions are compared as 32-bit values) or n_probe >= 2^24: PQHIP_EUNSUPPORTED.
+ * n_queries == 0 launches nothing; n_codes == 0 or n_lists == 0 writes the padding only.  Asynchronous on `stream`;
+ * the per-query segment plan and the partial lists live in the codebook's scratch (queries are processed in chunks
+ * that keep them within 512 MB).
+ */
+int32_t pqhip_adc_search_lists_f32_dev(pqhip_codebook *cb, int32_t device_slot, const float *d_tables, int64_t n_queries,
+                                       const void *d_codes, int32_t code_bytes, int64_t n_codes, int64_t codes_row_stride,
+                                       const int64_t *d_list_off, int64_t n_lists,
+                                       const int64_t *d_probes, int32_t n_probe, int64_t probes_row_stride,
+                                       int32_t k, float *d_dist, int64_t dist_row_stride,
+                                       int64_t *d_idx, int64_t idx_row_stride, void *stream);
+int32_t pqhip_adc_ip_search_lists_f32_dev(pqhip_codebook *cb, int32_t device_slot, const float *d_tables, int64_t n_queries,
+                                          const void *d_codes, int32_t code_bytes, int64_t n_codes, int64_t codes_row_stride,
+                                          const int64_t *d_list_off, int64_t n_lists,
+                                          const int64_t *d_probes, int32_t n_probe, int64_t probes_row_stride,
+                                          const float *d_scales, int32_t k, float *d_score, int64_t score_row_stride,
+                                          int64_t *d_idx, int64_t idx_row_stride, void *stream);
+
 /* Reconstruct's range check is asynchronous on the device path: returns PQHIP_ECODE_RANGE if any
  * device call since the last query saw a code >= K (synchronises `stream`). */
 int32_t pqhip_check_codes_dev(pqhip_codebook *cb, int32_t device_slot, void *stream);
@@ -346,6 +386,7 @@ int32_t pqhip_set_rotation_variant(int32_t variant);
  *   "opq_fused"            0 = OPQ encode as rotation -> scratch -> encode (default 1; PQHIP_FUSED2_OPQ=0 presets 0)
  *   "opq_gather_rotation"  0 = OPQ reconstruct as gather -> scratch -> rotation (default 1)
  *   "adc_single_query"     1 = one scan pass per query (default 0: 8 / 4 queries share a pass)
+ *   "adc_lists_wgs_per_query"  workgroups that share one query of the list searches (0 = chosen from the shape; at most 4096)
  *   "cross_product_exact"  0 = X^T.R of the OPQ training step / pqhip_at_dot_b_f32_dev as a plain split-K product:
  *                          within 1e-5 relative of the exact rule-2 result, no per-block partial matrices (default 1)
  *   "cross_product_group_bytes"  workspace of partial matrices per launch group (0 = 4 GiB)

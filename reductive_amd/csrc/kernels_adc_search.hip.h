@@ -197,10 +197,13 @@ struct SearchState {
 // After the row loop: flush the queues, merge the 16 waves' lists per query through LDS (`comb`: the whole dynamic LDS,
 // at least 16 NQ 64 L 8 bytes; the caller has synchronised the workgroup away from the table image) and write the
 // workgroup's list of query q to part_*[(q * gridDim.x + blockIdx.x) * 64 L ..] with indices made global.
-template <int NQ, int L>
+// QUERY_Y (NQ = 1): the grid is (workgroups of a query, queries) and the query of the list slot is blockIdx.y
+// (kernels_adc_search_lists.hip.h); the slot is formed where it is used, so the other producers compile as before.
+template <int NQ, int L, bool QUERY_Y = false>
 __device__ __forceinline__ void search_finish(SearchState<L> (&st)[NQ], unsigned* qk, unsigned* qi, unsigned* comb,
                                               int64_t row_begin, unsigned* __restrict__ part_k, uint64_t* __restrict__ part_i)
 {
+    static_assert(!QUERY_Y || NQ == 1, "one query per workgroup when the query comes from the grid");
     constexpr int LK = 64 * L;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
 #pragma unroll
@@ -225,7 +228,7 @@ __device__ __forceinline__ void search_finish(SearchState<L> (&st)[NQ], unsigned
     if (wave == 0) {
 #pragma unroll
         for (int q = 0; q < NQ; ++q) {
-            const size_t base = ((size_t)q * gridDim.x + blockIdx.x) * LK;
+            const size_t base = ((size_t)(QUERY_Y ? blockIdx.y : q) * gridDim.x + blockIdx.x) * LK;
 #pragma unroll
             for (int r = 0; r < L; ++r) {
                 const unsigned off = st[q].lst.i[r];

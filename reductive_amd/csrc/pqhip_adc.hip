@@ -4,6 +4,7 @@
 
 #include "kernels_adc.hip.h"
 #include "kernels_adc_search.hip.h"
+#include "kernels_adc_search_lists.hip.h"
 
 using namespace pqhip;
 
@@ -320,6 +321,137 @@ int32_t adc_search(pqhip_codebook* cb, int32_t slot, const float* d_tables, int6
     return PQHIP_OK;
 }
 
+// ---- ADC search over probed lists (kernels_adc_search_lists.hip.h) ----------------------------------------------------
+struct ListsLaunch {
+    int64_t n, c_rs;
+    unsigned G, nq;          // grid (G, nq)
+    int M, K, k, n_probe;
+    const float* scales;
+    const int64_t *seg_begin, *seg_cum;
+    unsigned* part_k;
+    uint64_t* part_i;
+    int* err;
+    hipStream_t st;
+};
+
+// Code dwords per row of the list producers: fewer widths than search_nv_bucket (a wider window is always correct)
+inline int lists_nv_bucket(int nv)
+{
+    for (int b : {4, 8, 13, kAdcMaxValueWords})
+        if (nv <= b) return b;
+    return 0;
+}
+
+template <bool IP, int NV, int L>
+int32_t launch_lists_u8(const ListsLaunch& a, const uint8_t* codes, const float* lut, size_t lds)
+{
+    HIPCHK(hipFuncSetAttribute((const void*)k_adc_search_lists_u8<IP, NV, L>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    hipLaunchKernelGGL((k_adc_search_lists_u8<IP, NV, L>), dim3(a.G, a.nq), dim3(1024), lds, a.st, codes, a.n, a.c_rs, lut,
+                       a.scales, a.M, a.K, a.k, a.seg_begin, a.seg_cum, a.n_probe, a.part_k, a.part_i, a.err);
+    note_kernel(IP ? "k_adc_ip_search_lists_u8" : "k_adc_search_lists_u8");
+    return PQHIP_OK;
+}
+
+template <bool IP, int L>
+int32_t launch_lists_u8_nv(int nvb, const ListsLaunch& a, const uint8_t* codes, const float* lut, size_t lds)
+{
+    switch (nvb) {
+    case 4: return launch_lists_u8<IP, 4, L>(a, codes, lut, lds);
+    case 8: return launch_lists_u8<IP, 8, L>(a, codes, lut, lds);
+    case 13: return launch_lists_u8<IP, 13, L>(a, codes, lut, lds);
+    case kAdcMaxValueWords: return launch_lists_u8<IP, kAdcMaxValueWords, L>(a, codes, lut, lds);
+    default: return PQHIP_EUNSUPPORTED;
+    }
+}
+
+template <bool IP>
+int32_t launch_lists_u8_l(int L, int nvb, const ListsLaunch& a, const uint8_t* codes, const float* lut, size_t lds)
+{
+    switch (L) {
+    case 1: return launch_lists_u8_nv<IP, 1>(nvb, a, codes, lut, lds);
+    case 2: return launch_lists_u8_nv<IP, 2>(nvb, a, codes, lut, lds);
+    case 4: return launch_lists_u8_nv<IP, 4>(nvb, a, codes, lut, lds);
+    case 8: return launch_lists_u8_nv<IP, 8>(nvb, a, codes, lut, lds);
+    case 16: return launch_lists_u8_nv<IP, 16>(nvb, a, codes, lut, lds);
+    default: return PQHIP_EUNSUPPORTED;
+    }
+}
+
+// Workgroups per query, from what the host knows: the expected number of probed rows (lists of average size) in units
+// of 4,096 rows -- below that a workgroup's table load and list merge outweigh its rows, the bound of the exhaustive
+// search -- and no more than the CUs the queries of a launch leave each other (one 1,024-thread workgroup per CU).
+inline int64_t lists_wgs_per_query(int64_t n, int64_t n_lists, int64_t n_probe, int64_t nq, int n_cus)
+{
+    const double frac = (double)std::min(n_probe, n_lists) / (double)n_lists;
+    const int64_t expected = (int64_t)((double)n * frac) + 1;
+    const int64_t by_rows = (expected + 4095) / 4096;
+    const int64_t by_cus = std::max<int64_t>(1, n_cus / std::max<int64_t>(nq, 1));
+    return std::max<int64_t>(1, std::min(by_rows, by_cus));
+}
+
+constexpr size_t kListsScratchBytes = 512u << 20;   // plan + partial lists of one chunk of queries
+
+// Both list searches: argument checks in the order of adc_search, the plan kernel (the only reader of the offsets and
+// probes), the producer over a (G, queries) grid and one merge, per chunk of queries that fits the scratch lease.
+template <bool IP>
+int32_t adc_search_lists(pqhip_codebook* cb, int32_t slot, const float* d_tables, int64_t nq, const void* d_codes,
+                         int32_t code_bytes, int64_t n, int64_t c_rs, const int64_t* d_list_off, int64_t n_lists,
+                         const int64_t* d_probes, int32_t n_probe, int64_t p_rs, const float* d_scales, int32_t k,
+                         float* d_val, int64_t v_rs, int64_t* d_idx, int64_t i_rs, void* stream)
+{
+    if (!cb || nq < 0 || n < 0 || k < 1 || n_lists < 0 || n_probe < 1) return PQHIP_EINVAL;
+    if (slot < 0 || slot >= (int)cb->dev.size()) return PQHIP_ENODEV;
+    const int M = (int)cb->M, K = (int)cb->K;
+    const size_t table = (size_t)M * K * sizeof(float);
+    const int nvb = lists_nv_bucket((M + 3) / 4);
+    if (code_bytes != 1 || k > kSearchMaxK) return PQHIP_EUNSUPPORTED;
+    const int L = search_list_regs(k);
+    if (nvb == 0 || search_lds(table, 1, L) > 160 * 1024) return PQHIP_EUNSUPPORTED;   // the table must fit LDS beside the queues
+    if (n > (int64_t)0xfffffffell) return PQHIP_EUNSUPPORTED;                          // positions are offered as 32-bit values
+    const size_t plan_q = ((size_t)n_probe * 2 + 1) * sizeof(int64_t);
+    if (plan_q > kListsScratchBytes / 2) return PQHIP_EUNSUPPORTED;
+    if (nq == 0) return PQHIP_OK;
+    if (!d_val || !d_idx || !d_list_off || !d_probes || (n > 0 && (!d_tables || !d_codes))) return PQHIP_EINVAL;
+    if ((n > 0 && c_rs < cb->M) || v_rs < k || i_rs < k || p_rs < n_probe) return PQHIP_ESHAPE;
+    SET_DEVICE(cb->ctx->devs[slot]->ordinal);
+    hipStream_t st = (hipStream_t)stream;
+    if (n == 0 || n_lists == 0) {      // padding only
+        for (int64_t q = 0; q < nq; q += 65535) {
+            const int nqp = (int)std::min<int64_t>(nq - q, 65535);
+            PQCHK(launch_search_merge<IP>(L, nqp, 0, k, nullptr, nullptr, d_val + q * v_rs, v_rs, d_idx + q * i_rs, i_rs, st));
+            HIPCHK(hipGetLastError());
+        }
+        return PQHIP_OK;
+    }
+    ErrFlag ef(cb, slot, st);
+    const int64_t forced = cb->ctx->opt.adc_lists_wgs_per_query.load(std::memory_order_relaxed);
+    const int64_t G = forced > 0 ? std::min<int64_t>(forced, 4096)
+                                 : lists_wgs_per_query(n, n_lists, n_probe, std::min<int64_t>(nq, 65535), cb->ctx->devs[slot]->n_cus);
+    const size_t lists_q = (size_t)G * 64 * L * (sizeof(unsigned) + sizeof(uint64_t));
+    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>({nq, (int64_t)65535, (int64_t)(kListsScratchBytes / (plan_q + lists_q))}));
+    ScratchLease lease(cb, slot, st);
+    PQCHK(lease.acquire((size_t)chunk * (plan_q + lists_q)));
+    // 8-byte items first: part_i [chunk][G][64 L], seg_begin [chunk][n_probe], seg_cum [chunk][n_probe + 1]; then the keys
+    uint64_t* part_i = (uint64_t*)lease.ptr();
+    int64_t* seg_begin = (int64_t*)(part_i + (size_t)chunk * G * 64 * L);
+    int64_t* seg_cum = seg_begin + (size_t)chunk * n_probe;
+    unsigned* part_k = (unsigned*)(seg_cum + (size_t)chunk * ((size_t)n_probe + 1));
+    const size_t lds = search_lds(table, 1, L);
+    for (int64_t q = 0; q < nq; q += chunk) {
+        const unsigned nqc = (unsigned)std::min<int64_t>(chunk, nq - q);
+        hipLaunchKernelGGL(k_adc_lists_plan, dim3(nqc), dim3(1024), 0, st, d_list_off, n_lists, d_probes + q * p_rs, (int)n_probe,
+                           p_rs, n, seg_begin, seg_cum, ef.flag);
+        HIPCHK(hipGetLastError());
+        note_kernel("k_adc_lists_plan");
+        ListsLaunch a{n, c_rs, (unsigned)G, nqc, M, K, k, (int)n_probe, d_scales, seg_begin, seg_cum, part_k, part_i, ef.flag, st};
+        PQCHK((launch_lists_u8_l<IP>(L, nvb, a, (const uint8_t*)d_codes, d_tables + q * (int64_t)M * K, lds)));
+        HIPCHK(hipGetLastError());
+        PQCHK(launch_search_merge<IP>(L, (int)nqc, (int)G, k, part_k, part_i, d_val + q * v_rs, v_rs, d_idx + q * i_rs, i_rs, st));
+        HIPCHK(hipGetLastError());
+    }
+    return PQHIP_OK;
+}
+
 }  // namespace pqh
 
 using namespace pqh;
@@ -414,6 +546,25 @@ int32_t pqhip_adc_ip_search_f32_dev(pqhip_codebook* cb, int32_t slot, const floa
                                     float* d_score, int64_t s_rs, int64_t* d_idx, int64_t i_rs, void* stream)
 {
     return adc_search<true>(cb, slot, d_tables, nq, d_codes, code_bytes, n, c_rs, d_scales, k, d_score, s_rs, d_idx, i_rs, stream);
+}
+
+int32_t pqhip_adc_search_lists_f32_dev(pqhip_codebook* cb, int32_t slot, const float* d_tables, int64_t nq, const void* d_codes,
+                                       int32_t code_bytes, int64_t n, int64_t c_rs, const int64_t* d_list_off, int64_t n_lists,
+                                       const int64_t* d_probes, int32_t n_probe, int64_t p_rs, int32_t k, float* d_dist,
+                                       int64_t d_rs, int64_t* d_idx, int64_t i_rs, void* stream)
+{
+    return adc_search_lists<false>(cb, slot, d_tables, nq, d_codes, code_bytes, n, c_rs, d_list_off, n_lists, d_probes, n_probe,
+                                   p_rs, nullptr, k, d_dist, d_rs, d_idx, i_rs, stream);
+}
+
+int32_t pqhip_adc_ip_search_lists_f32_dev(pqhip_codebook* cb, int32_t slot, const float* d_tables, int64_t nq,
+                                          const void* d_codes, int32_t code_bytes, int64_t n, int64_t c_rs,
+                                          const int64_t* d_list_off, int64_t n_lists, const int64_t* d_probes, int32_t n_probe,
+                                          int64_t p_rs, const float* d_scales, int32_t k, float* d_score, int64_t s_rs,
+                                          int64_t* d_idx, int64_t i_rs, void* stream)
+{
+    return adc_search_lists<true>(cb, slot, d_tables, nq, d_codes, code_bytes, n, c_rs, d_list_off, n_lists, d_probes, n_probe,
+                                  p_rs, d_scales, k, d_score, s_rs, d_idx, i_rs, stream);
 }
 
 }  // extern "C"

@@ -979,3 +979,70 @@ class Pq:
             if rc != _lib.OK:
                 raise _lib.PqHipError(rc, "pqhip_check_codes_dev")
         return (score[0], idx[0]) if single else (score, idx)
+
+    # ---- ADC search over a partitioned code matrix: exact top-k within the probed lists -----------------------------
+    def _adc_search_lists(self, ip, codes, tables, list_off, probes, k, scales, stream, check):
+        import torch
+        name = "pqhip_adc_ip_search_lists_f32_dev" if ip else "pqhip_adc_search_lists_f32_dev"
+        assert codes.is_cuda and codes.dtype == torch.uint8 and codes.dim() == 2
+        assert tables.is_cuda and tables.dtype == torch.float32 and tables.is_contiguous()
+        assert list_off.is_cuda and list_off.dtype == torch.int64 and list_off.dim() == 1 and list_off.is_contiguous()
+        assert probes.is_cuda and probes.dtype == torch.int64 and probes.dim() in (1, 2)
+        M, K = self.quantized_len(), self.n_quantizer_centroids()
+        if codes.shape[1] != M:
+            raise PanicError("Quantization length does not match number of subquantizers")
+        single = tables.dim() == 2
+        if tuple(tables.shape[-2:]) != (M, K):
+            raise PanicError("lookup tables must be [.., %d, %d]" % (M, K))
+        nq = 1 if single else tables.shape[0]
+        pr = probes[None] if probes.dim() == 1 else probes
+        if pr.shape[0] != nq or pr.shape[1] < 1 or list_off.shape[0] < 1:
+            raise PanicError("one probe row of at least one list id per query and n_lists + 1 offsets expected")
+        if pr.stride(1) != 1:
+            pr = pr.contiguous()
+        if codes.stride(1) != 1:
+            codes = codes.contiguous()
+        n = codes.shape[0]
+        if scales is not None:
+            assert scales.is_cuda and scales.dtype == torch.float32 and scales.is_contiguous()
+            if tuple(scales.shape) != (n,):
+                raise PanicError("scales must hold one value per code row")
+        val = torch.empty((nq, k), dtype=torch.float32, device=codes.device)
+        idx = torch.empty((nq, k), dtype=torch.int64, device=codes.device)
+        cb = self._cb()
+        if stream is None:
+            stream = torch.cuda.current_stream(codes.device).cuda_stream
+        slot = self._slot_for(codes)
+        n_probe = pr.shape[1]
+        head = (cb, slot, tables.data_ptr(), nq, codes.data_ptr(), codes.element_size(), n,
+                codes.stride(0) if n > 1 else max(codes.stride(0), M), list_off.data_ptr(), list_off.shape[0] - 1,
+                pr.data_ptr(), n_probe, pr.stride(0) if nq > 1 else max(pr.stride(0), n_probe))
+        tail = (k, val.data_ptr(), k, idx.data_ptr(), k, ctypes.c_void_p(stream))
+        if ip:
+            rc = _lib.lib().pqhip_adc_ip_search_lists_f32_dev(*head, scales.data_ptr() if scales is not None else None, *tail)
+        else:
+            rc = _lib.lib().pqhip_adc_search_lists_f32_dev(*head, *tail)
+        if rc != _lib.OK:
+            raise _lib.PqHipError(rc, name)
+        if check:
+            rc = _lib.lib().pqhip_check_codes_dev(cb, slot, ctypes.c_void_p(stream))
+            if rc == _lib.ECODE_RANGE:
+                raise PanicError("ndarray: index out of bounds")
+            if rc != _lib.OK:
+                raise _lib.PqHipError(rc, "pqhip_check_codes_dev")
+        return (val[0], idx[0]) if single else (val, idx)
+
+    def adc_search_lists_device(self, codes, tables, list_off, probes, k, stream=None, check=False):
+        """adc_search_device restricted, per query, to the rows of the probed lists: list l is rows
+        [list_off[l], list_off[l + 1]) of codes (CUDA uint8 [n, M]); list_off CUDA int64 [n_lists + 1]; probes CUDA int64
+        [nq, n_probe] ([n_probe] for 2-D tables) of list ids, -1 = padding -> (dist, idx) [nq, k] ([k]).  The result is
+        what adc_search_device returns on codes with every row outside the probed lists removed, idx being positions in
+        codes (pqhip_adc_search_lists_f32_dev).  Past the last probed row: index -1, distance +Inf.  check=True also
+        reports a list id or an offset out of range."""
+        return self._adc_search_lists(False, codes, tables, list_off, probes, k, None, stream, check)
+
+    def adc_ip_search_lists_device(self, codes, tables, list_off, probes, k, scales=None, stream=None, check=False):
+        """adc_ip_search_device restricted, per query, to the rows of the probed lists (arguments as for
+        adc_search_lists_device, tables from adc_ip_tables_device, scales None or CUDA float32 [n]) -> (score, idx).
+        Past the last probed row: index -1, score -Inf (pqhip_adc_ip_search_lists_f32_dev)."""
+        return self._adc_search_lists(True, codes, tables, list_off, probes, k, scales, stream, check)

@@ -149,6 +149,146 @@ class QuantizedMatrix:
         scales = self.norms if use_norms else None
         return self.pq.adc_ip_search_device(self.codes, self.pq.adc_ip_tables_device(queries), k, scales=scales)
 
+    def partition(self, n_lists, n_iterations=10, vectors=None, train_rows=None, rng=None):
+        """Partition the rows with a coarse k-means quantizer of n_lists centroids -> PartitionedMatrix (IVFADC without
+        residual encoding: the codes stay the codes of the vectors themselves).
+
+        The coarse quantizer is trained on `vectors` ([N, d] float32, numpy or CUDA, row i belonging to code row i) if
+        given, else on the reconstructions of the stored codes (reconstruct_batch_device, without the norms), so a
+        matrix loaded from a storage chunk can be partitioned without the original embeddings.  train_rows: train on
+        that many distinct rows drawn with `rng` instead of all of them (every row is assigned either way).  Initial
+        centroids are n_lists distinct training rows drawn with the numpy Generator `rng`, as train_pq draws them;
+        training is kmeans_iterations with one subquantizer, assignment is cluster_assignments.  Both take the slow
+        anchor kernel for sub-vectors wider than 256 floats: accepted for a build step.  1 <= n_lists <= 16384 (the
+        k-means limit) and n_lists <= number of training rows."""
+        import torch
+        from .pq import ReductiveError, cluster_assignments, kmeans_iterations
+        N, d = len(self), self.pq.reconstructed_len()
+        if not 1 <= n_lists <= 16384:
+            raise ReductiveError("The number of lists must be between 1 and 16384, was %d" % n_lists)
+        rng = rng or np.random.default_rng(0)
+        chunk = 1 << 20
+
+        def rows_of(sel):
+            """float32 [len(sel), d] on the device: the given vectors or the reconstructions of the code rows `sel`"""
+            if vectors is None:
+                if not isinstance(sel, slice):
+                    sel = torch.as_tensor(sel, dtype=torch.int64, device=self.codes.device)
+                return self.pq.reconstruct_batch_device(self.codes[sel])
+            v = vectors[sel]
+            if not hasattr(v, "is_cuda"):
+                v = torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32))
+            return v.to(self.codes.device, torch.float32).contiguous()
+
+        if vectors is not None and tuple(vectors.shape) != (N, d):
+            raise PanicError("vectors must be [%d, %d]" % (N, d))
+        n_train = N if train_rows is None else min(int(train_rows), N)
+        if n_lists > n_train:
+            raise ReductiveError("The number of lists (%d) exceeds the number of training rows (%d)" % (n_lists, n_train))
+        train_sel = slice(0, N) if n_train == N else np.sort(rng.choice(N, n_train, replace=False))
+        train = rows_of(train_sel)
+        init = train[torch.as_tensor(rng.choice(n_train, n_lists, replace=False), device=train.device)].cpu().numpy()
+        centroids, _ = kmeans_iterations(init[None], train, n_iterations, want_loss=False, ctx=self.pq._ctx)
+        centroids = np.ascontiguousarray(centroids[0])
+        del train
+        assign = np.empty(N, np.int64)
+        for r0 in range(0, N, chunk):
+            r1 = min(N, r0 + chunk)
+            assign[r0:r1] = cluster_assignments(centroids, rows_of(slice(r0, r1)).cpu().numpy(), ctx=self.pq._ctx)
+        return PartitionedMatrix(self, centroids, assign)
+
+
+def ivf_layout(assign, n_lists):
+    """assign [N] list id per row -> (perm, list_off): perm = the stable argsort of the assignments, so list l is
+    positions [list_off[l], list_off[l + 1]) of the permuted rows and positions inside a list ascend in original row
+    number; list_off [n_lists + 1] = prefix sums of the list sizes (empty lists are legal).  Pure numpy."""
+    a = np.asarray(assign)
+    if a.ndim != 1 or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError("assign must be a vector of integer list ids")
+    if n_lists < 0 or (a.size and (int(a.min()) < 0 or int(a.max()) >= n_lists)):
+        raise ValueError("list ids must lie in [0, %d)" % n_lists)
+    perm = np.argsort(a, kind="stable").astype(np.int64)
+    list_off = np.zeros(n_lists + 1, np.int64)
+    np.cumsum(np.bincount(a.astype(np.int64), minlength=n_lists), out=list_off[1:])
+    return perm, list_off
+
+
+class PartitionedMatrix:
+    """A QuantizedMatrix whose rows are grouped by a coarse quantizer: list l holds the rows nearest to centroid l,
+    stored contiguously, and a search reads only the `nprobe` lists nearest to the query.  The codes are those of the
+    vectors themselves, so a search is the exhaustive search restricted to the rows of the probed lists, bit for bit;
+    with nprobe = n_lists it is the exhaustive search.  Row numbers given and returned are those of the matrix it was
+    built from.
+
+    centroids [n_lists, d] float32 (host); list_off [n_lists + 1] and ids [N] int64 on the device (ids[p] = original row
+    of position p); codes / norms in list order."""
+
+    def __init__(self, qm, centroids, assign):
+        import torch
+        dev = qm.codes.device
+        self.pq = qm.pq
+        self.centroids = np.ascontiguousarray(centroids, dtype=np.float32)
+        self.n_lists = self.centroids.shape[0]
+        perm, list_off = ivf_layout(assign, self.n_lists)
+        if perm.size != len(qm):
+            raise PanicError("one list id per row expected")
+        self.ids = torch.from_numpy(perm).to(dev)
+        self.list_off = torch.from_numpy(list_off).to(dev)
+        self.positions = torch.empty_like(self.ids)
+        self.positions[self.ids] = torch.arange(perm.size, dtype=torch.int64, device=dev)
+        self.codes = qm.codes[self.ids].contiguous()
+        self.norms = None if qm.norms is None else qm.norms[self.ids].contiguous()
+        # the coarse quantizer as a codebook of one subquantizer: its distance tables order the lists
+        self.coarse = Pq(None, self.centroids[None], ctx=self.pq._ctx)
+        self._list_ids = torch.arange(self.n_lists, dtype=torch.int32, device=dev)[:, None].contiguous()
+
+    def __len__(self):
+        return self.codes.shape[0]
+
+    def probes(self, queries, nprobe):
+        """list ids [nq, nprobe] int64 ([nprobe] for one query): the nprobe first lists in the order (key(dist), list
+        id), dist the squared distance of the query to the coarse centroids as adc_tables_device of the one-subquantizer
+        codebook defines it, key the first-minimum order (NaN last).  nprobe is cut to n_lists; beyond 1,024 only
+        nprobe >= n_lists is served, by all list ids in ascending order (every list is read, no selection needed)."""
+        import torch
+        nprobe = min(int(nprobe), self.n_lists)
+        if nprobe < 1:
+            raise PanicError("nprobe must be at least 1")
+        single = queries.dim() == 1
+        if nprobe > 1024:
+            if nprobe < self.n_lists:
+                raise PanicError("more than 1024 probes are served only as all %d lists" % self.n_lists)
+            nq = 1 if single else queries.shape[0]
+            pr = torch.arange(self.n_lists, dtype=torch.int64, device=self.codes.device)
+            return pr if single else pr[None].expand(nq, -1).contiguous()
+        return self.coarse.adc_search_device(self._list_ids, self.coarse.adc_tables_device(queries), nprobe)[1]
+
+    def _original_rows(self, pos):
+        import torch
+        return torch.where(pos < 0, pos, self.ids[pos.clamp(min=0)])
+
+    def nearest(self, queries, k, nprobe):
+        """the k rows of smallest asymmetric squared distance among the rows of the nprobe nearest lists, ties to the
+        smaller position in list order -> (dist, idx) [k] or [nq, k]; idx are original row numbers, -1 past the last
+        probed row (distance +Inf)."""
+        d, pos = self.pq.adc_search_lists_device(self.codes, self.pq.adc_tables_device(queries), self.list_off,
+                                                 self.probes(queries, nprobe), k)
+        return d, self._original_rows(pos)
+
+    def most_similar(self, queries, k, nprobe, use_norms=True):
+        """QuantizedMatrix.most_similar among the rows of the nprobe nearest lists -> (score, idx), idx original row
+        numbers, -1 past the last probed row (score -Inf)."""
+        scales = self.norms if use_norms else None
+        s, pos = self.pq.adc_ip_search_lists_device(self.codes, self.pq.adc_ip_tables_device(queries), self.list_off,
+                                                    self.probes(queries, nprobe), k, scales=scales)
+        return s, self._original_rows(pos)
+
+    def embeddings(self, rows, out=None):
+        """QuantizedMatrix.embeddings of the original row numbers `rows`."""
+        import torch
+        rows = torch.as_tensor(rows, dtype=torch.int64, device=self.codes.device)
+        return self.pq.reconstruct_rows_device(self.codes, self.positions[rows], scales=self.norms, out=out)
+
 
 def dumps(pq, codes, norms=None):
     b = io.BytesIO()

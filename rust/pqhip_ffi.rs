@@ -59,6 +59,17 @@ extern "C" {
     pub fn pqhip_opq_train_step_f32_dev(ctx: *mut pqhip_ctx, device_slot: i32, quantizers: *mut f32,
         n_subquantizers: i64, n_centroids: i64, sub_dim: i64, projection: *const f32, d_x: *const f32,
         n_rows: i64, x_row_stride: i64, cross: *mut f32, stream: *mut c_void) -> i32;
+    // ADC search over a partitioned code matrix (declarations only: device pointers come from the caller's allocator)
+    pub fn pqhip_adc_search_lists_f32_dev(cb: *mut pqhip_codebook, device_slot: i32, d_tables: *const f32,
+        n_queries: i64, d_codes: *const c_void, code_bytes: i32, n_codes: i64, codes_row_stride: i64,
+        d_list_off: *const i64, n_lists: i64, d_probes: *const i64, n_probe: i32, probes_row_stride: i64,
+        k: i32, d_dist: *mut f32, dist_row_stride: i64, d_idx: *mut i64, idx_row_stride: i64,
+        stream: *mut c_void) -> i32;
+    pub fn pqhip_adc_ip_search_lists_f32_dev(cb: *mut pqhip_codebook, device_slot: i32, d_tables: *const f32,
+        n_queries: i64, d_codes: *const c_void, code_bytes: i32, n_codes: i64, codes_row_stride: i64,
+        d_list_off: *const i64, n_lists: i64, d_probes: *const i64, n_probe: i32, probes_row_stride: i64,
+        d_scales: *const f32, k: i32, d_score: *mut f32, score_row_stride: i64, d_idx: *mut i64,
+        idx_row_stride: i64, stream: *mut c_void) -> i32;
 }
 
 /// Batches smaller than this stay on the CPU path (a launch + PCIe round trip is pointless).
