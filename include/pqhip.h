@@ -256,6 +256,48 @@ int32_t pqhip_adc_ip_search_lists_f32_dev(pqhip_codebook *cb, int32_t device_slo
                                           const float *d_scales, int32_t k, float *d_score, int64_t score_row_stride,
                                           int64_t *d_idx, int64_t idx_row_stride, void *stream);
 
+/*
+ * ADC search over a partitioned matrix of RESIDUAL codes (IVFADC with residual encoding): row i of list l stores the
+ * code of x_i - c_l, c_l the coarse centroid of the list, and cb is the quantizer of those residuals.  With r^_i the
+ * reconstruction of the row's code (inverse rotation included for an OPQ quantizer),
+ *   |q - c_l - r^_i|^2 = |q - c_l|^2 + (|r^_i|^2 + 2 <c_l, r^_i>) - 2 <q, r^_i>      <q, c_l + r^_i> = <q, c_l> + <q, r^_i>
+ * so one table per query serves every list: d_tables are the INNER-PRODUCT tables of the query in both calls
+ * (pqhip_adc_ip_tables_f32_dev of the residual quantizer), the first term is the probe bias d_probe_bias
+ * [n_queries][bias_row_stride] f32, one value per (query, probe slot), and the middle term is the row term d_row_terms
+ * [n_codes] f32, query-free, laid out in row order as the scales are.  The caller computes both; the library does not
+ * interpret them.  The values, as definition -- every operation one rounded f32 operation, no contraction; s is the
+ * scan's sequential row sum over m from +0 of d_tables[q][m][codes[i][m]], p the probe slot through which row i is
+ * reached:
+ *   dist  = fl( fl(bias[q][p] + term[i]) - fl(s + s) )          ordered by (key(dist), position)
+ *   score = fl( fl(bias[q][p] + s) * scale[i] )                 ordered by (key(-score), position)
+ *           without d_scales (NULL): score = fl(bias[q][p] + s)
+ * Row q of the outputs receives the first min(k, |S_q|) rows of S_q under that strict order, with S_q, key, position,
+ * the canonical NaN, the similarity zero as +0 (a zero distance likewise comes back as +0: the key does not keep its
+ * sign), the padding with -1 and +Inf / -Inf, the treatment of -1 probes, bad ids, clamped and inverted ranges and
+ * codes >= K, the independence from the number of workgroups per query (option "adc_lists_wgs_per_query"), scratch and
+ * query chunking all as pqhip_adc_search_lists_f32_dev / pqhip_adc_ip_search_lists_f32_dev define them.  The bias of a
+ * skipped probe (-1, a bad id, an empty or emptied range) is never read into a result.
+ * Arguments, checks, status codes and precedence are those of pqhip_adc_ip_search_lists_f32_dev, plus: d_probe_bias ==
+ * NULL with n_queries > 0, or d_row_terms == NULL with n_queries > 0 in the distance call: PQHIP_EINVAL;
+ * bias_row_stride < n_probe: PQHIP_ESHAPE.
+ */
+int32_t pqhip_adc_search_lists_residual_f32_dev(pqhip_codebook *cb, int32_t device_slot, const float *d_tables,
+                                                int64_t n_queries, const void *d_codes, int32_t code_bytes,
+                                                int64_t n_codes, int64_t codes_row_stride,
+                                                const int64_t *d_list_off, int64_t n_lists,
+                                                const int64_t *d_probes, int32_t n_probe, int64_t probes_row_stride,
+                                                const float *d_probe_bias, int64_t bias_row_stride,
+                                                const float *d_row_terms, int32_t k, float *d_dist, int64_t dist_row_stride,
+                                                int64_t *d_idx, int64_t idx_row_stride, void *stream);
+int32_t pqhip_adc_ip_search_lists_residual_f32_dev(pqhip_codebook *cb, int32_t device_slot, const float *d_tables,
+                                                   int64_t n_queries, const void *d_codes, int32_t code_bytes,
+                                                   int64_t n_codes, int64_t codes_row_stride,
+                                                   const int64_t *d_list_off, int64_t n_lists,
+                                                   const int64_t *d_probes, int32_t n_probe, int64_t probes_row_stride,
+                                                   const float *d_probe_bias, int64_t bias_row_stride,
+                                                   const float *d_scales, int32_t k, float *d_score, int64_t score_row_stride,
+                                                   int64_t *d_idx, int64_t idx_row_stride, void *stream);
+
 /* Reconstruct's range check is asynchronous on the device path: returns PQHIP_ECODE_RANGE if any
  * device call since the last query saw a code >= K (synchronises `stream`). */
 int32_t pqhip_check_codes_dev(pqhip_codebook *cb, int32_t device_slot, void *stream);

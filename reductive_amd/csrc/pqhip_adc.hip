@@ -5,6 +5,7 @@
 #include "kernels_adc.hip.h"
 #include "kernels_adc_search.hip.h"
 #include "kernels_adc_search_lists.hip.h"
+#include "kernels_adc_search_lists_residual.hip.h"
 
 using namespace pqhip;
 
@@ -326,7 +327,9 @@ struct ListsLaunch {
     int64_t n, c_rs;
     unsigned G, nq;          // grid (G, nq)
     int M, K, k, n_probe;
-    const float* scales;
+    const float* scales;     // residual distance search: the row terms
+    const float* bias;       // residual searches: probe bias rows of the launch's queries, else null
+    int64_t b_rs;
     const int64_t *seg_begin, *seg_cum;
     unsigned* part_k;
     uint64_t* part_i;
@@ -345,6 +348,13 @@ inline int lists_nv_bucket(int nv)
 template <bool IP, int NV, int L>
 int32_t launch_lists_u8(const ListsLaunch& a, const uint8_t* codes, const float* lut, size_t lds)
 {
+    if (a.bias) {   // the residual producer
+        HIPCHK(hipFuncSetAttribute((const void*)k_adc_search_lists_residual_u8<IP, NV, L>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        hipLaunchKernelGGL((k_adc_search_lists_residual_u8<IP, NV, L>), dim3(a.G, a.nq), dim3(1024), lds, a.st, codes, a.n, a.c_rs, lut,
+                           a.bias, a.b_rs, a.scales, a.M, a.K, a.k, a.seg_begin, a.seg_cum, a.n_probe, a.part_k, a.part_i, a.err);
+        note_kernel(IP ? "k_adc_ip_search_lists_residual_u8" : "k_adc_search_lists_residual_u8");
+        return PQHIP_OK;
+    }
     HIPCHK(hipFuncSetAttribute((const void*)k_adc_search_lists_u8<IP, NV, L>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     hipLaunchKernelGGL((k_adc_search_lists_u8<IP, NV, L>), dim3(a.G, a.nq), dim3(1024), lds, a.st, codes, a.n, a.c_rs, lut,
                        a.scales, a.M, a.K, a.k, a.seg_begin, a.seg_cum, a.n_probe, a.part_k, a.part_i, a.err);
@@ -391,13 +401,22 @@ inline int64_t lists_wgs_per_query(int64_t n, int64_t n_lists, int64_t n_probe, 
 
 constexpr size_t kListsScratchBytes = 512u << 20;   // plan + partial lists of one chunk of queries
 
-// Both list searches: argument checks in the order of adc_search, the plan kernel (the only reader of the offsets and
+// Inputs of the residual searches beside those of the plain ones: bias [nq][b_rs] f32, one value per (query, probe
+// slot), and for the distance the row terms [n] f32 (they travel in the place of the scales).
+struct ListsResidual {
+    const float* bias;
+    int64_t b_rs;
+};
+
+// All list searches: argument checks in the order of adc_search, the plan kernel (the only reader of the offsets and
 // probes), the producer over a (G, queries) grid and one merge, per chunk of queries that fits the scratch lease.
+// res != null: the residual producer; d_scales then holds the row terms of the distance search (required).
 template <bool IP>
 int32_t adc_search_lists(pqhip_codebook* cb, int32_t slot, const float* d_tables, int64_t nq, const void* d_codes,
                          int32_t code_bytes, int64_t n, int64_t c_rs, const int64_t* d_list_off, int64_t n_lists,
                          const int64_t* d_probes, int32_t n_probe, int64_t p_rs, const float* d_scales, int32_t k,
-                         float* d_val, int64_t v_rs, int64_t* d_idx, int64_t i_rs, void* stream)
+                         float* d_val, int64_t v_rs, int64_t* d_idx, int64_t i_rs, void* stream,
+                         const ListsResidual* res = nullptr)
 {
     if (!cb || nq < 0 || n < 0 || k < 1 || n_lists < 0 || n_probe < 1) return PQHIP_EINVAL;
     if (slot < 0 || slot >= (int)cb->dev.size()) return PQHIP_ENODEV;
@@ -412,7 +431,9 @@ int32_t adc_search_lists(pqhip_codebook* cb, int32_t slot, const float* d_tables
     if (plan_q > kListsScratchBytes / 2) return PQHIP_EUNSUPPORTED;
     if (nq == 0) return PQHIP_OK;
     if (!d_val || !d_idx || !d_list_off || !d_probes || (n > 0 && (!d_tables || !d_codes))) return PQHIP_EINVAL;
+    if (res && (!res->bias || (!IP && !d_scales))) return PQHIP_EINVAL;
     if ((n > 0 && c_rs < cb->M) || v_rs < k || i_rs < k || p_rs < n_probe) return PQHIP_ESHAPE;
+    if (res && res->b_rs < n_probe) return PQHIP_ESHAPE;
     SET_DEVICE(cb->ctx->devs[slot]->ordinal);
     hipStream_t st = (hipStream_t)stream;
     if (n == 0 || n_lists == 0) {      // padding only
@@ -443,7 +464,8 @@ int32_t adc_search_lists(pqhip_codebook* cb, int32_t slot, const float* d_tables
                            p_rs, n, seg_begin, seg_cum, ef.flag);
         HIPCHK(hipGetLastError());
         note_kernel("k_adc_lists_plan");
-        ListsLaunch a{n, c_rs, (unsigned)G, nqc, M, K, k, (int)n_probe, d_scales, seg_begin, seg_cum, part_k, part_i, ef.flag, st};
+        ListsLaunch a{n, c_rs, (unsigned)G, nqc, M, K, k, (int)n_probe, d_scales, res ? res->bias + q * res->b_rs : nullptr,
+                      res ? res->b_rs : 0, seg_begin, seg_cum, part_k, part_i, ef.flag, st};
         PQCHK((launch_lists_u8_l<IP>(L, nvb, a, (const uint8_t*)d_codes, d_tables + q * (int64_t)M * K, lds)));
         HIPCHK(hipGetLastError());
         PQCHK(launch_search_merge<IP>(L, (int)nqc, (int)G, k, part_k, part_i, d_val + q * v_rs, v_rs, d_idx + q * i_rs, i_rs, st));
@@ -565,6 +587,30 @@ int32_t pqhip_adc_ip_search_lists_f32_dev(pqhip_codebook* cb, int32_t slot, cons
 {
     return adc_search_lists<true>(cb, slot, d_tables, nq, d_codes, code_bytes, n, c_rs, d_list_off, n_lists, d_probes, n_probe,
                                   p_rs, d_scales, k, d_score, s_rs, d_idx, i_rs, stream);
+}
+
+int32_t pqhip_adc_search_lists_residual_f32_dev(pqhip_codebook* cb, int32_t slot, const float* d_tables, int64_t nq,
+                                                const void* d_codes, int32_t code_bytes, int64_t n, int64_t c_rs,
+                                                const int64_t* d_list_off, int64_t n_lists, const int64_t* d_probes,
+                                                int32_t n_probe, int64_t p_rs, const float* d_probe_bias, int64_t b_rs,
+                                                const float* d_row_terms, int32_t k, float* d_dist, int64_t d_rs,
+                                                int64_t* d_idx, int64_t i_rs, void* stream)
+{
+    const ListsResidual res{d_probe_bias, b_rs};
+    return adc_search_lists<false>(cb, slot, d_tables, nq, d_codes, code_bytes, n, c_rs, d_list_off, n_lists, d_probes, n_probe,
+                                   p_rs, d_row_terms, k, d_dist, d_rs, d_idx, i_rs, stream, &res);
+}
+
+int32_t pqhip_adc_ip_search_lists_residual_f32_dev(pqhip_codebook* cb, int32_t slot, const float* d_tables, int64_t nq,
+                                                   const void* d_codes, int32_t code_bytes, int64_t n, int64_t c_rs,
+                                                   const int64_t* d_list_off, int64_t n_lists, const int64_t* d_probes,
+                                                   int32_t n_probe, int64_t p_rs, const float* d_probe_bias, int64_t b_rs,
+                                                   const float* d_scales, int32_t k, float* d_score, int64_t s_rs,
+                                                   int64_t* d_idx, int64_t i_rs, void* stream)
+{
+    const ListsResidual res{d_probe_bias, b_rs};
+    return adc_search_lists<true>(cb, slot, d_tables, nq, d_codes, code_bytes, n, c_rs, d_list_off, n_lists, d_probes, n_probe,
+                                  p_rs, d_scales, k, d_score, s_rs, d_idx, i_rs, stream, &res);
 }
 
 }  // extern "C"

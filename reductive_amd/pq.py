@@ -981,9 +981,12 @@ class Pq:
         return (score[0], idx[0]) if single else (score, idx)
 
     # ---- ADC search over a partitioned code matrix: exact top-k within the probed lists -----------------------------
-    def _adc_search_lists(self, ip, codes, tables, list_off, probes, k, scales, stream, check):
+    def _adc_search_lists(self, ip, codes, tables, list_off, probes, k, scales, stream, check, probe_bias=None,
+                          row_terms=None):
+        """All four list searches; probe_bias given: the residual ones (row_terms then required for the distance)."""
         import torch
-        name = "pqhip_adc_ip_search_lists_f32_dev" if ip else "pqhip_adc_search_lists_f32_dev"
+        residual = probe_bias is not None
+        name = "pqhip_adc_%ssearch_lists_%sf32_dev" % ("ip_" if ip else "", "residual_" if residual else "")
         assert codes.is_cuda and codes.dtype == torch.uint8 and codes.dim() == 2
         assert tables.is_cuda and tables.dtype == torch.float32 and tables.is_contiguous()
         assert list_off.is_cuda and list_off.dtype == torch.int64 and list_off.dim() == 1 and list_off.is_contiguous()
@@ -1007,18 +1010,38 @@ class Pq:
             assert scales.is_cuda and scales.dtype == torch.float32 and scales.is_contiguous()
             if tuple(scales.shape) != (n,):
                 raise PanicError("scales must hold one value per code row")
+        n_probe = pr.shape[1]
+        if residual:
+            assert probe_bias.is_cuda and probe_bias.dtype == torch.float32 and probe_bias.dim() in (1, 2)
+            pb = probe_bias[None] if probe_bias.dim() == 1 else probe_bias
+            if tuple(pb.shape) != (nq, n_probe):
+                raise PanicError("one probe bias per query and probe slot expected")
+            if pb.stride(1) != 1:
+                pb = pb.contiguous()
+            if not ip:
+                assert row_terms.is_cuda and row_terms.dtype == torch.float32 and row_terms.is_contiguous()
+                if tuple(row_terms.shape) != (n,):
+                    raise PanicError("row_terms must hold one value per code row")
         val = torch.empty((nq, k), dtype=torch.float32, device=codes.device)
         idx = torch.empty((nq, k), dtype=torch.int64, device=codes.device)
         cb = self._cb()
         if stream is None:
             stream = torch.cuda.current_stream(codes.device).cuda_stream
         slot = self._slot_for(codes)
-        n_probe = pr.shape[1]
         head = (cb, slot, tables.data_ptr(), nq, codes.data_ptr(), codes.element_size(), n,
                 codes.stride(0) if n > 1 else max(codes.stride(0), M), list_off.data_ptr(), list_off.shape[0] - 1,
                 pr.data_ptr(), n_probe, pr.stride(0) if nq > 1 else max(pr.stride(0), n_probe))
         tail = (k, val.data_ptr(), k, idx.data_ptr(), k, ctypes.c_void_p(stream))
-        if ip:
+        if residual:
+            head += (pb.data_ptr(), pb.stride(0) if nq > 1 else max(pb.stride(0), n_probe))
+            if ip:
+                rc = _lib.lib().pqhip_adc_ip_search_lists_residual_f32_dev(
+                    *head, scales.data_ptr() if scales is not None else None, *tail)
+            else:
+                # an empty tensor may have no address, and the C call wants one even when there is no row to read
+                rt = row_terms if n > 0 else torch.zeros(1, dtype=torch.float32, device=codes.device)
+                rc = _lib.lib().pqhip_adc_search_lists_residual_f32_dev(*head, rt.data_ptr(), *tail)
+        elif ip:
             rc = _lib.lib().pqhip_adc_ip_search_lists_f32_dev(*head, scales.data_ptr() if scales is not None else None, *tail)
         else:
             rc = _lib.lib().pqhip_adc_search_lists_f32_dev(*head, *tail)
@@ -1046,3 +1069,26 @@ class Pq:
         adc_search_lists_device, tables from adc_ip_tables_device, scales None or CUDA float32 [n]) -> (score, idx).
         Past the last probed row: index -1, score -Inf (pqhip_adc_ip_search_lists_f32_dev)."""
         return self._adc_search_lists(True, codes, tables, list_off, probes, k, scales, stream, check)
+
+    # ---- the same over residual codes (IVFADC with residual encoding): one table per query, a bias per probe ---------
+    def adc_search_lists_residual_device(self, codes, ip_tables, list_off, probes, probe_bias, row_terms, k, stream=None,
+                                         check=False):
+        """adc_search_lists_device over residual codes: self is the quantizer of the residuals x - c_list(x), ip_tables
+        are its INNER-PRODUCT tables (adc_ip_tables_device), probe_bias CUDA float32 [nq, n_probe] ([n_probe] for one
+        query) holds |q - c_l|^2 of the list in each probe slot and row_terms CUDA float32 [n] holds |r^|^2 + 2 <c_l, r^>
+        of each row -> (dist, idx) with dist = fl(fl(bias + term) - fl(s + s)), s the scan's row sum, ordered by
+        (key(dist), position) (pqhip_adc_search_lists_residual_f32_dev).  The bias of a skipped probe is never used."""
+        if probe_bias is None or row_terms is None:
+            raise PanicError("the residual distance search needs a probe bias and the row terms")
+        return self._adc_search_lists(False, codes, ip_tables, list_off, probes, k, None, stream, check,
+                                      probe_bias=probe_bias, row_terms=row_terms)
+
+    def adc_ip_search_lists_residual_device(self, codes, ip_tables, list_off, probes, probe_bias, k, scales=None,
+                                            stream=None, check=False):
+        """adc_ip_search_lists_device over residual codes: probe_bias holds <q, c_l> of the list in each probe slot ->
+        (score, idx) with score = fl(fl(bias + s) * scale), fl(bias + s) without scales, ordered by (key(-score),
+        position) (pqhip_adc_ip_search_lists_residual_f32_dev)."""
+        if probe_bias is None:
+            raise PanicError("the residual similarity search needs a probe bias")
+        return self._adc_search_lists(True, codes, ip_tables, list_off, probes, k, scales, stream, check,
+                                      probe_bias=probe_bias)

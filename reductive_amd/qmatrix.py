@@ -161,12 +161,20 @@ class QuantizedMatrix:
         training is kmeans_iterations with one subquantizer, assignment is cluster_assignments.  Both take the slow
         anchor kernel for sub-vectors wider than 256 floats: accepted for a build step.  1 <= n_lists <= 16384 (the
         k-means limit) and n_lists <= number of training rows."""
+        rng = rng or np.random.default_rng(0)
+        centroids, assign, _, _ = self._coarse_partition(n_lists, n_iterations, vectors, train_rows, rng)
+        return PartitionedMatrix(self, centroids, assign)
+
+    def _coarse_partition(self, n_lists, n_iterations, vectors, train_rows, rng):
+        """The part partition() and partition_residual() share: trains the coarse quantizer and assigns every row ->
+        (centroids [n_lists, d] f32, assign [N] int64, rows_of, train_sel): rows_of(sel) gives the float32 device rows
+        the partition is built from, train_sel the training rows (a slice or sorted row numbers).  Draws from rng:
+        the training rows (if fewer than all), then the initial centroids."""
         import torch
         from .pq import ReductiveError, cluster_assignments, kmeans_iterations
         N, d = len(self), self.pq.reconstructed_len()
         if not 1 <= n_lists <= 16384:
             raise ReductiveError("The number of lists must be between 1 and 16384, was %d" % n_lists)
-        rng = rng or np.random.default_rng(0)
         chunk = 1 << 20
 
         def rows_of(sel):
@@ -195,7 +203,52 @@ class QuantizedMatrix:
         for r0 in range(0, N, chunk):
             r1 = min(N, r0 + chunk)
             assign[r0:r1] = cluster_assignments(centroids, rows_of(slice(r0, r1)).cpu().numpy(), ctx=self.pq._ctx)
-        return PartitionedMatrix(self, centroids, assign)
+        return centroids, assign, rows_of, train_sel
+
+    def partition_residual(self, n_lists, n_subquantizers=None, n_subquantizer_bits=None, n_iterations=10,
+                           pq_iterations=10, n_attempts=1, vectors=None, train_rows=None, residual_pq=None, rng=None):
+        """Partition the rows as partition() does (the same coarse training, the same draws from `rng`, the same
+        assignment) and re-encode them as residuals -> ResidualPartitionedMatrix (IVFADC with residual encoding).
+
+        Row i of list l is stored as the code of vectors[i] - centroids[l], formed on the device in f32; `vectors`
+        defaults to the reconstructions of the stored codes, as in partition().  The residual quantizer is trained with
+        train_pq (pq_iterations, n_attempts, draws from `rng` after the coarse ones) on the residuals of the training
+        rows; n_subquantizers and n_subquantizer_bits default to those of self.pq (at most 8 bits: the list searches
+        read 1-byte codes); a given `residual_pq` (a Pq of the same width, OPQ allowed) skips the training.  All
+        residuals are encoded with quantize_batch_device, in chunks, and every row gets its query-free term
+        t_i = sum_j (r^_ij^2 + 2 c_lj r^_ij), r^ = reconstruct_batch_device of the residual quantizer, accumulated in
+        float64 on the device and rounded once to f32.  The norms are kept as they are."""
+        import torch
+        from .pq import ReductiveError, train_pq
+        rng = rng or np.random.default_rng(0)
+        N, d = len(self), self.pq.reconstructed_len()
+        M = self.pq.quantized_len() if n_subquantizers is None else int(n_subquantizers)
+        bits = n_subquantizer_bits
+        if bits is None:
+            bits = max(1, int(self.pq.n_quantizer_centroids() - 1).bit_length())
+        if residual_pq is None and bits > 8:
+            raise ReductiveError("The residual codes are 1-byte codes: at most 8 subquantizer bits, was %d" % bits)
+        if residual_pq is not None and (residual_pq.reconstructed_len() != d or residual_pq.n_quantizer_centroids() > 256):
+            raise PanicError("the residual quantizer must reconstruct %d columns from 1-byte codes" % d)
+        centroids, assign, rows_of, train_sel = self._coarse_partition(n_lists, n_iterations, vectors, train_rows, rng)
+        dev = self.codes.device
+        cd = torch.from_numpy(centroids).to(dev)
+        ad = torch.from_numpy(assign).to(dev)
+        if residual_pq is None:
+            sel = train_sel if isinstance(train_sel, slice) else torch.from_numpy(train_sel).to(dev)
+            resid = rows_of(train_sel) - cd[ad[sel]]
+            residual_pq = train_pq(M, int(bits), pq_iterations, n_attempts, resid.cpu().numpy(), rng=rng, ctx=self.pq._ctx)
+            del resid
+        codes = torch.empty((N, residual_pq.quantized_len()), dtype=torch.uint8, device=dev)
+        terms = torch.empty(N, dtype=torch.float32, device=dev)
+        chunk = 1 << 20
+        for r0 in range(0, N, chunk):
+            r1 = min(N, r0 + chunk)
+            c = cd[ad[r0:r1]]
+            residual_pq.quantize_batch_device(rows_of(slice(r0, r1)) - c, out=codes[r0:r1])
+            r = residual_pq.reconstruct_batch_device(codes[r0:r1]).double()
+            terms[r0:r1] = (r * r + 2.0 * c.double() * r).sum(1).float()
+        return ResidualPartitionedMatrix(residual_pq, codes, self.norms, terms, centroids, assign)
 
 
 def ivf_layout(assign, n_lists):
@@ -213,7 +266,60 @@ def ivf_layout(assign, n_lists):
     return perm, list_off
 
 
-class PartitionedMatrix:
+class _Lists:
+    """What both partitioned forms share: the list layout, the coarse quantizer and the probe selection."""
+
+    def _init_lists(self, centroids, assign, n_rows, dev, ctx):
+        import torch
+        self.centroids = np.ascontiguousarray(centroids, dtype=np.float32)
+        self.n_lists = self.centroids.shape[0]
+        perm, list_off = ivf_layout(assign, self.n_lists)
+        if perm.size != n_rows:
+            raise PanicError("one list id per row expected")
+        self.ids = torch.from_numpy(perm).to(dev)
+        self.list_off = torch.from_numpy(list_off).to(dev)
+        self.positions = torch.empty_like(self.ids)
+        self.positions[self.ids] = torch.arange(perm.size, dtype=torch.int64, device=dev)
+        # the coarse quantizer as a codebook of one subquantizer: its distance tables order the lists
+        self.coarse = Pq(None, self.centroids[None], ctx=ctx)
+        self._list_ids = torch.arange(self.n_lists, dtype=torch.int32, device=dev)[:, None].contiguous()
+
+    def __len__(self):
+        return self.codes.shape[0]
+
+    def _probes_and_dists(self, queries, nprobe):
+        """(list ids, their coarse distances) as probes() defines them; on the all-lists route beyond 1,024 probes the
+        distances are the coarse table rows themselves"""
+        import torch
+        nprobe = min(int(nprobe), self.n_lists)
+        if nprobe < 1:
+            raise PanicError("nprobe must be at least 1")
+        single = queries.dim() == 1
+        tables = self.coarse.adc_tables_device(queries)
+        if nprobe > 1024:
+            if nprobe < self.n_lists:
+                raise PanicError("more than 1024 probes are served only as all %d lists" % self.n_lists)
+            nq = 1 if single else queries.shape[0]
+            pr = torch.arange(self.n_lists, dtype=torch.int64, device=self.codes.device)
+            if single:
+                return pr, tables[0]
+            return pr[None].expand(nq, -1).contiguous(), tables[:, 0, :].contiguous()
+        d, pr = self.coarse.adc_search_device(self._list_ids, tables, nprobe)
+        return pr, d
+
+    def probes(self, queries, nprobe):
+        """list ids [nq, nprobe] int64 ([nprobe] for one query): the nprobe first lists in the order (key(dist), list
+        id), dist the squared distance of the query to the coarse centroids as adc_tables_device of the one-subquantizer
+        codebook defines it, key the first-minimum order (NaN last).  nprobe is cut to n_lists; beyond 1,024 only
+        nprobe >= n_lists is served, by all list ids in ascending order (every list is read, no selection needed)."""
+        return self._probes_and_dists(queries, nprobe)[0]
+
+    def _original_rows(self, pos):
+        import torch
+        return torch.where(pos < 0, pos, self.ids[pos.clamp(min=0)])
+
+
+class PartitionedMatrix(_Lists):
     """A QuantizedMatrix whose rows are grouped by a coarse quantizer: list l holds the rows nearest to centroid l,
     stored contiguously, and a search reads only the `nprobe` lists nearest to the query.  The codes are those of the
     vectors themselves, so a search is the exhaustive search restricted to the rows of the probed lists, bit for bit;
@@ -224,48 +330,10 @@ class PartitionedMatrix:
     of position p); codes / norms in list order."""
 
     def __init__(self, qm, centroids, assign):
-        import torch
-        dev = qm.codes.device
         self.pq = qm.pq
-        self.centroids = np.ascontiguousarray(centroids, dtype=np.float32)
-        self.n_lists = self.centroids.shape[0]
-        perm, list_off = ivf_layout(assign, self.n_lists)
-        if perm.size != len(qm):
-            raise PanicError("one list id per row expected")
-        self.ids = torch.from_numpy(perm).to(dev)
-        self.list_off = torch.from_numpy(list_off).to(dev)
-        self.positions = torch.empty_like(self.ids)
-        self.positions[self.ids] = torch.arange(perm.size, dtype=torch.int64, device=dev)
+        self._init_lists(centroids, assign, len(qm), qm.codes.device, self.pq._ctx)
         self.codes = qm.codes[self.ids].contiguous()
         self.norms = None if qm.norms is None else qm.norms[self.ids].contiguous()
-        # the coarse quantizer as a codebook of one subquantizer: its distance tables order the lists
-        self.coarse = Pq(None, self.centroids[None], ctx=self.pq._ctx)
-        self._list_ids = torch.arange(self.n_lists, dtype=torch.int32, device=dev)[:, None].contiguous()
-
-    def __len__(self):
-        return self.codes.shape[0]
-
-    def probes(self, queries, nprobe):
-        """list ids [nq, nprobe] int64 ([nprobe] for one query): the nprobe first lists in the order (key(dist), list
-        id), dist the squared distance of the query to the coarse centroids as adc_tables_device of the one-subquantizer
-        codebook defines it, key the first-minimum order (NaN last).  nprobe is cut to n_lists; beyond 1,024 only
-        nprobe >= n_lists is served, by all list ids in ascending order (every list is read, no selection needed)."""
-        import torch
-        nprobe = min(int(nprobe), self.n_lists)
-        if nprobe < 1:
-            raise PanicError("nprobe must be at least 1")
-        single = queries.dim() == 1
-        if nprobe > 1024:
-            if nprobe < self.n_lists:
-                raise PanicError("more than 1024 probes are served only as all %d lists" % self.n_lists)
-            nq = 1 if single else queries.shape[0]
-            pr = torch.arange(self.n_lists, dtype=torch.int64, device=self.codes.device)
-            return pr if single else pr[None].expand(nq, -1).contiguous()
-        return self.coarse.adc_search_device(self._list_ids, self.coarse.adc_tables_device(queries), nprobe)[1]
-
-    def _original_rows(self, pos):
-        import torch
-        return torch.where(pos < 0, pos, self.ids[pos.clamp(min=0)])
 
     def nearest(self, queries, k, nprobe):
         """the k rows of smallest asymmetric squared distance among the rows of the nprobe nearest lists, ties to the
@@ -288,6 +356,65 @@ class PartitionedMatrix:
         import torch
         rows = torch.as_tensor(rows, dtype=torch.int64, device=self.codes.device)
         return self.pq.reconstruct_rows_device(self.codes, self.positions[rows], scales=self.norms, out=out)
+
+
+class ResidualPartitionedMatrix(_Lists):
+    """A partitioned matrix whose codes encode the residual of each row against its list's centroid (IVFADC with
+    residual encoding, built by QuantizedMatrix.partition_residual): row i of list l stands for c_l + r^_i, r^_i the
+    reconstruction of its code by `pq`, the quantizer of the residuals.  A search keeps one table per query -- the
+    inner-product table of the residual quantizer -- plus one bias per probed list and, for distances, the stored
+    query-free term of each row (include/pqhip.h: pqhip_adc_search_lists_residual_f32_dev):
+        |q - c_l - r^_i|^2 = |q - c_l|^2 + row_terms[i] - 2 <q, r^_i>          <q, c_l + r^_i> = <q, c_l> + <q, r^_i>
+    Row numbers given and returned are those of the matrix it was built from.
+
+    pq: the residual quantizer; coarse: the one-subquantizer codebook of the centroids [n_lists, d] (host float32);
+    list_off [n_lists + 1], ids [N], positions [N] and lists [N] (the list of each position) int64 on the device; codes
+    [N, M] u8, norms [N] f32 or None and row_terms [N] f32 in list order.
+    Reading or writing such a matrix as a storage chunk is not provided: finalfusion has no chunk for residual codes."""
+
+    def __init__(self, pq, codes, norms, row_terms, centroids, assign):
+        """codes / norms / row_terms in original row order (device tensors); assign [N] the list of each row."""
+        import torch
+        dev = codes.device
+        self.pq = pq
+        self._init_lists(centroids, assign, codes.shape[0], dev, pq._ctx)
+        self.codes = codes[self.ids].contiguous()
+        self.norms = None if norms is None else norms[self.ids].contiguous()
+        self.row_terms = row_terms[self.ids].contiguous()
+        self.lists = torch.from_numpy(np.asarray(assign, dtype=np.int64)).to(dev)[self.ids].contiguous()
+        self._centroids_dev = torch.from_numpy(self.centroids).to(dev)
+
+    def nearest(self, queries, k, nprobe):
+        """the k rows of smallest dist = fl(fl(bias + row_term) - fl(s + s)) among the rows of the nprobe nearest lists:
+        s the row sum over the query's inner-product table, bias the coarse distance of the row's list as
+        coarse.adc_search_device returns it beside the probed ids (the coarse table row when more than 1,024 lists are
+        all probed) -> (dist, idx) [k] or [nq, k]; idx are original row numbers, -1 past the last probed row (+Inf)."""
+        pr, bias = self._probes_and_dists(queries, nprobe)
+        d, pos = self.pq.adc_search_lists_residual_device(self.codes, self.pq.adc_ip_tables_device(queries), self.list_off,
+                                                          pr, bias, self.row_terms, k)
+        return d, self._original_rows(pos)
+
+    def most_similar(self, queries, k, nprobe, use_norms=True):
+        """the k rows of largest score = fl(fl(bias + s) * norm) (fl(bias + s) with use_norms=False or without norms)
+        among the rows of the nprobe nearest lists, bias the entry of coarse.adc_ip_tables_device(queries)[:, 0, :] at
+        the row's list, i.e. <q, c_l> -> (score, idx), idx original row numbers, -1 past the last probed row (-Inf)."""
+        import torch
+        pr = self.probes(queries, nprobe)
+        ipt = self.coarse.adc_ip_tables_device(queries)
+        ipt = ipt[0] if queries.dim() == 1 else ipt[:, 0, :]
+        bias = torch.gather(ipt, -1, pr.clamp(min=0)).contiguous()
+        scales = self.norms if use_norms else None
+        s, pos = self.pq.adc_ip_search_lists_residual_device(self.codes, self.pq.adc_ip_tables_device(queries),
+                                                             self.list_off, pr, bias, k, scales=scales)
+        return s, self._original_rows(pos)
+
+    def embeddings(self, rows):
+        """fl(fl(r^ + c_l) * norm) of the original row numbers `rows` (fl(r^ + c_l) without norms) -> [len(rows), d]."""
+        import torch
+        rows = torch.as_tensor(rows, dtype=torch.int64, device=self.codes.device)
+        pos = self.positions[rows]
+        e = self.pq.reconstruct_rows_device(self.codes, pos) + self._centroids_dev[self.lists[pos]]
+        return e if self.norms is None else e * self.norms[pos][:, None]
 
 
 def dumps(pq, codes, norms=None):

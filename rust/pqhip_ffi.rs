@@ -70,6 +70,17 @@ extern "C" {
         d_list_off: *const i64, n_lists: i64, d_probes: *const i64, n_probe: i32, probes_row_stride: i64,
         d_scales: *const f32, k: i32, d_score: *mut f32, score_row_stride: i64, d_idx: *mut i64,
         idx_row_stride: i64, stream: *mut c_void) -> i32;
+    // the same over residual codes: inner-product tables, a probe bias per (query, probe slot), a row term per row
+    pub fn pqhip_adc_search_lists_residual_f32_dev(cb: *mut pqhip_codebook, device_slot: i32, d_tables: *const f32,
+        n_queries: i64, d_codes: *const c_void, code_bytes: i32, n_codes: i64, codes_row_stride: i64,
+        d_list_off: *const i64, n_lists: i64, d_probes: *const i64, n_probe: i32, probes_row_stride: i64,
+        d_probe_bias: *const f32, bias_row_stride: i64, d_row_terms: *const f32, k: i32, d_dist: *mut f32,
+        dist_row_stride: i64, d_idx: *mut i64, idx_row_stride: i64, stream: *mut c_void) -> i32;
+    pub fn pqhip_adc_ip_search_lists_residual_f32_dev(cb: *mut pqhip_codebook, device_slot: i32, d_tables: *const f32,
+        n_queries: i64, d_codes: *const c_void, code_bytes: i32, n_codes: i64, codes_row_stride: i64,
+        d_list_off: *const i64, n_lists: i64, d_probes: *const i64, n_probe: i32, probes_row_stride: i64,
+        d_probe_bias: *const f32, bias_row_stride: i64, d_scales: *const f32, k: i32, d_score: *mut f32,
+        score_row_stride: i64, d_idx: *mut i64, idx_row_stride: i64, stream: *mut c_void) -> i32;
 }
 
 /// Batches smaller than this stay on the CPU path (a launch + PCIe round trip is pointless).
