@@ -298,6 +298,48 @@ int32_t pqhip_adc_ip_search_lists_residual_f32_dev(pqhip_codebook *cb, int32_t d
                                                    const float *d_scales, int32_t k, float *d_score, int64_t score_row_stride,
                                                    int64_t *d_idx, int64_t idx_row_stride, void *stream);
 
+/*
+ * Exact re-ranking of search candidates against resident vectors ("IVFADC+R", refine): the stage after an ADC search
+ * that replaces the quantizer's estimate by the distance to the stored vector.  For query q, the first n_cand entries of
+ * row q of d_cand [n_queries][cand_row_stride] int64 name rows of d_vectors [n_rows][vec_row_stride], vec_bytes = 4 (f32)
+ * or 2 (IEEE f16; an element is converted exactly to f32 and then takes the same arithmetic); d_queries
+ * [n_queries][q_row_stride] f32; d is the width of both.  cb supplies the device slot, the scratch and the stream's range
+ * flag (pqhip_check_codes_dev), as for the other _dev calls; its quantizer is not read and d need not equal its width.
+ * Value of a row x for query q, as definition -- every operation one rounded f32 operation, no contraction:
+ *   for l = 0 .. 63 the partial p_l is the sequential chain from +0 over j = l, l + 64, l + 128, .. < d of
+ *       squared L2 (metric 0):     p_l <- fl(p_l + fl(t * t)),  t = fl(q_j - x_j)
+ *       inner product (metric 1):  p_l <- fl(p_l + fl(q_j * x_j))
+ *   then the fixed tree: for s = 32, 16, 8, 4, 2, 1:  p_l <- fl(p_l + p_(l+s)) for every l < s;  the value is p_0.
+ * (One wave reads a row with coalesced 256-byte loads, lane l owning chain l, and reduces with a fixed butterfly.)
+ * C_q = the entries of candidate row q that lie in [0, n_rows).  -1 is padding and is skipped; any other value outside
+ * the range is skipped and raises the stream's range flag (pqhip_check_codes_dev -> PQHIP_ECODE_RANGE); no byte outside
+ * d_vectors is read for it.  An id named twice is a caller error and may be returned twice.  Row q of d_val
+ * [n_queries][val_row_stride] f32 and d_idx [n_queries][idx_row_stride] int64 receives the first min(k, |C_q|) members
+ * of C_q ordered by (key(dist), row id) ascending -- inner product: (key(-score), row id), the largest score first -- key
+ * exactly as for pqhip_adc_search_f32_dev (-0 == +0, every NaN equal and after every number, ties to the smaller row
+ * id).  A returned value is the row's value bit for bit, except that a NaN comes back as the canonical quiet NaN and a
+ * zero as +0.  Slots past the last candidate hold index -1 and +Inf (inner product: -Inf).  The order is strict, so the
+ * result does not depend on how candidates are spread over waves and workgroups (chosen on the host from n_cand,
+ * n_queries and the CU count; option "rerank_wgs_per_query" forces the workgroups that share a query).
+ * Status codes, in the precedence of pqhip_adc_search_f32_dev (EINVAL, ENODEV, EUNSUPPORTED, ESHAPE):
+ *   k < 1, n_cand < 1, d < 1, n_queries < 0, n_rows < 0, metric not 0 / 1: PQHIP_EINVAL;
+ *   vec_bytes not 2 / 4, k > 1024, n_cand > 1024, d > 16384 (the query is held in 64 KB of LDS), n_rows > 2^32 - 2 (an
+ *   entry keeps the row id in 32 bits): PQHIP_EUNSUPPORTED;
+ *   with n_queries > 0, a null d_queries, d_cand, d_val or d_idx, or a null d_vectors with n_rows > 0: PQHIP_EINVAL;
+ *   q_row_stride < d, vec_row_stride < d (n_rows > 0), cand_row_stride < n_cand, val_row_stride < k or idx_row_stride < k:
+ *   PQHIP_ESHAPE.
+ * n_queries == 0 launches nothing; n_rows == 0 writes the padding only (every id other than -1 raises the flag).
+ * Asynchronous on `stream`; two kernels per chunk of queries (distances -> 64-bit (key, row id) entries in the codebook's
+ * scratch, at most 64 MB per chunk; one workgroup per query sorts them and writes the first k); the caller allocates only
+ * the outputs.
+ */
+int32_t pqhip_rerank_f32_dev(pqhip_codebook *cb, int32_t device_slot,
+                             const float *d_queries, int64_t n_queries, int64_t q_row_stride,
+                             const void *d_vectors, int32_t vec_bytes, int64_t n_rows, int64_t d, int64_t vec_row_stride,
+                             const int64_t *d_cand, int32_t n_cand, int64_t cand_row_stride,
+                             int32_t metric /* 0 = squared L2, 1 = inner product */, int32_t k,
+                             float *d_val, int64_t val_row_stride, int64_t *d_idx, int64_t idx_row_stride, void *stream);
+
 /* Reconstruct's range check is asynchronous on the device path: returns PQHIP_ECODE_RANGE if any
  * device call since the last query saw a code >= K (synchronises `stream`). */
 int32_t pqhip_check_codes_dev(pqhip_codebook *cb, int32_t device_slot, void *stream);
@@ -429,6 +471,8 @@ int32_t pqhip_set_rotation_variant(int32_t variant);
  *   "opq_gather_rotation"  0 = OPQ reconstruct as gather -> scratch -> rotation (default 1)
  *   "adc_single_query"     1 = one scan pass per query (default 0: 8 / 4 queries share a pass)
  *   "adc_lists_wgs_per_query"  workgroups that share one query of the list searches (0 = chosen from the shape; at most 4096)
+ *   "rerank_wgs_per_query" workgroups that share one query in the distance stage of pqhip_rerank_f32_dev (0 = chosen from the
+ *                          shape; at most 1024)
  *   "cross_product_exact"  0 = X^T.R of the OPQ training step / pqhip_at_dot_b_f32_dev as a plain split-K product:
  *                          within 1e-5 relative of the exact rule-2 result, no per-block partial matrices (default 1)
  *   "cross_product_group_bytes"  workspace of partial matrices per launch group (0 = 4 GiB)

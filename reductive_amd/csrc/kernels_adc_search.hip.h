@@ -19,6 +19,7 @@
 // one query and writes the first k entries (index -1 and +Inf past the last row).
 // The similarity search (k_adc_ip_search_*, at the end) offers the key of -score to the same selection.
 #pragma once
+#include "adc_key.hip.h"
 #include "kernels_adc.hip.h"
 
 namespace pqhip {
@@ -29,21 +30,7 @@ constexpr int kSearchWaves = 16;             // producer workgroups: 1,024 threa
 constexpr int kSearchMergeWaves = 8;         // k_adc_search_merge: 512 threads
 constexpr unsigned kSearchEmptyKey = 0xffffffffu;
 
-// the first-minimum order as an unsigned key: -0 -> +0, NaN above +Inf (all NaNs one key)
-__device__ __forceinline__ unsigned adc_order_key(float f)
-{
-    unsigned u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return 0xffffffffu;
-    if (u == 0x80000000u) u = 0u;
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-// the distance a key stands for (a sum from +0 is never -0; a NaN comes back as the canonical quiet NaN)
-__device__ __forceinline__ float adc_key_value(unsigned key)
-{
-    if (key == 0xffffffffu) return __uint_as_float(0x7fc00000u);
-    return __uint_as_float((key & 0x80000000u) ? (key & 0x7fffffffu) : ~key);
-}
+// adc_order_key, adc_key_value and adc_ip_key_score: adc_key.hip.h (shared with the re-ranking kernels)
 
 template <typename I>
 __device__ __forceinline__ bool ent_less(unsigned ka, I ia, unsigned kb, I ib)
@@ -517,14 +504,6 @@ __global__ __launch_bounds__(1024) void k_adc_ip_search_any(const IdxT* __restri
     }
     if (bad) atomicOr(err, 1);
     search_finish<1, L>(st, qk, qi, reinterpret_cast<unsigned*>(lds_a), row_begin, part_k, part_i);
-}
-
-// the score a similarity key stands for (the key is that of -score): a zero comes back as +0 (0 - (+0)), a NaN as the
-// canonical quiet NaN, every other score bit for bit (0 - v = -v exactly)
-__device__ __forceinline__ float adc_ip_key_score(unsigned key)
-{
-    if (key == 0xffffffffu) return __uint_as_float(0x7fc00000u);
-    return fsub(0.f, adc_key_value(key));
 }
 
 // k_adc_search_merge in similarity form: the same list merge; writes the scores of the first kk entries, and past the

@@ -1092,3 +1092,71 @@ class Pq:
             raise PanicError("the residual similarity search needs a probe bias")
         return self._adc_search_lists(True, codes, ip_tables, list_off, probes, k, scales, stream, check,
                                       probe_bias=probe_bias)
+
+    # ---- exact re-ranking of search candidates against resident vectors ("IVFADC+R") ---------------------------------
+    def rerank_device(self, queries, vectors, candidates, k, ip=False, stream=None, check=False):
+        """The k best of each query's candidates by their exact distance to the stored vectors: queries CUDA float32
+        [d] or [nq, d]; vectors CUDA float32 or float16 [N, d] (f16 elements are converted exactly); candidates CUDA
+        int64 [n_cand] or [nq, n_cand] of row numbers, -1 = padding, 1 <= n_cand <= 1024 -> (value, idx), CUDA float32
+        and int64 [nq, k] ([k] for one query).  value is the squared L2 distance, or with ip=True the inner product, in
+        the fixed f32 summation order of pqhip_rerank_f32_dev; rows are ordered by ascending distance (descending
+        product), NaN last, ties to the smaller row number.  Past the last candidate: index -1 and +Inf (ip: -Inf).
+        Row strides are respected (unit column stride is made by a copy if needed).  The quantizer of self is not
+        used: d is the width of the vectors.  check=True synchronises and raises on a candidate outside [0, N) other
+        than -1; with check=False it is skipped and stays pending on the stream's flag."""
+        import torch
+        for t, what in ((queries, "queries"), (vectors, "vectors"), (candidates, "candidates")):
+            if not hasattr(t, "is_cuda"):
+                raise PanicError("%s must be a torch tensor" % what)
+        if queries.dtype != torch.float32 or queries.dim() not in (1, 2):
+            raise PanicError("queries must be float32 [d] or [nq, d]")
+        if vectors.dtype not in (torch.float32, torch.float16) or vectors.dim() != 2:
+            raise PanicError("vectors must be float32 or float16 [N, d]")
+        if candidates.dtype != torch.int64 or candidates.dim() != queries.dim():
+            raise PanicError("candidates must be int64 with one row per query")
+        single = queries.dim() == 1
+        q2 = queries[None] if single else queries
+        c2 = candidates[None] if single else candidates
+        nq, d = q2.shape
+        N = vectors.shape[0]
+        if d < 1 or vectors.shape[1] != d:
+            raise PanicError("Query and vector length mismatch")
+        if c2.shape[0] != nq:
+            raise PanicError("candidates must be int64 with one row per query")
+        n_cand = c2.shape[1]
+        if not 1 <= n_cand <= 1024:
+            raise PanicError("between 1 and 1024 candidates per query expected, got %d" % n_cand)
+        k = int(k)
+        if not 1 <= k <= 1024:
+            raise PanicError("k must be between 1 and 1024, was %d" % k)
+        if not (queries.is_cuda and vectors.is_cuda and candidates.is_cuda):
+            raise PanicError("queries, vectors and candidates must be CUDA tensors")
+        if not (queries.device == vectors.device == candidates.device):
+            raise PanicError("queries, vectors and candidates must live on one device")
+        if q2.stride(1) != 1:
+            q2 = q2.contiguous()
+        if c2.stride(1) != 1:
+            c2 = c2.contiguous()
+        if N > 0 and vectors.stride(1) != 1:
+            vectors = vectors.contiguous()
+        val = torch.empty((nq, k), dtype=torch.float32, device=vectors.device)
+        idx = torch.empty((nq, k), dtype=torch.int64, device=vectors.device)
+        cb = self._cb()
+        if stream is None:
+            stream = torch.cuda.current_stream(vectors.device).cuda_stream
+        slot = self._slot_for(vectors)
+        rc = _lib.lib().pqhip_rerank_f32_dev(
+            cb, slot, q2.data_ptr(), nq, q2.stride(0) if nq > 1 else max(q2.stride(0), d),
+            vectors.data_ptr() if N > 0 else None, vectors.element_size(), N, d,
+            vectors.stride(0) if N > 1 else max(vectors.stride(0), d),
+            c2.data_ptr(), n_cand, c2.stride(0) if nq > 1 else max(c2.stride(0), n_cand),
+            1 if ip else 0, k, val.data_ptr(), k, idx.data_ptr(), k, ctypes.c_void_p(stream))
+        if rc != _lib.OK:
+            raise _lib.PqHipError(rc, "pqhip_rerank_f32_dev")
+        if check:
+            rc = _lib.lib().pqhip_check_codes_dev(cb, slot, ctypes.c_void_p(stream))
+            if rc == _lib.ECODE_RANGE:
+                raise PanicError("ndarray: index out of bounds")
+            if rc != _lib.OK:
+                raise _lib.PqHipError(rc, "pqhip_check_codes_dev")
+        return (val[0], idx[0]) if single else (val, idx)

@@ -100,7 +100,41 @@ def read_chunk(f, stream_offset=None, ctx=None):
     return Pq(P, q, ctx=ctx), codes, norms
 
 
-class QuantizedMatrix:
+class _Refine:
+    """Exact re-ranking against the original vectors, for all three matrix classes: `vectors` is an [N, d] device copy
+    in ORIGINAL row order (None until attach_vectors), so the row numbers a search returns address it as they are."""
+
+    vectors = None
+
+    def attach_vectors(self, vectors, dtype=None):
+        """Keep the original vectors ([N, d], numpy or torch, row i belonging to row i of the matrix this one was built
+        from) on the device as `dtype` (torch.float32, the default, or torch.float16: half the memory and half the
+        bytes a refinement reads, the elements rounded once here).  Enables `refine=` of nearest() / most_similar().
+        Returns self."""
+        import torch
+        dtype = torch.float32 if dtype is None else dtype
+        if dtype not in (torch.float32, torch.float16):
+            raise PanicError("vectors are kept as float32 or float16")
+        if tuple(vectors.shape) != (len(self), self.pq.reconstructed_len()):
+            raise PanicError("vectors must be [%d, %d]" % (len(self), self.pq.reconstructed_len()))
+        if not hasattr(vectors, "is_cuda"):
+            vectors = torch.from_numpy(np.ascontiguousarray(vectors))
+        self.vectors = vectors.to(self.codes.device, dtype).contiguous()
+        return self
+
+    def _check_refine(self, k, refine):
+        if self.vectors is None:
+            raise PanicError("refine needs the original vectors: call attach_vectors first")
+        if not k <= int(refine) <= 1024:
+            raise PanicError("refine must lie between k and 1024, was %d (k = %d)" % (refine, k))
+        return int(refine)
+
+    def _refined(self, queries, rows, k, ip):
+        """rows: the original row numbers of the candidates ([R] or [nq, R], -1 = padding), on the device"""
+        return self.pq.rerank_device(queries, self.vectors, rows, k, ip=ip)
+
+
+class QuantizedMatrix(_Refine):
     """Codes (+ norms) resident in HBM next to the device codebook: the lookup, scan and similarity-search consumer."""
 
     def __init__(self, pq, codes, norms=None, device="cuda:0"):
@@ -143,11 +177,24 @@ class QuantizedMatrix:
             ip = ip * self.norms
         return ip
 
-    def most_similar(self, queries, k, use_norms=True):
+    def nearest(self, queries, k, refine=None):
+        """the k rows of smallest asymmetric squared distance (adc_search_device over all rows), ties to the smaller
+        row -> (dist, idx) [k] or [nq, k].  refine=R (k <= R <= 1024, vectors attached): the R nearest rows by that
+        estimate are re-ranked by their exact squared distance to the attached vectors (Pq.rerank_device) on the
+        device; dist are then the exact distances."""
+        R = k if refine is None else self._check_refine(k, refine)
+        d, idx = self.pq.adc_search_device(self.codes, self.pq.adc_tables_device(queries), R)
+        return (d, idx) if refine is None else self._refined(queries, idx, k, False)
+
+    def most_similar(self, queries, k, use_norms=True, refine=None):
         """the k rows of largest inner product with what embeddings() returns (the stored vectors, unscaled, with
-        use_norms=False or without norms), largest first, ties to the smaller row -> (score, idx) [k] or [nq, k]."""
+        use_norms=False or without norms), largest first, ties to the smaller row -> (score, idx) [k] or [nq, k].
+        refine=R (k <= R <= 1024, vectors attached): the R most similar rows by that estimate are re-ranked by their
+        exact inner product with the attached vectors as they are; use_norms then only affects the candidate stage."""
+        R = k if refine is None else self._check_refine(k, refine)
         scales = self.norms if use_norms else None
-        return self.pq.adc_ip_search_device(self.codes, self.pq.adc_ip_tables_device(queries), k, scales=scales)
+        s, idx = self.pq.adc_ip_search_device(self.codes, self.pq.adc_ip_tables_device(queries), R, scales=scales)
+        return (s, idx) if refine is None else self._refined(queries, idx, k, True)
 
     def partition(self, n_lists, n_iterations=10, vectors=None, train_rows=None, rng=None):
         """Partition the rows with a coarse k-means quantizer of n_lists centroids -> PartitionedMatrix (IVFADC without
@@ -163,7 +210,9 @@ class QuantizedMatrix:
         k-means limit) and n_lists <= number of training rows."""
         rng = rng or np.random.default_rng(0)
         centroids, assign, _, _ = self._coarse_partition(n_lists, n_iterations, vectors, train_rows, rng)
-        return PartitionedMatrix(self, centroids, assign)
+        out = PartitionedMatrix(self, centroids, assign)
+        out.vectors = self.vectors           # attached vectors stay in original row order: handed on as they are
+        return out
 
     def _coarse_partition(self, n_lists, n_iterations, vectors, train_rows, rng):
         """The part partition() and partition_residual() share: trains the coarse quantizer and assigns every row ->
@@ -248,7 +297,9 @@ class QuantizedMatrix:
             residual_pq.quantize_batch_device(rows_of(slice(r0, r1)) - c, out=codes[r0:r1])
             r = residual_pq.reconstruct_batch_device(codes[r0:r1]).double()
             terms[r0:r1] = (r * r + 2.0 * c.double() * r).sum(1).float()
-        return ResidualPartitionedMatrix(residual_pq, codes, self.norms, terms, centroids, assign)
+        out = ResidualPartitionedMatrix(residual_pq, codes, self.norms, terms, centroids, assign)
+        out.vectors = self.vectors
+        return out
 
 
 def ivf_layout(assign, n_lists):
@@ -266,7 +317,7 @@ def ivf_layout(assign, n_lists):
     return perm, list_off
 
 
-class _Lists:
+class _Lists(_Refine):
     """What both partitioned forms share: the list layout, the coarse quantizer and the probe selection."""
 
     def _init_lists(self, centroids, assign, n_rows, dev, ctx):
@@ -335,21 +386,28 @@ class PartitionedMatrix(_Lists):
         self.codes = qm.codes[self.ids].contiguous()
         self.norms = None if qm.norms is None else qm.norms[self.ids].contiguous()
 
-    def nearest(self, queries, k, nprobe):
+    def nearest(self, queries, k, nprobe, refine=None):
         """the k rows of smallest asymmetric squared distance among the rows of the nprobe nearest lists, ties to the
         smaller position in list order -> (dist, idx) [k] or [nq, k]; idx are original row numbers, -1 past the last
-        probed row (distance +Inf)."""
+        probed row (distance +Inf).  refine=R (k <= R <= 1024, vectors attached): the R first rows of that search are
+        re-ranked by their exact squared distance to the attached vectors (Pq.rerank_device), ties to the smaller
+        original row number; dist are then the exact distances."""
+        R = k if refine is None else self._check_refine(k, refine)
         d, pos = self.pq.adc_search_lists_device(self.codes, self.pq.adc_tables_device(queries), self.list_off,
-                                                 self.probes(queries, nprobe), k)
-        return d, self._original_rows(pos)
+                                                 self.probes(queries, nprobe), R)
+        rows = self._original_rows(pos)
+        return (d, rows) if refine is None else self._refined(queries, rows, k, False)
 
-    def most_similar(self, queries, k, nprobe, use_norms=True):
+    def most_similar(self, queries, k, nprobe, use_norms=True, refine=None):
         """QuantizedMatrix.most_similar among the rows of the nprobe nearest lists -> (score, idx), idx original row
-        numbers, -1 past the last probed row (score -Inf)."""
+        numbers, -1 past the last probed row (score -Inf).  refine=R: the R first rows are re-ranked by their exact
+        inner product with the attached vectors as they are; use_norms then only affects the candidate stage."""
+        R = k if refine is None else self._check_refine(k, refine)
         scales = self.norms if use_norms else None
         s, pos = self.pq.adc_ip_search_lists_device(self.codes, self.pq.adc_ip_tables_device(queries), self.list_off,
-                                                    self.probes(queries, nprobe), k, scales=scales)
-        return s, self._original_rows(pos)
+                                                    self.probes(queries, nprobe), R, scales=scales)
+        rows = self._original_rows(pos)
+        return (s, rows) if refine is None else self._refined(queries, rows, k, True)
 
     def embeddings(self, rows, out=None):
         """QuantizedMatrix.embeddings of the original row numbers `rows`."""
@@ -384,29 +442,37 @@ class ResidualPartitionedMatrix(_Lists):
         self.lists = torch.from_numpy(np.asarray(assign, dtype=np.int64)).to(dev)[self.ids].contiguous()
         self._centroids_dev = torch.from_numpy(self.centroids).to(dev)
 
-    def nearest(self, queries, k, nprobe):
+    def nearest(self, queries, k, nprobe, refine=None):
         """the k rows of smallest dist = fl(fl(bias + row_term) - fl(s + s)) among the rows of the nprobe nearest lists:
         s the row sum over the query's inner-product table, bias the coarse distance of the row's list as
         coarse.adc_search_device returns it beside the probed ids (the coarse table row when more than 1,024 lists are
-        all probed) -> (dist, idx) [k] or [nq, k]; idx are original row numbers, -1 past the last probed row (+Inf)."""
+        all probed) -> (dist, idx) [k] or [nq, k]; idx are original row numbers, -1 past the last probed row (+Inf).
+        refine=R (k <= R <= 1024, vectors attached): the R first rows of that search are re-ranked by their exact
+        squared distance to the attached vectors (Pq.rerank_device); dist are then the exact distances."""
+        R = k if refine is None else self._check_refine(k, refine)
         pr, bias = self._probes_and_dists(queries, nprobe)
         d, pos = self.pq.adc_search_lists_residual_device(self.codes, self.pq.adc_ip_tables_device(queries), self.list_off,
-                                                          pr, bias, self.row_terms, k)
-        return d, self._original_rows(pos)
+                                                          pr, bias, self.row_terms, R)
+        rows = self._original_rows(pos)
+        return (d, rows) if refine is None else self._refined(queries, rows, k, False)
 
-    def most_similar(self, queries, k, nprobe, use_norms=True):
+    def most_similar(self, queries, k, nprobe, use_norms=True, refine=None):
         """the k rows of largest score = fl(fl(bias + s) * norm) (fl(bias + s) with use_norms=False or without norms)
         among the rows of the nprobe nearest lists, bias the entry of coarse.adc_ip_tables_device(queries)[:, 0, :] at
-        the row's list, i.e. <q, c_l> -> (score, idx), idx original row numbers, -1 past the last probed row (-Inf)."""
+        the row's list, i.e. <q, c_l> -> (score, idx), idx original row numbers, -1 past the last probed row (-Inf).
+        refine=R: the R first rows are re-ranked by their exact inner product with the attached vectors as they are;
+        use_norms then only affects the candidate stage."""
         import torch
+        R = k if refine is None else self._check_refine(k, refine)
         pr = self.probes(queries, nprobe)
         ipt = self.coarse.adc_ip_tables_device(queries)
         ipt = ipt[0] if queries.dim() == 1 else ipt[:, 0, :]
         bias = torch.gather(ipt, -1, pr.clamp(min=0)).contiguous()
         scales = self.norms if use_norms else None
         s, pos = self.pq.adc_ip_search_lists_residual_device(self.codes, self.pq.adc_ip_tables_device(queries),
-                                                             self.list_off, pr, bias, k, scales=scales)
-        return s, self._original_rows(pos)
+                                                             self.list_off, pr, bias, R, scales=scales)
+        rows = self._original_rows(pos)
+        return (s, rows) if refine is None else self._refined(queries, rows, k, True)
 
     def embeddings(self, rows):
         """fl(fl(r^ + c_l) * norm) of the original row numbers `rows` (fl(r^ + c_l) without norms) -> [len(rows), d]."""

@@ -81,6 +81,11 @@ extern "C" {
         d_list_off: *const i64, n_lists: i64, d_probes: *const i64, n_probe: i32, probes_row_stride: i64,
         d_probe_bias: *const f32, bias_row_stride: i64, d_scales: *const f32, k: i32, d_score: *mut f32,
         score_row_stride: i64, d_idx: *mut i64, idx_row_stride: i64, stream: *mut c_void) -> i32;
+    // exact re-ranking of candidates against resident f32 / f16 vectors (metric 0 = squared L2, 1 = inner product)
+    pub fn pqhip_rerank_f32_dev(cb: *mut pqhip_codebook, device_slot: i32, d_queries: *const f32, n_queries: i64,
+        q_row_stride: i64, d_vectors: *const c_void, vec_bytes: i32, n_rows: i64, d: i64, vec_row_stride: i64,
+        d_cand: *const i64, n_cand: i32, cand_row_stride: i64, metric: i32, k: i32, d_val: *mut f32,
+        val_row_stride: i64, d_idx: *mut i64, idx_row_stride: i64, stream: *mut c_void) -> i32;
 }
 
 /// Batches smaller than this stay on the CPU path (a launch + PCIe round trip is pointless).
