@@ -299,6 +299,85 @@ int32_t pqhip_adc_ip_search_lists_residual_f32_dev(pqhip_codebook *cb, int32_t d
                                                    int64_t *d_idx, int64_t idx_row_stride, void *stream);
 
 /*
+ * The six searches above restricted to an allowed set of rows (deleted rows, subsets, skip sets): each _masked call is
+ * the unmasked signature with a row mask d_allow inserted after codes_row_stride.  d_allow holds ceil(n_codes / 32)
+ * 32-bit words in HBM, in the row order of d_codes (position order for a partitioned matrix): bit i & 31 of word i >> 5
+ * set means that row i may be returned.  Bits of the last word at or beyond n_codes are ignored, whatever they hold; no
+ * byte outside those words is read, and a word is read only for a row that the unmasked call would have read.
+ * d_allow == NULL means no filter: the call then IS the unmasked call -- same kernels, same launch log, same results.
+ * With A the set of rows whose bit is set, row q of the outputs receives the first min(k, |A|) rows of A (exhaustive
+ * calls) resp. the first min(k, |S_q n A|) rows of S_q n A (list calls) in the unmasked call's own strict order.  Hence:
+ * the result is what the unmasked call returns on the matrix with every disallowed row removed, indices mapped back --
+ * values, keys, the canonical NaN, zeros as +0 and the padding (-1 with +Inf / -Inf) exactly the unmasked call's, bit for
+ * bit.  Everything else the unmasked call defines is unchanged: -1 probes, bad ids, clamped and inverted ranges, the
+ * independence from the number of workgroups per query, scratch, query chunking, status codes and their precedence.
+ * A row whose bit is clear is NOT READ: its codes are not interpreted (a code >= K in it does not raise the range flag)
+ * and its scale, row term or bias enters nothing (a NaN there changes nothing).  An all-zero mask writes the padding only.
+ * One mask serves all queries of a call.  Per-query masks are out of scope: at n_codes / 8 bytes per query they are a
+ * different design.
+ * Scope with a non-NULL mask: the exhaustive calls serve 1-byte codes whose table fits the 160 KB of LDS beside the
+ * queues and M <= 100 (the route of the 8 / 4 / 1 queries per pass); code_bytes == 4 or a larger table is
+ * PQHIP_EUNSUPPORTED (in the place of the k > 1024 check) -- never another path.  The list calls have the scope of the
+ * list calls.
+ */
+int32_t pqhip_adc_search_masked_f32_dev(pqhip_codebook *cb, int32_t device_slot, const float *d_tables, int64_t n_queries,
+                                        const void *d_codes, int32_t code_bytes, int64_t n_codes, int64_t codes_row_stride,
+                                        const uint32_t *d_allow,
+                                        int32_t k, float *d_dist, int64_t dist_row_stride,
+                                        int64_t *d_idx, int64_t idx_row_stride, void *stream);
+int32_t pqhip_adc_ip_search_masked_f32_dev(pqhip_codebook *cb, int32_t device_slot, const float *d_tables, int64_t n_queries,
+                                           const void *d_codes, int32_t code_bytes, int64_t n_codes, int64_t codes_row_stride,
+                                           const uint32_t *d_allow,
+                                           const float *d_scales, int32_t k, float *d_score, int64_t score_row_stride,
+                                           int64_t *d_idx, int64_t idx_row_stride, void *stream);
+int32_t pqhip_adc_search_lists_masked_f32_dev(pqhip_codebook *cb, int32_t device_slot, const float *d_tables,
+                                              int64_t n_queries, const void *d_codes, int32_t code_bytes,
+                                              int64_t n_codes, int64_t codes_row_stride, const uint32_t *d_allow,
+                                              const int64_t *d_list_off, int64_t n_lists,
+                                              const int64_t *d_probes, int32_t n_probe, int64_t probes_row_stride,
+                                              int32_t k, float *d_dist, int64_t dist_row_stride,
+                                              int64_t *d_idx, int64_t idx_row_stride, void *stream);
+int32_t pqhip_adc_ip_search_lists_masked_f32_dev(pqhip_codebook *cb, int32_t device_slot, const float *d_tables,
+                                                 int64_t n_queries, const void *d_codes, int32_t code_bytes,
+                                                 int64_t n_codes, int64_t codes_row_stride, const uint32_t *d_allow,
+                                                 const int64_t *d_list_off, int64_t n_lists,
+                                                 const int64_t *d_probes, int32_t n_probe, int64_t probes_row_stride,
+                                                 const float *d_scales, int32_t k, float *d_score, int64_t score_row_stride,
+                                                 int64_t *d_idx, int64_t idx_row_stride, void *stream);
+int32_t pqhip_adc_search_lists_residual_masked_f32_dev(pqhip_codebook *cb, int32_t device_slot, const float *d_tables,
+                                                       int64_t n_queries, const void *d_codes, int32_t code_bytes,
+                                                       int64_t n_codes, int64_t codes_row_stride, const uint32_t *d_allow,
+                                                       const int64_t *d_list_off, int64_t n_lists,
+                                                       const int64_t *d_probes, int32_t n_probe, int64_t probes_row_stride,
+                                                       const float *d_probe_bias, int64_t bias_row_stride,
+                                                       const float *d_row_terms, int32_t k, float *d_dist,
+                                                       int64_t dist_row_stride, int64_t *d_idx, int64_t idx_row_stride,
+                                                       void *stream);
+int32_t pqhip_adc_ip_search_lists_residual_masked_f32_dev(pqhip_codebook *cb, int32_t device_slot, const float *d_tables,
+                                                          int64_t n_queries, const void *d_codes, int32_t code_bytes,
+                                                          int64_t n_codes, int64_t codes_row_stride, const uint32_t *d_allow,
+                                                          const int64_t *d_list_off, int64_t n_lists,
+                                                          const int64_t *d_probes, int32_t n_probe, int64_t probes_row_stride,
+                                                          const float *d_probe_bias, int64_t bias_row_stride,
+                                                          const float *d_scales, int32_t k, float *d_score,
+                                                          int64_t score_row_stride, int64_t *d_idx, int64_t idx_row_stride,
+                                                          void *stream);
+
+/*
+ * Builds the words of a row mask on the device: for p in [0, n), bit p & 31 of d_words[p >> 5] is
+ * d_allow_bytes[d_perm ? d_perm[p] : p] != 0; the bits of the last word at or beyond n are written as 0.  d_allow_bytes
+ * [n_src] u8, nonzero = allowed; d_perm NULL or [n] int64 (for a partitioned matrix: the original row number of each
+ * position); d_words [ceil(n / 32)].  A source index outside [0, n_src) gives bit 0 and raises the stream's range flag
+ * (pqhip_check_codes_dev -> PQHIP_ECODE_RANGE).  n < 0, n_src < 0, or a null d_allow_bytes / d_words with n > 0:
+ * PQHIP_EINVAL; n > (2^31 - 1) 256 (one launch): PQHIP_EUNSUPPORTED; n == 0 launches nothing.  Asynchronous on `stream`.  A mask is rebuilt from its bytes; there are no
+ * in-place bit updates.
+ */
+int32_t pqhip_pack_row_mask_dev(pqhip_codebook *cb, int32_t device_slot,
+                                const uint8_t *d_allow_bytes, int64_t n_src,
+                                const int64_t *d_perm, int64_t n,
+                                uint32_t *d_words, void *stream);
+
+/*
  * Exact re-ranking of search candidates against resident vectors ("IVFADC+R", refine): the stage after an ADC search
  * that replaces the quantizer's estimate by the distance to the stored vector.  For query q, the first n_cand entries of
  * row q of d_cand [n_queries][cand_row_stride] int64 name rows of d_vectors [n_rows][vec_row_stride], vec_bytes = 4 (f32)

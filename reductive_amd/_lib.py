@@ -110,6 +110,15 @@ def lib():
     L.pqhip_adc_ip_search_lists_residual_f32_dev.restype = i32
     L.pqhip_adc_ip_search_lists_residual_f32_dev.argtypes = [vp, i32, vp, i64, vp, i32, i64, i64, vp, i64, vp, i32, i64,
                                                              vp, i64, vp, i32, vp, i64, vp, i64, vp]
+    # the masked searches: the signatures above with the mask words after codes_row_stride
+    for name in ("adc_search", "adc_ip_search", "adc_search_lists", "adc_ip_search_lists", "adc_search_lists_residual",
+                 "adc_ip_search_lists_residual"):
+        plain = getattr(L, "pqhip_%s_f32_dev" % name)
+        masked = getattr(L, "pqhip_%s_masked_f32_dev" % name)
+        masked.restype = i32
+        masked.argtypes = plain.argtypes[:8] + [vp] + plain.argtypes[8:]
+    L.pqhip_pack_row_mask_dev.restype = i32
+    L.pqhip_pack_row_mask_dev.argtypes = [vp, i32, vp, i64, vp, i64, vp, vp]
     L.pqhip_rerank_f32_dev.restype = i32
     L.pqhip_rerank_f32_dev.argtypes = [vp, i32, vp, i64, i64, vp, i32, i64, i64, i64, vp, i32, i64, i32, i32,
                                        vp, i64, vp, i64, vp]
@@ -168,6 +177,10 @@ EXPORTS = [
     "pqhip_adc_ip_tables_f32_dev", "pqhip_adc_ip_search_f32_dev",
     "pqhip_adc_search_lists_f32_dev", "pqhip_adc_ip_search_lists_f32_dev",
     "pqhip_adc_search_lists_residual_f32_dev", "pqhip_adc_ip_search_lists_residual_f32_dev",
+    "pqhip_adc_search_masked_f32_dev", "pqhip_adc_ip_search_masked_f32_dev",
+    "pqhip_adc_search_lists_masked_f32_dev", "pqhip_adc_ip_search_lists_masked_f32_dev",
+    "pqhip_adc_search_lists_residual_masked_f32_dev", "pqhip_adc_ip_search_lists_residual_masked_f32_dev",
+    "pqhip_pack_row_mask_dev",
     "pqhip_rerank_f32_dev",
     "pqhip_cluster_assignments_f32", "pqhip_kmeans_iterations_f32", "pqhip_kmeans_iterations_f32_dev",
     "pqhip_opq_train_step_f32_dev", "pqhip_at_dot_b_f32_dev", "pqhip_rotate_f32_dev",

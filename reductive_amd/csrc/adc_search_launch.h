@@ -1,0 +1,65 @@
+// adc_search_launch.h -- what the two translation units of the ADC searches share on the host: the launch structs that
+// pqhip_adc.hip fills (it owns the policy: checks, queries per pass, list length, grids, scratch, the plan and the merge)
+// and the row mask with the launchers of the masked producers, which pqhip_adc_masked.hip instantiates so that the build
+// compiles them beside pqhip_adc.hip.
+#pragma once
+#include "pqhip_internal.h"
+
+namespace pqh {
+
+struct SearchLaunch {
+    int64_t n, c_rs, rows_per_wg;
+    unsigned grid;
+    int M, K, k;
+    const float* scales;     // IP: [n] row scales or null; unused by the distance search
+    unsigned* part_k;
+    uint64_t* part_i;
+    int* err;
+    hipStream_t st;
+    const uint32_t* allow;   // row mask (ceil(n / 32) words) or null: the masked producers serve a non-null one
+};
+
+struct ListsLaunch {
+    int64_t n, c_rs;
+    unsigned G, nq;          // grid (G, nq)
+    int M, K, k, n_probe;
+    const float* scales;     // residual distance search: the row terms
+    const float* bias;       // residual searches: probe bias rows of the launch's queries, else null
+    int64_t b_rs;
+    const int64_t *seg_begin, *seg_cum;
+    unsigned* part_k;
+    uint64_t* part_i;
+    int* err;
+    hipStream_t st;
+    const uint32_t* allow;   // row mask in position order or null
+};
+
+// Inputs of the residual searches beside those of the plain ones: bias [nq][b_rs] f32, one value per (query, probe
+// slot), and for the distance the row terms [n] f32 (they travel in the place of the scales).
+struct ListsResidual {
+    const float* bias;
+    int64_t b_rs;
+};
+
+// A row mask as the search routines take it: the words and the launchers of the masked producers.  The launchers come
+// with the mask so that pqhip_adc.hip refers to nothing of pqhip_adc_masked.hip: the dependency runs one way, from the
+// masked entry points to the routines, and a program linked without the masked unit lacks those entry points only.
+// search: ip = the similarity form; nq_pass in {8, 4, 1}; L and nvb as chosen for the unmasked producers
+// (search_list_regs, search_nv_bucket / lists_nv_bucket); lds: the same budget.
+struct RowMask {
+    const uint32_t* words;
+    int32_t (*search)(bool ip, int nq_pass, int L, int nvb, const SearchLaunch& a, const uint8_t* codes, const float* lut, size_t lds);
+    int32_t (*lists)(bool ip, int L, int nvb, const ListsLaunch& a, const uint8_t* codes, const float* lut, size_t lds);
+};
+
+// pqhip_adc.hip: adc_search / adc_search_lists behind the masked entry points (mask.words != null)
+int32_t adc_search_masked(bool ip, pqhip_codebook* cb, int32_t slot, const float* d_tables, int64_t nq, const void* d_codes,
+                          int32_t code_bytes, int64_t n, int64_t c_rs, const float* d_scales, int32_t k, float* d_val, int64_t v_rs,
+                          int64_t* d_idx, int64_t i_rs, void* stream, const RowMask& mask);
+int32_t adc_search_lists_masked(bool ip, pqhip_codebook* cb, int32_t slot, const float* d_tables, int64_t nq, const void* d_codes,
+                                int32_t code_bytes, int64_t n, int64_t c_rs, const int64_t* d_list_off, int64_t n_lists,
+                                const int64_t* d_probes, int32_t n_probe, int64_t p_rs, const float* d_scales, int32_t k,
+                                float* d_val, int64_t v_rs, int64_t* d_idx, int64_t i_rs, void* stream, const ListsResidual* res,
+                                const RowMask& mask);
+
+}  // namespace pqh

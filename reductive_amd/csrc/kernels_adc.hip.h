@@ -1,7 +1,8 @@
 // kernels_adc.hip.h -- "next" row: asymmetric distance computation over a
 // resident code matrix.  Lookup tables from the reference's own vector-to-matrix distance
 // (linalg.rs:118-148), then a table-sum scan over the u8 codes -- HBM-bound: M bytes in, 4 bytes out
-// per code row.  (Non-template kernels: include from exactly one translation unit, pqhip_adc.hip.)
+// per code row.  (The non-template kernels belong to one translation unit, pqhip_adc.hip; pqhip_adc_masked.hip takes the
+// device functions and templates alone by defining PQHIP_ADC_TEMPLATES_ONLY before it includes this file.)
 #pragma once
 #include "common.hip.h"
 
@@ -25,6 +26,7 @@ __device__ inline float dot_unrolled_global(const float* __restrict__ a, const f
     return s;
 }
 
+#ifndef PQHIP_ADC_TEMPLATES_ONLY
 // y[q][c] = sum_k x[q][k] * P[k][c], the 1-D x 2-D ndarray dot of pq.rs:293 (`x.dot(projection)` for a
 // single vector): per output column one sequential  s = s + x[k] * P[k][c]  (separately rounded).
 __global__ void k_adc_rotate_queries(const float* __restrict__ x, int64_t x_rs, int nq, const float* __restrict__ P,
@@ -71,6 +73,8 @@ __global__ void k_adc_ip_tables(const float* __restrict__ y, int64_t y_rs, int n
     const float* ym = y + q * y_rs + (int64_t)m * dsub;
     tables[idx] = dot_unrolled_global(cb + ((int64_t)m * K + j) * dsub, ym, dsub);
 }
+
+#endif  // PQHIP_ADC_TEMPLATES_ONLY
 
 // ---------------------------------------------------------------------------------------------
 // Table-sum scan: out[i] = sum_{m = 0..M-1, in order, from +0} lut[m][codes[i][m]]   (u8 codes)
@@ -294,6 +298,7 @@ __global__ __launch_bounds__(1024) void k_adc_scan_u8_mq(const uint8_t* __restri
     if (bad) atomicOr(err, 1);
 }
 
+#ifndef PQHIP_ADC_TEMPLATES_ONLY
 // 32-bit codes (K > 256) whose M x K table still fits LDS (M K <= 40,960 entries: K = 1,024 at M = 15 takes 60 KB, K = 2,048
 // 120 KB): the table in LDS as in the u8 kernel, one 1,024-thread workgroup per CU over a contiguous row range, a lane owns
 // whole rows and fetches its 4 M code bytes with 16-byte loads (rows are 4-byte aligned; consecutive lanes read consecutive
@@ -334,6 +339,8 @@ __global__ __launch_bounds__(1024) void k_adc_scan_wide(const uint32_t* __restri
     }
     if (bad) atomicOr(err, 1);
 }
+
+#endif  // PQHIP_ADC_TEMPLATES_ONLY
 
 // any index width / any table size: tables read through L2, one thread per row.  No throughput claim.
 template <typename IdxT>

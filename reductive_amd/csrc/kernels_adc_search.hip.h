@@ -1,6 +1,7 @@
 // kernels_adc_search.hip.h -- ADC search: the table-sum scan of kernels_adc.hip.h fused with an exact top-k selection,
 // so that a search returns the k nearest rows of every query without writing the n_codes distances.
-// (Non-template parts and all launches: included from exactly one translation unit, pqhip_adc.hip.)
+// (Launched from pqhip_adc.hip; pqhip_adc_masked.hip includes the file for the selection -- SearchState, search_finish --
+// and launches none of its kernels.)
 //
 // Order.  A row is the pair (key(dist), row index) and rows compare lexicographically: key() is the first-minimum order
 // of cluster_assignments (kmeans.rs:133-159, oracle of_less) -- -0 == +0, every NaN equal to every other and above

@@ -1,6 +1,6 @@
 // pqhip_adc.hip -- asymmetric distance computation over a resident code matrix ("next" row):
 // per-query lookup tables (linalg.rs:118-148 applied to the sub-vectors of the query) and the table-sum scans.
-#include "pqhip_internal.h"
+#include "adc_search_launch.h"
 
 #include "kernels_adc.hip.h"
 #include "kernels_adc_search.hip.h"
@@ -65,16 +65,7 @@ inline int search_nv_bucket(int nv)
     return 0;
 }
 
-struct SearchLaunch {
-    int64_t n, c_rs, rows_per_wg;
-    unsigned grid;
-    int M, K, k;
-    const float* scales;     // IP: [n] row scales or null; unused by the distance search
-    unsigned* part_k;
-    uint64_t* part_i;
-    int* err;
-    hipStream_t st;
-};
+// SearchLaunch: adc_search_launch.h (shared with the masked producers of pqhip_adc_masked.hip)
 
 // the producer's dynamic LDS: max(table image + queues, combine lists)
 inline size_t search_lds(size_t table_bytes, int nq, int L)
@@ -245,15 +236,21 @@ int32_t adc_tables(bool ip, pqhip_codebook* cb, int32_t slot, const float* d_q, 
 // The fused scan + exact top-k of both searches, one policy: argument checks, queries per pass (NQ L <= 16 and the
 // 160 KB of LDS, option "adc_single_query"), the u8 fast path or the generic kernel, the partial lists in the
 // codebook's scratch, one merge per pass.  IP: similarity (k_adc_ip_search_*, d_scales may be null); else distance.
+// d_allow != null: the same choices with the masked producer in the place of the u8 one; a call that the u8 route does
+// not serve (4-byte codes, a table beyond LDS) is PQHIP_EUNSUPPORTED -- never another path.
 template <bool IP>
 int32_t adc_search(pqhip_codebook* cb, int32_t slot, const float* d_tables, int64_t nq, const void* d_codes, int32_t code_bytes,
                    int64_t n, int64_t c_rs, const float* d_scales, int32_t k, float* d_dist, int64_t d_rs, int64_t* d_idx,
-                   int64_t i_rs, void* stream)
+                   int64_t i_rs, void* stream, const RowMask* mask = nullptr)
 {
+    const uint32_t* d_allow = mask ? mask->words : nullptr;
     if (!cb || nq < 0 || n < 0 || k < 1) return PQHIP_EINVAL;
     if (slot < 0 || slot >= (int)cb->dev.size()) return PQHIP_ENODEV;
     if (code_bytes != 1 && code_bytes != 4) return PQHIP_EUNSUPPORTED;
     if (k > kSearchMaxK) return PQHIP_EUNSUPPORTED;
+    if (d_allow && (code_bytes != 1 || search_nv_bucket(((int)cb->M + 3) / 4) == 0 ||
+                    search_lds((size_t)cb->M * cb->K * sizeof(float), 1, search_list_regs(k)) > 160 * 1024))
+        return PQHIP_EUNSUPPORTED;                                  // a mask: the u8 route or nothing
     if (nq == 0) return PQHIP_OK;
     if (!d_dist || !d_idx || (n > 0 && (!d_tables || !d_codes))) return PQHIP_EINVAL;
     if ((n > 0 && c_rs < cb->M) || d_rs < k || i_rs < k) return PQHIP_ESHAPE;
@@ -296,7 +293,7 @@ int32_t adc_search(pqhip_codebook* cb, int32_t slot, const float* d_tables, int6
     PQCHK(part.acquire(list_entries * (sizeof(unsigned) + sizeof(uint64_t))));
     uint64_t* part_i = (uint64_t*)part.ptr();
     unsigned* part_k = (unsigned*)(part_i + list_entries);
-    SearchLaunch a{n, c_rs, rows_per_wg, (unsigned)grid, M, K, k, d_scales, part_k, part_i, ef.flag, st};
+    SearchLaunch a{n, c_rs, rows_per_wg, (unsigned)grid, M, K, k, d_scales, part_k, part_i, ef.flag, st, d_allow};
     const bool adc_any = diag().adc_any;
     int64_t q = 0;
     for (int nqp : {8, 4, 1}) {
@@ -304,7 +301,9 @@ int32_t adc_search(pqhip_codebook* cb, int32_t slot, const float* d_tables, int6
         if (nqp == 4 && !(fast && mq_on && 4 * L <= 16 && search_lds(table * 4, 4, L) <= 160 * 1024)) continue;
         for (; q + nqp <= nq; q += nqp) {
             const float* lut = d_tables + q * (int64_t)M * K;
-            if (fast) {
+            if (fast && d_allow) {
+                PQCHK(mask->search(IP, nqp, L, nvb, a, (const uint8_t*)d_codes, lut, search_lds(table * nqp, nqp, L)));
+            } else if (fast) {
                 const size_t lds = search_lds(table * nqp, nqp, L);
                 if (nqp == 8) PQCHK((launch_search_u8_l<IP, 8>(L, nvb, a, (const uint8_t*)d_codes, lut, lds)));
                 else if (nqp == 4) PQCHK((launch_search_u8_l<IP, 4>(L, nvb, a, (const uint8_t*)d_codes, lut, lds)));
@@ -323,19 +322,7 @@ int32_t adc_search(pqhip_codebook* cb, int32_t slot, const float* d_tables, int6
 }
 
 // ---- ADC search over probed lists (kernels_adc_search_lists.hip.h) ----------------------------------------------------
-struct ListsLaunch {
-    int64_t n, c_rs;
-    unsigned G, nq;          // grid (G, nq)
-    int M, K, k, n_probe;
-    const float* scales;     // residual distance search: the row terms
-    const float* bias;       // residual searches: probe bias rows of the launch's queries, else null
-    int64_t b_rs;
-    const int64_t *seg_begin, *seg_cum;
-    unsigned* part_k;
-    uint64_t* part_i;
-    int* err;
-    hipStream_t st;
-};
+// ListsLaunch: adc_search_launch.h
 
 // Code dwords per row of the list producers: fewer widths than search_nv_bucket (a wider window is always correct)
 inline int lists_nv_bucket(int nv)
@@ -401,23 +388,20 @@ inline int64_t lists_wgs_per_query(int64_t n, int64_t n_lists, int64_t n_probe, 
 
 constexpr size_t kListsScratchBytes = 512u << 20;   // plan + partial lists of one chunk of queries
 
-// Inputs of the residual searches beside those of the plain ones: bias [nq][b_rs] f32, one value per (query, probe
-// slot), and for the distance the row terms [n] f32 (they travel in the place of the scales).
-struct ListsResidual {
-    const float* bias;
-    int64_t b_rs;
-};
+// ListsResidual (probe bias rows; the row terms travel in the place of the scales): adc_search_launch.h
 
 // All list searches: argument checks in the order of adc_search, the plan kernel (the only reader of the offsets and
 // probes), the producer over a (G, queries) grid and one merge, per chunk of queries that fits the scratch lease.
 // res != null: the residual producer; d_scales then holds the row terms of the distance search (required).
+// d_allow != null: the masked producers (pqhip_adc_masked.hip) behind the same plan, before the same merge.
 template <bool IP>
 int32_t adc_search_lists(pqhip_codebook* cb, int32_t slot, const float* d_tables, int64_t nq, const void* d_codes,
                          int32_t code_bytes, int64_t n, int64_t c_rs, const int64_t* d_list_off, int64_t n_lists,
                          const int64_t* d_probes, int32_t n_probe, int64_t p_rs, const float* d_scales, int32_t k,
                          float* d_val, int64_t v_rs, int64_t* d_idx, int64_t i_rs, void* stream,
-                         const ListsResidual* res = nullptr)
+                         const ListsResidual* res = nullptr, const RowMask* mask = nullptr)
 {
+    const uint32_t* d_allow = mask ? mask->words : nullptr;
     if (!cb || nq < 0 || n < 0 || k < 1 || n_lists < 0 || n_probe < 1) return PQHIP_EINVAL;
     if (slot < 0 || slot >= (int)cb->dev.size()) return PQHIP_ENODEV;
     const int M = (int)cb->M, K = (int)cb->K;
@@ -465,13 +449,36 @@ int32_t adc_search_lists(pqhip_codebook* cb, int32_t slot, const float* d_tables
         HIPCHK(hipGetLastError());
         note_kernel("k_adc_lists_plan");
         ListsLaunch a{n, c_rs, (unsigned)G, nqc, M, K, k, (int)n_probe, d_scales, res ? res->bias + q * res->b_rs : nullptr,
-                      res ? res->b_rs : 0, seg_begin, seg_cum, part_k, part_i, ef.flag, st};
-        PQCHK((launch_lists_u8_l<IP>(L, nvb, a, (const uint8_t*)d_codes, d_tables + q * (int64_t)M * K, lds)));
+                      res ? res->b_rs : 0, seg_begin, seg_cum, part_k, part_i, ef.flag, st, d_allow};
+        if (d_allow) PQCHK(mask->lists(IP, L, nvb, a, (const uint8_t*)d_codes, d_tables + q * (int64_t)M * K, lds));
+        else PQCHK((launch_lists_u8_l<IP>(L, nvb, a, (const uint8_t*)d_codes, d_tables + q * (int64_t)M * K, lds)));
         HIPCHK(hipGetLastError());
         PQCHK(launch_search_merge<IP>(L, (int)nqc, (int)G, k, part_k, part_i, d_val + q * v_rs, v_rs, d_idx + q * i_rs, i_rs, st));
         HIPCHK(hipGetLastError());
     }
     return PQHIP_OK;
+}
+
+// The doors of pqhip_adc_masked.hip into the two routines above
+int32_t adc_search_masked(bool ip, pqhip_codebook* cb, int32_t slot, const float* d_tables, int64_t nq, const void* d_codes,
+                          int32_t code_bytes, int64_t n, int64_t c_rs, const float* d_scales, int32_t k, float* d_val, int64_t v_rs,
+                          int64_t* d_idx, int64_t i_rs, void* stream, const RowMask& mask)
+{
+    if (ip) return adc_search<true>(cb, slot, d_tables, nq, d_codes, code_bytes, n, c_rs, d_scales, k, d_val, v_rs, d_idx, i_rs, stream, &mask);
+    return adc_search<false>(cb, slot, d_tables, nq, d_codes, code_bytes, n, c_rs, nullptr, k, d_val, v_rs, d_idx, i_rs, stream, &mask);
+}
+
+int32_t adc_search_lists_masked(bool ip, pqhip_codebook* cb, int32_t slot, const float* d_tables, int64_t nq, const void* d_codes,
+                                int32_t code_bytes, int64_t n, int64_t c_rs, const int64_t* d_list_off, int64_t n_lists,
+                                const int64_t* d_probes, int32_t n_probe, int64_t p_rs, const float* d_scales, int32_t k,
+                                float* d_val, int64_t v_rs, int64_t* d_idx, int64_t i_rs, void* stream, const ListsResidual* res,
+                                const RowMask& mask)
+{
+    if (ip)
+        return adc_search_lists<true>(cb, slot, d_tables, nq, d_codes, code_bytes, n, c_rs, d_list_off, n_lists, d_probes, n_probe,
+                                      p_rs, d_scales, k, d_val, v_rs, d_idx, i_rs, stream, res, &mask);
+    return adc_search_lists<false>(cb, slot, d_tables, nq, d_codes, code_bytes, n, c_rs, d_list_off, n_lists, d_probes, n_probe,
+                                   p_rs, d_scales, k, d_val, v_rs, d_idx, i_rs, stream, res, &mask);
 }
 
 }  // namespace pqh

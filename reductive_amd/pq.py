@@ -875,11 +875,60 @@ class Pq:
                 raise _lib.PqHipError(rc, "pqhip_check_codes_dev")
         return out
 
-    def adc_search_device(self, codes, tables, k, stream=None, check=False):
+    # ---- row masks: restrict a search to an allowed set of rows ------------------------------------------------------
+    def pack_row_mask_device(self, allow, perm=None, stream=None, check=False):
+        """allow: CUDA bool or uint8 [n_src], nonzero = the row may be returned; perm: None or CUDA int64 [n] -> the mask
+        words of the searches' `allow=`, CUDA int32 [ceil(n / 32)]: bit p & 31 of word p >> 5 is allow[perm[p]] (allow[p]
+        without perm, n = n_src), the tail bits of the last word 0 (pqhip_pack_row_mask_dev).  A perm entry outside
+        [0, n_src) gives bit 0 and raises the range flag (check=True: PanicError)."""
+        import torch
+        assert allow.is_cuda and allow.dtype in (torch.bool, torch.uint8) and allow.dim() == 1
+        ab = allow.contiguous()
+        if ab.dtype == torch.bool:
+            ab = ab.view(torch.uint8)
+        n_src = ab.shape[0]
+        n = n_src
+        if perm is not None:
+            assert perm.is_cuda and perm.dtype == torch.int64 and perm.dim() == 1 and perm.device == allow.device
+            perm = perm.contiguous()
+            n = perm.shape[0]
+        words = torch.empty(((n + 31) // 32,), dtype=torch.int32, device=allow.device)
+        if n == 0:
+            return words
+        if n_src == 0:      # an empty tensor may have no address
+            ab = torch.zeros(1, dtype=torch.uint8, device=allow.device)
+        cb = self._cb()
+        if stream is None:
+            stream = torch.cuda.current_stream(allow.device).cuda_stream
+        slot = self._slot_for(allow)
+        rc = _lib.lib().pqhip_pack_row_mask_dev(cb, slot, ab.data_ptr(), n_src, perm.data_ptr() if perm is not None else None,
+                                               n, words.data_ptr(), ctypes.c_void_p(stream))
+        if rc != _lib.OK:
+            raise _lib.PqHipError(rc, "pqhip_pack_row_mask_dev")
+        if check:
+            rc = _lib.lib().pqhip_check_codes_dev(cb, slot, ctypes.c_void_p(stream))
+            if rc == _lib.ECODE_RANGE:
+                raise PanicError("ndarray: index out of bounds")
+            if rc != _lib.OK:
+                raise _lib.PqHipError(rc, "pqhip_check_codes_dev")
+        return words
+
+    @staticmethod
+    def _mask_words(allow, codes):
+        """The words tensor of a search's `allow=`: CUDA int32 [ceil(n / 32)] on the device of the codes."""
+        import torch
+        assert allow.is_cuda and allow.dtype == torch.int32 and allow.dim() == 1 and allow.is_contiguous()
+        if allow.device != codes.device or allow.shape[0] != (codes.shape[0] + 31) // 32:
+            raise PanicError("the row mask must hold ceil(n / 32) words for the n code rows")
+        # an empty tensor may have no address; a non-NULL mask must stay a mask (n = 0 reads no word)
+        return allow if allow.shape[0] > 0 else torch.zeros(1, dtype=torch.int32, device=codes.device)
+
+    def adc_search_device(self, codes, tables, k, stream=None, check=False, allow=None):
         """The k nearest rows per query without the distance matrix: codes and tables as for adc_scan_device ->
         (dist, idx), CUDA float32 and int64 [nq, k] ([k] for 2-D tables).  dist[q, j] is the scan's distance of row
         idx[q, j]; rows are ordered by distance -- NaN above +Inf -- then by index (pqhip_adc_search_f32_dev).  Past
-        the last row: index -1, distance +Inf."""
+        the last row: index -1, distance +Inf.  allow: None or the words of pack_row_mask_device -- the search then
+        ranks the allowed rows only, as if the others were not in the matrix (pqhip_adc_search_masked_f32_dev)."""
         import torch
         assert codes.is_cuda and codes.dtype in (torch.uint8, torch.int32) and codes.dim() == 2
         assert tables.is_cuda and tables.dtype == torch.float32 and tables.is_contiguous()
@@ -899,11 +948,19 @@ class Pq:
         if stream is None:
             stream = torch.cuda.current_stream(codes.device).cuda_stream
         slot = self._slot_for(codes)
-        rc = _lib.lib().pqhip_adc_search_f32_dev(cb, slot, tables.data_ptr(), nq, codes.data_ptr(), codes.element_size(), n,
-                                                codes.stride(0) if n > 1 else max(codes.stride(0), M), k,
-                                                dist.data_ptr(), k, idx.data_ptr(), k, ctypes.c_void_p(stream))
+        c_rs = codes.stride(0) if n > 1 else max(codes.stride(0), M)
+        if allow is not None:
+            name = "pqhip_adc_search_masked_f32_dev"
+            rc = _lib.lib().pqhip_adc_search_masked_f32_dev(cb, slot, tables.data_ptr(), nq, codes.data_ptr(),
+                                                           codes.element_size(), n, c_rs,
+                                                           self._mask_words(allow, codes).data_ptr(), k,
+                                                           dist.data_ptr(), k, idx.data_ptr(), k, ctypes.c_void_p(stream))
+        else:
+            name = "pqhip_adc_search_f32_dev"
+            rc = _lib.lib().pqhip_adc_search_f32_dev(cb, slot, tables.data_ptr(), nq, codes.data_ptr(), codes.element_size(), n,
+                                                    c_rs, k, dist.data_ptr(), k, idx.data_ptr(), k, ctypes.c_void_p(stream))
         if rc != _lib.OK:
-            raise _lib.PqHipError(rc, "pqhip_adc_search_f32_dev")
+            raise _lib.PqHipError(rc, name)
         if check:
             rc = _lib.lib().pqhip_check_codes_dev(cb, slot, ctypes.c_void_p(stream))
             if rc == _lib.ECODE_RANGE:
@@ -937,12 +994,13 @@ class Pq:
             raise _lib.PqHipError(rc, "pqhip_adc_ip_tables_f32_dev")
         return out[0] if single else out
 
-    def adc_ip_search_device(self, codes, tables, k, scales=None, stream=None, check=False):
+    def adc_ip_search_device(self, codes, tables, k, scales=None, stream=None, check=False, allow=None):
         """The k most similar rows per query: codes as for adc_scan_device, tables from adc_ip_tables_device, scales None
         or CUDA float32 [n] -> (score, idx), CUDA float32 and int64 [nq, k] ([k] for 2-D tables).  score[q, j] =
         fl(scan[q, i] * scales[i]) of row i = idx[q, j] (the scan's sum alone without scales); rows are ordered by
         descending score -- NaN after -Inf -- then by index (pqhip_adc_ip_search_f32_dev).  A zero score comes back as
-        +0, a NaN as the canonical NaN.  Past the last row: index -1, score -Inf."""
+        +0, a NaN as the canonical NaN.  Past the last row: index -1, score -Inf.  allow: as for adc_search_device
+        (pqhip_adc_ip_search_masked_f32_dev)."""
         import torch
         assert codes.is_cuda and codes.dtype in (torch.uint8, torch.int32) and codes.dim() == 2
         assert tables.is_cuda and tables.dtype == torch.float32 and tables.is_contiguous()
@@ -966,12 +1024,18 @@ class Pq:
         if stream is None:
             stream = torch.cuda.current_stream(codes.device).cuda_stream
         slot = self._slot_for(codes)
-        rc = _lib.lib().pqhip_adc_ip_search_f32_dev(cb, slot, tables.data_ptr(), nq, codes.data_ptr(), codes.element_size(),
-                                                   n, codes.stride(0) if n > 1 else max(codes.stride(0), M),
-                                                   scales.data_ptr() if scales is not None else None, k,
-                                                   score.data_ptr(), k, idx.data_ptr(), k, ctypes.c_void_p(stream))
+        head = (cb, slot, tables.data_ptr(), nq, codes.data_ptr(), codes.element_size(), n,
+                codes.stride(0) if n > 1 else max(codes.stride(0), M))
+        tail = (scales.data_ptr() if scales is not None else None, k, score.data_ptr(), k, idx.data_ptr(), k,
+                ctypes.c_void_p(stream))
+        if allow is not None:
+            name = "pqhip_adc_ip_search_masked_f32_dev"
+            rc = _lib.lib().pqhip_adc_ip_search_masked_f32_dev(*head, self._mask_words(allow, codes).data_ptr(), *tail)
+        else:
+            name = "pqhip_adc_ip_search_f32_dev"
+            rc = _lib.lib().pqhip_adc_ip_search_f32_dev(*head, *tail)
         if rc != _lib.OK:
-            raise _lib.PqHipError(rc, "pqhip_adc_ip_search_f32_dev")
+            raise _lib.PqHipError(rc, name)
         if check:
             rc = _lib.lib().pqhip_check_codes_dev(cb, slot, ctypes.c_void_p(stream))
             if rc == _lib.ECODE_RANGE:
@@ -982,11 +1046,13 @@ class Pq:
 
     # ---- ADC search over a partitioned code matrix: exact top-k within the probed lists -----------------------------
     def _adc_search_lists(self, ip, codes, tables, list_off, probes, k, scales, stream, check, probe_bias=None,
-                          row_terms=None):
-        """All four list searches; probe_bias given: the residual ones (row_terms then required for the distance)."""
+                          row_terms=None, allow=None):
+        """All four list searches; probe_bias given: the residual ones (row_terms then required for the distance);
+        allow given: their masked forms (the words of pack_row_mask_device, in position order)."""
         import torch
         residual = probe_bias is not None
-        name = "pqhip_adc_%ssearch_lists_%sf32_dev" % ("ip_" if ip else "", "residual_" if residual else "")
+        name = "pqhip_adc_%ssearch_lists_%s%sf32_dev" % ("ip_" if ip else "", "residual_" if residual else "",
+                                                        "masked_" if allow is not None else "")
         assert codes.is_cuda and codes.dtype == torch.uint8 and codes.dim() == 2
         assert tables.is_cuda and tables.dtype == torch.float32 and tables.is_contiguous()
         assert list_off.is_cuda and list_off.dtype == torch.int64 and list_off.dim() == 1 and list_off.is_contiguous()
@@ -1029,22 +1095,25 @@ class Pq:
             stream = torch.cuda.current_stream(codes.device).cuda_stream
         slot = self._slot_for(codes)
         head = (cb, slot, tables.data_ptr(), nq, codes.data_ptr(), codes.element_size(), n,
-                codes.stride(0) if n > 1 else max(codes.stride(0), M), list_off.data_ptr(), list_off.shape[0] - 1,
-                pr.data_ptr(), n_probe, pr.stride(0) if nq > 1 else max(pr.stride(0), n_probe))
+                codes.stride(0) if n > 1 else max(codes.stride(0), M))
+        if allow is not None:
+            head += (self._mask_words(allow, codes).data_ptr(),)
+        head += (list_off.data_ptr(), list_off.shape[0] - 1,
+                 pr.data_ptr(), n_probe, pr.stride(0) if nq > 1 else max(pr.stride(0), n_probe))
         tail = (k, val.data_ptr(), k, idx.data_ptr(), k, ctypes.c_void_p(stream))
+        fn = getattr(_lib.lib(), name)
         if residual:
             head += (pb.data_ptr(), pb.stride(0) if nq > 1 else max(pb.stride(0), n_probe))
             if ip:
-                rc = _lib.lib().pqhip_adc_ip_search_lists_residual_f32_dev(
-                    *head, scales.data_ptr() if scales is not None else None, *tail)
+                rc = fn(*head, scales.data_ptr() if scales is not None else None, *tail)
             else:
                 # an empty tensor may have no address, and the C call wants one even when there is no row to read
                 rt = row_terms if n > 0 else torch.zeros(1, dtype=torch.float32, device=codes.device)
-                rc = _lib.lib().pqhip_adc_search_lists_residual_f32_dev(*head, rt.data_ptr(), *tail)
+                rc = fn(*head, rt.data_ptr(), *tail)
         elif ip:
-            rc = _lib.lib().pqhip_adc_ip_search_lists_f32_dev(*head, scales.data_ptr() if scales is not None else None, *tail)
+            rc = fn(*head, scales.data_ptr() if scales is not None else None, *tail)
         else:
-            rc = _lib.lib().pqhip_adc_search_lists_f32_dev(*head, *tail)
+            rc = fn(*head, *tail)
         if rc != _lib.OK:
             raise _lib.PqHipError(rc, name)
         if check:
@@ -1055,43 +1124,47 @@ class Pq:
                 raise _lib.PqHipError(rc, "pqhip_check_codes_dev")
         return (val[0], idx[0]) if single else (val, idx)
 
-    def adc_search_lists_device(self, codes, tables, list_off, probes, k, stream=None, check=False):
+    def adc_search_lists_device(self, codes, tables, list_off, probes, k, stream=None, check=False, allow=None):
         """adc_search_device restricted, per query, to the rows of the probed lists: list l is rows
         [list_off[l], list_off[l + 1]) of codes (CUDA uint8 [n, M]); list_off CUDA int64 [n_lists + 1]; probes CUDA int64
         [nq, n_probe] ([n_probe] for 2-D tables) of list ids, -1 = padding -> (dist, idx) [nq, k] ([k]).  The result is
         what adc_search_device returns on codes with every row outside the probed lists removed, idx being positions in
         codes (pqhip_adc_search_lists_f32_dev).  Past the last probed row: index -1, distance +Inf.  check=True also
-        reports a list id or an offset out of range."""
-        return self._adc_search_lists(False, codes, tables, list_off, probes, k, None, stream, check)
+        reports a list id or an offset out of range.  allow: None or the words of pack_row_mask_device in position order
+        (row order of codes): only allowed rows of the probed lists are ranked (pqhip_adc_search_lists_masked_f32_dev)."""
+        return self._adc_search_lists(False, codes, tables, list_off, probes, k, None, stream, check, allow=allow)
 
-    def adc_ip_search_lists_device(self, codes, tables, list_off, probes, k, scales=None, stream=None, check=False):
+    def adc_ip_search_lists_device(self, codes, tables, list_off, probes, k, scales=None, stream=None, check=False,
+                                   allow=None):
         """adc_ip_search_device restricted, per query, to the rows of the probed lists (arguments as for
         adc_search_lists_device, tables from adc_ip_tables_device, scales None or CUDA float32 [n]) -> (score, idx).
-        Past the last probed row: index -1, score -Inf (pqhip_adc_ip_search_lists_f32_dev)."""
-        return self._adc_search_lists(True, codes, tables, list_off, probes, k, scales, stream, check)
+        Past the last probed row: index -1, score -Inf (pqhip_adc_ip_search_lists_f32_dev).  allow: as for
+        adc_search_lists_device."""
+        return self._adc_search_lists(True, codes, tables, list_off, probes, k, scales, stream, check, allow=allow)
 
     # ---- the same over residual codes (IVFADC with residual encoding): one table per query, a bias per probe ---------
     def adc_search_lists_residual_device(self, codes, ip_tables, list_off, probes, probe_bias, row_terms, k, stream=None,
-                                         check=False):
+                                         check=False, allow=None):
         """adc_search_lists_device over residual codes: self is the quantizer of the residuals x - c_list(x), ip_tables
         are its INNER-PRODUCT tables (adc_ip_tables_device), probe_bias CUDA float32 [nq, n_probe] ([n_probe] for one
         query) holds |q - c_l|^2 of the list in each probe slot and row_terms CUDA float32 [n] holds |r^|^2 + 2 <c_l, r^>
         of each row -> (dist, idx) with dist = fl(fl(bias + term) - fl(s + s)), s the scan's row sum, ordered by
-        (key(dist), position) (pqhip_adc_search_lists_residual_f32_dev).  The bias of a skipped probe is never used."""
+        (key(dist), position) (pqhip_adc_search_lists_residual_f32_dev).  The bias of a skipped probe is never used.
+        allow: as for adc_search_lists_device; the row term of a disallowed row is never read."""
         if probe_bias is None or row_terms is None:
             raise PanicError("the residual distance search needs a probe bias and the row terms")
         return self._adc_search_lists(False, codes, ip_tables, list_off, probes, k, None, stream, check,
-                                      probe_bias=probe_bias, row_terms=row_terms)
+                                      probe_bias=probe_bias, row_terms=row_terms, allow=allow)
 
     def adc_ip_search_lists_residual_device(self, codes, ip_tables, list_off, probes, probe_bias, k, scales=None,
-                                            stream=None, check=False):
+                                            stream=None, check=False, allow=None):
         """adc_ip_search_lists_device over residual codes: probe_bias holds <q, c_l> of the list in each probe slot ->
         (score, idx) with score = fl(fl(bias + s) * scale), fl(bias + s) without scales, ordered by (key(-score),
-        position) (pqhip_adc_ip_search_lists_residual_f32_dev)."""
+        position) (pqhip_adc_ip_search_lists_residual_f32_dev).  allow: as for adc_search_lists_device."""
         if probe_bias is None:
             raise PanicError("the residual similarity search needs a probe bias")
         return self._adc_search_lists(True, codes, ip_tables, list_off, probes, k, scales, stream, check,
-                                      probe_bias=probe_bias)
+                                      probe_bias=probe_bias, allow=allow)
 
     # ---- exact re-ranking of search candidates against resident vectors ("IVFADC+R") ---------------------------------
     def rerank_device(self, queries, vectors, candidates, k, ip=False, stream=None, check=False):

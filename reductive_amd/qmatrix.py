@@ -134,7 +134,60 @@ class _Refine:
         return self.pq.rerank_device(queries, self.vectors, rows, k, ip=ip)
 
 
-class QuantizedMatrix(_Refine):
+class RowFilter:
+    """The set of rows a search may return, packed for one matrix: `words` is the device mask of the searches' `allow=`
+    (int32 [ceil(N / 32)], bit p of the matrix's own row order -- position order for a partitioned matrix), `matrix` the
+    matrix it was built for (row_filter of that matrix; using it on another raises PanicError), `n_allowed` the number of
+    allowed rows.  A filter is rebuilt from its N flags; there are no in-place updates."""
+
+    def __init__(self, matrix, words, n_allowed):
+        self.matrix = matrix
+        self.words = words
+        self.n_allowed = n_allowed
+
+
+class _Filter:
+    """Row filters for all three matrix classes.  Flags are given in ORIGINAL row order; a partitioned matrix packs them
+    through its permutation, bit p = allow[ids[p]] (Pq.pack_row_mask_device with perm = ids)."""
+
+    def row_filter(self, allow=None, rows=None, allowed=True):
+        """allow: bool [N] (numpy or torch), True = the row may be returned, in original row order; or rows=: original
+        row numbers with allowed=True (only these rows may be returned) or allowed=False (these rows are excluded --
+        deleted rows, a skip set -- and every other row may be returned) -> RowFilter for `allow=` of nearest() /
+        most_similar() of THIS matrix.  partition() / partition_residual() do not carry filters over: build the filter
+        from the same flags on the partitioned matrix."""
+        import torch
+        N, dev = len(self), self.codes.device
+        if (allow is None) == (rows is None):
+            raise PanicError("give either the flags of all rows or a list of row numbers")
+        if rows is not None:
+            r = torch.as_tensor(np.asarray(rows, dtype=np.int64) if not hasattr(rows, "is_cuda") else rows,
+                                dtype=torch.int64, device=dev).reshape(-1)
+            if r.numel() and (int(r.min()) < 0 or int(r.max()) >= N):
+                raise PanicError("row numbers must lie in [0, %d)" % N)
+            flags = torch.full((N,), 0 if allowed else 1, dtype=torch.uint8, device=dev)
+            flags[r] = 1 if allowed else 0
+        else:
+            if not hasattr(allow, "is_cuda"):
+                allow = torch.from_numpy(np.ascontiguousarray(allow))
+            if allow.dtype != torch.bool or tuple(allow.shape) != (N,):
+                raise PanicError("allow must be a bool array with one flag per row (%d)" % N)
+            flags = allow.to(dev).contiguous().view(torch.uint8)
+        words = self.pq.pack_row_mask_device(flags, perm=getattr(self, "ids", None))
+        return RowFilter(self, words, int(flags.count_nonzero()))
+
+    def _allow_words(self, allow):
+        """`allow=` of a search -> the mask words or None: a RowFilter of this matrix, or flags packed on the spot"""
+        if allow is None:
+            return None
+        if isinstance(allow, RowFilter):
+            if allow.matrix is not self:
+                raise PanicError("the row filter was built for another matrix")
+            return allow.words
+        return self.row_filter(allow).words
+
+
+class QuantizedMatrix(_Refine, _Filter):
     """Codes (+ norms) resident in HBM next to the device codebook: the lookup, scan and similarity-search consumer."""
 
     def __init__(self, pq, codes, norms=None, device="cuda:0"):
@@ -177,23 +230,27 @@ class QuantizedMatrix(_Refine):
             ip = ip * self.norms
         return ip
 
-    def nearest(self, queries, k, refine=None):
+    def nearest(self, queries, k, refine=None, allow=None):
         """the k rows of smallest asymmetric squared distance (adc_search_device over all rows), ties to the smaller
         row -> (dist, idx) [k] or [nq, k].  refine=R (k <= R <= 1024, vectors attached): the R nearest rows by that
         estimate are re-ranked by their exact squared distance to the attached vectors (Pq.rerank_device) on the
-        device; dist are then the exact distances."""
+        device; dist are then the exact distances.  allow: None, a RowFilter of this matrix (row_filter) or a bool
+        array [N] packed on the spot -- only allowed rows are ranked, exactly as if the others were not stored (index
+        -1 past the last allowed row); with refine= the shortlist holds allowed rows only."""
         R = k if refine is None else self._check_refine(k, refine)
-        d, idx = self.pq.adc_search_device(self.codes, self.pq.adc_tables_device(queries), R)
+        d, idx = self.pq.adc_search_device(self.codes, self.pq.adc_tables_device(queries), R, allow=self._allow_words(allow))
         return (d, idx) if refine is None else self._refined(queries, idx, k, False)
 
-    def most_similar(self, queries, k, use_norms=True, refine=None):
+    def most_similar(self, queries, k, use_norms=True, refine=None, allow=None):
         """the k rows of largest inner product with what embeddings() returns (the stored vectors, unscaled, with
         use_norms=False or without norms), largest first, ties to the smaller row -> (score, idx) [k] or [nq, k].
         refine=R (k <= R <= 1024, vectors attached): the R most similar rows by that estimate are re-ranked by their
-        exact inner product with the attached vectors as they are; use_norms then only affects the candidate stage."""
+        exact inner product with the attached vectors as they are; use_norms then only affects the candidate stage.
+        allow: as for nearest()."""
         R = k if refine is None else self._check_refine(k, refine)
         scales = self.norms if use_norms else None
-        s, idx = self.pq.adc_ip_search_device(self.codes, self.pq.adc_ip_tables_device(queries), R, scales=scales)
+        s, idx = self.pq.adc_ip_search_device(self.codes, self.pq.adc_ip_tables_device(queries), R, scales=scales,
+                                              allow=self._allow_words(allow))
         return (s, idx) if refine is None else self._refined(queries, idx, k, True)
 
     def partition(self, n_lists, n_iterations=10, vectors=None, train_rows=None, rng=None):
@@ -207,7 +264,8 @@ class QuantizedMatrix(_Refine):
         centroids are n_lists distinct training rows drawn with the numpy Generator `rng`, as train_pq draws them;
         training is kmeans_iterations with one subquantizer, assignment is cluster_assignments.  Both take the slow
         anchor kernel for sub-vectors wider than 256 floats: accepted for a build step.  1 <= n_lists <= 16384 (the
-        k-means limit) and n_lists <= number of training rows."""
+        k-means limit) and n_lists <= number of training rows.  Row filters are not carried over: a RowFilter belongs
+        to the matrix that built it (call row_filter on the result)."""
         rng = rng or np.random.default_rng(0)
         centroids, assign, _, _ = self._coarse_partition(n_lists, n_iterations, vectors, train_rows, rng)
         out = PartitionedMatrix(self, centroids, assign)
@@ -266,7 +324,8 @@ class QuantizedMatrix(_Refine):
         read 1-byte codes); a given `residual_pq` (a Pq of the same width, OPQ allowed) skips the training.  All
         residuals are encoded with quantize_batch_device, in chunks, and every row gets its query-free term
         t_i = sum_j (r^_ij^2 + 2 c_lj r^_ij), r^ = reconstruct_batch_device of the residual quantizer, accumulated in
-        float64 on the device and rounded once to f32.  The norms are kept as they are."""
+        float64 on the device and rounded once to f32.  The norms are kept as they are.  Row filters are not carried
+        over (row_filter on the result builds one from the same flags)."""
         import torch
         from .pq import ReductiveError, train_pq
         rng = rng or np.random.default_rng(0)
@@ -317,7 +376,7 @@ def ivf_layout(assign, n_lists):
     return perm, list_off
 
 
-class _Lists(_Refine):
+class _Lists(_Refine, _Filter):
     """What both partitioned forms share: the list layout, the coarse quantizer and the probe selection."""
 
     def _init_lists(self, centroids, assign, n_rows, dev, ctx):
@@ -386,26 +445,29 @@ class PartitionedMatrix(_Lists):
         self.codes = qm.codes[self.ids].contiguous()
         self.norms = None if qm.norms is None else qm.norms[self.ids].contiguous()
 
-    def nearest(self, queries, k, nprobe, refine=None):
+    def nearest(self, queries, k, nprobe, refine=None, allow=None):
         """the k rows of smallest asymmetric squared distance among the rows of the nprobe nearest lists, ties to the
         smaller position in list order -> (dist, idx) [k] or [nq, k]; idx are original row numbers, -1 past the last
         probed row (distance +Inf).  refine=R (k <= R <= 1024, vectors attached): the R first rows of that search are
         re-ranked by their exact squared distance to the attached vectors (Pq.rerank_device), ties to the smaller
-        original row number; dist are then the exact distances."""
+        original row number; dist are then the exact distances.  allow: None, a RowFilter of this matrix or a bool array
+        [N] in ORIGINAL row order -- only allowed rows of the probed lists are ranked, as if the others were not stored."""
         R = k if refine is None else self._check_refine(k, refine)
         d, pos = self.pq.adc_search_lists_device(self.codes, self.pq.adc_tables_device(queries), self.list_off,
-                                                 self.probes(queries, nprobe), R)
+                                                 self.probes(queries, nprobe), R, allow=self._allow_words(allow))
         rows = self._original_rows(pos)
         return (d, rows) if refine is None else self._refined(queries, rows, k, False)
 
-    def most_similar(self, queries, k, nprobe, use_norms=True, refine=None):
+    def most_similar(self, queries, k, nprobe, use_norms=True, refine=None, allow=None):
         """QuantizedMatrix.most_similar among the rows of the nprobe nearest lists -> (score, idx), idx original row
         numbers, -1 past the last probed row (score -Inf).  refine=R: the R first rows are re-ranked by their exact
-        inner product with the attached vectors as they are; use_norms then only affects the candidate stage."""
+        inner product with the attached vectors as they are; use_norms then only affects the candidate stage.
+        allow: as for nearest()."""
         R = k if refine is None else self._check_refine(k, refine)
         scales = self.norms if use_norms else None
         s, pos = self.pq.adc_ip_search_lists_device(self.codes, self.pq.adc_ip_tables_device(queries), self.list_off,
-                                                    self.probes(queries, nprobe), R, scales=scales)
+                                                    self.probes(queries, nprobe), R, scales=scales,
+                                                    allow=self._allow_words(allow))
         rows = self._original_rows(pos)
         return (s, rows) if refine is None else self._refined(queries, rows, k, True)
 
@@ -442,26 +504,27 @@ class ResidualPartitionedMatrix(_Lists):
         self.lists = torch.from_numpy(np.asarray(assign, dtype=np.int64)).to(dev)[self.ids].contiguous()
         self._centroids_dev = torch.from_numpy(self.centroids).to(dev)
 
-    def nearest(self, queries, k, nprobe, refine=None):
+    def nearest(self, queries, k, nprobe, refine=None, allow=None):
         """the k rows of smallest dist = fl(fl(bias + row_term) - fl(s + s)) among the rows of the nprobe nearest lists:
         s the row sum over the query's inner-product table, bias the coarse distance of the row's list as
         coarse.adc_search_device returns it beside the probed ids (the coarse table row when more than 1,024 lists are
         all probed) -> (dist, idx) [k] or [nq, k]; idx are original row numbers, -1 past the last probed row (+Inf).
         refine=R (k <= R <= 1024, vectors attached): the R first rows of that search are re-ranked by their exact
-        squared distance to the attached vectors (Pq.rerank_device); dist are then the exact distances."""
+        squared distance to the attached vectors (Pq.rerank_device); dist are then the exact distances.  allow: as for
+        PartitionedMatrix.nearest."""
         R = k if refine is None else self._check_refine(k, refine)
         pr, bias = self._probes_and_dists(queries, nprobe)
         d, pos = self.pq.adc_search_lists_residual_device(self.codes, self.pq.adc_ip_tables_device(queries), self.list_off,
-                                                          pr, bias, self.row_terms, R)
+                                                          pr, bias, self.row_terms, R, allow=self._allow_words(allow))
         rows = self._original_rows(pos)
         return (d, rows) if refine is None else self._refined(queries, rows, k, False)
 
-    def most_similar(self, queries, k, nprobe, use_norms=True, refine=None):
+    def most_similar(self, queries, k, nprobe, use_norms=True, refine=None, allow=None):
         """the k rows of largest score = fl(fl(bias + s) * norm) (fl(bias + s) with use_norms=False or without norms)
         among the rows of the nprobe nearest lists, bias the entry of coarse.adc_ip_tables_device(queries)[:, 0, :] at
         the row's list, i.e. <q, c_l> -> (score, idx), idx original row numbers, -1 past the last probed row (-Inf).
         refine=R: the R first rows are re-ranked by their exact inner product with the attached vectors as they are;
-        use_norms then only affects the candidate stage."""
+        use_norms then only affects the candidate stage.  allow: as for PartitionedMatrix.nearest."""
         import torch
         R = k if refine is None else self._check_refine(k, refine)
         pr = self.probes(queries, nprobe)
@@ -470,7 +533,8 @@ class ResidualPartitionedMatrix(_Lists):
         bias = torch.gather(ipt, -1, pr.clamp(min=0)).contiguous()
         scales = self.norms if use_norms else None
         s, pos = self.pq.adc_ip_search_lists_residual_device(self.codes, self.pq.adc_ip_tables_device(queries),
-                                                             self.list_off, pr, bias, R, scales=scales)
+                                                             self.list_off, pr, bias, R, scales=scales,
+                                                             allow=self._allow_words(allow))
         rows = self._original_rows(pos)
         return (s, rows) if refine is None else self._refined(queries, rows, k, True)
 
