@@ -378,6 +378,92 @@ int32_t pqhip_pack_row_mask_dev(pqhip_codebook *cb, int32_t device_slot,
                                 uint32_t *d_words, void *stream);
 
 /*
+ * ADC range search: EVERY row within a radius resp. at or above a similarity, exhaustive and over probed lists, without
+ * the [n_queries][n_codes] matrix -- the question beside "the best k".  Everything is exact; there is no tolerance and no
+ * k.  Query q has a threshold d_threshold[q] (f32) and a value v[q][i] per row:
+ *   pqhip_adc_range_f32_dev        v = what pqhip_adc_scan_f32_dev writes for row i (the sequential f32 sum over m from
+ *                                  +0); row i qualifies iff v <= thr[q] as an IEEE comparison: a NaN value never
+ *                                  qualifies, a NaN threshold matches nothing, +Inf matches every non-NaN row.
+ *   pqhip_adc_ip_range_f32_dev     v = fl(s * scale[i]), s without d_scales, exactly the score of
+ *                                  pqhip_adc_ip_search_f32_dev; row i qualifies iff v >= thr[q] (-Inf: every non-NaN row).
+ *   pqhip_adc_range_lists_f32_dev / pqhip_adc_ip_range_lists_f32_dev
+ *                                  the same two values over S_q, the rows of the probed lists.  Probes, -1 padding, bad
+ *                                  ids, clamped and inverted ranges and the range flag are exactly those of
+ *                                  pqhip_adc_search_lists_f32_dev (the same plan kernel reads them).
+ *   pqhip_adc_range_lists_residual_f32_dev / pqhip_adc_ip_range_lists_residual_f32_dev
+ *                                  dist = fl(fl(bias[q][p] + term[i]) - fl(s + s)), score = fl(fl(bias[q][p] + s) *
+ *                                  scale[i]) (without d_scales: fl(bias[q][p] + s)), the formulas of
+ *                                  pqhip_adc_search_lists_residual_f32_dev over the same inner-product tables.  The bias
+ *                                  of a skipped probe is never read into a result.
+ * Output is CSR.  d_lims [n_queries + 1] int64: lims[0] = 0 and lims[q + 1] - lims[q] is the number of qualifying rows
+ * of query q.  d_val (f32) and d_idx (int64) are flat arrays of `capacity` entries.  Exhaustive calls: the rows of query
+ * q occupy slots lims[q] .. lims[q + 1] - 1 in ascending row index.  List calls: they come in the order of the
+ * concatenation of the probed lists -- probe slot first, then position; a list named twice returns its rows twice.
+ * d_idx holds row indices (positions in d_codes for the list calls); d_val holds the value bit for bit -- nothing is
+ * ordered by value, so there is no key: the sign of a zero is kept.  The order is a function of the inputs alone: the
+ * result does not depend on the grid, the row ranges, the number of queries per pass or the number of workgroups per
+ * query (options "adc_range_wgs", "adc_range_wgs_per_query" force them).
+ * Capacity protocol.  d_lims always receives the true counts.  An entry whose global slot is < capacity is written; an
+ * entry at or beyond capacity is not, and no byte past `capacity` entries is touched: what was written is a valid prefix
+ * of the result.  capacity == 0 is a pure count call (d_val / d_idx may be NULL).  A caller reads lims[n_queries]; if it
+ * exceeds the capacity it passed, it allocates that many entries and calls again: the second call always suffices.
+ * Row filter.  d_allow is NULL (no filter) or the mask words of pqhip_pack_row_mask_dev, as in the _masked searches: the
+ * result is that of the unmasked call on the matrix with every disallowed row removed, indices mapped back.  A row whose
+ * bit is clear is NOT READ: a code >= K there raises no flag, a NaN scale, term or bias there changes nothing.
+ * Scope: code_bytes == 1, M <= 100 and a table that fits the 160 KB of LDS -- anything else is PQHIP_EUNSUPPORTED, never
+ * another path; the list calls also want n_codes <= 2^32 - 2 and n_probe < 2^24.  Status codes in the precedence of
+ * pqhip_adc_search_f32_dev (EINVAL, ENODEV, EUNSUPPORTED, ESHAPE): a null cb, a negative count, capacity < 0 (list calls:
+ * n_lists < 0, n_probe < 1): PQHIP_EINVAL; then the slot, then the scope; n_queries == 0 launches nothing and writes
+ * nothing; then a null d_lims or d_threshold, null outputs with capacity > 0, null tables or codes with n_codes > 0 (list
+ * calls: null d_list_off / d_probes; residual: null d_probe_bias, null d_row_terms in the distance call): PQHIP_EINVAL;
+ * then codes_row_stride < M, probes_row_stride or bias_row_stride < n_probe: PQHIP_ESHAPE.  n_codes == 0 (list calls: or
+ * n_lists == 0) writes all-zero lims.  A code >= K in a row that is read reads entry 0 and raises the stream's range flag.
+ * All calls are asynchronous on `stream`; partial counts (and the plan of the list calls) live in the codebook's scratch,
+ * and queries are processed in chunks that keep them bounded.  Results are not sorted by value: sort on the caller's side.
+ */
+int32_t pqhip_adc_range_f32_dev(pqhip_codebook *cb, int32_t device_slot, const float *d_tables, int64_t n_queries,
+                                const void *d_codes, int32_t code_bytes, int64_t n_codes, int64_t codes_row_stride,
+                                const uint32_t *d_allow,
+                                const float *d_threshold /* [n_queries] */, int64_t *d_lims, float *d_val, int64_t *d_idx,
+                                int64_t capacity, void *stream);
+int32_t pqhip_adc_ip_range_f32_dev(pqhip_codebook *cb, int32_t device_slot, const float *d_tables, int64_t n_queries,
+                                   const void *d_codes, int32_t code_bytes, int64_t n_codes, int64_t codes_row_stride,
+                                   const uint32_t *d_allow, const float *d_scales,
+                                   const float *d_threshold /* [n_queries] */, int64_t *d_lims, float *d_val, int64_t *d_idx,
+                                   int64_t capacity, void *stream);
+int32_t pqhip_adc_range_lists_f32_dev(pqhip_codebook *cb, int32_t device_slot, const float *d_tables, int64_t n_queries,
+                                      const void *d_codes, int32_t code_bytes, int64_t n_codes, int64_t codes_row_stride,
+                                      const uint32_t *d_allow, const int64_t *d_list_off, int64_t n_lists,
+                                      const int64_t *d_probes, int32_t n_probe, int64_t probes_row_stride,
+                                      const float *d_threshold /* [n_queries] */, int64_t *d_lims, float *d_val,
+                                      int64_t *d_idx, int64_t capacity, void *stream);
+int32_t pqhip_adc_ip_range_lists_f32_dev(pqhip_codebook *cb, int32_t device_slot, const float *d_tables, int64_t n_queries,
+                                         const void *d_codes, int32_t code_bytes, int64_t n_codes, int64_t codes_row_stride,
+                                         const uint32_t *d_allow, const int64_t *d_list_off, int64_t n_lists,
+                                         const int64_t *d_probes, int32_t n_probe, int64_t probes_row_stride,
+                                         const float *d_scales,
+                                         const float *d_threshold /* [n_queries] */, int64_t *d_lims, float *d_val,
+                                         int64_t *d_idx, int64_t capacity, void *stream);
+int32_t pqhip_adc_range_lists_residual_f32_dev(pqhip_codebook *cb, int32_t device_slot, const float *d_tables,
+                                               int64_t n_queries, const void *d_codes, int32_t code_bytes,
+                                               int64_t n_codes, int64_t codes_row_stride, const uint32_t *d_allow,
+                                               const int64_t *d_list_off, int64_t n_lists,
+                                               const int64_t *d_probes, int32_t n_probe, int64_t probes_row_stride,
+                                               const float *d_probe_bias, int64_t bias_row_stride,
+                                               const float *d_row_terms,
+                                               const float *d_threshold /* [n_queries] */, int64_t *d_lims, float *d_val,
+                                               int64_t *d_idx, int64_t capacity, void *stream);
+int32_t pqhip_adc_ip_range_lists_residual_f32_dev(pqhip_codebook *cb, int32_t device_slot, const float *d_tables,
+                                                  int64_t n_queries, const void *d_codes, int32_t code_bytes,
+                                                  int64_t n_codes, int64_t codes_row_stride, const uint32_t *d_allow,
+                                                  const int64_t *d_list_off, int64_t n_lists,
+                                                  const int64_t *d_probes, int32_t n_probe, int64_t probes_row_stride,
+                                                  const float *d_probe_bias, int64_t bias_row_stride,
+                                                  const float *d_scales,
+                                                  const float *d_threshold /* [n_queries] */, int64_t *d_lims, float *d_val,
+                                                  int64_t *d_idx, int64_t capacity, void *stream);
+
+/*
  * Exact re-ranking of search candidates against resident vectors ("IVFADC+R", refine): the stage after an ADC search
  * that replaces the quantizer's estimate by the distance to the stored vector.  For query q, the first n_cand entries of
  * row q of d_cand [n_queries][cand_row_stride] int64 name rows of d_vectors [n_rows][vec_row_stride], vec_bytes = 4 (f32)
@@ -550,6 +636,10 @@ int32_t pqhip_set_rotation_variant(int32_t variant);
  *   "opq_gather_rotation"  0 = OPQ reconstruct as gather -> scratch -> rotation (default 1)
  *   "adc_single_query"     1 = one scan pass per query (default 0: 8 / 4 queries share a pass)
  *   "adc_lists_wgs_per_query"  workgroups that share one query of the list searches (0 = chosen from the shape; at most 4096)
+ *   "adc_range_wgs"        producer workgroups of the exhaustive range searches (0 = chosen from the shape; at most 8192,
+ *                          so that the one-workgroup prefix scan of a pass sums at most 2^20 counts)
+ *   "adc_range_wgs_per_query"  workgroups that share one query of the list range searches (0 = chosen from the shape; at
+ *                          most 4096, as "adc_lists_wgs_per_query")
  *   "rerank_wgs_per_query" workgroups that share one query in the distance stage of pqhip_rerank_f32_dev (0 = chosen from the
  *                          shape; at most 1024)
  *   "cross_product_exact"  0 = X^T.R of the OPQ training step / pqhip_at_dot_b_f32_dev as a plain split-K product:

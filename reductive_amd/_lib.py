@@ -117,6 +117,14 @@ def lib():
         masked = getattr(L, "pqhip_%s_masked_f32_dev" % name)
         masked.restype = i32
         masked.argtypes = plain.argtypes[:8] + [vp] + plain.argtypes[8:]
+    # the range searches: the masked signatures with (threshold, lims, val, idx, capacity) in the place of k and the
+    # four output arguments
+    for name in ("adc_search", "adc_ip_search", "adc_search_lists", "adc_ip_search_lists", "adc_search_lists_residual",
+                 "adc_ip_search_lists_residual"):
+        masked = getattr(L, "pqhip_%s_masked_f32_dev" % name)
+        rng = getattr(L, "pqhip_%s_f32_dev" % name.replace("search", "range"))
+        rng.restype = i32
+        rng.argtypes = masked.argtypes[:-6] + [vp, vp, vp, vp, i64, vp]
     L.pqhip_pack_row_mask_dev.restype = i32
     L.pqhip_pack_row_mask_dev.argtypes = [vp, i32, vp, i64, vp, i64, vp, vp]
     L.pqhip_rerank_f32_dev.restype = i32
@@ -181,6 +189,9 @@ EXPORTS = [
     "pqhip_adc_search_lists_masked_f32_dev", "pqhip_adc_ip_search_lists_masked_f32_dev",
     "pqhip_adc_search_lists_residual_masked_f32_dev", "pqhip_adc_ip_search_lists_residual_masked_f32_dev",
     "pqhip_pack_row_mask_dev",
+    "pqhip_adc_range_f32_dev", "pqhip_adc_ip_range_f32_dev",
+    "pqhip_adc_range_lists_f32_dev", "pqhip_adc_ip_range_lists_f32_dev",
+    "pqhip_adc_range_lists_residual_f32_dev", "pqhip_adc_ip_range_lists_residual_f32_dev",
     "pqhip_rerank_f32_dev",
     "pqhip_cluster_assignments_f32", "pqhip_kmeans_iterations_f32", "pqhip_kmeans_iterations_f32_dev",
     "pqhip_opq_train_step_f32_dev", "pqhip_at_dot_b_f32_dev", "pqhip_rotate_f32_dev",

@@ -62,4 +62,15 @@ int32_t adc_search_lists_masked(bool ip, pqhip_codebook* cb, int32_t slot, const
                                 float* d_val, int64_t v_rs, int64_t* d_idx, int64_t i_rs, void* stream, const ListsResidual* res,
                                 const RowMask& mask);
 
+// pqhip_adc.hip: what the range searches (pqhip_adc_range.hip) take from the searches' policy, so that a range call and
+// the search of the same shape make the same choices: the code dwords fetched per row (0: no instantiation), the
+// workgroups that share a query of a list call, the scratch bound of one chunk of queries, and the launch of
+// k_adc_lists_plan -- the only reader of the offsets and probes, for both.
+int search_nv_bucket(int nv);
+int lists_nv_bucket(int nv);
+int64_t lists_wgs_per_query(int64_t n, int64_t n_lists, int64_t n_probe, int64_t nq, int n_cus);
+constexpr size_t kListsScratchBytes = 512u << 20;   // plan + partial lists of one chunk of queries
+int32_t launch_lists_plan(const int64_t* d_list_off, int64_t n_lists, const int64_t* d_probes, int n_probe, int64_t p_rs, int64_t n,
+                          int64_t* seg_begin, int64_t* seg_cum, unsigned nq, int* err, hipStream_t st);
+
 }  // namespace pqh

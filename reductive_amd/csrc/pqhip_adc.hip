@@ -58,7 +58,7 @@ inline int search_list_regs(int k) { int lk = 64; while (lk < k) lk <<= 1; retur
 
 // Code dwords fetched per row on the u8 path: ceil(M / 4) rounded up to one of the instantiated widths (a wider window
 // only reads past the row inside the code matrix -- adc_fetch_row falls back to byte loads at its end).
-inline int search_nv_bucket(int nv)
+int search_nv_bucket(int nv)
 {
     for (int b : {1, 2, 4, 8, 13, kAdcMaxValueWords})
         if (nv <= b) return b;
@@ -325,7 +325,7 @@ int32_t adc_search(pqhip_codebook* cb, int32_t slot, const float* d_tables, int6
 // ListsLaunch: adc_search_launch.h
 
 // Code dwords per row of the list producers: fewer widths than search_nv_bucket (a wider window is always correct)
-inline int lists_nv_bucket(int nv)
+int lists_nv_bucket(int nv)
 {
     for (int b : {4, 8, 13, kAdcMaxValueWords})
         if (nv <= b) return b;
@@ -377,7 +377,7 @@ int32_t launch_lists_u8_l(int L, int nvb, const ListsLaunch& a, const uint8_t* c
 // Workgroups per query, from what the host knows: the expected number of probed rows (lists of average size) in units
 // of 4,096 rows -- below that a workgroup's table load and list merge outweigh its rows, the bound of the exhaustive
 // search -- and no more than the CUs the queries of a launch leave each other (one 1,024-thread workgroup per CU).
-inline int64_t lists_wgs_per_query(int64_t n, int64_t n_lists, int64_t n_probe, int64_t nq, int n_cus)
+int64_t lists_wgs_per_query(int64_t n, int64_t n_lists, int64_t n_probe, int64_t nq, int n_cus)
 {
     const double frac = (double)std::min(n_probe, n_lists) / (double)n_lists;
     const int64_t expected = (int64_t)((double)n * frac) + 1;
@@ -386,7 +386,17 @@ inline int64_t lists_wgs_per_query(int64_t n, int64_t n_lists, int64_t n_probe, 
     return std::max<int64_t>(1, std::min(by_rows, by_cus));
 }
 
-constexpr size_t kListsScratchBytes = 512u << 20;   // plan + partial lists of one chunk of queries
+// kListsScratchBytes (plan + partial lists of one chunk of queries): adc_search_launch.h
+
+int32_t launch_lists_plan(const int64_t* d_list_off, int64_t n_lists, const int64_t* d_probes, int n_probe, int64_t p_rs, int64_t n,
+                          int64_t* seg_begin, int64_t* seg_cum, unsigned nq, int* err, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_adc_lists_plan, dim3(nq), dim3(1024), 0, st, d_list_off, n_lists, d_probes, n_probe, p_rs, n, seg_begin,
+                       seg_cum, err);
+    HIPCHK(hipGetLastError());
+    note_kernel("k_adc_lists_plan");
+    return PQHIP_OK;
+}
 
 // ListsResidual (probe bias rows; the row terms travel in the place of the scales): adc_search_launch.h
 
@@ -444,10 +454,7 @@ int32_t adc_search_lists(pqhip_codebook* cb, int32_t slot, const float* d_tables
     const size_t lds = search_lds(table, 1, L);
     for (int64_t q = 0; q < nq; q += chunk) {
         const unsigned nqc = (unsigned)std::min<int64_t>(chunk, nq - q);
-        hipLaunchKernelGGL(k_adc_lists_plan, dim3(nqc), dim3(1024), 0, st, d_list_off, n_lists, d_probes + q * p_rs, (int)n_probe,
-                           p_rs, n, seg_begin, seg_cum, ef.flag);
-        HIPCHK(hipGetLastError());
-        note_kernel("k_adc_lists_plan");
+        PQCHK(launch_lists_plan(d_list_off, n_lists, d_probes + q * p_rs, (int)n_probe, p_rs, n, seg_begin, seg_cum, nqc, ef.flag, st));
         ListsLaunch a{n, c_rs, (unsigned)G, nqc, M, K, k, (int)n_probe, d_scales, res ? res->bias + q * res->b_rs : nullptr,
                       res ? res->b_rs : 0, seg_begin, seg_cum, part_k, part_i, ef.flag, st, d_allow};
         if (d_allow) PQCHK(mask->lists(IP, L, nvb, a, (const uint8_t*)d_codes, d_tables + q * (int64_t)M * K, lds));

@@ -8,6 +8,7 @@
 //     pqhip_rotate.hip    x.P / r.P^T dispatch (rotation kernels v8 / v9, slab fallback)
 //     pqhip_opq.hip       quantize / reconstruct / lookup on device-resident rows (two-kernel OPQ paths, gather)
 //     pqhip_adc.hip       asymmetric-distance tables and scans
+//     pqhip_adc_range.hip ADC range search: every row within a radius, as CSR
 //     pqhip_rerank.hip    exact re-ranking of search candidates against resident vectors
 //     pqhip_train.hip     k-means iterations, X^T.R, the OPQ training step, resident matrices
 //     pqhip_host.hip      host-resident entry points: row sharding over devices, pinned double-buffered staging
@@ -89,6 +90,8 @@ struct Options {
     std::atomic<int64_t> cross_product_group_bytes{0};   // workspace of partial matrices per launch group (0: 4 GiB; tests shrink it)
     std::atomic<int64_t> candidate_tables{1};       // 0: Pq handles are created without the candidate tables of the 1- / 2-float encode kernel (vor2_prep.h)
     std::atomic<int64_t> rerank_wgs_per_query{0};   // re-ranking: workgroups per query of the distance stage (0: chosen from the shape)
+    std::atomic<int64_t> adc_range_wgs{0};          // exhaustive range search: producer workgroups (0: chosen from the shape)
+    std::atomic<int64_t> adc_range_wgs_per_query{0};   // list range searches: workgroups per query (0: chosen from the shape)
 };
 
 struct Diag {

@@ -1166,6 +1166,160 @@ class Pq:
         return self._adc_search_lists(True, codes, ip_tables, list_off, probes, k, scales, stream, check,
                                       probe_bias=probe_bias, allow=allow)
 
+    # ---- ADC range search: every row within a radius / at or above a similarity, as CSR ------------------------------
+    def _adc_range(self, ip, codes, tables, threshold, scales, stream, check, allow, capacity, lists=None, probe_bias=None,
+                   row_terms=None):
+        """All six range searches -> (lims, val, idx).  lists: (list_off, probes) for the list forms; probe_bias given:
+        the residual ones (row_terms then required for the distance).  The capacity protocol of include/pqhip.h: one call
+        with `capacity` entries (default 1 << 20), one read of lims[-1] -- the only synchronisation -- and, if the result
+        is larger, one more call with exactly that many entries."""
+        import torch
+        residual = probe_bias is not None
+        name = "pqhip_adc_%srange_%s%sf32_dev" % ("ip_" if ip else "", "lists_" if lists is not None else "",
+                                                 "residual_" if residual else "")
+        assert codes.is_cuda and codes.dtype in (torch.uint8, torch.int32) and codes.dim() == 2
+        assert tables.is_cuda and tables.dtype == torch.float32 and tables.is_contiguous()
+        M, K = self.quantized_len(), self.n_quantizer_centroids()
+        if codes.shape[1] != M:
+            raise PanicError("Quantization length does not match number of subquantizers")
+        single = tables.dim() == 2
+        if tuple(tables.shape[-2:]) != (M, K):
+            raise PanicError("lookup tables must be [.., %d, %d]" % (M, K))
+        nq = 1 if single else tables.shape[0]
+        if codes.stride(1) != 1:
+            codes = codes.contiguous()
+        n, dev = codes.shape[0], codes.device
+        if hasattr(threshold, "is_cuda"):
+            thr = threshold.to(dev, torch.float32).reshape(-1)
+        else:
+            thr = torch.from_numpy(np.asarray(threshold, dtype=np.float32).reshape(-1).copy()).to(dev)
+        if thr.shape[0] == 1 and nq != 1:
+            thr = thr.expand(nq)
+        if thr.shape[0] != nq:
+            raise PanicError("one threshold, or one per query (%d), expected" % nq)
+        thr = thr.contiguous()
+        if scales is not None:
+            assert scales.is_cuda and scales.dtype == torch.float32 and scales.is_contiguous()
+            if tuple(scales.shape) != (n,):
+                raise PanicError("scales must hold one value per code row")
+        head = (tables.data_ptr(), nq, codes.data_ptr(), codes.element_size(), n,
+                codes.stride(0) if n > 1 else max(codes.stride(0), M),
+                self._mask_words(allow, codes).data_ptr() if allow is not None else None)
+        keep = []       # tensors made here that the call reads
+        if lists is not None:
+            list_off, probes = lists
+            assert list_off.is_cuda and list_off.dtype == torch.int64 and list_off.dim() == 1 and list_off.is_contiguous()
+            assert probes.is_cuda and probes.dtype == torch.int64 and probes.dim() in (1, 2)
+            pr = probes[None] if probes.dim() == 1 else probes
+            if pr.shape[0] != nq or pr.shape[1] < 1 or list_off.shape[0] < 1:
+                raise PanicError("one probe row of at least one list id per query and n_lists + 1 offsets expected")
+            if pr.stride(1) != 1:
+                pr = pr.contiguous()
+            n_probe = pr.shape[1]
+            head += (list_off.data_ptr(), list_off.shape[0] - 1,
+                     pr.data_ptr(), n_probe, pr.stride(0) if nq > 1 else max(pr.stride(0), n_probe))
+            keep.append(pr)
+            if residual:
+                assert probe_bias.is_cuda and probe_bias.dtype == torch.float32 and probe_bias.dim() in (1, 2)
+                pb = probe_bias[None] if probe_bias.dim() == 1 else probe_bias
+                if tuple(pb.shape) != (nq, n_probe):
+                    raise PanicError("one probe bias per query and probe slot expected")
+                if pb.stride(1) != 1:
+                    pb = pb.contiguous()
+                keep.append(pb)
+                head += (pb.data_ptr(), pb.stride(0) if nq > 1 else max(pb.stride(0), n_probe))
+                if not ip:
+                    assert row_terms.is_cuda and row_terms.dtype == torch.float32 and row_terms.is_contiguous()
+                    if tuple(row_terms.shape) != (n,):
+                        raise PanicError("row_terms must hold one value per code row")
+                    # an empty tensor may have no address, and the C call wants one even when there is no row to read
+                    rt = row_terms if n > 0 else torch.zeros(1, dtype=torch.float32, device=dev)
+                    keep.append(rt)
+                    head += (rt.data_ptr(),)
+        if ip:
+            head += (scales.data_ptr() if scales is not None else None,)
+        cb = self._cb()
+        own_stream = stream is None
+        if own_stream:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        slot = self._slot_for(codes)
+        fn = getattr(_lib.lib(), name)
+        lims = torch.empty(nq + 1, dtype=torch.int64, device=dev)
+        cap = (1 << 20) if capacity is None else int(capacity)
+        if cap < 0:
+            raise PanicError("capacity must not be negative")
+        while True:
+            val = torch.empty(cap, dtype=torch.float32, device=dev)
+            idx = torch.empty(cap, dtype=torch.int64, device=dev)
+            rc = fn(cb, slot, *head, thr.data_ptr(), lims.data_ptr(), val.data_ptr() if cap else None,
+                    idx.data_ptr() if cap else None, cap, ctypes.c_void_p(stream))
+            if rc != _lib.OK:
+                raise _lib.PqHipError(rc, name)
+            if not own_stream:
+                torch.cuda.ExternalStream(stream, device=dev).synchronize()
+            total = int(lims[-1])
+            if total <= cap:
+                break
+            cap = total             # the second call always suffices
+        if check:
+            rc = _lib.lib().pqhip_check_codes_dev(cb, slot, ctypes.c_void_p(stream))
+            if rc == _lib.ECODE_RANGE:
+                raise PanicError("ndarray: index out of bounds")
+            if rc != _lib.OK:
+                raise _lib.PqHipError(rc, "pqhip_check_codes_dev")
+        del keep
+        return lims, val[:total], idx[:total]
+
+    def adc_range_device(self, codes, tables, threshold, stream=None, check=False, allow=None, capacity=None):
+        """EVERY row whose asymmetric squared distance is <= threshold, without the distance matrix: codes (CUDA uint8
+        [n, M]) and tables as for adc_search_device, threshold a scalar or one value per query (float, numpy or tensor)
+        -> (lims, dist, idx): CSR, lims CUDA int64 [nq + 1] ([2] for 2-D tables), the rows of query q at
+        dist[lims[q]:lims[q + 1]] / idx[..] in ascending row index, dist the scan's value bit for bit
+        (pqhip_adc_range_f32_dev).  A NaN distance never qualifies; threshold +Inf returns every non-NaN row.  capacity:
+        entries allocated for the first call (default 1 << 20); if the result is larger the call is repeated once with
+        exactly its size -- lims[-1] is read in between, the one synchronisation.  allow: None or the words of
+        pack_row_mask_device; a disallowed row is not read."""
+        return self._adc_range(False, codes, tables, threshold, None, stream, check, allow, capacity)
+
+    def adc_ip_range_device(self, codes, tables, threshold, scales=None, stream=None, check=False, allow=None,
+                            capacity=None):
+        """Every row whose score fl(scan * scales) (the scan's sum alone without scales) is >= threshold: tables from
+        adc_ip_tables_device, the rest as for adc_range_device -> (lims, score, idx), rows in ascending row index, a zero
+        score with its sign (pqhip_adc_ip_range_f32_dev).  Threshold -Inf returns every non-NaN row."""
+        return self._adc_range(True, codes, tables, threshold, scales, stream, check, allow, capacity)
+
+    def adc_range_lists_device(self, codes, tables, list_off, probes, threshold, stream=None, check=False, allow=None,
+                               capacity=None):
+        """adc_range_device restricted, per query, to the rows of the probed lists (list_off, probes as for
+        adc_search_lists_device) -> (lims, dist, idx); idx are positions in codes and the rows of a query come in the order
+        of the concatenation of its probed lists: probe slot first, then position (pqhip_adc_range_lists_f32_dev)."""
+        return self._adc_range(False, codes, tables, threshold, None, stream, check, allow, capacity, lists=(list_off, probes))
+
+    def adc_ip_range_lists_device(self, codes, tables, list_off, probes, threshold, scales=None, stream=None, check=False,
+                                  allow=None, capacity=None):
+        """adc_ip_range_device restricted to the rows of the probed lists -> (lims, score, idx), order as for
+        adc_range_lists_device (pqhip_adc_ip_range_lists_f32_dev)."""
+        return self._adc_range(True, codes, tables, threshold, scales, stream, check, allow, capacity, lists=(list_off, probes))
+
+    def adc_range_lists_residual_device(self, codes, ip_tables, list_off, probes, probe_bias, row_terms, threshold,
+                                        stream=None, check=False, allow=None, capacity=None):
+        """adc_range_lists_device over residual codes: dist = fl(fl(bias + term) - fl(s + s)) <= threshold, the arguments
+        of adc_search_lists_residual_device with the threshold in the place of k (pqhip_adc_range_lists_residual_f32_dev)."""
+        if probe_bias is None or row_terms is None:
+            raise PanicError("the residual distance search needs a probe bias and the row terms")
+        return self._adc_range(False, codes, ip_tables, threshold, None, stream, check, allow, capacity,
+                               lists=(list_off, probes), probe_bias=probe_bias, row_terms=row_terms)
+
+    def adc_ip_range_lists_residual_device(self, codes, ip_tables, list_off, probes, probe_bias, threshold, scales=None,
+                                           stream=None, check=False, allow=None, capacity=None):
+        """adc_ip_range_lists_device over residual codes: score = fl(fl(bias + s) * scale) >= threshold (fl(bias + s)
+        without scales), the arguments of adc_ip_search_lists_residual_device with the threshold in the place of k
+        (pqhip_adc_ip_range_lists_residual_f32_dev)."""
+        if probe_bias is None:
+            raise PanicError("the residual similarity search needs a probe bias")
+        return self._adc_range(True, codes, ip_tables, threshold, scales, stream, check, allow, capacity,
+                               lists=(list_off, probes), probe_bias=probe_bias)
+
     # ---- exact re-ranking of search candidates against resident vectors ("IVFADC+R") ---------------------------------
     def rerank_device(self, queries, vectors, candidates, k, ip=False, stream=None, check=False):
         """The k best of each query's candidates by their exact distance to the stored vectors: queries CUDA float32

@@ -100,6 +100,18 @@ def read_chunk(f, stream_offset=None, ctx=None):
     return Pq(P, q, ctx=ctx), codes, norms
 
 
+def sort_ranges(lims, val, idx, descending=False):
+    """Order every segment of a CSR range result by value: lims [nq + 1], val / idx flat (torch tensors, CPU or CUDA)
+    -> (val, idx) with segment q, entries lims[q]:lims[q + 1], ascending in val (descending=True: descending); equal
+    values keep the order they came in.  Two stable sorts: by value over all entries, then by segment."""
+    import torch
+    counts = lims[1:] - lims[:-1]
+    seg = torch.repeat_interleave(torch.arange(counts.shape[0], dtype=torch.int64, device=val.device), counts.to(val.device))
+    by_val = torch.sort(val, stable=True, descending=descending).indices
+    order = by_val[torch.sort(seg[by_val], stable=True).indices]
+    return val[order], idx[order]
+
+
 class _Refine:
     """Exact re-ranking against the original vectors, for all three matrix classes: `vectors` is an [N, d] device copy
     in ORIGINAL row order (None until attach_vectors), so the row numbers a search returns address it as they are."""
@@ -252,6 +264,30 @@ class QuantizedMatrix(_Refine, _Filter):
         s, idx = self.pq.adc_ip_search_device(self.codes, self.pq.adc_ip_tables_device(queries), R, scales=scales,
                                               allow=self._allow_words(allow))
         return (s, idx) if refine is None else self._refined(queries, idx, k, True)
+
+    def within(self, queries, radius, allow=None, sort=False):
+        """EVERY row whose asymmetric squared distance to the query is <= radius (a scalar or one value per query) ->
+        (lims, dist, idx): CSR over the queries, lims int64 [nq + 1] ([2] for one query), the rows of query q at
+        lims[q]:lims[q + 1] in ascending row number (Pq.adc_range_device; the result is allocated to its size, after one
+        read of the count).  sort=True: each query's rows ascending in distance instead, ties in row order
+        (sort_ranges).  allow: as for nearest().  There is no refine=: re-ranking is defined for at most 1,024
+        candidates per query, and a range result has no such bound."""
+        lims, d, idx = self.pq.adc_range_device(self.codes, self.pq.adc_tables_device(queries), radius,
+                                                allow=self._allow_words(allow))
+        if sort:
+            d, idx = sort_ranges(lims, d, idx, False)
+        return lims, d, idx
+
+    def similar_above(self, queries, threshold, use_norms=True, allow=None, sort=False):
+        """Every row whose inner product with the query, as most_similar() scores it, is >= threshold (a scalar or one
+        value per query) -> (lims, score, idx), CSR as for within() (Pq.adc_ip_range_device).  sort=True: each query's
+        rows descending in score, ties in row order.  No refine=, as for within()."""
+        scales = self.norms if use_norms else None
+        lims, sc, idx = self.pq.adc_ip_range_device(self.codes, self.pq.adc_ip_tables_device(queries), threshold,
+                                                    scales=scales, allow=self._allow_words(allow))
+        if sort:
+            sc, idx = sort_ranges(lims, sc, idx, True)
+        return lims, sc, idx
 
     def partition(self, n_lists, n_iterations=10, vectors=None, train_rows=None, rng=None):
         """Partition the rows with a coarse k-means quantizer of n_lists centroids -> PartitionedMatrix (IVFADC without
@@ -471,6 +507,30 @@ class PartitionedMatrix(_Lists):
         rows = self._original_rows(pos)
         return (s, rows) if refine is None else self._refined(queries, rows, k, True)
 
+    def within(self, queries, radius, nprobe, allow=None, sort=False):
+        """QuantizedMatrix.within among the rows of the nprobe nearest lists -> (lims, dist, idx), idx original row
+        numbers; the rows of a query come list by list in probe order, inside a list in ascending original row number
+        (Pq.adc_range_lists_device).  sort=True: ascending in distance, ties in that order.  No refine=: re-ranking is
+        defined for at most 1,024 candidates per query."""
+        lims, d, pos = self.pq.adc_range_lists_device(self.codes, self.pq.adc_tables_device(queries), self.list_off,
+                                                      self.probes(queries, nprobe), radius, allow=self._allow_words(allow))
+        rows = self._original_rows(pos)
+        if sort:
+            d, rows = sort_ranges(lims, d, rows, False)
+        return lims, d, rows
+
+    def similar_above(self, queries, threshold, nprobe, use_norms=True, allow=None, sort=False):
+        """QuantizedMatrix.similar_above among the rows of the nprobe nearest lists -> (lims, score, idx), idx original
+        row numbers, order as for within() (Pq.adc_ip_range_lists_device).  sort=True: descending in score."""
+        scales = self.norms if use_norms else None
+        lims, sc, pos = self.pq.adc_ip_range_lists_device(self.codes, self.pq.adc_ip_tables_device(queries), self.list_off,
+                                                          self.probes(queries, nprobe), threshold, scales=scales,
+                                                          allow=self._allow_words(allow))
+        rows = self._original_rows(pos)
+        if sort:
+            sc, rows = sort_ranges(lims, sc, rows, True)
+        return lims, sc, rows
+
     def embeddings(self, rows, out=None):
         """QuantizedMatrix.embeddings of the original row numbers `rows`."""
         import torch
@@ -519,24 +579,57 @@ class ResidualPartitionedMatrix(_Lists):
         rows = self._original_rows(pos)
         return (d, rows) if refine is None else self._refined(queries, rows, k, False)
 
+    def _probes_and_ips(self, queries, nprobe):
+        """(list ids as probes() defines them, <q, c_l> of each: the entry of the coarse inner-product table at the list;
+        at a padded id the entry of list 0, which no result reads)"""
+        import torch
+        pr = self.probes(queries, nprobe)
+        ipt = self.coarse.adc_ip_tables_device(queries)
+        ipt = ipt[0] if queries.dim() == 1 else ipt[:, 0, :]
+        return pr, torch.gather(ipt, -1, pr.clamp(min=0)).contiguous()
+
     def most_similar(self, queries, k, nprobe, use_norms=True, refine=None, allow=None):
         """the k rows of largest score = fl(fl(bias + s) * norm) (fl(bias + s) with use_norms=False or without norms)
         among the rows of the nprobe nearest lists, bias the entry of coarse.adc_ip_tables_device(queries)[:, 0, :] at
         the row's list, i.e. <q, c_l> -> (score, idx), idx original row numbers, -1 past the last probed row (-Inf).
         refine=R: the R first rows are re-ranked by their exact inner product with the attached vectors as they are;
         use_norms then only affects the candidate stage.  allow: as for PartitionedMatrix.nearest."""
-        import torch
         R = k if refine is None else self._check_refine(k, refine)
-        pr = self.probes(queries, nprobe)
-        ipt = self.coarse.adc_ip_tables_device(queries)
-        ipt = ipt[0] if queries.dim() == 1 else ipt[:, 0, :]
-        bias = torch.gather(ipt, -1, pr.clamp(min=0)).contiguous()
+        pr, bias = self._probes_and_ips(queries, nprobe)
         scales = self.norms if use_norms else None
         s, pos = self.pq.adc_ip_search_lists_residual_device(self.codes, self.pq.adc_ip_tables_device(queries),
                                                              self.list_off, pr, bias, R, scales=scales,
                                                              allow=self._allow_words(allow))
         rows = self._original_rows(pos)
         return (s, rows) if refine is None else self._refined(queries, rows, k, True)
+
+    def within(self, queries, radius, nprobe, allow=None, sort=False):
+        """every row of the nprobe nearest lists with dist = fl(fl(bias + row_term) - fl(s + s)) <= radius, bias obtained
+        exactly as nearest() obtains it -> (lims, dist, idx), idx original row numbers, rows list by list in probe order
+        (Pq.adc_range_lists_residual_device).  sort=True: ascending in distance.  No refine=: re-ranking is defined for
+        at most 1,024 candidates per query."""
+        pr, bias = self._probes_and_dists(queries, nprobe)
+        lims, d, pos = self.pq.adc_range_lists_residual_device(self.codes, self.pq.adc_ip_tables_device(queries),
+                                                               self.list_off, pr, bias, self.row_terms, radius,
+                                                               allow=self._allow_words(allow))
+        rows = self._original_rows(pos)
+        if sort:
+            d, rows = sort_ranges(lims, d, rows, False)
+        return lims, d, rows
+
+    def similar_above(self, queries, threshold, nprobe, use_norms=True, allow=None, sort=False):
+        """every row of the nprobe nearest lists with score = fl(fl(bias + s) * norm) >= threshold (fl(bias + s) with
+        use_norms=False or without norms), bias obtained exactly as most_similar() obtains it -> (lims, score, idx)
+        (Pq.adc_ip_range_lists_residual_device).  sort=True: descending in score."""
+        pr, bias = self._probes_and_ips(queries, nprobe)
+        scales = self.norms if use_norms else None
+        lims, sc, pos = self.pq.adc_ip_range_lists_residual_device(self.codes, self.pq.adc_ip_tables_device(queries),
+                                                                   self.list_off, pr, bias, threshold, scales=scales,
+                                                                   allow=self._allow_words(allow))
+        rows = self._original_rows(pos)
+        if sort:
+            sc, rows = sort_ranges(lims, sc, rows, True)
+        return lims, sc, rows
 
     def embeddings(self, rows):
         """fl(fl(r^ + c_l) * norm) of the original row numbers `rows` (fl(r^ + c_l) without norms) -> [len(rows), d]."""

@@ -116,6 +116,39 @@ extern "C" {
     // builds the mask words on the device: bit p = d_allow_bytes[d_perm ? d_perm[p] : p] != 0, tail bits 0
     pub fn pqhip_pack_row_mask_dev(cb: *mut pqhip_codebook, device_slot: i32, d_allow_bytes: *const u8, n_src: i64,
         d_perm: *const i64, n: i64, d_words: *mut u32, stream: *mut c_void) -> i32;
+    // range searches: every row with dist <= threshold[q] resp. score >= threshold[q] as CSR (lims [n_queries + 1],
+    // val / idx of `capacity` entries; lims always holds the true counts, entries at or beyond capacity are not written);
+    // d_allow NULL or a row mask; options "adc_range_wgs", "adc_range_wgs_per_query" force the grids
+    pub fn pqhip_adc_range_f32_dev(cb: *mut pqhip_codebook, device_slot: i32, d_tables: *const f32,
+        n_queries: i64, d_codes: *const c_void, code_bytes: i32, n_codes: i64, codes_row_stride: i64,
+        d_allow: *const u32, d_threshold: *const f32, d_lims: *mut i64, d_val: *mut f32, d_idx: *mut i64,
+        capacity: i64, stream: *mut c_void) -> i32;
+    pub fn pqhip_adc_ip_range_f32_dev(cb: *mut pqhip_codebook, device_slot: i32, d_tables: *const f32,
+        n_queries: i64, d_codes: *const c_void, code_bytes: i32, n_codes: i64, codes_row_stride: i64,
+        d_allow: *const u32, d_scales: *const f32, d_threshold: *const f32, d_lims: *mut i64, d_val: *mut f32, d_idx: *mut i64,
+        capacity: i64, stream: *mut c_void) -> i32;
+    pub fn pqhip_adc_range_lists_f32_dev(cb: *mut pqhip_codebook, device_slot: i32, d_tables: *const f32,
+        n_queries: i64, d_codes: *const c_void, code_bytes: i32, n_codes: i64, codes_row_stride: i64,
+        d_allow: *const u32, d_list_off: *const i64, n_lists: i64, d_probes: *const i64, n_probe: i32,
+        probes_row_stride: i64, d_threshold: *const f32, d_lims: *mut i64, d_val: *mut f32, d_idx: *mut i64,
+        capacity: i64, stream: *mut c_void) -> i32;
+    pub fn pqhip_adc_ip_range_lists_f32_dev(cb: *mut pqhip_codebook, device_slot: i32, d_tables: *const f32,
+        n_queries: i64, d_codes: *const c_void, code_bytes: i32, n_codes: i64, codes_row_stride: i64,
+        d_allow: *const u32, d_list_off: *const i64, n_lists: i64, d_probes: *const i64, n_probe: i32,
+        probes_row_stride: i64, d_scales: *const f32, d_threshold: *const f32, d_lims: *mut i64, d_val: *mut f32, d_idx: *mut i64,
+        capacity: i64, stream: *mut c_void) -> i32;
+    pub fn pqhip_adc_range_lists_residual_f32_dev(cb: *mut pqhip_codebook, device_slot: i32, d_tables: *const f32,
+        n_queries: i64, d_codes: *const c_void, code_bytes: i32, n_codes: i64, codes_row_stride: i64,
+        d_allow: *const u32, d_list_off: *const i64, n_lists: i64, d_probes: *const i64, n_probe: i32,
+        probes_row_stride: i64, d_probe_bias: *const f32, bias_row_stride: i64, d_row_terms: *const f32,
+        d_threshold: *const f32, d_lims: *mut i64, d_val: *mut f32, d_idx: *mut i64,
+        capacity: i64, stream: *mut c_void) -> i32;
+    pub fn pqhip_adc_ip_range_lists_residual_f32_dev(cb: *mut pqhip_codebook, device_slot: i32, d_tables: *const f32,
+        n_queries: i64, d_codes: *const c_void, code_bytes: i32, n_codes: i64, codes_row_stride: i64,
+        d_allow: *const u32, d_list_off: *const i64, n_lists: i64, d_probes: *const i64, n_probe: i32,
+        probes_row_stride: i64, d_probe_bias: *const f32, bias_row_stride: i64, d_scales: *const f32,
+        d_threshold: *const f32, d_lims: *mut i64, d_val: *mut f32, d_idx: *mut i64,
+        capacity: i64, stream: *mut c_void) -> i32;
     // exact re-ranking of candidates against resident f32 / f16 vectors (metric 0 = squared L2, 1 = inner product)
     pub fn pqhip_rerank_f32_dev(cb: *mut pqhip_codebook, device_slot: i32, d_queries: *const f32, n_queries: i64,
         q_row_stride: i64, d_vectors: *const c_void, vec_bytes: i32, n_rows: i64, d: i64, vec_row_stride: i64,
