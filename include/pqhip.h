@@ -505,6 +505,39 @@ int32_t pqhip_rerank_f32_dev(pqhip_codebook *cb, int32_t device_slot,
                              int32_t metric /* 0 = squared L2, 1 = inner product */, int32_t k,
                              float *d_val, int64_t val_row_stride, int64_t *d_idx, int64_t idx_row_stride, void *stream);
 
+/*
+ * Merge of two list-ordered row arrays: the primitive under growing a partitioned matrix (rows added to an index, two
+ * indexes over the same lists joined).  d_a is [n_a] rows of row_bytes bytes in list order under d_off_a [n_lists + 1]
+ * (list l = rows off_a[l] .. off_a[l + 1] - 1), d_b likewise [n_b] rows under d_off_b; d_out is [n_a + n_b] rows.  For
+ * every list l the output rows from off_a[l] + off_b[l] on are the rows a[off_a[l] : off_a[l + 1]] followed by the rows
+ * b[off_b[l] : off_b[l + 1]], copied byte for byte; d_off_out, if given, receives off_out[l] = off_a[l] + off_b[l] for
+ * l in [0, n_lists], the offsets of the merged lists.  Rows are contiguous: the stride of all three arrays is row_bytes.
+ * None of the three base pointers needs any alignment (stores are 16 bytes wide on the 16-byte grid of the destination
+ * address whatever it is; the sources are read at the byte addresses they have).  d_out must not overlap an input.
+ * cb supplies the device slot, the scratch and the stream's range flag, as for pqhip_rerank_f32_dev; its quantizer is
+ * not read.
+ * The offsets are device memory and are NOT TRUSTED.  An offset array is valid iff off[0] == 0, it is non-decreasing
+ * and off[n_lists] == n.  If either array is invalid, no byte of d_out is written, no byte outside the inputs is read
+ * (no row is read at all), the stream's range flag is raised (pqhip_check_codes_dev -> PQHIP_ECODE_RANGE) and the
+ * contents of d_off_out are unspecified.  A small plan kernel is the only reader of the offsets; it writes the table
+ * of the 2 n_lists output segments into the codebook's scratch, and the mover -- each workgroup a contiguous slice of
+ * the output bytes -- runs only behind a valid plan.  The value of an output byte depends on its position alone: the
+ * result does not depend on the number of workgroups (chosen from the size and the CU count; option "lists_merge_wgs"
+ * forces it).
+ * Status codes: a null cb, a negative count, row_bytes < 1, n_lists == 0 with n_a + n_b > 0: PQHIP_EINVAL; then the
+ * slot (PQHIP_ENODEV); row_bytes > PQHIP_LISTS_MERGE_MAX_ROW_BYTES, n_lists > PQHIP_LISTS_MERGE_MAX_LISTS (the plan is
+ * one workgroup, the table 32 bytes per list) or more than 2^49 rows in an input: PQHIP_EUNSUPPORTED; with n_a + n_b > 0
+ * a null d_off_a, d_off_b or d_out, a null d_a with n_a > 0 or a null d_b with n_b > 0: PQHIP_EINVAL.  n_a + n_b == 0
+ * writes d_off_out (all zeros; the offsets are not read) and launches no kernel.  Asynchronous on `stream`.
+ */
+#define PQHIP_LISTS_MERGE_MAX_ROW_BYTES 4096
+#define PQHIP_LISTS_MERGE_MAX_LISTS 1048576
+int32_t pqhip_lists_merge_dev(pqhip_codebook *cb, int32_t device_slot,
+                              const int64_t *d_off_a, int64_t n_a,
+                              const int64_t *d_off_b, int64_t n_b, int64_t n_lists,
+                              int64_t row_bytes, const void *d_a, const void *d_b, void *d_out,
+                              int64_t *d_off_out /* or NULL */, void *stream);
+
 /* Reconstruct's range check is asynchronous on the device path: returns PQHIP_ECODE_RANGE if any
  * device call since the last query saw a code >= K (synchronises `stream`). */
 int32_t pqhip_check_codes_dev(pqhip_codebook *cb, int32_t device_slot, void *stream);
@@ -640,6 +673,8 @@ int32_t pqhip_set_rotation_variant(int32_t variant);
  *                          so that the one-workgroup prefix scan of a pass sums at most 2^20 counts)
  *   "adc_range_wgs_per_query"  workgroups that share one query of the list range searches (0 = chosen from the shape; at
  *                          most 4096, as "adc_lists_wgs_per_query")
+ *   "lists_merge_wgs"      workgroups of the mover of pqhip_lists_merge_dev (0 = chosen from the size and the CU count; at
+ *                          most 2^20, and never more than one per 1,024 16-byte chunks of output)
  *   "rerank_wgs_per_query" workgroups that share one query in the distance stage of pqhip_rerank_f32_dev (0 = chosen from the
  *                          shape; at most 1024)
  *   "cross_product_exact"  0 = X^T.R of the OPQ training step / pqhip_at_dot_b_f32_dev as a plain split-K product:

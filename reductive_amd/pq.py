@@ -1387,3 +1387,61 @@ class Pq:
             if rc != _lib.OK:
                 raise _lib.PqHipError(rc, "pqhip_check_codes_dev")
         return (val[0], idx[0]) if single else (val, idx)
+
+    # ---- growing a partitioned matrix: merge of two list-ordered arrays ------------------------------------------------
+    def merge_lists_device(self, list_off_a, a, list_off_b, b, out=None, stream=None, check=False):
+        """a, b: CUDA tensors of one dtype, [n_a] / [n_b] or [n_a, c] / [n_b, c], contiguous, their rows in list order
+        under list_off_a / list_off_b (CUDA int64 [n_lists + 1]) -> (out, list_off_out): out [n_a + n_b(, c)] holds, for
+        every list, its rows of a followed by its rows of b, copied byte for byte (a row is element size x c bytes, at
+        most 4,096); list_off_out = list_off_a + list_off_b (pqhip_lists_merge_dev).  None of the tensors needs any
+        alignment; out, if given, must not overlap an input.  The offsets are checked on the device: if one of them
+        does not start at 0, decreases somewhere or does not end at the number of rows, out is left as it was and
+        the stream's range flag is raised (check=True: synchronises and raises PanicError).  The quantizer of self is
+        not used."""
+        import torch
+        for t, what in ((list_off_a, "list_off_a"), (a, "a"), (list_off_b, "list_off_b"), (b, "b")):
+            if not hasattr(t, "is_cuda"):
+                raise PanicError("%s must be a torch tensor" % what)
+        if a.dtype != b.dtype:
+            raise PanicError("a and b must have one dtype, got %s and %s" % (a.dtype, b.dtype))
+        if a.dim() not in (1, 2) or b.dim() != a.dim() or tuple(a.shape[1:]) != tuple(b.shape[1:]):
+            raise PanicError("a and b must be vectors, or matrices with the same number of columns")
+        if list_off_a.dtype != torch.int64 or list_off_b.dtype != torch.int64 or list_off_a.dim() != 1 \
+                or list_off_a.shape != list_off_b.shape or list_off_a.shape[0] < 1:
+            raise PanicError("the list offsets must be two int64 vectors of one length, n_lists + 1")
+        n_a, n_b, n_lists = a.shape[0], b.shape[0], list_off_a.shape[0] - 1
+        shape = (n_a + n_b,) + tuple(a.shape[1:])
+        row_bytes = a.element_size() * (a.shape[1] if a.dim() == 2 else 1)
+        if not 1 <= row_bytes <= 4096:
+            raise PanicError("a row must have between 1 and 4096 bytes, has %d" % row_bytes)
+        if n_lists == 0 and n_a + n_b > 0:
+            raise PanicError("rows need at least one list")
+        if out is not None and (not hasattr(out, "is_cuda") or out.dtype != a.dtype or tuple(out.shape) != shape):
+            raise PanicError("out must be a %s tensor of shape %s" % (a.dtype, list(shape)))
+        for t in (a, b, list_off_a, list_off_b) + (() if out is None else (out,)):
+            if not t.is_contiguous():
+                raise PanicError("merge_lists_device takes contiguous tensors")
+        if not (a.is_cuda and b.is_cuda and list_off_a.is_cuda and list_off_b.is_cuda and (out is None or out.is_cuda)):
+            raise PanicError("merge_lists_device takes CUDA tensors")
+        if not (a.device == b.device == list_off_a.device == list_off_b.device and (out is None or out.device == a.device)):
+            raise PanicError("all tensors of a merge must live on one device")
+        if out is None:
+            out = torch.empty(shape, dtype=a.dtype, device=a.device)
+        off_out = torch.empty(n_lists + 1, dtype=torch.int64, device=a.device)
+        cb = self._cb()
+        if stream is None:
+            stream = torch.cuda.current_stream(a.device).cuda_stream
+        slot = self._slot_for(a)
+        rc = _lib.lib().pqhip_lists_merge_dev(
+            cb, slot, list_off_a.data_ptr(), n_a, list_off_b.data_ptr(), n_b, n_lists, row_bytes,
+            a.data_ptr() if n_a else None, b.data_ptr() if n_b else None, out.data_ptr() if n_a + n_b else None,
+            off_out.data_ptr(), ctypes.c_void_p(stream))
+        if rc != _lib.OK:
+            raise _lib.PqHipError(rc, "pqhip_lists_merge_dev")
+        if check:
+            rc = _lib.lib().pqhip_check_codes_dev(cb, slot, ctypes.c_void_p(stream))
+            if rc == _lib.ECODE_RANGE:
+                raise PanicError("ndarray: index out of bounds")
+            if rc != _lib.OK:
+                raise _lib.PqHipError(rc, "pqhip_check_codes_dev")
+        return out, off_out

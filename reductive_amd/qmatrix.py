@@ -112,6 +112,39 @@ def sort_ranges(lims, val, idx, descending=False):
     return val[order], idx[order]
 
 
+def _device_rows(vectors, width, dev, what="vectors"):
+    """vectors [B, width] (numpy or torch, any float dtype torch converts) -> float32 [B, width] on `dev`, contiguous"""
+    import torch
+    if len(vectors.shape) != 2 or vectors.shape[1] != width:
+        raise PanicError("%s must be [B, %d]" % (what, width))
+    if not hasattr(vectors, "is_cuda"):
+        vectors = torch.from_numpy(np.ascontiguousarray(vectors, dtype=np.float32))
+    return vectors.to(dev, torch.float32).contiguous()
+
+
+def _batch_norms(norms, has_norms, B, dev):
+    """the norms= of an add(): required iff the matrix has norms -> float32 [B] on `dev`, or None"""
+    import torch
+    if (norms is not None) != has_norms:
+        raise PanicError("norms are required for a matrix with norms and forbidden for one without")
+    if norms is None:
+        return None
+    if not hasattr(norms, "is_cuda"):
+        norms = torch.from_numpy(np.ascontiguousarray(norms, dtype=np.float32))
+    if tuple(norms.shape) != (B,):
+        raise PanicError("one norm per added vector expected")
+    return norms.to(dev, torch.float32).contiguous()
+
+
+def _residual_codes_terms(residual_pq, rows, c, codes_out):
+    """What a residual matrix stores for `rows` [n, d] f32 of the lists whose centroids are `c` [n, d] (device tensors):
+    the codes of rows - c go to codes_out [n, M]; returns the query-free terms t_i = sum_j (r^_ij^2 + 2 c_ij r^_ij),
+    accumulated in float64 and rounded once to f32.  The loop body of partition_residual and of encode()."""
+    residual_pq.quantize_batch_device(rows - c, out=codes_out)
+    r = residual_pq.reconstruct_batch_device(codes_out).double()
+    return (r * r + 2.0 * c.double() * r).sum(1).float()
+
+
 class _Refine:
     """Exact re-ranking against the original vectors, for all three matrix classes: `vectors` is an [N, d] device copy
     in ORIGINAL row order (None until attach_vectors), so the row numbers a search returns address it as they are."""
@@ -289,6 +322,26 @@ class QuantizedMatrix(_Refine, _Filter):
             sc, idx = sort_ranges(lims, sc, idx, True)
         return lims, sc, idx
 
+    def add(self, vectors, norms=None):
+        """The matrix with the rows of `vectors` ([B, d] float32, numpy or CUDA) appended as rows len(self) .. len(self) +
+        B - 1 -> a NEW QuantizedMatrix; self is left as it is (and so are the row filters built for it, which the new
+        matrix refuses).  The codes are quantize_batch_device of the vectors; norms [B] is required iff the matrix has
+        norms.  Attached vectors are extended by the new ones in the attached dtype."""
+        import torch
+        dev = self.codes.device
+        x = _device_rows(vectors, self.pq.reconstructed_len(), dev)
+        nb = _batch_norms(norms, self.norms is not None, x.shape[0], dev)
+        new = object.__new__(type(self))
+        new.pq = self.pq
+        codes = self.pq.quantize_batch_device(x) if x.shape[0] else self.codes[:0]
+        if codes.dtype != self.codes.dtype:
+            raise PanicError("the matrix holds 1-byte codes")
+        new.codes = torch.cat([self.codes, codes])
+        new.norms = None if nb is None else torch.cat([self.norms, nb])
+        if self.vectors is not None:
+            new.vectors = torch.cat([self.vectors, x.to(self.vectors.dtype)])
+        return new
+
     def partition(self, n_lists, n_iterations=10, vectors=None, train_rows=None, rng=None):
         """Partition the rows with a coarse k-means quantizer of n_lists centroids -> PartitionedMatrix (IVFADC without
         residual encoding: the codes stay the codes of the vectors themselves).
@@ -388,10 +441,7 @@ class QuantizedMatrix(_Refine, _Filter):
         chunk = 1 << 20
         for r0 in range(0, N, chunk):
             r1 = min(N, r0 + chunk)
-            c = cd[ad[r0:r1]]
-            residual_pq.quantize_batch_device(rows_of(slice(r0, r1)) - c, out=codes[r0:r1])
-            r = residual_pq.reconstruct_batch_device(codes[r0:r1]).double()
-            terms[r0:r1] = (r * r + 2.0 * c.double() * r).sum(1).float()
+            terms[r0:r1] = _residual_codes_terms(residual_pq, rows_of(slice(r0, r1)), cd[ad[r0:r1]], codes[r0:r1])
         out = ResidualPartitionedMatrix(residual_pq, codes, self.norms, terms, centroids, assign)
         out.vectors = self.vectors
         return out
@@ -464,6 +514,80 @@ class _Lists(_Refine, _Filter):
         import torch
         return torch.where(pos < 0, pos, self.ids[pos.clamp(min=0)])
 
+    # ---- growth: every method returns a NEW matrix and leaves self (and the row filters built for it) untouched ----
+    def assign(self, vectors):
+        """the list of each vector ([B, d] float32, numpy or CUDA) -> int64 [B] on the device: the nearest centroid, as
+        cluster_assignments(self.centroids, vectors) gives it row for row (the encode kernels of the one-subquantizer
+        coarse codebook with a 4-byte index, entirely on the device)"""
+        import torch
+        x = _device_rows(vectors, self.centroids.shape[1], self.codes.device)
+        out = torch.empty((x.shape[0], 1), dtype=torch.int32, device=x.device)
+        chunk = 1 << 20
+        for r0 in range(0, x.shape[0], chunk):
+            self.coarse.quantize_batch_device(x[r0:r0 + chunk], out=out[r0:r0 + chunk])
+        return out[:, 0].long()
+
+    _ROW_ARRAYS = ("codes", "norms")          # what a matrix stores per row, in list order, beside ids
+
+    def _shell(self):
+        """a matrix of this class that shares what growth does not change: quantizers, centroids, probe selection"""
+        new = object.__new__(type(self))
+        for name in ("pq", "centroids", "n_lists", "coarse", "_list_ids", "_centroids_dev"):
+            if hasattr(self, name):
+                setattr(new, name, getattr(self, name))
+        return new
+
+    def _piece(self, assign, vectors, **row_arrays):
+        """A batch laid out as a matrix of this class over the same lists: `assign` int64 [B] on the device, row_arrays
+        the per-row arrays in batch order (None where the matrix has none).  B-sized torch operations only: a stable
+        sort of the list ids, bincount and cumsum -- ivf_layout on the device."""
+        import torch
+        dev = assign.device
+        p = self._shell()
+        p.ids = torch.sort(assign, stable=True).indices
+        p.list_off = torch.zeros(self.n_lists + 1, dtype=torch.int64, device=dev)
+        p.list_off[1:] = torch.cumsum(torch.bincount(assign, minlength=self.n_lists), 0)
+        p.positions = torch.empty_like(p.ids)
+        p.positions[p.ids] = torch.arange(assign.shape[0], dtype=torch.int64, device=dev)
+        for name, t in row_arrays.items():
+            setattr(p, name, None if t is None else t[p.ids].contiguous())
+        p.vectors = vectors
+        return p
+
+    def extend(self, other):
+        """The matrix that holds the rows of self followed by the rows of `other`, a matrix of the same class over the
+        same lists (equal pq, equal centroids, norms in both or in neither; PanicError otherwise) -> a NEW matrix; the
+        rows of other are renumbered from len(self).  List l of the result is list l of self followed by list l of
+        other, which is what the constructor builds from the concatenated rows and assignments: every stored array is
+        merged on the device (Pq.merge_lists_device), positions are rebuilt by a scatter, and nothing of length N
+        goes to the host or through a sort.  Attached vectors are concatenated, in the dtype of self, if both
+        matrices have them, and dropped otherwise.  Row filters are not carried over."""
+        import torch
+        if type(other) is not type(self):
+            raise PanicError("only a matrix of the same class can be merged")
+        if not (other.pq == self.pq) or not np.array_equal(other.centroids, self.centroids):
+            raise PanicError("the matrices must share the quantizer and the centroids of the lists")
+        if (other.norms is None) != (self.norms is None):
+            raise PanicError("either both matrices have norms or neither")
+        if other.codes.device != self.codes.device or other.codes.dtype != self.codes.dtype:
+            raise PanicError("the matrices must live on one device and hold codes of one width")
+        new = self._shell()
+        merge = self.pq.merge_lists_device
+        new.ids, new.list_off = merge(self.list_off, self.ids, other.list_off, other.ids + len(self))
+        for name in self._ROW_ARRAYS:
+            mine = getattr(self, name)
+            setattr(new, name, None if mine is None else merge(self.list_off, mine, other.list_off, getattr(other, name))[0])
+        new.positions = torch.empty_like(new.ids)
+        new.positions[new.ids] = torch.arange(new.ids.shape[0], dtype=torch.int64, device=new.ids.device)
+        if self.vectors is not None and other.vectors is not None:
+            new.vectors = torch.cat([self.vectors, other.vectors.to(self.vectors.device, self.vectors.dtype)])
+        return new
+
+    def _add_encoded(self, x, norms, assign, **row_arrays):
+        """add() of both classes: extend() applied to the batch laid out as a piece"""
+        nb = _batch_norms(norms, self.norms is not None, x.shape[0], x.device)
+        return self.extend(self._piece(assign, x if self.vectors is not None else None, norms=nb, **row_arrays))
+
 
 class PartitionedMatrix(_Lists):
     """A QuantizedMatrix whose rows are grouped by a coarse quantizer: list l holds the rows nearest to centroid l,
@@ -530,6 +654,15 @@ class PartitionedMatrix(_Lists):
         if sort:
             sc, rows = sort_ranges(lims, sc, rows, True)
         return lims, sc, rows
+
+    def add(self, vectors, norms=None):
+        """The matrix with `vectors` ([B, d] float32, numpy or CUDA) added as rows len(self) .. len(self) + B - 1 -> a NEW
+        PartitionedMatrix: each vector goes to the end of the list assign() names, stored as quantize_batch_device
+        encodes it.  The result is, tensor for tensor, the matrix the constructor builds from all rows in row order.
+        norms [B] is required iff the matrix has norms.  Attached vectors are extended in the attached dtype."""
+        x = _device_rows(vectors, self.pq.reconstructed_len(), self.codes.device)
+        codes = self.pq.quantize_batch_device(x) if x.shape[0] else self.codes[:0]
+        return self._add_encoded(x, norms, self.assign(x), codes=codes)
 
     def embeddings(self, rows, out=None):
         """QuantizedMatrix.embeddings of the original row numbers `rows`."""
@@ -630,6 +763,33 @@ class ResidualPartitionedMatrix(_Lists):
         if sort:
             sc, rows = sort_ranges(lims, sc, rows, True)
         return lims, sc, rows
+
+    _ROW_ARRAYS = ("codes", "norms", "row_terms", "lists")
+
+    def encode(self, vectors):
+        """What the matrix would store for `vectors` ([B, d] float32, numpy or CUDA) -> (lists int64 [B], codes u8 [B, M],
+        row_terms f32 [B]) on the device: the list assign() names, the code of the f32 residual against that list's
+        centroid, and the row's query-free term -- the loop body of partition_residual."""
+        import torch
+        x = _device_rows(vectors, self.pq.reconstructed_len(), self.codes.device)
+        lists = self.assign(x)
+        codes = torch.empty((x.shape[0], self.pq.quantized_len()), dtype=torch.uint8, device=x.device)
+        terms = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
+        chunk = 1 << 20
+        for r0 in range(0, x.shape[0], chunk):
+            r1 = min(x.shape[0], r0 + chunk)
+            terms[r0:r1] = _residual_codes_terms(self.pq, x[r0:r1], self._centroids_dev[lists[r0:r1]], codes[r0:r1])
+        return lists, codes, terms
+
+    def add(self, vectors, norms=None):
+        """The matrix with `vectors` ([B, d] float32, numpy or CUDA) added as rows len(self) .. len(self) + B - 1 -> a NEW
+        ResidualPartitionedMatrix: each vector goes to the end of its list, stored as encode() gives it.  The result
+        is, tensor for tensor, the matrix the constructor builds from all rows in row order.  norms [B] is required
+        iff the matrix has norms.  Attached vectors are extended in the attached dtype.  Neither quantizer is
+        re-trained."""
+        x = _device_rows(vectors, self.pq.reconstructed_len(), self.codes.device)
+        lists, codes, terms = self.encode(x)
+        return self._add_encoded(x, norms, lists, codes=codes, row_terms=terms, lists=lists)
 
     def embeddings(self, rows):
         """fl(fl(r^ + c_l) * norm) of the original row numbers `rows` (fl(r^ + c_l) without norms) -> [len(rows), d]."""

@@ -154,6 +154,12 @@ extern "C" {
         q_row_stride: i64, d_vectors: *const c_void, vec_bytes: i32, n_rows: i64, d: i64, vec_row_stride: i64,
         d_cand: *const i64, n_cand: i32, cand_row_stride: i64, metric: i32, k: i32, d_val: *mut f32,
         val_row_stride: i64, d_idx: *mut i64, idx_row_stride: i64, stream: *mut c_void) -> i32;
+    // merge of two list-ordered row arrays: list l of d_out = list l of d_a, then list l of d_b (rows of row_bytes bytes,
+    // any alignment); the offsets are validated on the device (invalid: nothing written, the stream's range flag raised);
+    // d_off_out NULL or [n_lists + 1]; option "lists_merge_wgs" forces the grid
+    pub fn pqhip_lists_merge_dev(cb: *mut pqhip_codebook, device_slot: i32, d_off_a: *const i64, n_a: i64,
+        d_off_b: *const i64, n_b: i64, n_lists: i64, row_bytes: i64, d_a: *const c_void, d_b: *const c_void,
+        d_out: *mut c_void, d_off_out: *mut i64, stream: *mut c_void) -> i32;
 }
 
 /// Batches smaller than this stay on the CPU path (a launch + PCIe round trip is pointless).
