@@ -378,6 +378,90 @@ int32_t pqhip_pack_row_mask_dev(pqhip_codebook *cb, int32_t device_slot,
                                 uint32_t *d_words, void *stream);
 
 /*
+ * 4-bit packed codes: two codes per byte for quantizers with K <= 16 centroids, and the six top-k searches over them.
+ * Format.  A packed row of M codes is PB = ceil(M / 2) bytes.  Code m lives in byte m >> 1: the low nibble holds even m
+ * and the high nibble holds odd m.  For odd M the high nibble of the last byte is written as 0 by the packer and IGNORED
+ * by every reader: it enters no sum and raises no flag whatever it holds.  Rows are packed_row_stride >= PB bytes apart.
+ * No alignment is required of the base pointer or of the stride (M = 5 gives 3-byte rows at odd addresses).  Only
+ * quantizers with K <= 16 are served; K need not be 16 or a power of two.  A nibble >= K in a row that is read raises the
+ * stream's range flag (pqhip_check_codes_dev -> PQHIP_ECODE_RANGE) and reads entry 0, as a byte code >= K does.
+ *
+ * pqhip_pack_codes4_dev packs d_codes [n][M] (code_bytes 1 or 4, codes_row_stride in elements) into d_packed.  A code
+ * >= K packs as 0 and raises the range flag.  Only the PB bytes of each row are written: bytes between PB and the stride
+ * are left alone.
+ * pqhip_unpack_codes4_dev writes u8 codes [*][M] (out_row_stride >= M bytes).  d_rows == NULL: all n rows in order
+ * (n_rows is ignored).  Else d_rows is int64 [n_rows] and row r of the output is packed row d_rows[r]; a row id outside
+ * [0, n) writes a zero row and raises the range flag.  Nibbles are copied as they are (no range check); the pad nibble of
+ * an odd M is not emitted.
+ * Both: a null cb or a negative count PQHIP_EINVAL; the slot PQHIP_ENODEV; K > 16, code_bytes not 1 or 4, or more than
+ * 2^39 output bytes (one launch) PQHIP_EUNSUPPORTED; nothing to write: PQHIP_OK without a launch; then null buffers
+ * PQHIP_EINVAL and a stride below the row PQHIP_ESHAPE.  Asynchronous on `stream`.
+ *
+ * The six searches: each is the _masked search of the same name with (d_packed, n_codes, packed_row_stride) in the place
+ * of (d_codes, code_bytes, n_codes, codes_row_stride).  d_allow may be NULL for no filter.  The tables are the ones
+ * pqhip_adc_tables_f32_dev / pqhip_adc_ip_tables_f32_dev produce ([n_queries][M][K]).
+ * Definition: the result of a packed call equals, bit for bit, values and indices and padding, the result of the corresponding existing entry point on the unpacked u8 codes with the same tables, probes, biases, row terms, scales and mask.
+ * The row sum stays the sequential f32 chain over m = 0 .. M-1 from +0, one table entry per code.  Order key, NaN and zero
+ * handling, -1 probes, bad ids, clamped and inverted ranges, disallowed rows not being read, the independence from the
+ * grid and from the queries per pass, scratch and chunking are all inherited.
+ * Status codes, in the precedence of pqhip_adc_search_f32_dev (EINVAL, ENODEV, EUNSUPPORTED, then nq == 0, null buffers,
+ * ESHAPE): K > 16, M > 100 (13 packed dwords per row) or k > 1024 is PQHIP_EUNSUPPORTED; packed_row_stride < PB (with
+ * n_codes > 0) is PQHIP_ESHAPE; the list calls keep their own limits (n_codes <= 2^32 - 2, n_probe < 2^24).  Anything
+ * not served is PQHIP_EUNSUPPORTED, never another path.
+ * Host policy: queries per pass (8 / 4 / 1, option "adc_single_query"), list length, grid and workgroups per query
+ * (option "adc_lists_wgs_per_query") are chosen as for the u8 searches; option "adc_packed4_wgs" forces the producer
+ * workgroups of the exhaustive packed calls.
+ */
+int32_t pqhip_pack_codes4_dev(pqhip_codebook *cb, int32_t device_slot, const void *d_codes, int32_t code_bytes,
+                              int64_t n, int64_t codes_row_stride, uint8_t *d_packed, int64_t packed_row_stride,
+                              void *stream);
+int32_t pqhip_unpack_codes4_dev(pqhip_codebook *cb, int32_t device_slot, const uint8_t *d_packed, int64_t n,
+                                int64_t packed_row_stride, const int64_t *d_rows /* or NULL */, int64_t n_rows,
+                                uint8_t *d_codes_out, int64_t out_row_stride, void *stream);
+int32_t pqhip_adc_search_packed4_f32_dev(pqhip_codebook *cb, int32_t device_slot, const float *d_tables, int64_t n_queries,
+                                         const uint8_t *d_packed, int64_t n_codes, int64_t packed_row_stride,
+                                         const uint32_t *d_allow,
+                                         int32_t k, float *d_dist, int64_t dist_row_stride,
+                                         int64_t *d_idx, int64_t idx_row_stride, void *stream);
+int32_t pqhip_adc_ip_search_packed4_f32_dev(pqhip_codebook *cb, int32_t device_slot, const float *d_tables, int64_t n_queries,
+                                            const uint8_t *d_packed, int64_t n_codes, int64_t packed_row_stride,
+                                            const uint32_t *d_allow,
+                                            const float *d_scales, int32_t k, float *d_score, int64_t score_row_stride,
+                                            int64_t *d_idx, int64_t idx_row_stride, void *stream);
+int32_t pqhip_adc_search_lists_packed4_f32_dev(pqhip_codebook *cb, int32_t device_slot, const float *d_tables,
+                                               int64_t n_queries, const uint8_t *d_packed,
+                                               int64_t n_codes, int64_t packed_row_stride, const uint32_t *d_allow,
+                                               const int64_t *d_list_off, int64_t n_lists,
+                                               const int64_t *d_probes, int32_t n_probe, int64_t probes_row_stride,
+                                               int32_t k, float *d_dist, int64_t dist_row_stride,
+                                               int64_t *d_idx, int64_t idx_row_stride, void *stream);
+int32_t pqhip_adc_ip_search_lists_packed4_f32_dev(pqhip_codebook *cb, int32_t device_slot, const float *d_tables,
+                                                  int64_t n_queries, const uint8_t *d_packed,
+                                                  int64_t n_codes, int64_t packed_row_stride, const uint32_t *d_allow,
+                                                  const int64_t *d_list_off, int64_t n_lists,
+                                                  const int64_t *d_probes, int32_t n_probe, int64_t probes_row_stride,
+                                                  const float *d_scales, int32_t k, float *d_score, int64_t score_row_stride,
+                                                  int64_t *d_idx, int64_t idx_row_stride, void *stream);
+int32_t pqhip_adc_search_lists_residual_packed4_f32_dev(pqhip_codebook *cb, int32_t device_slot, const float *d_tables,
+                                                        int64_t n_queries, const uint8_t *d_packed,
+                                                        int64_t n_codes, int64_t packed_row_stride, const uint32_t *d_allow,
+                                                        const int64_t *d_list_off, int64_t n_lists,
+                                                        const int64_t *d_probes, int32_t n_probe, int64_t probes_row_stride,
+                                                        const float *d_probe_bias, int64_t bias_row_stride,
+                                                        const float *d_row_terms, int32_t k, float *d_dist,
+                                                        int64_t dist_row_stride, int64_t *d_idx, int64_t idx_row_stride,
+                                                        void *stream);
+int32_t pqhip_adc_ip_search_lists_residual_packed4_f32_dev(pqhip_codebook *cb, int32_t device_slot, const float *d_tables,
+                                                           int64_t n_queries, const uint8_t *d_packed,
+                                                           int64_t n_codes, int64_t packed_row_stride, const uint32_t *d_allow,
+                                                           const int64_t *d_list_off, int64_t n_lists,
+                                                           const int64_t *d_probes, int32_t n_probe, int64_t probes_row_stride,
+                                                           const float *d_probe_bias, int64_t bias_row_stride,
+                                                           const float *d_scales, int32_t k, float *d_score,
+                                                           int64_t score_row_stride, int64_t *d_idx, int64_t idx_row_stride,
+                                                           void *stream);
+
+/*
  * ADC range search: EVERY row within a radius resp. at or above a similarity, exhaustive and over probed lists, without
  * the [n_queries][n_codes] matrix -- the question beside "the best k".  Everything is exact; there is no tolerance and no
  * k.  Query q has a threshold d_threshold[q] (f32) and a value v[q][i] per row:
@@ -673,6 +757,8 @@ int32_t pqhip_set_rotation_variant(int32_t variant);
  *                          so that the one-workgroup prefix scan of a pass sums at most 2^20 counts)
  *   "adc_range_wgs_per_query"  workgroups that share one query of the list range searches (0 = chosen from the shape; at
  *                          most 4096, as "adc_lists_wgs_per_query")
+ *   "adc_packed4_wgs"      producer workgroups of the exhaustive searches over 4-bit packed codes (0 = chosen from the shape,
+ *                          as for the u8 searches; at most 65536; rows per workgroup stay a multiple of 1,024)
  *   "lists_merge_wgs"      workgroups of the mover of pqhip_lists_merge_dev (0 = chosen from the size and the CU count; at
  *                          most 2^20, and never more than one per 1,024 16-byte chunks of output)
  *   "rerank_wgs_per_query" workgroups that share one query in the distance stage of pqhip_rerank_f32_dev (0 = chosen from the

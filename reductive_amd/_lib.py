@@ -125,6 +125,17 @@ def lib():
         rng = getattr(L, "pqhip_%s_f32_dev" % name.replace("search", "range"))
         rng.restype = i32
         rng.argtypes = masked.argtypes[:-6] + [vp, vp, vp, vp, i64, vp]
+    # the searches over 4-bit packed codes: the masked signatures without code_bytes
+    for name in ("adc_search", "adc_ip_search", "adc_search_lists", "adc_ip_search_lists", "adc_search_lists_residual",
+                 "adc_ip_search_lists_residual"):
+        masked = getattr(L, "pqhip_%s_masked_f32_dev" % name)
+        packed = getattr(L, "pqhip_%s_packed4_f32_dev" % name)
+        packed.restype = i32
+        packed.argtypes = masked.argtypes[:5] + masked.argtypes[6:]
+    L.pqhip_pack_codes4_dev.restype = i32
+    L.pqhip_pack_codes4_dev.argtypes = [vp, i32, vp, i32, i64, i64, vp, i64, vp]
+    L.pqhip_unpack_codes4_dev.restype = i32
+    L.pqhip_unpack_codes4_dev.argtypes = [vp, i32, vp, i64, i64, vp, i64, vp, i64, vp]
     L.pqhip_pack_row_mask_dev.restype = i32
     L.pqhip_pack_row_mask_dev.argtypes = [vp, i32, vp, i64, vp, i64, vp, vp]
     L.pqhip_rerank_f32_dev.restype = i32
@@ -191,6 +202,10 @@ EXPORTS = [
     "pqhip_adc_search_lists_masked_f32_dev", "pqhip_adc_ip_search_lists_masked_f32_dev",
     "pqhip_adc_search_lists_residual_masked_f32_dev", "pqhip_adc_ip_search_lists_residual_masked_f32_dev",
     "pqhip_pack_row_mask_dev",
+    "pqhip_pack_codes4_dev", "pqhip_unpack_codes4_dev",
+    "pqhip_adc_search_packed4_f32_dev", "pqhip_adc_ip_search_packed4_f32_dev",
+    "pqhip_adc_search_lists_packed4_f32_dev", "pqhip_adc_ip_search_lists_packed4_f32_dev",
+    "pqhip_adc_search_lists_residual_packed4_f32_dev", "pqhip_adc_ip_search_lists_residual_packed4_f32_dev",
     "pqhip_adc_range_f32_dev", "pqhip_adc_ip_range_f32_dev",
     "pqhip_adc_range_lists_f32_dev", "pqhip_adc_ip_range_lists_f32_dev",
     "pqhip_adc_range_lists_residual_f32_dev", "pqhip_adc_ip_range_lists_residual_f32_dev",

@@ -67,10 +67,23 @@ int32_t adc_search_lists_masked(bool ip, pqhip_codebook* cb, int32_t slot, const
 // workgroups that share a query of a list call, the scratch bound of one chunk of queries, and the launch of
 // k_adc_lists_plan -- the only reader of the offsets and probes, for both.
 int search_nv_bucket(int nv);
+int search_list_regs(int k);                                   // L: 64 L >= k entries per (wave, query)
+size_t search_lds(size_t table_bytes, int nq, int L);          // a producer's dynamic LDS: max(table image + queues, combine lists)
 int lists_nv_bucket(int nv);
 int64_t lists_wgs_per_query(int64_t n, int64_t n_lists, int64_t n_probe, int64_t nq, int n_cus);
 constexpr size_t kListsScratchBytes = 512u << 20;   // plan + partial lists of one chunk of queries
 int32_t launch_lists_plan(const int64_t* d_list_off, int64_t n_lists, const int64_t* d_probes, int n_probe, int64_t p_rs, int64_t n,
                           int64_t* seg_begin, int64_t* seg_cum, unsigned nq, int* err, hipStream_t st);
+
+
+// pqhip_adc.hip: k_adc_search_merge / k_adc_ip_search_merge over the partial lists of nq queries, for the units that
+// bring producers of their own (pqhip_adc_packed4.hip); n_lists == 0 writes the padding only.
+int32_t adc_search_merge(bool ip, int L, int nq, int n_lists, int k, const unsigned* part_k, const uint64_t* part_i, float* d_val,
+                         int64_t v_rs, int64_t* d_idx, int64_t i_rs, hipStream_t st);
+
+// pqhip_adc_packed4_lists.hip: the list producers over 4-bit packed codes (kernels_adc_packed4.hip.h), a unit of their
+// own so that the build compiles them beside the exhaustive ones.  nvb in {2, 8, 13} packed dwords; a.allow and a.bias
+// may be null.
+int32_t launch_lists_packed4(bool ip, int L, int nvb, const ListsLaunch& a, const uint8_t* packed, const float* lut, size_t lds);
 
 }  // namespace pqh

@@ -54,7 +54,7 @@ int32_t launch_adc_mq(int nv, const uint8_t* codes, int64_t n, int64_t c_rs, con
 
 // ---- ADC search (kernels_adc_search.hip.h) ---------------------------------------------------------------------------
 // List length: 64 L >= k entries per (wave, query), L in {1, 2, 4, 8, 16}.
-inline int search_list_regs(int k) { int lk = 64; while (lk < k) lk <<= 1; return lk / 64; }
+int search_list_regs(int k) { int lk = 64; while (lk < k) lk <<= 1; return lk / 64; }
 
 // Code dwords fetched per row on the u8 path: ceil(M / 4) rounded up to one of the instantiated widths (a wider window
 // only reads past the row inside the code matrix -- adc_fetch_row falls back to byte loads at its end).
@@ -68,7 +68,7 @@ int search_nv_bucket(int nv)
 // SearchLaunch: adc_search_launch.h (shared with the masked producers of pqhip_adc_masked.hip)
 
 // the producer's dynamic LDS: max(table image + queues, combine lists)
-inline size_t search_lds(size_t table_bytes, int nq, int L)
+size_t search_lds(size_t table_bytes, int nq, int L)
 {
     const size_t queues = (size_t)kSearchWaves * nq * kSearchQueue * 2 * sizeof(unsigned);
     const size_t comb = (size_t)kSearchWaves * nq * 64 * L * 2 * sizeof(unsigned);
@@ -464,6 +464,14 @@ int32_t adc_search_lists(pqhip_codebook* cb, int32_t slot, const float* d_tables
         HIPCHK(hipGetLastError());
     }
     return PQHIP_OK;
+}
+
+// The merge of both searches for the units that bring producers of their own (pqhip_adc_packed4.hip)
+int32_t adc_search_merge(bool ip, int L, int nq, int n_lists, int k, const unsigned* part_k, const uint64_t* part_i, float* d_val,
+                         int64_t v_rs, int64_t* d_idx, int64_t i_rs, hipStream_t st)
+{
+    if (ip) return launch_search_merge<true>(L, nq, n_lists, k, part_k, part_i, d_val, v_rs, d_idx, i_rs, st);
+    return launch_search_merge<false>(L, nq, n_lists, k, part_k, part_i, d_val, v_rs, d_idx, i_rs, st);
 }
 
 // The doors of pqhip_adc_masked.hip into the two routines above

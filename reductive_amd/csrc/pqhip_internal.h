@@ -8,6 +8,8 @@
 //     pqhip_rotate.hip    x.P / r.P^T dispatch (rotation kernels v8 / v9, slab fallback)
 //     pqhip_opq.hip       quantize / reconstruct / lookup on device-resident rows (two-kernel OPQ paths, gather)
 //     pqhip_adc.hip       asymmetric-distance tables and scans
+//     pqhip_adc_packed4.hip  4-bit packed codes: pack / unpack and the searches over packed rows (list producers:
+//                         pqhip_adc_packed4_lists.hip)
 //     pqhip_adc_range.hip ADC range search: every row within a radius, as CSR
 //     pqhip_rerank.hip    exact re-ranking of search candidates against resident vectors
 //     pqhip_lists_merge.hip  merge of two list-ordered row arrays (growing a partitioned matrix)
@@ -94,6 +96,7 @@ struct Options {
     std::atomic<int64_t> adc_range_wgs{0};          // exhaustive range search: producer workgroups (0: chosen from the shape)
     std::atomic<int64_t> adc_range_wgs_per_query{0};   // list range searches: workgroups per query (0: chosen from the shape)
     std::atomic<int64_t> lists_merge_wgs{0};        // list merge: workgroups of the mover (0: chosen from the size)
+    std::atomic<int64_t> adc_packed4_wgs{0};        // exhaustive searches over 4-bit packed codes: producer workgroups (0: chosen from the shape)
 };
 
 struct Diag {

@@ -433,6 +433,43 @@ def train_opq(n_subquantizers, n_subquantizer_bits, n_iterations, n_attempts, in
     return Pq(P, q, ctx=ctx)
 
 
+def pack_codes4(codes, n_centroids=16):
+    """codes: integer array [n, M] (or [M]) of a quantizer with n_centroids <= 16 -> the 4-bit packed rows, uint8
+    [n, ceil(M / 2)]: code m lives in byte m >> 1, even m in the low nibble and odd m in the high nibble; the high nibble
+    of the last byte of an odd M is 0 (include/pqhip.h, "4-bit packed codes").  Raises on a code >= n_centroids."""
+    if n_centroids > 16:
+        raise PanicError("4-bit packed codes need a quantizer of at most 16 centroids")
+    c = np.asarray(codes)
+    single = c.ndim == 1
+    c = np.atleast_2d(c)
+    if c.ndim != 2 or c.dtype.kind not in "ui":
+        raise PanicError("codes must be an integer array [n, n_subquantizers]")
+    if c.size and (int(c.min()) < 0 or int(c.max()) >= n_centroids):
+        raise PanicError("ndarray: index out of bounds")
+    n, M = c.shape
+    even = np.zeros((n, (M + 1) // 2), dtype=np.uint8)
+    odd = np.zeros_like(even)
+    even[:, :] = c[:, 0::2]
+    odd[:, :M // 2] = c[:, 1::2]
+    out = even | (odd << 4)
+    return out[0] if single else out
+
+
+def unpack_codes4(packed, n_subquantizers):
+    """The inverse of pack_codes4: uint8 [n, ceil(M / 2)] (or [ceil(M / 2)]) -> uint8 [n, M].  The pad nibble of an odd M
+    is ignored whatever it holds."""
+    p = np.asarray(packed)
+    single = p.ndim == 1
+    p = np.atleast_2d(p)
+    M = int(n_subquantizers)
+    if p.ndim != 2 or p.dtype != np.uint8 or p.shape[1] != (M + 1) // 2:
+        raise PanicError("4-bit packed codes must be uint8 [n, ceil(n_subquantizers / 2)]")
+    out = np.empty((p.shape[0], M), dtype=np.uint8)
+    out[:, 0::2] = p & 0xf
+    out[:, 1::2] = (p >> 4)[:, :M // 2]
+    return out[0] if single else out
+
+
 class Pq:
     """Product quantizer (Jegou et al., 2011) -- mirror of `reductive::pq::Pq<f32>`."""
 
@@ -875,6 +912,100 @@ class Pq:
                 raise _lib.PqHipError(rc, "pqhip_check_codes_dev")
         return out
 
+    # ---- 4-bit packed codes: two codes per byte for K <= 16 ----------------------------------------------------------
+    def _packed4_served(self):
+        if self.n_quantizer_centroids() > 16:
+            raise PanicError("4-bit packed codes need a quantizer of at most 16 centroids")
+
+    def _code_row_bytes(self, codes, packed4):
+        """The row width the searches expect of `codes`: M elements, or ceil(M / 2) bytes of 4-bit packed rows."""
+        import torch
+        M = self.quantized_len()
+        if not packed4:
+            if codes.shape[1] != M:
+                raise PanicError("Quantization length does not match number of subquantizers")
+            return M
+        if codes.dtype != torch.uint8 or codes.shape[1] != (M + 1) // 2:
+            raise PanicError("4-bit packed codes must be uint8 [n, ceil(n_subquantizers / 2)]")
+        return (M + 1) // 2
+
+    def pack_codes4_device(self, codes, out=None, stream=None, check=False):
+        """codes: CUDA uint8 or int32 [n, M] of a quantizer with K <= 16 -> 4-bit packed rows, CUDA uint8
+        [n, ceil(M / 2)]: code m in byte m >> 1, even m in the low nibble, the pad nibble of an odd M written as 0
+        (pqhip_pack_codes4_dev).  A code >= K packs as 0 and raises the range flag (check=True: PanicError)."""
+        import torch
+        self._packed4_served()
+        assert codes.is_cuda and codes.dtype in (torch.uint8, torch.int32) and codes.dim() == 2
+        M = self.quantized_len()
+        PB = (M + 1) // 2
+        if codes.shape[1] != M:
+            raise PanicError("Quantization length does not match number of subquantizers")
+        if codes.stride(1) != 1:
+            codes = codes.contiguous()
+        n = codes.shape[0]
+        if out is None:
+            out = torch.empty((n, PB), dtype=torch.uint8, device=codes.device)
+        assert out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == (n, PB) and (PB == 1 or out.stride(1) == 1)
+        if n == 0:
+            return out
+        cb = self._cb()
+        if stream is None:
+            stream = torch.cuda.current_stream(codes.device).cuda_stream
+        slot = self._slot_for(codes)
+        rc = _lib.lib().pqhip_pack_codes4_dev(cb, slot, codes.data_ptr(), codes.element_size(), n,
+                                             codes.stride(0) if n > 1 else max(codes.stride(0), M), out.data_ptr(),
+                                             out.stride(0) if n > 1 else max(out.stride(0), PB), ctypes.c_void_p(stream))
+        if rc != _lib.OK:
+            raise _lib.PqHipError(rc, "pqhip_pack_codes4_dev")
+        if check:
+            rc = _lib.lib().pqhip_check_codes_dev(cb, slot, ctypes.c_void_p(stream))
+            if rc == _lib.ECODE_RANGE:
+                raise PanicError("ndarray: index out of bounds")
+            if rc != _lib.OK:
+                raise _lib.PqHipError(rc, "pqhip_check_codes_dev")
+        return out
+
+    def unpack_codes4_device(self, packed, rows=None, out=None, stream=None, check=False):
+        """packed: CUDA uint8 [n, ceil(M / 2)] -> the codes, CUDA uint8 [n, M]; rows: CUDA int64 [r] -> the codes of those
+        rows, [r, M] (pqhip_unpack_codes4_dev).  Nibbles come back as they are.  A row id outside [0, n) gives a zero row
+        and raises the range flag (check=True: PanicError)."""
+        import torch
+        self._packed4_served()
+        assert packed.is_cuda and packed.dim() == 2
+        M = self.quantized_len()
+        PB = self._code_row_bytes(packed, True)
+        if packed.stride(1) != 1:
+            packed = packed.contiguous()
+        n = packed.shape[0]
+        n_out = n
+        if rows is not None:
+            assert rows.is_cuda and rows.dtype == torch.int64 and rows.dim() == 1 and rows.device == packed.device
+            rows = rows.contiguous()
+            n_out = rows.shape[0]
+        if out is None:
+            out = torch.empty((n_out, M), dtype=torch.uint8, device=packed.device)
+        assert out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == (n_out, M) and (M == 1 or out.stride(1) == 1)
+        if n_out == 0:
+            return out
+        # an empty tensor may have no address: every row id is then out of range and no packed byte is read
+        src = packed if n > 0 else torch.zeros((1, PB), dtype=torch.uint8, device=packed.device)
+        cb = self._cb()
+        if stream is None:
+            stream = torch.cuda.current_stream(packed.device).cuda_stream
+        slot = self._slot_for(packed)
+        rc = _lib.lib().pqhip_unpack_codes4_dev(cb, slot, src.data_ptr(), n, src.stride(0) if n > 1 else max(src.stride(0), PB),
+                                               rows.data_ptr() if rows is not None else None, n_out, out.data_ptr(),
+                                               out.stride(0) if n_out > 1 else max(out.stride(0), M), ctypes.c_void_p(stream))
+        if rc != _lib.OK:
+            raise _lib.PqHipError(rc, "pqhip_unpack_codes4_dev")
+        if check:
+            rc = _lib.lib().pqhip_check_codes_dev(cb, slot, ctypes.c_void_p(stream))
+            if rc == _lib.ECODE_RANGE:
+                raise PanicError("ndarray: index out of bounds")
+            if rc != _lib.OK:
+                raise _lib.PqHipError(rc, "pqhip_check_codes_dev")
+        return out
+
     # ---- row masks: restrict a search to an allowed set of rows ------------------------------------------------------
     def pack_row_mask_device(self, allow, perm=None, stream=None, check=False):
         """allow: CUDA bool or uint8 [n_src], nonzero = the row may be returned; perm: None or CUDA int64 [n] -> the mask
@@ -923,18 +1054,21 @@ class Pq:
         # an empty tensor may have no address; a non-NULL mask must stay a mask (n = 0 reads no word)
         return allow if allow.shape[0] > 0 else torch.zeros(1, dtype=torch.int32, device=codes.device)
 
-    def adc_search_device(self, codes, tables, k, stream=None, check=False, allow=None):
+    def adc_search_device(self, codes, tables, k, stream=None, check=False, allow=None, packed4=False):
         """The k nearest rows per query without the distance matrix: codes and tables as for adc_scan_device ->
         (dist, idx), CUDA float32 and int64 [nq, k] ([k] for 2-D tables).  dist[q, j] is the scan's distance of row
         idx[q, j]; rows are ordered by distance -- NaN above +Inf -- then by index (pqhip_adc_search_f32_dev).  Past
         the last row: index -1, distance +Inf.  allow: None or the words of pack_row_mask_device -- the search then
-        ranks the allowed rows only, as if the others were not in the matrix (pqhip_adc_search_masked_f32_dev)."""
+        ranks the allowed rows only, as if the others were not in the matrix (pqhip_adc_search_masked_f32_dev).
+        packed4=True: codes are 4-bit packed rows, CUDA uint8 [n, ceil(M / 2)] (pack_codes4_device; K <= 16), and the
+        result is bit for bit that of the unpacked codes (pqhip_adc_search_packed4_f32_dev)."""
         import torch
+        if packed4:
+            self._packed4_served()
         assert codes.is_cuda and codes.dtype in (torch.uint8, torch.int32) and codes.dim() == 2
         assert tables.is_cuda and tables.dtype == torch.float32 and tables.is_contiguous()
         M, K = self.quantized_len(), self.n_quantizer_centroids()
-        if codes.shape[1] != M:
-            raise PanicError("Quantization length does not match number of subquantizers")
+        W = self._code_row_bytes(codes, packed4)
         single = tables.dim() == 2
         if tuple(tables.shape[-2:]) != (M, K):
             raise PanicError("lookup tables must be [.., %d, %d]" % (M, K))
@@ -948,8 +1082,13 @@ class Pq:
         if stream is None:
             stream = torch.cuda.current_stream(codes.device).cuda_stream
         slot = self._slot_for(codes)
-        c_rs = codes.stride(0) if n > 1 else max(codes.stride(0), M)
-        if allow is not None:
+        c_rs = codes.stride(0) if n > 1 else max(codes.stride(0), W)
+        if packed4:
+            name = "pqhip_adc_search_packed4_f32_dev"
+            rc = _lib.lib().pqhip_adc_search_packed4_f32_dev(cb, slot, tables.data_ptr(), nq, codes.data_ptr(), n, c_rs,
+                                                            self._mask_words(allow, codes).data_ptr() if allow is not None else None,
+                                                            k, dist.data_ptr(), k, idx.data_ptr(), k, ctypes.c_void_p(stream))
+        elif allow is not None:
             name = "pqhip_adc_search_masked_f32_dev"
             rc = _lib.lib().pqhip_adc_search_masked_f32_dev(cb, slot, tables.data_ptr(), nq, codes.data_ptr(),
                                                            codes.element_size(), n, c_rs,
@@ -994,19 +1133,20 @@ class Pq:
             raise _lib.PqHipError(rc, "pqhip_adc_ip_tables_f32_dev")
         return out[0] if single else out
 
-    def adc_ip_search_device(self, codes, tables, k, scales=None, stream=None, check=False, allow=None):
+    def adc_ip_search_device(self, codes, tables, k, scales=None, stream=None, check=False, allow=None, packed4=False):
         """The k most similar rows per query: codes as for adc_scan_device, tables from adc_ip_tables_device, scales None
         or CUDA float32 [n] -> (score, idx), CUDA float32 and int64 [nq, k] ([k] for 2-D tables).  score[q, j] =
         fl(scan[q, i] * scales[i]) of row i = idx[q, j] (the scan's sum alone without scales); rows are ordered by
         descending score -- NaN after -Inf -- then by index (pqhip_adc_ip_search_f32_dev).  A zero score comes back as
         +0, a NaN as the canonical NaN.  Past the last row: index -1, score -Inf.  allow: as for adc_search_device
-        (pqhip_adc_ip_search_masked_f32_dev)."""
+        (pqhip_adc_ip_search_masked_f32_dev).  packed4: as for adc_search_device (pqhip_adc_ip_search_packed4_f32_dev)."""
         import torch
+        if packed4:
+            self._packed4_served()
         assert codes.is_cuda and codes.dtype in (torch.uint8, torch.int32) and codes.dim() == 2
         assert tables.is_cuda and tables.dtype == torch.float32 and tables.is_contiguous()
         M, K = self.quantized_len(), self.n_quantizer_centroids()
-        if codes.shape[1] != M:
-            raise PanicError("Quantization length does not match number of subquantizers")
+        W = self._code_row_bytes(codes, packed4)
         single = tables.dim() == 2
         if tuple(tables.shape[-2:]) != (M, K):
             raise PanicError("lookup tables must be [.., %d, %d]" % (M, K))
@@ -1025,10 +1165,14 @@ class Pq:
             stream = torch.cuda.current_stream(codes.device).cuda_stream
         slot = self._slot_for(codes)
         head = (cb, slot, tables.data_ptr(), nq, codes.data_ptr(), codes.element_size(), n,
-                codes.stride(0) if n > 1 else max(codes.stride(0), M))
+                codes.stride(0) if n > 1 else max(codes.stride(0), W))
         tail = (scales.data_ptr() if scales is not None else None, k, score.data_ptr(), k, idx.data_ptr(), k,
                 ctypes.c_void_p(stream))
-        if allow is not None:
+        if packed4:
+            name = "pqhip_adc_ip_search_packed4_f32_dev"
+            rc = _lib.lib().pqhip_adc_ip_search_packed4_f32_dev(
+                *head[:5], *head[6:], self._mask_words(allow, codes).data_ptr() if allow is not None else None, *tail)
+        elif allow is not None:
             name = "pqhip_adc_ip_search_masked_f32_dev"
             rc = _lib.lib().pqhip_adc_ip_search_masked_f32_dev(*head, self._mask_words(allow, codes).data_ptr(), *tail)
         else:
@@ -1046,20 +1190,22 @@ class Pq:
 
     # ---- ADC search over a partitioned code matrix: exact top-k within the probed lists -----------------------------
     def _adc_search_lists(self, ip, codes, tables, list_off, probes, k, scales, stream, check, probe_bias=None,
-                          row_terms=None, allow=None):
+                          row_terms=None, allow=None, packed4=False):
         """All four list searches; probe_bias given: the residual ones (row_terms then required for the distance);
-        allow given: their masked forms (the words of pack_row_mask_device, in position order)."""
+        allow given: their masked forms (the words of pack_row_mask_device, in position order); packed4: their forms
+        over 4-bit packed rows (a mask or none)."""
         import torch
+        if packed4:
+            self._packed4_served()
         residual = probe_bias is not None
         name = "pqhip_adc_%ssearch_lists_%s%sf32_dev" % ("ip_" if ip else "", "residual_" if residual else "",
-                                                        "masked_" if allow is not None else "")
+                                                        "packed4_" if packed4 else "masked_" if allow is not None else "")
         assert codes.is_cuda and codes.dtype == torch.uint8 and codes.dim() == 2
         assert tables.is_cuda and tables.dtype == torch.float32 and tables.is_contiguous()
         assert list_off.is_cuda and list_off.dtype == torch.int64 and list_off.dim() == 1 and list_off.is_contiguous()
         assert probes.is_cuda and probes.dtype == torch.int64 and probes.dim() in (1, 2)
         M, K = self.quantized_len(), self.n_quantizer_centroids()
-        if codes.shape[1] != M:
-            raise PanicError("Quantization length does not match number of subquantizers")
+        W = self._code_row_bytes(codes, packed4)
         single = tables.dim() == 2
         if tuple(tables.shape[-2:]) != (M, K):
             raise PanicError("lookup tables must be [.., %d, %d]" % (M, K))
@@ -1095,8 +1241,10 @@ class Pq:
             stream = torch.cuda.current_stream(codes.device).cuda_stream
         slot = self._slot_for(codes)
         head = (cb, slot, tables.data_ptr(), nq, codes.data_ptr(), codes.element_size(), n,
-                codes.stride(0) if n > 1 else max(codes.stride(0), M))
-        if allow is not None:
+                codes.stride(0) if n > 1 else max(codes.stride(0), W))
+        if packed4:
+            head = head[:5] + head[6:] + (self._mask_words(allow, codes).data_ptr() if allow is not None else None,)
+        elif allow is not None:
             head += (self._mask_words(allow, codes).data_ptr(),)
         head += (list_off.data_ptr(), list_off.shape[0] - 1,
                  pr.data_ptr(), n_probe, pr.stride(0) if nq > 1 else max(pr.stride(0), n_probe))
@@ -1124,47 +1272,52 @@ class Pq:
                 raise _lib.PqHipError(rc, "pqhip_check_codes_dev")
         return (val[0], idx[0]) if single else (val, idx)
 
-    def adc_search_lists_device(self, codes, tables, list_off, probes, k, stream=None, check=False, allow=None):
+    def adc_search_lists_device(self, codes, tables, list_off, probes, k, stream=None, check=False, allow=None,
+                                packed4=False):
         """adc_search_device restricted, per query, to the rows of the probed lists: list l is rows
         [list_off[l], list_off[l + 1]) of codes (CUDA uint8 [n, M]); list_off CUDA int64 [n_lists + 1]; probes CUDA int64
         [nq, n_probe] ([n_probe] for 2-D tables) of list ids, -1 = padding -> (dist, idx) [nq, k] ([k]).  The result is
         what adc_search_device returns on codes with every row outside the probed lists removed, idx being positions in
         codes (pqhip_adc_search_lists_f32_dev).  Past the last probed row: index -1, distance +Inf.  check=True also
         reports a list id or an offset out of range.  allow: None or the words of pack_row_mask_device in position order
-        (row order of codes): only allowed rows of the probed lists are ranked (pqhip_adc_search_lists_masked_f32_dev)."""
-        return self._adc_search_lists(False, codes, tables, list_off, probes, k, None, stream, check, allow=allow)
+        (row order of codes): only allowed rows of the probed lists are ranked (pqhip_adc_search_lists_masked_f32_dev).
+        packed4=True: codes are 4-bit packed rows, CUDA uint8 [n, ceil(M / 2)]; the result is bit for bit that of the
+        unpacked codes (pqhip_adc_search_lists_packed4_f32_dev)."""
+        return self._adc_search_lists(False, codes, tables, list_off, probes, k, None, stream, check, allow=allow,
+                                      packed4=packed4)
 
     def adc_ip_search_lists_device(self, codes, tables, list_off, probes, k, scales=None, stream=None, check=False,
-                                   allow=None):
+                                   allow=None, packed4=False):
         """adc_ip_search_device restricted, per query, to the rows of the probed lists (arguments as for
         adc_search_lists_device, tables from adc_ip_tables_device, scales None or CUDA float32 [n]) -> (score, idx).
-        Past the last probed row: index -1, score -Inf (pqhip_adc_ip_search_lists_f32_dev).  allow: as for
+        Past the last probed row: index -1, score -Inf (pqhip_adc_ip_search_lists_f32_dev).  allow, packed4: as for
         adc_search_lists_device."""
-        return self._adc_search_lists(True, codes, tables, list_off, probes, k, scales, stream, check, allow=allow)
+        return self._adc_search_lists(True, codes, tables, list_off, probes, k, scales, stream, check, allow=allow,
+                                      packed4=packed4)
 
     # ---- the same over residual codes (IVFADC with residual encoding): one table per query, a bias per probe ---------
     def adc_search_lists_residual_device(self, codes, ip_tables, list_off, probes, probe_bias, row_terms, k, stream=None,
-                                         check=False, allow=None):
+                                         check=False, allow=None, packed4=False):
         """adc_search_lists_device over residual codes: self is the quantizer of the residuals x - c_list(x), ip_tables
         are its INNER-PRODUCT tables (adc_ip_tables_device), probe_bias CUDA float32 [nq, n_probe] ([n_probe] for one
         query) holds |q - c_l|^2 of the list in each probe slot and row_terms CUDA float32 [n] holds |r^|^2 + 2 <c_l, r^>
         of each row -> (dist, idx) with dist = fl(fl(bias + term) - fl(s + s)), s the scan's row sum, ordered by
         (key(dist), position) (pqhip_adc_search_lists_residual_f32_dev).  The bias of a skipped probe is never used.
-        allow: as for adc_search_lists_device; the row term of a disallowed row is never read."""
+        allow, packed4: as for adc_search_lists_device; the row term of a disallowed row is never read."""
         if probe_bias is None or row_terms is None:
             raise PanicError("the residual distance search needs a probe bias and the row terms")
         return self._adc_search_lists(False, codes, ip_tables, list_off, probes, k, None, stream, check,
-                                      probe_bias=probe_bias, row_terms=row_terms, allow=allow)
+                                      probe_bias=probe_bias, row_terms=row_terms, allow=allow, packed4=packed4)
 
     def adc_ip_search_lists_residual_device(self, codes, ip_tables, list_off, probes, probe_bias, k, scales=None,
-                                            stream=None, check=False, allow=None):
+                                            stream=None, check=False, allow=None, packed4=False):
         """adc_ip_search_lists_device over residual codes: probe_bias holds <q, c_l> of the list in each probe slot ->
         (score, idx) with score = fl(fl(bias + s) * scale), fl(bias + s) without scales, ordered by (key(-score),
-        position) (pqhip_adc_ip_search_lists_residual_f32_dev).  allow: as for adc_search_lists_device."""
+        position) (pqhip_adc_ip_search_lists_residual_f32_dev).  allow, packed4: as for adc_search_lists_device."""
         if probe_bias is None:
             raise PanicError("the residual similarity search needs a probe bias")
         return self._adc_search_lists(True, codes, ip_tables, list_off, probes, k, scales, stream, check,
-                                      probe_bias=probe_bias, allow=allow)
+                                      probe_bias=probe_bias, allow=allow, packed4=packed4)
 
     # ---- ADC range search: every row within a radius / at or above a similarity, as CSR ------------------------------
     def _adc_range(self, ip, codes, tables, threshold, scales, stream, check, allow, capacity, lists=None, probe_bias=None,

@@ -232,7 +232,57 @@ class _Filter:
         return self.row_filter(allow).words
 
 
-class QuantizedMatrix(_Refine, _Filter):
+class _Packed4:
+    """4-bit packed codes for all three matrix classes (quantizers of at most 16 centroids): pack4() gives a matrix of
+    the same class whose `codes` hold two codes per byte, [N, ceil(M / 2)] (include/pqhip.h, "4-bit packed codes"), at
+    half the bytes in HBM and per search.  nearest() and most_similar() with every option, embeddings(), row_filter(),
+    attach_vectors() and growth work on it and return exactly what the unpacked matrix returns; the range searches, the
+    full scans and the partitioning do not read packed codes and raise PanicError: call unpack4() first."""
+
+    packed4 = False
+
+    def _with_codes(self, codes, packed4):
+        new = object.__new__(type(self))
+        new.__dict__.update(self.__dict__)      # norms, ids, positions, lists, row terms, centroids, vectors: shared
+        new.codes = codes
+        new.packed4 = packed4
+        return new
+
+    def pack4(self):
+        """The same matrix with 4-bit packed codes -> a NEW matrix of this class (self if it is packed already) that
+        shares every other tensor with self; row filters are not carried over (row_filter on the result).  PanicError
+        for a quantizer of more than 16 centroids."""
+        if self.packed4:
+            return self
+        return self._with_codes(self.pq.pack_codes4_device(self.codes), True)
+
+    def unpack4(self):
+        """The inverse of pack4(): one byte per code again -> a NEW matrix (self if it is not packed)."""
+        if not self.packed4:
+            return self
+        return self._with_codes(self.pq.unpack_codes4_device(self.codes), False)
+
+    def _unpacked_only(self, what):
+        if self.packed4:
+            raise PanicError("%s() does not read 4-bit packed codes: call unpack4() first" % what)
+
+    def _stored_codes(self, codes):
+        """the codes of a batch ([B, M] u8) as this matrix stores them"""
+        return self.pq.pack_codes4_device(codes) if self.packed4 else codes
+
+    def _reconstruct_rows(self, pos, scales=None, out=None):
+        """reconstruct_rows_device of the stored rows `pos`; a packed matrix unpacks the selected rows first"""
+        import torch
+        if not self.packed4:
+            return self.pq.reconstruct_rows_device(self.codes, pos, scales=scales, out=out)
+        if pos.shape[0] == 0:
+            return out if out is not None else torch.empty((0, self.pq.reconstructed_len()), dtype=torch.float32, device=pos.device)
+        codes = self.pq.unpack_codes4_device(self.codes, rows=pos, check=True)
+        sel = torch.arange(pos.shape[0], dtype=torch.int64, device=pos.device)
+        return self.pq.reconstruct_rows_device(codes, sel, scales=None if scales is None else scales[pos].contiguous(), out=out)
+
+
+class QuantizedMatrix(_Refine, _Filter, _Packed4):
     """Codes (+ norms) resident in HBM next to the device codebook: the lookup, scan and similarity-search consumer."""
 
     def __init__(self, pq, codes, norms=None, device="cuda:0"):
@@ -261,15 +311,19 @@ class QuantizedMatrix(_Refine, _Filter):
         """`reconstruct_batch(codes.select(Axis(0), rows)) * norms.select(rows)` in one pass over HBM."""
         import torch
         rows = torch.as_tensor(rows, dtype=torch.int64, device=self.codes.device)
-        return self.pq.reconstruct_rows_device(self.codes, rows, scales=self.norms, out=out)
+        return self._reconstruct_rows(rows, scales=self.norms, out=out)
 
     def distances(self, queries):
-        """asymmetric squared distances of the query vector(s) to every (un-normalised) code row."""
+        """asymmetric squared distances of the query vector(s) to every (un-normalised) code row.  Not served on a
+        packed matrix: unpack4() first."""
+        self._unpacked_only("distances")
         return self.pq.adc_scan_device(self.codes, self.pq.adc_tables_device(queries))
 
     def inner_products(self, queries, use_norms=True):
         """inner products of the query vector(s) with every row: the scan over the inner-product tables, times the
-        stored norms when use_norms (and the matrix has them) -> [n] or [nq, n]."""
+        stored norms when use_norms (and the matrix has them) -> [n] or [nq, n].  Not served on a packed matrix:
+        unpack4() first."""
+        self._unpacked_only("inner_products")
         ip = self.pq.adc_scan_device(self.codes, self.pq.adc_ip_tables_device(queries))
         if use_norms and self.norms is not None:
             ip = ip * self.norms
@@ -283,7 +337,8 @@ class QuantizedMatrix(_Refine, _Filter):
         array [N] packed on the spot -- only allowed rows are ranked, exactly as if the others were not stored (index
         -1 past the last allowed row); with refine= the shortlist holds allowed rows only."""
         R = k if refine is None else self._check_refine(k, refine)
-        d, idx = self.pq.adc_search_device(self.codes, self.pq.adc_tables_device(queries), R, allow=self._allow_words(allow))
+        d, idx = self.pq.adc_search_device(self.codes, self.pq.adc_tables_device(queries), R, allow=self._allow_words(allow),
+                                           packed4=self.packed4)
         return (d, idx) if refine is None else self._refined(queries, idx, k, False)
 
     def most_similar(self, queries, k, use_norms=True, refine=None, allow=None):
@@ -295,7 +350,7 @@ class QuantizedMatrix(_Refine, _Filter):
         R = k if refine is None else self._check_refine(k, refine)
         scales = self.norms if use_norms else None
         s, idx = self.pq.adc_ip_search_device(self.codes, self.pq.adc_ip_tables_device(queries), R, scales=scales,
-                                              allow=self._allow_words(allow))
+                                              allow=self._allow_words(allow), packed4=self.packed4)
         return (s, idx) if refine is None else self._refined(queries, idx, k, True)
 
     def within(self, queries, radius, allow=None, sort=False):
@@ -304,7 +359,8 @@ class QuantizedMatrix(_Refine, _Filter):
         lims[q]:lims[q + 1] in ascending row number (Pq.adc_range_device; the result is allocated to its size, after one
         read of the count).  sort=True: each query's rows ascending in distance instead, ties in row order
         (sort_ranges).  allow: as for nearest().  There is no refine=: re-ranking is defined for at most 1,024
-        candidates per query, and a range result has no such bound."""
+        candidates per query, and a range result has no such bound.  Not served on a packed matrix: unpack4() first."""
+        self._unpacked_only("within")
         lims, d, idx = self.pq.adc_range_device(self.codes, self.pq.adc_tables_device(queries), radius,
                                                 allow=self._allow_words(allow))
         if sort:
@@ -314,7 +370,9 @@ class QuantizedMatrix(_Refine, _Filter):
     def similar_above(self, queries, threshold, use_norms=True, allow=None, sort=False):
         """Every row whose inner product with the query, as most_similar() scores it, is >= threshold (a scalar or one
         value per query) -> (lims, score, idx), CSR as for within() (Pq.adc_ip_range_device).  sort=True: each query's
-        rows descending in score, ties in row order.  No refine=, as for within()."""
+        rows descending in score, ties in row order.  No refine=, as for within().  Not served on a packed matrix:
+        unpack4() first."""
+        self._unpacked_only("similar_above")
         scales = self.norms if use_norms else None
         lims, sc, idx = self.pq.adc_ip_range_device(self.codes, self.pq.adc_ip_tables_device(queries), threshold,
                                                     scales=scales, allow=self._allow_words(allow))
@@ -326,14 +384,16 @@ class QuantizedMatrix(_Refine, _Filter):
         """The matrix with the rows of `vectors` ([B, d] float32, numpy or CUDA) appended as rows len(self) .. len(self) +
         B - 1 -> a NEW QuantizedMatrix; self is left as it is (and so are the row filters built for it, which the new
         matrix refuses).  The codes are quantize_batch_device of the vectors; norms [B] is required iff the matrix has
-        norms.  Attached vectors are extended by the new ones in the attached dtype."""
+        norms.  Attached vectors are extended by the new ones in the attached dtype.  A packed matrix packs the new codes:
+        m.pack4().add(x) is m.add(x).pack4()."""
         import torch
         dev = self.codes.device
         x = _device_rows(vectors, self.pq.reconstructed_len(), dev)
         nb = _batch_norms(norms, self.norms is not None, x.shape[0], dev)
         new = object.__new__(type(self))
         new.pq = self.pq
-        codes = self.pq.quantize_batch_device(x) if x.shape[0] else self.codes[:0]
+        new.packed4 = self.packed4
+        codes = self._stored_codes(self.pq.quantize_batch_device(x)) if x.shape[0] else self.codes[:0]
         if codes.dtype != self.codes.dtype:
             raise PanicError("the matrix holds 1-byte codes")
         new.codes = torch.cat([self.codes, codes])
@@ -354,7 +414,8 @@ class QuantizedMatrix(_Refine, _Filter):
         training is kmeans_iterations with one subquantizer, assignment is cluster_assignments.  Both take the slow
         anchor kernel for sub-vectors wider than 256 floats: accepted for a build step.  1 <= n_lists <= 16384 (the
         k-means limit) and n_lists <= number of training rows.  Row filters are not carried over: a RowFilter belongs
-        to the matrix that built it (call row_filter on the result)."""
+        to the matrix that built it (call row_filter on the result).  Not served on a packed matrix: unpack4() first."""
+        self._unpacked_only("partition")
         rng = rng or np.random.default_rng(0)
         centroids, assign, _, _ = self._coarse_partition(n_lists, n_iterations, vectors, train_rows, rng)
         out = PartitionedMatrix(self, centroids, assign)
@@ -414,9 +475,10 @@ class QuantizedMatrix(_Refine, _Filter):
         residuals are encoded with quantize_batch_device, in chunks, and every row gets its query-free term
         t_i = sum_j (r^_ij^2 + 2 c_lj r^_ij), r^ = reconstruct_batch_device of the residual quantizer, accumulated in
         float64 on the device and rounded once to f32.  The norms are kept as they are.  Row filters are not carried
-        over (row_filter on the result builds one from the same flags)."""
+        over (row_filter on the result builds one from the same flags).  Not served on a packed matrix: unpack4() first."""
         import torch
         from .pq import ReductiveError, train_pq
+        self._unpacked_only("partition_residual")
         rng = rng or np.random.default_rng(0)
         N, d = len(self), self.pq.reconstructed_len()
         M = self.pq.quantized_len() if n_subquantizers is None else int(n_subquantizers)
@@ -462,7 +524,7 @@ def ivf_layout(assign, n_lists):
     return perm, list_off
 
 
-class _Lists(_Refine, _Filter):
+class _Lists(_Refine, _Filter, _Packed4):
     """What both partitioned forms share: the list layout, the coarse quantizer and the probe selection."""
 
     def _init_lists(self, centroids, assign, n_rows, dev, ctx):
@@ -532,7 +594,7 @@ class _Lists(_Refine, _Filter):
     def _shell(self):
         """a matrix of this class that shares what growth does not change: quantizers, centroids, probe selection"""
         new = object.__new__(type(self))
-        for name in ("pq", "centroids", "n_lists", "coarse", "_list_ids", "_centroids_dev"):
+        for name in ("pq", "centroids", "n_lists", "coarse", "_list_ids", "_centroids_dev", "packed4"):
             if hasattr(self, name):
                 setattr(new, name, getattr(self, name))
         return new
@@ -561,10 +623,13 @@ class _Lists(_Refine, _Filter):
         other, which is what the constructor builds from the concatenated rows and assignments: every stored array is
         merged on the device (Pq.merge_lists_device), positions are rebuilt by a scatter, and nothing of length N
         goes to the host or through a sort.  Attached vectors are concatenated, in the dtype of self, if both
-        matrices have them, and dropped otherwise.  Row filters are not carried over."""
+        matrices have them, and dropped otherwise.  Row filters are not carried over.  Both matrices hold 4-bit packed
+        codes or neither does (PanicError otherwise: pack4() or unpack4() one of them); the merge moves the packed rows."""
         import torch
         if type(other) is not type(self):
             raise PanicError("only a matrix of the same class can be merged")
+        if other.packed4 != self.packed4:
+            raise PanicError("a packed and an unpacked matrix cannot be merged: call pack4() or unpack4() on one of them")
         if not (other.pq == self.pq) or not np.array_equal(other.centroids, self.centroids):
             raise PanicError("the matrices must share the quantizer and the centroids of the lists")
         if (other.norms is None) != (self.norms is None):
@@ -614,7 +679,8 @@ class PartitionedMatrix(_Lists):
         [N] in ORIGINAL row order -- only allowed rows of the probed lists are ranked, as if the others were not stored."""
         R = k if refine is None else self._check_refine(k, refine)
         d, pos = self.pq.adc_search_lists_device(self.codes, self.pq.adc_tables_device(queries), self.list_off,
-                                                 self.probes(queries, nprobe), R, allow=self._allow_words(allow))
+                                                 self.probes(queries, nprobe), R, allow=self._allow_words(allow),
+                                                 packed4=self.packed4)
         rows = self._original_rows(pos)
         return (d, rows) if refine is None else self._refined(queries, rows, k, False)
 
@@ -627,7 +693,7 @@ class PartitionedMatrix(_Lists):
         scales = self.norms if use_norms else None
         s, pos = self.pq.adc_ip_search_lists_device(self.codes, self.pq.adc_ip_tables_device(queries), self.list_off,
                                                     self.probes(queries, nprobe), R, scales=scales,
-                                                    allow=self._allow_words(allow))
+                                                    allow=self._allow_words(allow), packed4=self.packed4)
         rows = self._original_rows(pos)
         return (s, rows) if refine is None else self._refined(queries, rows, k, True)
 
@@ -635,7 +701,8 @@ class PartitionedMatrix(_Lists):
         """QuantizedMatrix.within among the rows of the nprobe nearest lists -> (lims, dist, idx), idx original row
         numbers; the rows of a query come list by list in probe order, inside a list in ascending original row number
         (Pq.adc_range_lists_device).  sort=True: ascending in distance, ties in that order.  No refine=: re-ranking is
-        defined for at most 1,024 candidates per query."""
+        defined for at most 1,024 candidates per query.  Not served on a packed matrix: unpack4() first."""
+        self._unpacked_only("within")
         lims, d, pos = self.pq.adc_range_lists_device(self.codes, self.pq.adc_tables_device(queries), self.list_off,
                                                       self.probes(queries, nprobe), radius, allow=self._allow_words(allow))
         rows = self._original_rows(pos)
@@ -645,7 +712,9 @@ class PartitionedMatrix(_Lists):
 
     def similar_above(self, queries, threshold, nprobe, use_norms=True, allow=None, sort=False):
         """QuantizedMatrix.similar_above among the rows of the nprobe nearest lists -> (lims, score, idx), idx original
-        row numbers, order as for within() (Pq.adc_ip_range_lists_device).  sort=True: descending in score."""
+        row numbers, order as for within() (Pq.adc_ip_range_lists_device).  sort=True: descending in score.  Not served
+        on a packed matrix: unpack4() first."""
+        self._unpacked_only("similar_above")
         scales = self.norms if use_norms else None
         lims, sc, pos = self.pq.adc_ip_range_lists_device(self.codes, self.pq.adc_ip_tables_device(queries), self.list_off,
                                                           self.probes(queries, nprobe), threshold, scales=scales,
@@ -661,14 +730,14 @@ class PartitionedMatrix(_Lists):
         encodes it.  The result is, tensor for tensor, the matrix the constructor builds from all rows in row order.
         norms [B] is required iff the matrix has norms.  Attached vectors are extended in the attached dtype."""
         x = _device_rows(vectors, self.pq.reconstructed_len(), self.codes.device)
-        codes = self.pq.quantize_batch_device(x) if x.shape[0] else self.codes[:0]
+        codes = self._stored_codes(self.pq.quantize_batch_device(x)) if x.shape[0] else self.codes[:0]
         return self._add_encoded(x, norms, self.assign(x), codes=codes)
 
     def embeddings(self, rows, out=None):
         """QuantizedMatrix.embeddings of the original row numbers `rows`."""
         import torch
         rows = torch.as_tensor(rows, dtype=torch.int64, device=self.codes.device)
-        return self.pq.reconstruct_rows_device(self.codes, self.positions[rows], scales=self.norms, out=out)
+        return self._reconstruct_rows(self.positions[rows], scales=self.norms, out=out)
 
 
 class ResidualPartitionedMatrix(_Lists):
@@ -708,7 +777,8 @@ class ResidualPartitionedMatrix(_Lists):
         R = k if refine is None else self._check_refine(k, refine)
         pr, bias = self._probes_and_dists(queries, nprobe)
         d, pos = self.pq.adc_search_lists_residual_device(self.codes, self.pq.adc_ip_tables_device(queries), self.list_off,
-                                                          pr, bias, self.row_terms, R, allow=self._allow_words(allow))
+                                                          pr, bias, self.row_terms, R, allow=self._allow_words(allow),
+                                                          packed4=self.packed4)
         rows = self._original_rows(pos)
         return (d, rows) if refine is None else self._refined(queries, rows, k, False)
 
@@ -732,7 +802,7 @@ class ResidualPartitionedMatrix(_Lists):
         scales = self.norms if use_norms else None
         s, pos = self.pq.adc_ip_search_lists_residual_device(self.codes, self.pq.adc_ip_tables_device(queries),
                                                              self.list_off, pr, bias, R, scales=scales,
-                                                             allow=self._allow_words(allow))
+                                                             allow=self._allow_words(allow), packed4=self.packed4)
         rows = self._original_rows(pos)
         return (s, rows) if refine is None else self._refined(queries, rows, k, True)
 
@@ -740,7 +810,8 @@ class ResidualPartitionedMatrix(_Lists):
         """every row of the nprobe nearest lists with dist = fl(fl(bias + row_term) - fl(s + s)) <= radius, bias obtained
         exactly as nearest() obtains it -> (lims, dist, idx), idx original row numbers, rows list by list in probe order
         (Pq.adc_range_lists_residual_device).  sort=True: ascending in distance.  No refine=: re-ranking is defined for
-        at most 1,024 candidates per query."""
+        at most 1,024 candidates per query.  Not served on a packed matrix: unpack4() first."""
+        self._unpacked_only("within")
         pr, bias = self._probes_and_dists(queries, nprobe)
         lims, d, pos = self.pq.adc_range_lists_residual_device(self.codes, self.pq.adc_ip_tables_device(queries),
                                                                self.list_off, pr, bias, self.row_terms, radius,
@@ -753,7 +824,9 @@ class ResidualPartitionedMatrix(_Lists):
     def similar_above(self, queries, threshold, nprobe, use_norms=True, allow=None, sort=False):
         """every row of the nprobe nearest lists with score = fl(fl(bias + s) * norm) >= threshold (fl(bias + s) with
         use_norms=False or without norms), bias obtained exactly as most_similar() obtains it -> (lims, score, idx)
-        (Pq.adc_ip_range_lists_residual_device).  sort=True: descending in score."""
+        (Pq.adc_ip_range_lists_residual_device).  sort=True: descending in score.  Not served on a packed matrix:
+        unpack4() first."""
+        self._unpacked_only("similar_above")
         pr, bias = self._probes_and_ips(queries, nprobe)
         scales = self.norms if use_norms else None
         lims, sc, pos = self.pq.adc_ip_range_lists_residual_device(self.codes, self.pq.adc_ip_tables_device(queries),
@@ -789,14 +862,14 @@ class ResidualPartitionedMatrix(_Lists):
         re-trained."""
         x = _device_rows(vectors, self.pq.reconstructed_len(), self.codes.device)
         lists, codes, terms = self.encode(x)
-        return self._add_encoded(x, norms, lists, codes=codes, row_terms=terms, lists=lists)
+        return self._add_encoded(x, norms, lists, codes=self._stored_codes(codes), row_terms=terms, lists=lists)
 
     def embeddings(self, rows):
         """fl(fl(r^ + c_l) * norm) of the original row numbers `rows` (fl(r^ + c_l) without norms) -> [len(rows), d]."""
         import torch
         rows = torch.as_tensor(rows, dtype=torch.int64, device=self.codes.device)
         pos = self.positions[rows]
-        e = self.pq.reconstruct_rows_device(self.codes, pos) + self._centroids_dev[self.lists[pos]]
+        e = self._reconstruct_rows(pos) + self._centroids_dev[self.lists[pos]]
         return e if self.norms is None else e * self.norms[pos][:, None]
 
 

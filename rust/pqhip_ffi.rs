@@ -160,6 +160,47 @@ extern "C" {
     pub fn pqhip_lists_merge_dev(cb: *mut pqhip_codebook, device_slot: i32, d_off_a: *const i64, n_a: i64,
         d_off_b: *const i64, n_b: i64, n_lists: i64, row_bytes: i64, d_a: *const c_void, d_b: *const c_void,
         d_out: *mut c_void, d_off_out: *mut i64, stream: *mut c_void) -> i32;
+    // 4-bit packed codes (K <= 16): a row is ceil(M / 2) bytes, code m in byte m >> 1, even m in the low nibble, the pad
+    // nibble of an odd M written as 0 and ignored by every reader; no alignment of base or stride
+    pub fn pqhip_pack_codes4_dev(cb: *mut pqhip_codebook, device_slot: i32, d_codes: *const c_void, code_bytes: i32,
+        n: i64, codes_row_stride: i64, d_packed: *mut u8, packed_row_stride: i64, stream: *mut c_void) -> i32;
+    // d_rows NULL: all n rows in order; else the rows d_rows[0 .. n_rows) (a row id outside [0, n): a zero row, range flag)
+    pub fn pqhip_unpack_codes4_dev(cb: *mut pqhip_codebook, device_slot: i32, d_packed: *const u8, n: i64,
+        packed_row_stride: i64, d_rows: *const i64, n_rows: i64, d_codes_out: *mut u8, out_row_stride: i64,
+        stream: *mut c_void) -> i32;
+    // the six searches over packed rows: the masked signatures with (d_packed, n_codes, packed_row_stride) in the place
+    // of (d_codes, code_bytes, n_codes, codes_row_stride); d_allow NULL = no filter; results bit for bit those of the
+    // unpacked codes; option "adc_packed4_wgs" forces the producer workgroups of the two exhaustive calls
+    pub fn pqhip_adc_search_packed4_f32_dev(cb: *mut pqhip_codebook, device_slot: i32, d_tables: *const f32,
+        n_queries: i64, d_packed: *const u8, n_codes: i64, packed_row_stride: i64,
+        d_allow: *const u32, k: i32, d_dist: *mut f32, dist_row_stride: i64, d_idx: *mut i64, idx_row_stride: i64,
+        stream: *mut c_void) -> i32;
+    pub fn pqhip_adc_ip_search_packed4_f32_dev(cb: *mut pqhip_codebook, device_slot: i32, d_tables: *const f32,
+        n_queries: i64, d_packed: *const u8, n_codes: i64, packed_row_stride: i64,
+        d_allow: *const u32, d_scales: *const f32, k: i32, d_score: *mut f32, score_row_stride: i64, d_idx: *mut i64,
+        idx_row_stride: i64, stream: *mut c_void) -> i32;
+    pub fn pqhip_adc_search_lists_packed4_f32_dev(cb: *mut pqhip_codebook, device_slot: i32, d_tables: *const f32,
+        n_queries: i64, d_packed: *const u8, n_codes: i64, packed_row_stride: i64,
+        d_allow: *const u32, d_list_off: *const i64, n_lists: i64, d_probes: *const i64, n_probe: i32,
+        probes_row_stride: i64, k: i32, d_dist: *mut f32, dist_row_stride: i64, d_idx: *mut i64, idx_row_stride: i64,
+        stream: *mut c_void) -> i32;
+    pub fn pqhip_adc_ip_search_lists_packed4_f32_dev(cb: *mut pqhip_codebook, device_slot: i32, d_tables: *const f32,
+        n_queries: i64, d_packed: *const u8, n_codes: i64, packed_row_stride: i64,
+        d_allow: *const u32, d_list_off: *const i64, n_lists: i64, d_probes: *const i64, n_probe: i32,
+        probes_row_stride: i64, d_scales: *const f32, k: i32, d_score: *mut f32, score_row_stride: i64,
+        d_idx: *mut i64, idx_row_stride: i64, stream: *mut c_void) -> i32;
+    pub fn pqhip_adc_search_lists_residual_packed4_f32_dev(cb: *mut pqhip_codebook, device_slot: i32,
+        d_tables: *const f32, n_queries: i64, d_packed: *const u8, n_codes: i64,
+        packed_row_stride: i64, d_allow: *const u32, d_list_off: *const i64, n_lists: i64, d_probes: *const i64,
+        n_probe: i32, probes_row_stride: i64, d_probe_bias: *const f32, bias_row_stride: i64,
+        d_row_terms: *const f32, k: i32, d_dist: *mut f32, dist_row_stride: i64, d_idx: *mut i64,
+        idx_row_stride: i64, stream: *mut c_void) -> i32;
+    pub fn pqhip_adc_ip_search_lists_residual_packed4_f32_dev(cb: *mut pqhip_codebook, device_slot: i32,
+        d_tables: *const f32, n_queries: i64, d_packed: *const u8, n_codes: i64,
+        packed_row_stride: i64, d_allow: *const u32, d_list_off: *const i64, n_lists: i64, d_probes: *const i64,
+        n_probe: i32, probes_row_stride: i64, d_probe_bias: *const f32, bias_row_stride: i64, d_scales: *const f32,
+        k: i32, d_score: *mut f32, score_row_stride: i64, d_idx: *mut i64, idx_row_stride: i64,
+        stream: *mut c_void) -> i32;
 }
 
 /// Batches smaller than this stay on the CPU path (a launch + PCIe round trip is pointless).
