@@ -622,6 +622,69 @@ int32_t pqhip_lists_merge_dev(pqhip_codebook *cb, int32_t device_slot,
                               int64_t row_bytes, const void *d_a, const void *d_b, void *d_out,
                               int64_t *d_off_out /* or NULL */, void *stream);
 
+/*
+ * Building a partitioned index on the device: the layout of the lists, the residuals and the query-free row terms.
+ *
+ * pqhip_lists_layout_dev: d_assign is [n] list ids, signed integers of idx_bytes (4 or 8) bytes each.  With `ids` the
+ * STABLE argsort of the assignments (positions inside a list ascend in row number) the outputs are
+ *     d_list_off [n_lists + 1]   prefix sums of the list sizes (empty lists are legal)
+ *     d_ids [n]                  ids[p] = the row at position p
+ *     d_positions [n]            positions[ids[p]] = p
+ *     d_lists [n] or NULL        lists[p] = assign[ids[p]]
+ * all int64.  A counting sort in one pass over the ids: every workgroup counts a contiguous slice of rows, a scan gives
+ * the offsets and each workgroup's first position in each list, and the workgroups walk their slices again in row
+ * order.  The result is a function of the input alone: it does not depend on the number of workgroups (chosen from the
+ * size, the number of lists and the CU count; option "lists_layout_wgs" forces it).  cb supplies the device slot, the
+ * scratch (8 bytes per list and workgroup) and the stream's range flag, as for pqhip_lists_merge_dev; its quantizer is
+ * not read.
+ * The ids are device memory and are NOT TRUSTED.  If any id is negative or >= n_lists, no element of d_ids, d_positions
+ * or d_lists is written, the stream's range flag is raised (pqhip_check_codes_dev -> PQHIP_ECODE_RANGE) and the
+ * contents of d_list_off are unspecified: the counting pass validates, and the placing pass runs only behind a validity
+ * word.
+ * Status codes: a null cb, n < 0, n_lists < 1, idx_bytes other than 4 or 8, a null d_list_off, with n > 0 a null d_assign,
+ * d_ids or d_positions: PQHIP_EINVAL; then the slot (PQHIP_ENODEV); n_lists > PQHIP_LISTS_LAYOUT_MAX_LISTS (the k-means
+ * limit; it bounds the table of counts a workgroup keeps in LDS) or n > 2^49: PQHIP_EUNSUPPORTED, as is a table of counts
+ * beyond the scratch limit (a workgroup takes at most 2^31 rows).  n == 0 writes an all-zero d_list_off and launches no
+ * kernel.  Asynchronous on `stream`.
+ *
+ * pqhip_residuals_f32_dev: out[i][j] = x[i][j] - centroids[assign[i]][j] for i < n, j < d: one IEEE f32 subtraction per
+ * element.  d_x and d_out are [n][d] with row strides in elements (>= d, PQHIP_ESHAPE otherwise), d_assign int64 [n],
+ * d_centroids [n_lists][d] contiguous.  A list id outside [0, n_lists) writes a zero row and raises the range flag.  No
+ * base or stride needs any alignment: loads and stores are 16 bytes wide where the three addresses allow it and single
+ * elements elsewhere.  d_out must not overlap an input.  d <= PQHIP_RESIDUALS_MAX_D (PQHIP_EUNSUPPORTED).
+ *
+ * pqhip_residual_terms_f32_dev: the query-free term of a residual-encoded row (pqhip_adc_search_lists_residual_f32_dev:
+ * row_terms) without a reconstruction.  cb is the residual quantizer (M subquantizers of K <= 256 centroids, sub-vectors
+ * of ds floats), d_codes [n][M] one byte per code with a row stride (>= M, PQHIP_ESHAPE otherwise), d_assign int64 [n],
+ * d_centroids [n_lists][M ds] contiguous, d_out f32 [n].  With r = quantizers[m][code[i][m]][e] and
+ * c = centroids[assign[i]][m ds + e], both widened to f64:
+ *     p[i][m] = the sequential f64 sum over e = 0 .. ds - 1, starting from +0, of (r r + 2 c r): both products are exact,
+ *               their sum is one rounded addition, adding it to the running sum a second one; nothing is fused
+ *     out[i]  = (float) of the sequential f64 sum over m = 0 .. M - 1, starting from +0, of p[i][m] (to nearest even)
+ * A code >= K reads entry 0 and raises the range flag; a list id outside [0, n_lists) writes +0 and raises it.
+ * A codebook WITH A PROJECTION is PQHIP_EUNSUPPORTED (its reconstruction includes the inverse rotation, which this call
+ * does not apply), as are K > 256, M > PQHIP_RESIDUAL_TERMS_MAX_M and M ds > PQHIP_RESIDUALS_MAX_D.
+ *
+ * Status codes of the two residual calls: a null cb, n < 0, n_lists < 1 (d < 1): PQHIP_EINVAL; then the slot
+ * (PQHIP_ENODEV); then PQHIP_EUNSUPPORTED as above; n == 0 is PQHIP_OK and launches nothing; then a null pointer
+ * (PQHIP_EINVAL) and the strides (PQHIP_ESHAPE).  Asynchronous on `stream`.
+ */
+#define PQHIP_LISTS_LAYOUT_MAX_LISTS 16384
+#define PQHIP_RESIDUALS_MAX_D 1048576
+#define PQHIP_RESIDUAL_TERMS_MAX_M 8192
+int32_t pqhip_lists_layout_dev(pqhip_codebook *cb, int32_t device_slot,
+                               const void *d_assign, int32_t idx_bytes, int64_t n, int64_t n_lists,
+                               int64_t *d_list_off, int64_t *d_ids, int64_t *d_positions,
+                               int64_t *d_lists /* or NULL */, void *stream);
+int32_t pqhip_residuals_f32_dev(pqhip_codebook *cb, int32_t device_slot,
+                                const float *d_x, int64_t n, int64_t d, int64_t x_row_stride,
+                                const int64_t *d_assign, const float *d_centroids, int64_t n_lists,
+                                float *d_out, int64_t out_row_stride, void *stream);
+int32_t pqhip_residual_terms_f32_dev(pqhip_codebook *cb, int32_t device_slot,
+                                     const uint8_t *d_codes, int64_t n, int64_t codes_row_stride,
+                                     const int64_t *d_assign, const float *d_centroids, int64_t n_lists,
+                                     float *d_out, void *stream);
+
 /* Reconstruct's range check is asynchronous on the device path: returns PQHIP_ECODE_RANGE if any
  * device call since the last query saw a code >= K (synchronises `stream`). */
 int32_t pqhip_check_codes_dev(pqhip_codebook *cb, int32_t device_slot, void *stream);
@@ -761,6 +824,8 @@ int32_t pqhip_set_rotation_variant(int32_t variant);
  *                          as for the u8 searches; at most 65536; rows per workgroup stay a multiple of 1,024)
  *   "lists_merge_wgs"      workgroups of the mover of pqhip_lists_merge_dev (0 = chosen from the size and the CU count; at
  *                          most 2^20, and never more than one per 1,024 16-byte chunks of output)
+ *   "lists_layout_wgs"     workgroups (row slices) of pqhip_lists_layout_dev (0 = chosen from the size, the number of lists and
+ *                          the CU count; at most 65536, never more than one per 1,024 rows; the result does not depend on it)
  *   "rerank_wgs_per_query" workgroups that share one query in the distance stage of pqhip_rerank_f32_dev (0 = chosen from the
  *                          shape; at most 1024)
  *   "cross_product_exact"  0 = X^T.R of the OPQ training step / pqhip_at_dot_b_f32_dev as a plain split-K product:

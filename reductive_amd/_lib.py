@@ -143,6 +143,12 @@ def lib():
                                        vp, i64, vp, i64, vp]
     L.pqhip_lists_merge_dev.restype = i32
     L.pqhip_lists_merge_dev.argtypes = [vp, i32, vp, i64, vp, i64, i64, i64, vp, vp, vp, vp, vp]
+    L.pqhip_lists_layout_dev.restype = i32
+    L.pqhip_lists_layout_dev.argtypes = [vp, i32, vp, i32, i64, i64, vp, vp, vp, vp, vp]
+    L.pqhip_residuals_f32_dev.restype = i32
+    L.pqhip_residuals_f32_dev.argtypes = [vp, i32, vp, i64, i64, i64, vp, vp, i64, vp, i64, vp]
+    L.pqhip_residual_terms_f32_dev.restype = i32
+    L.pqhip_residual_terms_f32_dev.argtypes = [vp, i32, vp, i64, i64, vp, vp, i64, vp, vp]
     L.pqhip_check_codes_dev.restype = i32
     L.pqhip_check_codes_dev.argtypes = [vp, i32, vp]
     L.pqhip_cluster_assignments_f32.restype = i32
@@ -210,6 +216,7 @@ EXPORTS = [
     "pqhip_adc_range_lists_f32_dev", "pqhip_adc_ip_range_lists_f32_dev",
     "pqhip_adc_range_lists_residual_f32_dev", "pqhip_adc_ip_range_lists_residual_f32_dev",
     "pqhip_rerank_f32_dev", "pqhip_lists_merge_dev",
+    "pqhip_lists_layout_dev", "pqhip_residuals_f32_dev", "pqhip_residual_terms_f32_dev",
     "pqhip_cluster_assignments_f32", "pqhip_kmeans_iterations_f32", "pqhip_kmeans_iterations_f32_dev",
     "pqhip_opq_train_step_f32_dev", "pqhip_at_dot_b_f32_dev", "pqhip_rotate_f32_dev",
     "pqhip_matrix_upload_f32", "pqhip_matrix_device_ptr", "pqhip_matrix_rows", "pqhip_matrix_destroy",

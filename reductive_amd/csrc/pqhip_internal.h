@@ -13,6 +13,7 @@
 //     pqhip_adc_range.hip ADC range search: every row within a radius, as CSR
 //     pqhip_rerank.hip    exact re-ranking of search candidates against resident vectors
 //     pqhip_lists_merge.hip  merge of two list-ordered row arrays (growing a partitioned matrix)
+//     pqhip_lists_layout.hip  building a partitioned index: layout of the lists, residuals, query-free row terms
 //     pqhip_train.hip     k-means iterations, X^T.R, the OPQ training step, resident matrices
 //     pqhip_host.hip      host-resident entry points: row sharding over devices, pinned double-buffered staging
 // There is deliberately NO CPU compute fallback anywhere: without HIP or a gfx950 device every compute entry
@@ -97,6 +98,7 @@ struct Options {
     std::atomic<int64_t> adc_range_wgs_per_query{0};   // list range searches: workgroups per query (0: chosen from the shape)
     std::atomic<int64_t> lists_merge_wgs{0};        // list merge: workgroups of the mover (0: chosen from the size)
     std::atomic<int64_t> adc_packed4_wgs{0};        // exhaustive searches over 4-bit packed codes: producer workgroups (0: chosen from the shape)
+    std::atomic<int64_t> lists_layout_wgs{0};       // list layout: workgroups, one row slice each (0: chosen from the size)
 };
 
 struct Diag {

@@ -1598,3 +1598,149 @@ class Pq:
             if rc != _lib.OK:
                 raise _lib.PqHipError(rc, "pqhip_check_codes_dev")
         return out, off_out
+
+    # ---- building a partitioned matrix on the device: list layout, residuals, query-free row terms -----------------------
+    def _raise_range(self, cb, slot, stream):
+        rc = _lib.lib().pqhip_check_codes_dev(cb, slot, ctypes.c_void_p(stream))
+        if rc == _lib.ECODE_RANGE:
+            raise PanicError("ndarray: index out of bounds")
+        if rc != _lib.OK:
+            raise _lib.PqHipError(rc, "pqhip_check_codes_dev")
+
+    def lists_layout_device(self, assign, n_lists, want_lists=False, stream=None, check=False):
+        """assign: CUDA int32 or int64 vector [n] of list ids in [0, n_lists), contiguous -> (ids, list_off, positions) or,
+        with want_lists, (ids, list_off, positions, lists), all CUDA int64: what qmatrix.ivf_layout defines, computed on
+        the device (pqhip_lists_layout_dev).  ids [n] is the STABLE argsort of the assignments (positions inside a list
+        ascend in row number), list_off [n_lists + 1] the prefix sums of the list sizes (empty lists are legal),
+        positions[ids[p]] = p and lists[p] = assign[ids[p]].  1 <= n_lists <= 16384.  The ids are checked on the device:
+        if one lies outside [0, n_lists), ids, positions and lists are left as allocated and the stream's range flag is
+        raised (check=True: synchronises and raises PanicError).  The quantizer of self is not used."""
+        import torch
+        if not hasattr(assign, "is_cuda"):
+            raise PanicError("assign must be a torch tensor")
+        if assign.dtype not in (torch.int32, torch.int64) or assign.dim() != 1:
+            raise PanicError("assign must be an int32 or int64 vector of list ids")
+        n_lists = int(n_lists)
+        if not 1 <= n_lists <= 16384:
+            raise PanicError("the number of lists must be between 1 and 16384, was %d" % n_lists)
+        if not assign.is_contiguous():
+            raise PanicError("lists_layout_device takes a contiguous vector")
+        if not assign.is_cuda:
+            raise PanicError("lists_layout_device takes a CUDA tensor")
+        n, dev = assign.shape[0], assign.device
+        ids = torch.empty(n, dtype=torch.int64, device=dev)
+        positions = torch.empty(n, dtype=torch.int64, device=dev)
+        lists = torch.empty(n, dtype=torch.int64, device=dev) if want_lists else None
+        list_off = torch.empty(n_lists + 1, dtype=torch.int64, device=dev)
+        cb = self._cb()
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        slot = self._slot_for(assign)
+        rc = _lib.lib().pqhip_lists_layout_dev(
+            cb, slot, assign.data_ptr() if n else None, assign.element_size(), n, n_lists, list_off.data_ptr(),
+            ids.data_ptr() if n else None, positions.data_ptr() if n else None,
+            lists.data_ptr() if want_lists and n else None, ctypes.c_void_p(stream))
+        if rc != _lib.OK:
+            raise _lib.PqHipError(rc, "pqhip_lists_layout_dev")
+        if check:
+            self._raise_range(cb, slot, stream)
+        return (ids, list_off, positions, lists) if want_lists else (ids, list_off, positions)
+
+    @staticmethod
+    def _check_rows_lists(what, assign, centroids, n, d):
+        """the (assign, centroids) pair of the two residual calls: int64 [n] and float32 [n_lists, d], contiguous"""
+        import torch
+        for t, name in ((assign, "assign"), (centroids, "centroids")):
+            if not hasattr(t, "is_cuda"):
+                raise PanicError("%s must be a torch tensor" % name)
+        if assign.dtype != torch.int64 or tuple(assign.shape) != (n,):
+            raise PanicError("assign must be an int64 vector with one list id per row (%d)" % n)
+        if centroids.dtype != torch.float32 or centroids.dim() != 2 or centroids.shape[1] != d or centroids.shape[0] < 1:
+            raise PanicError("centroids must be float32 [n_lists, %d] with at least one list" % d)
+        if not assign.is_contiguous() or not centroids.is_contiguous():
+            raise PanicError("%s takes contiguous assign and centroids" % what)
+
+    def residuals_device(self, x, assign, centroids, out=None, stream=None, check=False):
+        """x: CUDA float32 [n, d] (unit column stride, any row stride), assign: CUDA int64 [n], centroids: CUDA float32
+        [n_lists, d] -> out float32 [n, d] with out[i] = x[i] - centroids[assign[i]], one IEEE subtraction per element:
+        bit for bit what the torch expression x - centroids[assign] gives, in one pass and without the gathered
+        temporary (pqhip_residuals_f32_dev).  out, if given, is float32 [n, d] with unit column stride and must not
+        overlap x.  A list id outside [0, n_lists) gives a zero row and raises the stream's range flag (check=True:
+        synchronises and raises PanicError).  d is the width of x: the quantizer of self is not used."""
+        import torch
+        if not hasattr(x, "is_cuda"):
+            raise PanicError("x must be a torch tensor")
+        if x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] < 1:
+            raise PanicError("x must be float32 [n, d]")
+        n, d = x.shape
+        self._check_rows_lists("residuals_device", assign, centroids, n, d)
+        if out is not None and (not hasattr(out, "is_cuda") or out.dtype != torch.float32 or tuple(out.shape) != (n, d)):
+            raise PanicError("out must be a float32 tensor of shape [%d, %d]" % (n, d))
+        if x.stride(1) != 1 or (out is not None and out.stride(1) != 1):
+            raise PanicError("residuals_device takes rows with unit column stride")
+        if not (x.is_cuda and assign.is_cuda and centroids.is_cuda and (out is None or out.is_cuda)):
+            raise PanicError("residuals_device takes CUDA tensors")
+        if not (x.device == assign.device == centroids.device and (out is None or out.device == x.device)):
+            raise PanicError("all tensors of residuals_device must live on one device")
+        if out is None:
+            out = torch.empty((n, d), dtype=torch.float32, device=x.device)
+        cb = self._cb()
+        if stream is None:
+            stream = torch.cuda.current_stream(x.device).cuda_stream
+        slot = self._slot_for(x)
+        rc = _lib.lib().pqhip_residuals_f32_dev(
+            cb, slot, x.data_ptr() if n else None, n, d, x.stride(0) if n > 1 else max(x.stride(0), d),
+            assign.data_ptr() if n else None, centroids.data_ptr(), centroids.shape[0],
+            out.data_ptr() if n else None, out.stride(0) if n > 1 else max(out.stride(0), d), ctypes.c_void_p(stream))
+        if rc != _lib.OK:
+            raise _lib.PqHipError(rc, "pqhip_residuals_f32_dev")
+        if check:
+            self._raise_range(cb, slot, stream)
+        return out
+
+    def residual_terms_device(self, codes, assign, centroids, out=None, stream=None, check=False):
+        """self is the residual quantizer (no projection, at most 256 centroids); codes: CUDA uint8 [n, M] (unit column
+        stride, any row stride), assign: CUDA int64 [n], centroids: CUDA float32 [n_lists, d] -> out float32 [n], the
+        query-free terms t_i = sum_j (r_ij^2 + 2 c_ij r_ij) of the rows, r the reconstruction of the code row and c
+        the centroid of its list -- computed from the codebook entries, no reconstruction is written anywhere
+        (pqhip_residual_terms_f32_dev).  The order of the f64 arithmetic is fixed: per subquantizer the sequential sum
+        over its columns of (r r + 2 c r), then the sequential sum of these over the subquantizers, rounded once to f32
+        (tests/residual_terms_ref.py is this definition in numpy).  A code >= K reads entry 0, a list id outside
+        [0, n_lists) gives +0; both raise the stream's range flag (check=True: synchronises and raises PanicError).
+        A quantizer with a projection is refused (PanicError): its reconstruction includes the inverse rotation."""
+        import torch
+        if not hasattr(codes, "is_cuda"):
+            raise PanicError("codes must be a torch tensor")
+        if self._projection is not None:
+            raise PanicError("residual_terms_device does not serve a quantizer with a projection")
+        if self.n_quantizer_centroids() > 256:
+            raise PanicError("residual_terms_device reads 1-byte codes: at most 256 centroids")
+        if codes.dtype != torch.uint8 or codes.dim() != 2 or codes.shape[1] != self.quantized_len():
+            raise PanicError("codes must be uint8 [n, %d]" % self.quantized_len())
+        n, d = codes.shape[0], self.reconstructed_len()
+        self._check_rows_lists("residual_terms_device", assign, centroids, n, d)
+        if out is not None and (not hasattr(out, "is_cuda") or out.dtype != torch.float32 or tuple(out.shape) != (n,)
+                                or not out.is_contiguous()):
+            raise PanicError("out must be a contiguous float32 tensor of shape [%d]" % n)
+        if codes.stride(1) != 1:
+            raise PanicError("residual_terms_device takes code rows with unit column stride")
+        if not (codes.is_cuda and assign.is_cuda and centroids.is_cuda and (out is None or out.is_cuda)):
+            raise PanicError("residual_terms_device takes CUDA tensors")
+        if not (codes.device == assign.device == centroids.device and (out is None or out.device == codes.device)):
+            raise PanicError("all tensors of residual_terms_device must live on one device")
+        if out is None:
+            out = torch.empty(n, dtype=torch.float32, device=codes.device)
+        cb = self._cb()
+        if stream is None:
+            stream = torch.cuda.current_stream(codes.device).cuda_stream
+        slot = self._slot_for(codes)
+        M = self.quantized_len()
+        rc = _lib.lib().pqhip_residual_terms_f32_dev(
+            cb, slot, codes.data_ptr() if n else None, n, codes.stride(0) if n > 1 else max(codes.stride(0), M),
+            assign.data_ptr() if n else None, centroids.data_ptr(), centroids.shape[0],
+            out.data_ptr() if n else None, ctypes.c_void_p(stream))
+        if rc != _lib.OK:
+            raise _lib.PqHipError(rc, "pqhip_residual_terms_f32_dev")
+        if check:
+            self._raise_range(cb, slot, stream)
+        return out

@@ -145,6 +145,33 @@ def _residual_codes_terms(residual_pq, rows, c, codes_out):
     return (r * r + 2.0 * c.double() * r).sum(1).float()
 
 
+def _residual_codes_terms_device(residual_pq, rows, lists, centroids, codes_out, terms_out, buf):
+    """_residual_codes_terms on the device route: `lists` int64 [n] and `centroids` [n_lists, d] on the device in the
+    place of the gathered centroids.  The residuals go through residuals_device into buf[:n] (bit for bit rows - c), the
+    codes to codes_out, and the terms come from residual_terms_device -- defined by its own fixed f64 order, not by
+    torch's reduction -- into terms_out [n].  A quantizer with a projection keeps the torch tail, so its terms are
+    those of _residual_codes_terms."""
+    resid = residual_pq.residuals_device(rows, lists, centroids, out=buf[:rows.shape[0]])
+    residual_pq.quantize_batch_device(resid, out=codes_out)
+    if residual_pq.projection() is None:
+        residual_pq.residual_terms_device(codes_out, lists, centroids, out=terms_out)
+    else:
+        r = residual_pq.reconstruct_batch_device(codes_out).double()
+        terms_out.copy_((r * r + 2.0 * centroids[lists].double() * r).sum(1).float())
+
+
+def _assign_device(coarse, n, rows_of_range, dev):
+    """the nearest centroid of n rows -> int64 [n] on `dev`: the encode kernels of the one-subquantizer codebook
+    `coarse` with a 4-byte index, in chunks of 2^20 rows; rows_of_range(r0, r1) gives the float32 device rows [r0, r1)"""
+    import torch
+    out = torch.empty((n, 1), dtype=torch.int32, device=dev)
+    chunk = 1 << 20
+    for r0 in range(0, n, chunk):
+        r1 = min(n, r0 + chunk)
+        coarse.quantize_batch_device(rows_of_range(r0, r1), out=out[r0:r1])
+    return out[:, 0].long()
+
+
 class _Refine:
     """Exact re-ranking against the original vectors, for all three matrix classes: `vectors` is an [N, d] device copy
     in ORIGINAL row order (None until attach_vectors), so the row numbers a search returns address it as they are."""
@@ -402,7 +429,7 @@ class QuantizedMatrix(_Refine, _Filter, _Packed4):
             new.vectors = torch.cat([self.vectors, x.to(self.vectors.dtype)])
         return new
 
-    def partition(self, n_lists, n_iterations=10, vectors=None, train_rows=None, rng=None):
+    def partition(self, n_lists, n_iterations=10, vectors=None, train_rows=None, rng=None, on_device=False):
         """Partition the rows with a coarse k-means quantizer of n_lists centroids -> PartitionedMatrix (IVFADC without
         residual encoding: the codes stay the codes of the vectors themselves).
 
@@ -414,25 +441,33 @@ class QuantizedMatrix(_Refine, _Filter, _Packed4):
         training is kmeans_iterations with one subquantizer, assignment is cluster_assignments.  Both take the slow
         anchor kernel for sub-vectors wider than 256 floats: accepted for a build step.  1 <= n_lists <= 16384 (the
         k-means limit) and n_lists <= number of training rows.  Row filters are not carried over: a RowFilter belongs
-        to the matrix that built it (call row_filter on the result).  Not served on a packed matrix: unpack4() first."""
+        to the matrix that built it (call row_filter on the result).  Not served on a packed matrix: unpack4() first.
+
+        on_device=True: the same training and the same draws from `rng`, but the rows are assigned by the coarse
+        codebook's quantize_batch_device (as _Lists.assign does) and laid out by Pq.lists_layout_device: no array of
+        length N goes to the host.  The result equals that of the default route tensor for tensor (ids, list_off,
+        positions, codes, norms, centroids)."""
         self._unpacked_only("partition")
         rng = rng or np.random.default_rng(0)
-        centroids, assign, _, _ = self._coarse_partition(n_lists, n_iterations, vectors, train_rows, rng)
+        centroids, assign, _, _ = self._coarse_partition(n_lists, n_iterations, vectors, train_rows, rng, on_device)
         out = PartitionedMatrix(self, centroids, assign)
         out.vectors = self.vectors           # attached vectors stay in original row order: handed on as they are
         return out
 
-    def _coarse_partition(self, n_lists, n_iterations, vectors, train_rows, rng):
+    def _coarse_partition(self, n_lists, n_iterations, vectors, train_rows, rng, on_device=False):
         """The part partition() and partition_residual() share: trains the coarse quantizer and assigns every row ->
         (centroids [n_lists, d] f32, assign [N] int64, rows_of, train_sel): rows_of(sel) gives the float32 device rows
         the partition is built from, train_sel the training rows (a slice or sorted row numbers).  Draws from rng:
-        the training rows (if fewer than all), then the initial centroids."""
+        the training rows (if fewer than all), then the initial centroids.  assign is a numpy array, or with on_device
+        a device tensor (_assign_device: the rows never leave the device)."""
         import torch
         from .pq import ReductiveError, cluster_assignments, kmeans_iterations
         N, d = len(self), self.pq.reconstructed_len()
         if not 1 <= n_lists <= 16384:
             raise ReductiveError("The number of lists must be between 1 and 16384, was %d" % n_lists)
         chunk = 1 << 20
+        if on_device and not self.codes.is_cuda:
+            raise PanicError("on_device=True needs a matrix that is resident on a GPU")
 
         def rows_of(sel):
             """float32 [len(sel), d] on the device: the given vectors or the reconstructions of the code rows `sel`"""
@@ -456,6 +491,10 @@ class QuantizedMatrix(_Refine, _Filter, _Packed4):
         centroids, _ = kmeans_iterations(init[None], train, n_iterations, want_loss=False, ctx=self.pq._ctx)
         centroids = np.ascontiguousarray(centroids[0])
         del train
+        if on_device:
+            coarse = Pq(None, centroids[None], ctx=self.pq._ctx)
+            assign = _assign_device(coarse, N, lambda r0, r1: rows_of(slice(r0, r1)), self.codes.device)
+            return centroids, assign, rows_of, train_sel
         assign = np.empty(N, np.int64)
         for r0 in range(0, N, chunk):
             r1 = min(N, r0 + chunk)
@@ -463,7 +502,8 @@ class QuantizedMatrix(_Refine, _Filter, _Packed4):
         return centroids, assign, rows_of, train_sel
 
     def partition_residual(self, n_lists, n_subquantizers=None, n_subquantizer_bits=None, n_iterations=10,
-                           pq_iterations=10, n_attempts=1, vectors=None, train_rows=None, residual_pq=None, rng=None):
+                           pq_iterations=10, n_attempts=1, vectors=None, train_rows=None, residual_pq=None, rng=None,
+                           on_device=False):
         """Partition the rows as partition() does (the same coarse training, the same draws from `rng`, the same
         assignment) and re-encode them as residuals -> ResidualPartitionedMatrix (IVFADC with residual encoding).
 
@@ -475,7 +515,16 @@ class QuantizedMatrix(_Refine, _Filter, _Packed4):
         residuals are encoded with quantize_batch_device, in chunks, and every row gets its query-free term
         t_i = sum_j (r^_ij^2 + 2 c_lj r^_ij), r^ = reconstruct_batch_device of the residual quantizer, accumulated in
         float64 on the device and rounded once to f32.  The norms are kept as they are.  Row filters are not carried
-        over (row_filter on the result builds one from the same flags).  Not served on a packed matrix: unpack4() first."""
+        over (row_filter on the result builds one from the same flags).  Not served on a packed matrix: unpack4() first.
+
+        on_device=True: assignment and layout as partition(on_device=True); the residuals are formed by
+        Pq.residuals_device (bit for bit rows - centroids[assign]) and the row terms by Pq.residual_terms_device, which
+        reads the codebook entries instead of a reconstruction.  Only the training rows go to the host (train_pq).  The
+        result equals that of the default route in everything except row_terms: the device terms are defined by the
+        fixed f64 order of pqhip_residual_terms_f32_dev, not by torch's reduction, and agree with the default route's
+        within 2^-23 |t| + 2^-40 sum_j (r^2 + |2 c r|); searches over the two may differ where two rows tie to the
+        last bit.  A residual quantizer with a projection keeps the torch tail (its terms then equal the default
+        route's).  The matrix carries device_terms = True, so add() / encode() compute the terms of new rows the same way."""
         import torch
         from .pq import ReductiveError, train_pq
         self._unpacked_only("partition_residual")
@@ -489,22 +538,31 @@ class QuantizedMatrix(_Refine, _Filter, _Packed4):
             raise ReductiveError("The residual codes are 1-byte codes: at most 8 subquantizer bits, was %d" % bits)
         if residual_pq is not None and (residual_pq.reconstructed_len() != d or residual_pq.n_quantizer_centroids() > 256):
             raise PanicError("the residual quantizer must reconstruct %d columns from 1-byte codes" % d)
-        centroids, assign, rows_of, train_sel = self._coarse_partition(n_lists, n_iterations, vectors, train_rows, rng)
+        centroids, assign, rows_of, train_sel = self._coarse_partition(n_lists, n_iterations, vectors, train_rows, rng,
+                                                                       on_device)
         dev = self.codes.device
         cd = torch.from_numpy(centroids).to(dev)
-        ad = torch.from_numpy(assign).to(dev)
+        ad = assign if on_device else torch.from_numpy(assign).to(dev)
         if residual_pq is None:
             sel = train_sel if isinstance(train_sel, slice) else torch.from_numpy(train_sel).to(dev)
-            resid = rows_of(train_sel) - cd[ad[sel]]
+            if on_device:
+                resid = self.pq.residuals_device(rows_of(train_sel), ad[sel].contiguous(), cd)
+            else:
+                resid = rows_of(train_sel) - cd[ad[sel]]
             residual_pq = train_pq(M, int(bits), pq_iterations, n_attempts, resid.cpu().numpy(), rng=rng, ctx=self.pq._ctx)
             del resid
         codes = torch.empty((N, residual_pq.quantized_len()), dtype=torch.uint8, device=dev)
         terms = torch.empty(N, dtype=torch.float32, device=dev)
         chunk = 1 << 20
+        buf = torch.empty((min(chunk, N), d), dtype=torch.float32, device=dev) if on_device else None
         for r0 in range(0, N, chunk):
             r1 = min(N, r0 + chunk)
-            terms[r0:r1] = _residual_codes_terms(residual_pq, rows_of(slice(r0, r1)), cd[ad[r0:r1]], codes[r0:r1])
+            if on_device:
+                _residual_codes_terms_device(residual_pq, rows_of(slice(r0, r1)), ad[r0:r1], cd, codes[r0:r1], terms[r0:r1], buf)
+            else:
+                terms[r0:r1] = _residual_codes_terms(residual_pq, rows_of(slice(r0, r1)), cd[ad[r0:r1]], codes[r0:r1])
         out = ResidualPartitionedMatrix(residual_pq, codes, self.norms, terms, centroids, assign)
+        out.device_terms = bool(on_device)
         out.vectors = self.vectors
         return out
 
@@ -527,10 +585,25 @@ def ivf_layout(assign, n_lists):
 class _Lists(_Refine, _Filter, _Packed4):
     """What both partitioned forms share: the list layout, the coarse quantizer and the probe selection."""
 
-    def _init_lists(self, centroids, assign, n_rows, dev, ctx):
+    device_terms = False        # ResidualPartitionedMatrix: the row terms come from Pq.residual_terms_device
+
+    def _init_lists(self, centroids, assign, n_rows, dev, ctx, want_lists=False):
+        """The layout of the lists from `assign`: a numpy array of list ids (ivf_layout on the host) or an int64 CUDA
+        tensor (Pq.lists_layout_device: nothing of length N touches the host) -> with want_lists the list of every
+        position (device int64 [N]; device route only), else None."""
         import torch
         self.centroids = np.ascontiguousarray(centroids, dtype=np.float32)
         self.n_lists = self.centroids.shape[0]
+        if hasattr(assign, "is_cuda"):
+            if not assign.is_cuda or assign.dtype != torch.int64 or assign.device != torch.device(dev):
+                raise PanicError("a device assignment must be an int64 CUDA tensor on the device of the codes")
+            if tuple(assign.shape) != (n_rows,):
+                raise PanicError("one list id per row expected")
+            self.coarse = Pq(None, self.centroids[None], ctx=ctx)
+            laid = self.coarse.lists_layout_device(assign.contiguous(), self.n_lists, want_lists=want_lists, check=True)
+            self.ids, self.list_off, self.positions = laid[:3]
+            self._list_ids = torch.arange(self.n_lists, dtype=torch.int32, device=dev)[:, None].contiguous()
+            return laid[3] if want_lists else None
         perm, list_off = ivf_layout(assign, self.n_lists)
         if perm.size != n_rows:
             raise PanicError("one list id per row expected")
@@ -581,20 +654,15 @@ class _Lists(_Refine, _Filter, _Packed4):
         """the list of each vector ([B, d] float32, numpy or CUDA) -> int64 [B] on the device: the nearest centroid, as
         cluster_assignments(self.centroids, vectors) gives it row for row (the encode kernels of the one-subquantizer
         coarse codebook with a 4-byte index, entirely on the device)"""
-        import torch
         x = _device_rows(vectors, self.centroids.shape[1], self.codes.device)
-        out = torch.empty((x.shape[0], 1), dtype=torch.int32, device=x.device)
-        chunk = 1 << 20
-        for r0 in range(0, x.shape[0], chunk):
-            self.coarse.quantize_batch_device(x[r0:r0 + chunk], out=out[r0:r0 + chunk])
-        return out[:, 0].long()
+        return _assign_device(self.coarse, x.shape[0], lambda r0, r1: x[r0:r1], x.device)
 
     _ROW_ARRAYS = ("codes", "norms")          # what a matrix stores per row, in list order, beside ids
 
     def _shell(self):
         """a matrix of this class that shares what growth does not change: quantizers, centroids, probe selection"""
         new = object.__new__(type(self))
-        for name in ("pq", "centroids", "n_lists", "coarse", "_list_ids", "_centroids_dev", "packed4"):
+        for name in ("pq", "centroids", "n_lists", "coarse", "_list_ids", "_centroids_dev", "packed4", "device_terms"):
             if hasattr(self, name):
                 setattr(new, name, getattr(self, name))
         return new
@@ -630,6 +698,8 @@ class _Lists(_Refine, _Filter, _Packed4):
             raise PanicError("only a matrix of the same class can be merged")
         if other.packed4 != self.packed4:
             raise PanicError("a packed and an unpacked matrix cannot be merged: call pack4() or unpack4() on one of them")
+        if other.device_terms != self.device_terms:
+            raise PanicError("the row terms of the two matrices come from different routes (device_terms differs)")
         if not (other.pq == self.pq) or not np.array_equal(other.centroids, self.centroids):
             raise PanicError("the matrices must share the quantizer and the centroids of the lists")
         if (other.norms is None) != (self.norms is None):
@@ -755,15 +825,18 @@ class ResidualPartitionedMatrix(_Lists):
     Reading or writing such a matrix as a storage chunk is not provided: finalfusion has no chunk for residual codes."""
 
     def __init__(self, pq, codes, norms, row_terms, centroids, assign):
-        """codes / norms / row_terms in original row order (device tensors); assign [N] the list of each row."""
+        """codes / norms / row_terms in original row order (device tensors); assign [N] the list of each row: a numpy
+        array, or an int64 CUDA tensor, which is laid out on the device (`lists` is then the kernel's fourth output)."""
         import torch
         dev = codes.device
         self.pq = pq
-        self._init_lists(centroids, assign, codes.shape[0], dev, pq._ctx)
+        lists = self._init_lists(centroids, assign, codes.shape[0], dev, pq._ctx, want_lists=True)
         self.codes = codes[self.ids].contiguous()
         self.norms = None if norms is None else norms[self.ids].contiguous()
         self.row_terms = row_terms[self.ids].contiguous()
-        self.lists = torch.from_numpy(np.asarray(assign, dtype=np.int64)).to(dev)[self.ids].contiguous()
+        if lists is None:
+            lists = torch.from_numpy(np.asarray(assign, dtype=np.int64)).to(dev)[self.ids].contiguous()
+        self.lists = lists
         self._centroids_dev = torch.from_numpy(self.centroids).to(dev)
 
     def nearest(self, queries, k, nprobe, refine=None, allow=None):
@@ -842,16 +915,25 @@ class ResidualPartitionedMatrix(_Lists):
     def encode(self, vectors):
         """What the matrix would store for `vectors` ([B, d] float32, numpy or CUDA) -> (lists int64 [B], codes u8 [B, M],
         row_terms f32 [B]) on the device: the list assign() names, the code of the f32 residual against that list's
-        centroid, and the row's query-free term -- the loop body of partition_residual."""
+        centroid, and the row's query-free term -- the loop body of partition_residual, on the route the matrix was
+        built by (device_terms: Pq.residuals_device and Pq.residual_terms_device), so add() stays the constructor
+        applied to the concatenation."""
         import torch
         x = _device_rows(vectors, self.pq.reconstructed_len(), self.codes.device)
         lists = self.assign(x)
         codes = torch.empty((x.shape[0], self.pq.quantized_len()), dtype=torch.uint8, device=x.device)
         terms = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
         chunk = 1 << 20
+        buf = None
+        if self.device_terms and x.shape[0]:
+            buf = torch.empty((min(chunk, x.shape[0]), x.shape[1]), dtype=torch.float32, device=x.device)
         for r0 in range(0, x.shape[0], chunk):
             r1 = min(x.shape[0], r0 + chunk)
-            terms[r0:r1] = _residual_codes_terms(self.pq, x[r0:r1], self._centroids_dev[lists[r0:r1]], codes[r0:r1])
+            if self.device_terms:
+                _residual_codes_terms_device(self.pq, x[r0:r1], lists[r0:r1], self._centroids_dev, codes[r0:r1],
+                                             terms[r0:r1], buf)
+            else:
+                terms[r0:r1] = _residual_codes_terms(self.pq, x[r0:r1], self._centroids_dev[lists[r0:r1]], codes[r0:r1])
         return lists, codes, terms
 
     def add(self, vectors, norms=None):

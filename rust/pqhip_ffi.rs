@@ -160,6 +160,22 @@ extern "C" {
     pub fn pqhip_lists_merge_dev(cb: *mut pqhip_codebook, device_slot: i32, d_off_a: *const i64, n_a: i64,
         d_off_b: *const i64, n_b: i64, n_lists: i64, row_bytes: i64, d_a: *const c_void, d_b: *const c_void,
         d_out: *mut c_void, d_off_out: *mut i64, stream: *mut c_void) -> i32;
+    // building a partitioned index on the device.  Layout: d_assign [n] signed list ids of idx_bytes (4 / 8) bytes ->
+    // d_list_off [n_lists + 1], d_ids [n] (the stable argsort), d_positions [n], d_lists NULL or [n]; the ids are validated
+    // on the device (one out of range: ids / positions / lists untouched, the stream's range flag raised); n_lists <= 16384;
+    // option "lists_layout_wgs" forces the grid, on which the result does not depend
+    pub fn pqhip_lists_layout_dev(cb: *mut pqhip_codebook, device_slot: i32, d_assign: *const c_void, idx_bytes: i32,
+        n: i64, n_lists: i64, d_list_off: *mut i64, d_ids: *mut i64, d_positions: *mut i64, d_lists: *mut i64,
+        stream: *mut c_void) -> i32;
+    // out[i][j] = x[i][j] - centroids[assign[i]][j], one f32 subtraction each (a bad list id: a zero row, range flag)
+    pub fn pqhip_residuals_f32_dev(cb: *mut pqhip_codebook, device_slot: i32, d_x: *const f32, n: i64, d: i64,
+        x_row_stride: i64, d_assign: *const i64, d_centroids: *const f32, n_lists: i64, d_out: *mut f32,
+        out_row_stride: i64, stream: *mut c_void) -> i32;
+    // the query-free row terms sum_j (r^2 + 2 c r) of residual codes in the f64 order of include/pqhip.h, without a
+    // reconstruction; cb is the residual quantizer (one with a projection: PQHIP_EUNSUPPORTED)
+    pub fn pqhip_residual_terms_f32_dev(cb: *mut pqhip_codebook, device_slot: i32, d_codes: *const u8, n: i64,
+        codes_row_stride: i64, d_assign: *const i64, d_centroids: *const f32, n_lists: i64, d_out: *mut f32,
+        stream: *mut c_void) -> i32;
     // 4-bit packed codes (K <= 16): a row is ceil(M / 2) bytes, code m in byte m >> 1, even m in the low nibble, the pad
     // nibble of an odd M written as 0 and ignored by every reader; no alignment of base or stride
     pub fn pqhip_pack_codes4_dev(cb: *mut pqhip_codebook, device_slot: i32, d_codes: *const c_void, code_bytes: i32,
