@@ -177,6 +177,118 @@ __device__ __forceinline__ void adc_row_sum_mq(const unsigned (&w)[NV + 1], unsi
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// What the search and range producers (kernels_adc_search*.hip.h, kernels_adc_packed4.hip.h, kernels_adc_range.hip.h)
+// share beside the fetch and the row sums above.
+// ---------------------------------------------------------------------------------------------
+
+// A row mask is ceil(n / 32) words in row order: bit row & 31 of word row >> 5 set means that the row may be returned.
+// Callers test it BEFORE the code fetch and only for a row in range, so no word past ceil(n / 32) is read and a
+// disallowed row loads nothing.
+__device__ __forceinline__ bool adc_mask_bit(const uint32_t* __restrict__ allow, int64_t row)
+{
+    return (allow[row >> 5] >> ((unsigned)row & 31u)) & 1u;
+}
+
+// [NQ][M][K] tables (MK = M K) -> the LDS image of the u8 row sums, by a 1,024-thread workgroup: [M][K] for one query
+// (adc_row_sum), the interleaved [NQ / 4][M][K][4] for 4 / 8 (adc_row_sum_mq).  The caller synchronises.
+template <int NQ>
+__device__ __forceinline__ void adc_stage_tables(float* lds, const float* __restrict__ lut, int MK)
+{
+    if (NQ == 1) {
+        for (int i = threadIdx.x; i < MK; i += 1024) lds[i] = lut[i];
+    } else {
+        for (int i = threadIdx.x; i < NQ * MK; i += 1024) {
+            const int q = i / MK, r = i - q * MK;
+            lds[((q >> 2) * MK + r) * 4 + (q & 3)] = lut[i];
+        }
+    }
+}
+
+// the sums of adc_row_sum_mq / adc_row_sum_p4_mq, one value per query
+template <int NH>
+__device__ __forceinline__ void adc_spread_mq(const f32x2 (&s)[NH][2], float (&val)[4 * NH])
+{
+#pragma unroll
+    for (int hq = 0; hq < NH; ++hq) {
+        val[4 * hq + 0] = s[hq][0][0];
+        val[4 * hq + 1] = s[hq][0][1];
+        val[4 * hq + 2] = s[hq][1][0];
+        val[4 * hq + 3] = s[hq][1][1];
+    }
+}
+
+// Workgroup blockIdx.x of the gridDim.x that share a query of a list call takes the places [s0, s1) =
+// [ceil(T / G) b, ceil(T / G) (b + 1)), clamped to T, of the T concatenated probed rows; per = ceil(T / G).
+struct ListsSlice {
+    int64_t per, s0, s1;
+};
+__device__ __forceinline__ ListsSlice adc_lists_wg_slice(int64_t total)
+{
+    const int64_t per = (total + gridDim.x - 1) / gridDim.x;
+    const int64_t s0 = (int64_t)blockIdx.x * per < total ? (int64_t)blockIdx.x * per : total;
+    const int64_t s1 = s0 + per < total ? s0 + per : total;
+    return {per, s0, s1};
+}
+
+// The place of a lane in one query's plan (k_adc_lists_plan: seg_begin [n_probe], the first row of every probed list,
+// and seg_cum [n_probe + 1], the probed rows before it; a skipped probe is an empty segment): segment j, its end in the
+// concatenation, and delta, with row = place + delta inside it.  State travels by value: behind reference parameters
+// the same lines cost the kernels scalar registers.
+struct SegmentPos {
+    int j;
+    int64_t seg_end, delta;
+    float bias;                                                     // the caller's per-segment value of segment j, if any
+};
+
+// The segment that holds place s0 of the caller's slice [s0, s1): the first j with seg_cum[j + 1] > s0 (it exists while
+// s0 < T, and is not empty); segment 0 for an empty slice.
+template <bool BIASED = false>
+__device__ __forceinline__ SegmentPos adc_segment_start(const int64_t* sb, const int64_t* sc, const float* pb, int n_probe,
+                                                        int64_t s0, int64_t s1)
+{
+    int j = 0;
+    float b = 0.f;
+    if (s0 < s1) {
+        int lo_j = 0, hi_j = n_probe - 1;
+        while (lo_j < hi_j) {
+            const int mid = (lo_j + hi_j) >> 1;
+            if (sc[mid + 1] > s0) hi_j = mid; else lo_j = mid + 1;
+        }
+        j = lo_j;
+        if (BIASED || pb) b = pb[j];
+    }
+    return {j, sc[j + 1], sb[j] - sc[j], b};
+}
+
+// The position for place c >= every place asked before: monotone, one compare while the lane stays inside a list.
+// Places < T end inside some segment, so j stops at the segment that holds c and c + delta never leaves a probed list;
+// segments that are stepped over are looked at for their seg_cum alone.  PER_STEP: delta follows every step (the
+// spelling the producers without a per-segment value compile best from); else it is loaded once, for the segment
+// reached, and `moved` tells the caller to load what it keeps per segment (the probe bias) for that segment too.
+template <bool PER_STEP, bool BIASED = false>
+__device__ __forceinline__ SegmentPos adc_segment_seek(SegmentPos p, int64_t c, const int64_t* sb, const int64_t* sc,
+                                                       const float* pb, int n_probe)
+{
+    if constexpr (PER_STEP) {
+        while (c >= p.seg_end && p.j + 1 < n_probe) {
+            ++p.j;
+            p.seg_end = sc[p.j + 1];
+            p.delta = sb[p.j] - sc[p.j];
+        }
+    } else {
+        if (c >= p.seg_end) {
+            while (c >= p.seg_end && p.j + 1 < n_probe) {
+                ++p.j;
+                p.seg_end = sc[p.j + 1];
+            }
+            p.delta = sb[p.j] - sc[p.j];
+            if (BIASED || pb) p.bias = pb[p.j];
+        }
+    }
+    return p;
+}
+
 // NV = ceil(M / 4) dwords of code bytes per row; the window fetched is NV + 1 aligned dwords.
 template <int NV>
 __global__ __launch_bounds__(256) void k_adc_scan_u8(const uint8_t* __restrict__ codes, int64_t n, int64_t c_rs,

@@ -6,13 +6,16 @@
 // The high nibble of the last byte of an odd M is written as 0 and never looked at.  Rows are `stride` >= PB bytes
 // apart; nothing is assumed of the base address or of the stride.
 //
-// Definition.  Every producer here is a sibling of a u8 producer -- k_adc_search_u8 / k_adc_ip_search_u8,
-// k_adc_search_lists_u8, k_adc_search_lists_residual_u8 and their masked forms -- and offers, for every row, the value
-// that sibling offers for the unpacked row: the row sum is the same sequential f32 chain over m = 0 .. M-1 from +0 (one
-// table entry per code, never a sum of two entries looked up by a whole byte), a nibble >= K raises the range flag and
-// reads entry 0, score / residual arithmetic is restated operation for operation.  Selection (SearchState, offer,
-// search_finish), the row ranges, the segment walk and the order are the siblings'; the partial lists go to the same
-// merge kernels.  So a packed search returns, bit for bit, what the u8 search returns on the unpacked codes.
+// Definition.  Every producer here is a sibling of a u8 producer -- k_adc_search_u8 and k_adc_search_lists_u8 with
+// their IP, RESIDUAL and MASKED flags -- and offers, for every row, the value that sibling offers for the unpacked row:
+// the row sum is the same sequential f32 chain over m = 0 .. M-1 from +0 (one table entry per code, never a sum of two
+// entries looked up by a whole byte), a nibble >= K raises the range flag and reads entry 0, and the score / residual
+// arithmetic is the siblings' operation for operation.  Selection (SearchState, offer, search_finish), the mask bit,
+// the slices and the segment walk (adc_mask_bit, adc_lists_wg_slice, adc_segment_start / adc_segment_seek of
+// kernels_adc.hip.h) and the order are shared with them; the partial lists go to the same merge kernel.  So a packed
+// search returns, bit for bit, what the u8 search returns on the unpacked codes.  The bodies stay apart from the u8
+// ones because the code format differs: another table image, another row sum, and flags that are run-time null pointers
+// here (below).
 //
 // What differs.  adc_fetch_row is called with PB in the place of M (it takes a byte count): NV counts packed dwords,
 // eight codes each.  The table image in LDS has a stride of 16 entries per m whatever K is -- [M][16] f32 for one
@@ -28,11 +31,6 @@
 namespace pqhip {
 
 constexpr int kPacked4MaxValueWords = 13;   // M <= 100: 50 bytes per row
-
-__device__ __forceinline__ bool p4_mask_bit(const uint32_t* __restrict__ allow, int64_t row)
-{
-    return (allow[row >> 5] >> ((unsigned)row & 31u)) & 1u;
-}
 
 // [M][K] table of one query -> [M][16] image
 __device__ __forceinline__ void p4_stage_table(float* lds, const float* __restrict__ lut, int M, int K)
@@ -110,9 +108,9 @@ __device__ __forceinline__ void adc_row_sum_p4_mq(const unsigned (&w)[NV + 1], u
 }
 
 // ---------------------------------------------------------------------------------------------
-// Exhaustive producers: k_adc_search_u8 (IP = false) and k_adc_ip_search_u8 (IP = true) over packed rows, with the row
-// mask of their masked forms when allow != null.  NV = packed dwords per row (>= ceil(PB / 4)); LDS: the table image
-// (NQ M 64 bytes), then the queues [16][NQ][kSearchQueue] keys and indices; later the combine lists.
+// Exhaustive producers: k_adc_search_u8 over packed rows, with its row mask when allow != null.  NV = packed dwords
+// per row (>= ceil(PB / 4)); LDS: the table image (NQ M 64 bytes), then the queues [16][NQ][kSearchQueue] keys and
+// indices; later the combine lists.
 // ---------------------------------------------------------------------------------------------
 template <bool IP, int NV, int NQ, int L>
 __global__ __launch_bounds__(1024) void k_adc_search_p4(const uint8_t* __restrict__ codes, int64_t n, int64_t c_rs,
@@ -146,7 +144,7 @@ __global__ __launch_bounds__(1024) void k_adc_search_p4(const uint8_t* __restric
     for (int64_t base = row_begin; base < row_end; base += 1024) {  // wave-uniform trip count: the selection is wave-wide
         const int64_t row = base + threadIdx.x;
         bool valid = row < row_end;
-        if (allow && valid) valid = p4_mask_bit(allow, row);        // before the fetch: a disallowed row is not read
+        if (allow && valid) valid = adc_mask_bit(allow, row);       // before the fetch: a disallowed row is not read
         float val[NQ];                                              // distance, or -score
 #pragma unroll
         for (int q = 0; q < NQ; ++q) val[q] = 0.f;
@@ -158,22 +156,19 @@ __global__ __launch_bounds__(1024) void k_adc_search_p4(const uint8_t* __restric
             adc_fetch_row<NW>(a, lo, hi, PB, w);
             const unsigned sh = (unsigned)(a & 3);
             if constexpr (NQ == 1) {
-                const float s = full ? adc_row_sum_p4<NV, true>(w, sh, lds_s, M, KS, bad)
-                                     : adc_row_sum_p4<NV, false>(w, sh, lds_s, M, KS, bad);
-                val[0] = IP ? -fmul(s, sc) : s;
+                val[0] = full ? adc_row_sum_p4<NV, true>(w, sh, lds_s, M, KS, bad)
+                              : adc_row_sum_p4<NV, false>(w, sh, lds_s, M, KS, bad);
             } else {
                 f32x2 s[NH][2];
 #pragma unroll
                 for (int hq = 0; hq < NH; ++hq) { s[hq][0] = (f32x2){0.f, 0.f}; s[hq][1] = (f32x2){0.f, 0.f}; }
                 if (full) adc_row_sum_p4_mq<NV, NH, true>(w, sh, lds_s, M, KS, bad, s);
                 else adc_row_sum_p4_mq<NV, NH, false>(w, sh, lds_s, M, KS, bad, s);
+                adc_spread_mq<NH>(s, val);
+            }
+            if constexpr (IP) {
 #pragma unroll
-                for (int hq = 0; hq < NH; ++hq) {
-                    val[4 * hq + 0] = IP ? -fmul(s[hq][0][0], sc) : s[hq][0][0];
-                    val[4 * hq + 1] = IP ? -fmul(s[hq][0][1], sc) : s[hq][0][1];
-                    val[4 * hq + 2] = IP ? -fmul(s[hq][1][0], sc) : s[hq][1][0];
-                    val[4 * hq + 3] = IP ? -fmul(s[hq][1][1], sc) : s[hq][1][1];
-                }
+                for (int q = 0; q < NQ; ++q) val[q] = -fmul(val[q], sc);
             }
         }
         const unsigned off = (unsigned)(row - row_begin);
@@ -186,9 +181,9 @@ __global__ __launch_bounds__(1024) void k_adc_search_p4(const uint8_t* __restric
 }
 
 // ---------------------------------------------------------------------------------------------
-// List producer: k_adc_search_lists_u8 (bias == null) and k_adc_search_lists_residual_u8 (bias != null) over packed
-// rows, behind the same plan (seg_begin, seg_cum of k_adc_lists_plan); allow != null: their masked forms, the mask in
-// position order.  With s the row sum, b the bias of the probe slot through which the row is reached, x = extra[row]:
+// List producer: k_adc_search_lists_u8 without (bias == null) and with RESIDUAL (bias != null) over packed rows, behind
+// the same plan (seg_begin, seg_cum of k_adc_lists_plan); allow != null: its MASKED form, the mask in position order.
+// With s the row sum, b the bias of the probe slot through which the row is reached, x = extra[row]:
 //   bias == null:  IP = false: s                            IP = true: -fl(s * x)            (x = 1 when extra == null)
 //   bias != null:  IP = false: fl(fl(b + x) - fl(s + s))    IP = true: -fl(fl(b + s) * x)    (IP: x = 1 when extra == null)
 // lut [queries of the launch][M][K]; bias [queries of the launch][b_rs]; part_* [queries][G][64 L].
@@ -213,24 +208,9 @@ __global__ __launch_bounds__(1024) void k_adc_search_lists_p4(
     const int64_t* sb = seg_begin + (size_t)blockIdx.y * n_probe;
     const int64_t* sc = seg_cum + (size_t)blockIdx.y * ((size_t)n_probe + 1);
     const float* pb = bias ? bias + (int64_t)blockIdx.y * b_rs : nullptr;
-    const int64_t total = sc[n_probe];
-    const int64_t per = (total + gridDim.x - 1) / gridDim.x;
-    const int64_t s0 = (int64_t)blockIdx.x * per < total ? (int64_t)blockIdx.x * per : total;
-    const int64_t s1 = s0 + per < total ? s0 + per : total;
-    // the segment that holds place s0: the first j with seg_cum[j + 1] > s0 (it exists while s0 < T, and is not empty)
-    int j = 0;
-    float b = 0.f;
-    if (s0 < s1) {
-        int lo_j = 0, hi_j = n_probe - 1;
-        while (lo_j < hi_j) {
-            const int mid = (lo_j + hi_j) >> 1;
-            if (sc[mid + 1] > s0) hi_j = mid; else lo_j = mid + 1;
-        }
-        j = lo_j;
-        if (pb) b = pb[j];
-    }
-    int64_t seg_end = sc[j + 1];
-    int64_t delta = sb[j] - sc[j];                                  // row = place + delta inside segment j
+    const ListsSlice slice = adc_lists_wg_slice(sc[n_probe]);
+    const int64_t s0 = slice.s0, s1 = slice.s1;
+    SegmentPos pos = adc_segment_start(sb, sc, pb, n_probe, s0, s1);
     const int PB = (M + 1) >> 1;
     const uintptr_t lo = reinterpret_cast<uintptr_t>(codes);
     const uintptr_t hi = lo + (uintptr_t)((n - 1) * c_rs + PB);     // one past the last code byte
@@ -243,18 +223,11 @@ __global__ __launch_bounds__(1024) void k_adc_search_lists_p4(
         float v = 0.f;
         int64_t row = 0;
         if (valid) {
-            if (c >= seg_end) {
-                while (c >= seg_end && j + 1 < n_probe) {           // places < T end inside some segment
-                    ++j;
-                    seg_end = sc[j + 1];
-                }
-                delta = sb[j] - sc[j];
-                if (pb) b = pb[j];                                  // the segment that holds c: a probed, non-empty list
-            }
-            row = c + delta;
+            pos = adc_segment_seek<false>(pos, c, sb, sc, pb, n_probe);
+            row = c + pos.delta;
             valid = (uint64_t)row < (uint64_t)n;                    // holds by construction of the plan
         }
-        if (allow && valid) valid = p4_mask_bit(allow, row);        // before the fetch: a disallowed row is not read
+        if (allow && valid) valid = adc_mask_bit(allow, row);       // before the fetch: a disallowed row is not read
         if (valid) {
             float x = 1.f;
             if (IP ? extra != nullptr : pb != nullptr) x = extra[row];   // issued with the row's code words
@@ -264,7 +237,7 @@ __global__ __launch_bounds__(1024) void k_adc_search_lists_p4(
             const unsigned sh = (unsigned)(a & 3);
             const float s = full ? adc_row_sum_p4<NV, true>(w, sh, lds_s, M, K4, bad)
                                  : adc_row_sum_p4<NV, false>(w, sh, lds_s, M, K4, bad);
-            if (pb) v = IP ? -fmul(fadd(b, s), x) : fsub(fadd(b, x), fadd(s, s));
+            if (pb) v = IP ? -fmul(fadd(pos.bias, s), x) : fsub(fadd(pos.bias, x), fadd(s, s));
             else v = IP ? -fmul(s, x) : s;
         }
         st[0].offer(v, (unsigned)row, valid, qk + wave * kSearchQueue, qi + wave * kSearchQueue, kk);

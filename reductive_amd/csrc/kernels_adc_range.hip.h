@@ -3,9 +3,11 @@
 // (Launched from exactly one translation unit, pqhip_adc_range.hip.)
 //
 // A range call is the searches' producer with another consumer: the same table image in LDS, the same row fetch and row
-// sum (adc_fetch_row, adc_row_sum / adc_row_sum_mq), the same value formulas -- and in the place of the register lists,
-// the LDS queues and the merge tree one compare per (row, query).  Nothing is ordered by value, so there is no key: the
-// predicate is the IEEE comparison itself (a NaN never qualifies) and a value is stored bit for bit.
+// sums (adc_stage_tables, adc_fetch_row, adc_row_sum / adc_row_sum_mq + adc_spread_mq), the same mask bit, slices and
+// segment walk (adc_mask_bit, adc_lists_wg_slice, adc_segment_start / adc_segment_seek: all of kernels_adc.hip.h), the
+// same value formulas -- and in the place of the register lists, the LDS queues and the merge tree one compare per
+// (row, query).  Nothing is ordered by value, so there is no key: the predicate is the IEEE comparison itself (a NaN
+// never qualifies) and a value is stored bit for bit.
 //
 // Two passes over the codes with a scan between them, all three on the caller's stream:
 //   count  every producer unit counts its qualifying rows per query            -> part[query][unit]
@@ -29,11 +31,6 @@ namespace pqhip {
 constexpr int kRangeWaves = 16;   // waves (producer units) per 1,024-thread workgroup
 
 enum : int { kRangeL2 = 0, kRangeIP = 1, kRangeResL2 = 2, kRangeResIP = 3 };
-
-__device__ __forceinline__ bool range_allowed(const uint32_t* __restrict__ allow, int64_t row)
-{
-    return (allow[row >> 5] >> ((unsigned)row & 31u)) & 1u;
-}
 
 // lanes of `ballot` below this lane
 __device__ __forceinline__ unsigned range_rank(unsigned long long ballot)
@@ -81,14 +78,7 @@ __global__ __launch_bounds__(1024) void k_adc_range_u8(const uint8_t* __restrict
     constexpr int NW = NV + 1, NH = NQ / 4;
     extern __shared__ __attribute__((aligned(16))) float lds_s[];
     const int MK = M * K;
-    if (NQ == 1) {
-        for (int i = threadIdx.x; i < MK; i += 1024) lds_s[i] = lut[i];
-    } else {
-        for (int i = threadIdx.x; i < NQ * MK; i += 1024) {
-            const int q = i / MK, r = i - q * MK;
-            lds_s[((q >> 2) * MK + r) * 4 + (q & 3)] = lut[i];
-        }
-    }
+    adc_stage_tables<NQ>(lds_s, lut, MK);
     __syncthreads();
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int64_t units = (int64_t)gridDim.x * kRangeWaves;
@@ -112,7 +102,7 @@ __global__ __launch_bounds__(1024) void k_adc_range_u8(const uint8_t* __restrict
     for (int64_t b0 = row_begin; b0 < row_end; b0 += 64) {          // wave-uniform: the ballots are wave-wide
         const int64_t row = b0 + lane;
         bool valid = row < row_end;
-        if (allow && valid) valid = range_allowed(allow, row);      // before the fetch: a disallowed row is not read
+        if (allow && valid) valid = adc_mask_bit(allow, row);       // before the fetch: a disallowed row is not read
         float v[NQ];
 #pragma unroll
         for (int q = 0; q < NQ; ++q) v[q] = 0.f;
@@ -130,13 +120,7 @@ __global__ __launch_bounds__(1024) void k_adc_range_u8(const uint8_t* __restrict
 #pragma unroll
                 for (int hq = 0; hq < NH; ++hq) { s[hq][0] = (f32x2){0.f, 0.f}; s[hq][1] = (f32x2){0.f, 0.f}; }
                 adc_row_sum_mq<NV, NH>(w, sh, lds_s, M, K, MK, bad, s);
-#pragma unroll
-                for (int hq = 0; hq < NH; ++hq) {
-                    v[4 * hq + 0] = s[hq][0][0];
-                    v[4 * hq + 1] = s[hq][0][1];
-                    v[4 * hq + 2] = s[hq][1][0];
-                    v[4 * hq + 3] = s[hq][1][1];
-                }
+                adc_spread_mq<NH>(s, v);
             }
             if constexpr (IP) {
                 if (scales) {
@@ -159,11 +143,11 @@ __global__ __launch_bounds__(1024) void k_adc_range_u8(const uint8_t* __restrict
 }
 
 // Range search over probed lists: grid (G, queries), the walk of k_adc_search_lists_u8 -- the segment plan of
-// k_adc_lists_plan, workgroup b takes the slice [ceil(T / G) b, ceil(T / G) (b + 1)) of the T concatenated probed rows
-// -- cut once more into 16 contiguous wave sub-ranges (a multiple of 64 places each).  Every lane maps its place to a
-// row by stepping through the segments.  POL: kRangeL2 / kRangeIP the values of the flat list searches, kRangeResL2 /
-// kRangeResIP those of the residual ones (bias [queries][b_rs], extra = row terms resp. scales); the bias is read per
-// segment for a place that exists, so the bias of a skipped probe enters nothing.  part [queries][16 G].
+// k_adc_lists_plan, the workgroup's slice of the T concatenated probed rows (adc_lists_wg_slice) -- cut once more into
+// 16 contiguous wave sub-ranges (a multiple of 64 places each).  Every lane maps its place to a row by stepping
+// through the segments.  POL: kRangeL2 / kRangeIP the values of the flat list searches, kRangeResL2 / kRangeResIP
+// those of the residual ones (bias [queries][b_rs], extra = row terms resp. scales); the bias is read per segment for a
+// place that exists, so the bias of a skipped probe enters nothing.  part [queries][16 G].
 template <int POL, int NV>
 __global__ __launch_bounds__(1024) void k_adc_range_lists_u8(const uint8_t* __restrict__ codes, int64_t n, int64_t c_rs,
                                                              const uint32_t* __restrict__ allow /* or null */,
@@ -181,8 +165,7 @@ __global__ __launch_bounds__(1024) void k_adc_range_lists_u8(const uint8_t* __re
     constexpr bool IP = POL == kRangeIP || POL == kRangeResIP, RES = POL == kRangeResL2 || POL == kRangeResIP;
     extern __shared__ __attribute__((aligned(16))) float lds_s[];
     const int MK = M * K;
-    const float* tab = lut + (size_t)blockIdx.y * MK;
-    for (int i = threadIdx.x; i < MK; i += 1024) lds_s[i] = tab[i];
+    adc_stage_tables<1>(lds_s, lut + (size_t)blockIdx.y * MK, MK);
     __syncthreads();
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int64_t units = (int64_t)gridDim.x * kRangeWaves;
@@ -191,27 +174,11 @@ __global__ __launch_bounds__(1024) void k_adc_range_lists_u8(const uint8_t* __re
     const int64_t* sc = seg_cum + (size_t)blockIdx.y * ((size_t)n_probe + 1);
     const float* pb = RES ? bias + (int64_t)blockIdx.y * b_rs : nullptr;
     const float t = thr[blockIdx.y];
-    const int64_t total = sc[n_probe];
-    const int64_t per = (total + gridDim.x - 1) / gridDim.x;
-    const int64_t g0 = (int64_t)blockIdx.x * per < total ? (int64_t)blockIdx.x * per : total;
-    const int64_t g1 = g0 + per < total ? g0 + per : total;
-    const int64_t sub = ((per + kRangeWaves - 1) / kRangeWaves + 63) / 64 * 64;
-    const int64_t s0 = g0 + wave * sub < g1 ? g0 + wave * sub : g1;
-    const int64_t s1 = s0 + sub < g1 ? s0 + sub : g1;
-    // the segment that holds place s0: the first j with seg_cum[j + 1] > s0 (it exists while s0 < T, and is not empty)
-    int j = 0;
-    float b = 0.f;
-    if (s0 < s1) {
-        int lo_j = 0, hi_j = n_probe - 1;
-        while (lo_j < hi_j) {
-            const int mid = (lo_j + hi_j) >> 1;
-            if (sc[mid + 1] > s0) hi_j = mid; else lo_j = mid + 1;
-        }
-        j = lo_j;
-        if constexpr (RES) b = pb[j];
-    }
-    int64_t seg_end = sc[j + 1];
-    int64_t delta = sb[j] - sc[j];                                  // row = place + delta inside segment j
+    const ListsSlice g = adc_lists_wg_slice(sc[n_probe]);
+    const int64_t sub = ((g.per + kRangeWaves - 1) / kRangeWaves + 63) / 64 * 64;
+    const int64_t s0 = g.s0 + wave * sub < g.s1 ? g.s0 + wave * sub : g.s1;
+    const int64_t s1 = s0 + sub < g.s1 ? s0 + sub : g.s1;
+    SegmentPos pos = adc_segment_start<RES>(sb, sc, pb, n_probe, s0, s1);
     int64_t run = fill ? range_uniform(part[slot_u]) : 0;           // count: matches so far; fill: the next slot
     const uintptr_t lo = reinterpret_cast<uintptr_t>(codes);
     const uintptr_t hi = lo + (uintptr_t)((n - 1) * c_rs + M);      // one past the last code byte
@@ -222,18 +189,11 @@ __global__ __launch_bounds__(1024) void k_adc_range_lists_u8(const uint8_t* __re
         float v = 0.f;
         int64_t row = 0;
         if (valid) {
-            if (c >= seg_end) {
-                while (c >= seg_end && j + 1 < n_probe) {           // places < T end inside some segment
-                    ++j;
-                    seg_end = sc[j + 1];
-                }
-                delta = sb[j] - sc[j];
-                if constexpr (RES) b = pb[j];                       // the segment that holds c: a probed, non-empty list
-            }
-            row = c + delta;
+            pos = adc_segment_seek<false, RES>(pos, c, sb, sc, pb, n_probe);
+            row = c + pos.delta;
             valid = (uint64_t)row < (uint64_t)n;                    // holds by construction of the plan
         }
-        if (allow && valid) valid = range_allowed(allow, row);      // before the fetch: a disallowed row is not read
+        if (allow && valid) valid = adc_mask_bit(allow, row);       // before the fetch: a disallowed row is not read
         if (valid) {
             float x = 1.f;
             if constexpr (POL == kRangeResL2) x = extra[row];       // issued with the row's code words
@@ -241,12 +201,11 @@ __global__ __launch_bounds__(1024) void k_adc_range_lists_u8(const uint8_t* __re
             const uintptr_t a = lo + (uintptr_t)(row * c_rs);
             unsigned w[NW];
             adc_fetch_row<NW>(a, lo, hi, M, w);
-            const unsigned sh = (unsigned)(a & 3);
-            const float s = adc_row_sum<NV>(w, sh, lds_s, M, K, bad);
+            const float s = adc_row_sum<NV>(w, (unsigned)(a & 3), lds_s, M, K, bad);
             if constexpr (POL == kRangeL2) v = s;
             else if constexpr (POL == kRangeIP) v = extra ? fmul(s, x) : s;
-            else if constexpr (POL == kRangeResL2) v = fsub(fadd(b, x), fadd(s, s));
-            else v = extra ? fmul(fadd(b, s), x) : fadd(b, s);
+            else if constexpr (POL == kRangeResL2) v = fsub(fadd(pos.bias, x), fadd(s, s));
+            else v = extra ? fmul(fadd(pos.bias, s), x) : fadd(pos.bias, s);
         }
         const bool hit = valid && (IP ? v >= t : v <= t);
         range_emit(hit, v, row, fill != 0, run, capacity, out_v, out_i);

@@ -1,7 +1,6 @@
 // kernels_adc_search.hip.h -- ADC search: the table-sum scan of kernels_adc.hip.h fused with an exact top-k selection,
 // so that a search returns the k nearest rows of every query without writing the n_codes distances.
-// (Launched from pqhip_adc.hip; pqhip_adc_masked.hip includes the file for the selection -- SearchState, search_finish --
-// and launches none of its kernels.)
+// (pqhip_adc.hip instantiates the kernels without a row mask and the merge, pqhip_adc_masked.hip those with one.)
 //
 // Order.  A row is the pair (key(dist), row index) and rows compare lexicographically: key() is the first-minimum order
 // of cluster_assignments (kmeans.rs:133-159, oracle of_less) -- -0 == +0, every NaN equal to every other and above
@@ -18,7 +17,7 @@
 // no harm.  After the row loop the 16 waves' lists are merged in a tree through LDS (the table image is dead by then)
 // and the workgroup writes one sorted list per query to scratch.  k_adc_search_merge merges the workgroups' lists of
 // one query and writes the first k entries (index -1 and +Inf past the last row).
-// The similarity search (k_adc_ip_search_*, at the end) offers the key of -score to the same selection.
+// The similarity search (the IP flag of every kernel) offers the key of -score to the same selection.
 #pragma once
 #include "adc_key.hip.h"
 #include "kernels_adc.hip.h"
@@ -232,25 +231,29 @@ __device__ __forceinline__ void search_finish(SearchState<L> (&st)[NQ], unsigned
 // scan's interleaved [NQ/4][M][K][4] image and row sum).  One 1,024-thread workgroup per CU over a contiguous row range
 // of rows_per_wg < 2^31 rows; NV = the code dwords fetched per row (>= ceil(M / 4)).  LDS: the table image, then the
 // queues [16][NQ][kSearchQueue] keys and indices; later the combine lists.
+//
+// One body serves the four exhaustive searches; a flag that is off leaves no instruction and no argument load behind.
+// IP (pqhip_adc_ip_search_f32_dev): the value offered to the unchanged SearchState is -fl(s * scale), s the row sum over
+// inner-product tables and scale = scales[i] (1 without scales: exact), loaded once per row for all NQ queries; negation
+// is exact, so the smallest key is the largest score.  Without IP `scales` is not looked at.
+// MASKED (pqhip_adc_masked.hip instantiates these): the row's bit of `allow` (adc_mask_bit) is one more term of the
+// `valid` that offer() takes, formed before the fetch -- a row whose bit is clear loads no code and no scale and cannot
+// raise the range flag.  Row ranges start on multiples of 1,024, so a wave reads two mask words per trip; the trip
+// count does not depend on the mask (offer is wave-wide).  Without MASKED `allow` is not looked at.
 // ---------------------------------------------------------------------------------------------
-template <int NV, int NQ, int L>
+template <bool IP, bool MASKED, int NV, int NQ, int L>
 __global__ __launch_bounds__(1024) void k_adc_search_u8(const uint8_t* __restrict__ codes, int64_t n, int64_t c_rs,
-                                                        const float* __restrict__ lut /* [NQ][M][K] */, int M, int K, int kk,
-                                                        int64_t rows_per_wg, unsigned* __restrict__ part_k,
+                                                        const uint32_t* __restrict__ allow /* MASKED */,
+                                                        const float* __restrict__ lut /* [NQ][M][K] */,
+                                                        const float* __restrict__ scales /* IP: [n] or null */, int M, int K,
+                                                        int kk, int64_t rows_per_wg, unsigned* __restrict__ part_k,
                                                         uint64_t* __restrict__ part_i, int* __restrict__ err)
 {
     static_assert(NQ == 1 || NQ == 4 || NQ == 8, "queries per pass");
     constexpr int NW = NV + 1, NH = NQ / 4;
     extern __shared__ __attribute__((aligned(16))) float lds_s[];
     const int MK = M * K;
-    if (NQ == 1) {
-        for (int i = threadIdx.x; i < MK; i += 1024) lds_s[i] = lut[i];
-    } else {
-        for (int i = threadIdx.x; i < NQ * MK; i += 1024) {
-            const int q = i / MK, r = i - q * MK;
-            lds_s[((q >> 2) * MK + r) * 4 + (q & 3)] = lut[i];
-        }
-    }
+    adc_stage_tables<NQ>(lds_s, lut, MK);
     unsigned* qk = reinterpret_cast<unsigned*>(lds_s + NQ * MK);   // [16][NQ][kSearchQueue]
     unsigned* qi = qk + kSearchWaves * NQ * kSearchQueue;
     __syncthreads();
@@ -266,46 +269,51 @@ __global__ __launch_bounds__(1024) void k_adc_search_u8(const uint8_t* __restric
     bool bad = false;
     for (int64_t base = row_begin; base < row_end; base += 1024) {  // wave-uniform trip count: the selection is wave-wide
         const int64_t row = base + threadIdx.x;
-        const bool valid = row < row_end;
-        float dist[NQ];
+        bool valid = row < row_end;
+        if constexpr (MASKED) {
+            if (valid) valid = adc_mask_bit(allow, row);            // before the fetch: a disallowed row is not read
+        }
+        float val[NQ];                                              // distance, or -score
 #pragma unroll
-        for (int q = 0; q < NQ; ++q) dist[q] = 0.f;
+        for (int q = 0; q < NQ; ++q) val[q] = 0.f;
         if (valid) {
+            float sc = 1.f;
+            if constexpr (IP) sc = scales ? scales[row] : 1.f;      // issued with the row's code words
             const uintptr_t a = lo + (uintptr_t)(row * c_rs);
             unsigned w[NW];
             adc_fetch_row<NW>(a, lo, hi, M, w);
             const unsigned sh = (unsigned)(a & 3);
             if constexpr (NQ == 1) {
-                dist[0] = adc_row_sum<NV>(w, sh, lds_s, M, K, bad);
+                val[0] = adc_row_sum<NV>(w, sh, lds_s, M, K, bad);
             } else {
                 f32x2 s[NH][2];
 #pragma unroll
                 for (int hq = 0; hq < NH; ++hq) { s[hq][0] = (f32x2){0.f, 0.f}; s[hq][1] = (f32x2){0.f, 0.f}; }
                 adc_row_sum_mq<NV, NH>(w, sh, lds_s, M, K, MK, bad, s);
+                adc_spread_mq<NH>(s, val);
+            }
+            if constexpr (IP) {
 #pragma unroll
-                for (int hq = 0; hq < NH; ++hq) {
-                    dist[4 * hq + 0] = s[hq][0][0];
-                    dist[4 * hq + 1] = s[hq][0][1];
-                    dist[4 * hq + 2] = s[hq][1][0];
-                    dist[4 * hq + 3] = s[hq][1][1];
-                }
+                for (int q = 0; q < NQ; ++q) val[q] = -fmul(val[q], sc);
             }
         }
         const unsigned off = (unsigned)(row - row_begin);
 #pragma unroll
         for (int q = 0; q < NQ; ++q)
-            st[q].offer(dist[q], off, valid, qk + (wave * NQ + q) * kSearchQueue, qi + (wave * NQ + q) * kSearchQueue, kk);
+            st[q].offer(val[q], off, valid, qk + (wave * NQ + q) * kSearchQueue, qi + (wave * NQ + q) * kSearchQueue, kk);
     }
     if (bad) atomicOr(err, 1);
     search_finish<NQ, L>(st, qk, qi, reinterpret_cast<unsigned*>(lds_s), row_begin, part_k, part_i);
 }
 
 // Any code width, any table: one query, the table in LDS when TAB_LDS (k_adc_scan_wide's condition) else read through
-// L2 as in k_adc_scan_any; the sum is theirs (sequential over m from +0).  Same selection.  No throughput claim.
-template <typename IdxT, int L, bool TAB_LDS>
+// L2 as in k_adc_scan_any; the sum is theirs (sequential over m from +0).  Same selection, and IP as above.  No
+// throughput claim.
+template <bool IP, typename IdxT, int L, bool TAB_LDS>
 __global__ __launch_bounds__(1024) void k_adc_search_any(const IdxT* __restrict__ codes, int64_t n, int64_t c_rs,
-                                                         const float* __restrict__ lut, int M, int K, int kk,
-                                                         int64_t rows_per_wg, unsigned* __restrict__ part_k,
+                                                         const float* __restrict__ lut,
+                                                         const float* __restrict__ scales /* IP: [n] or null */, int M, int K,
+                                                         int kk, int64_t rows_per_wg, unsigned* __restrict__ part_k,
                                                          uint64_t* __restrict__ part_i, int* __restrict__ err)
 {
     extern __shared__ __attribute__((aligned(16))) float lds_a[];
@@ -313,7 +321,7 @@ __global__ __launch_bounds__(1024) void k_adc_search_any(const IdxT* __restrict_
     const float* tab = lut;
     unsigned* qk = reinterpret_cast<unsigned*>(lds_a);
     if (TAB_LDS) {
-        for (int i = threadIdx.x; i < MK; i += 1024) lds_a[i] = lut[i];
+        adc_stage_tables<1>(lds_a, lut, MK);
         tab = lds_a;
         qk = reinterpret_cast<unsigned*>(lds_a + MK);
     }
@@ -337,6 +345,7 @@ __global__ __launch_bounds__(1024) void k_adc_search_any(const IdxT* __restrict_
                 if (c >= (uint64_t)K) { bad = true; c = 0; }
                 s = fadd(s, tab[(int64_t)m * K + (int64_t)c]);
             }
+            if constexpr (IP) s = -fmul(s, scales ? scales[row] : 1.f);
         }
         st[0].offer(s, (unsigned)(row - row_begin), valid, qk + wave * kSearchQueue, qi + wave * kSearchQueue, kk);
     }
@@ -345,11 +354,12 @@ __global__ __launch_bounds__(1024) void k_adc_search_any(const IdxT* __restrict_
 }
 
 // One workgroup per query: merges the n_lists workgroup lists of query blockIdx.x (sorted, 64 L entries each, global
-// indices) and writes the first kk entries; past the last row, index -1 and +Inf.  n_lists = 0 writes the padding only.
+// indices) and writes the first kk entries: distances, or (IP) the scores that the keys of -score stand for; past the
+// last row, index -1 and +Inf resp. -Inf.  n_lists = 0 writes the padding only.
 // LDS: 8 lists of 64 L keys + 64 L indices (12 KB L).
-template <int L>
+template <bool IP, int L>
 __global__ __launch_bounds__(512) void k_adc_search_merge(const unsigned* __restrict__ part_k, const uint64_t* __restrict__ part_i,
-                                                          int n_lists, int kk, float* __restrict__ dist, int64_t d_rs,
+                                                          int n_lists, int kk, float* __restrict__ val, int64_t v_rs,
                                                           int64_t* __restrict__ idx, int64_t i_rs)
 {
     constexpr int LK = 64 * L;
@@ -378,170 +388,8 @@ __global__ __launch_bounds__(512) void k_adc_search_merge(const unsigned* __rest
             const int e = r * 64 + lane;
             if (e < kk) {
                 const bool pad = lst.i[r] == ~0ull;
-                dist[(int64_t)q * d_rs + e] = pad ? __uint_as_float(0x7f800000u) : adc_key_value(lst.k[r]);
-                idx[(int64_t)q * i_rs + e] = pad ? (int64_t)-1 : (int64_t)lst.i[r];
-            }
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// Similarity search (pqhip_adc_ip_search_f32_dev): the same producers and merge with one change per row -- the value
-// offered to the unchanged SearchState is -fl(s * scale), s the row sum over inner-product tables and scale = scales[i]
-// (1 without scales: exact), loaded once per row for all NQ queries; negation is exact, so the smallest key is the
-// largest score.  The loops are restated here rather than shared through a template flag so that the distance kernels
-// above keep their code objects instruction for instruction (a shared body changed their register allocation).
-// ---------------------------------------------------------------------------------------------
-template <int NV, int NQ, int L>
-__global__ __launch_bounds__(1024) void k_adc_ip_search_u8(const uint8_t* __restrict__ codes, int64_t n, int64_t c_rs,
-                                                           const float* __restrict__ lut /* [NQ][M][K] */,
-                                                           const float* __restrict__ scales /* [n] or null */, int M, int K,
-                                                           int kk, int64_t rows_per_wg, unsigned* __restrict__ part_k,
-                                                           uint64_t* __restrict__ part_i, int* __restrict__ err)
-{
-    static_assert(NQ == 1 || NQ == 4 || NQ == 8, "queries per pass");
-    constexpr int NW = NV + 1, NH = NQ / 4;
-    extern __shared__ __attribute__((aligned(16))) float lds_s[];
-    const int MK = M * K;
-    if (NQ == 1) {
-        for (int i = threadIdx.x; i < MK; i += 1024) lds_s[i] = lut[i];
-    } else {
-        for (int i = threadIdx.x; i < NQ * MK; i += 1024) {
-            const int q = i / MK, r = i - q * MK;
-            lds_s[((q >> 2) * MK + r) * 4 + (q & 3)] = lut[i];
-        }
-    }
-    unsigned* qk = reinterpret_cast<unsigned*>(lds_s + NQ * MK);   // [16][NQ][kSearchQueue]
-    unsigned* qi = qk + kSearchWaves * NQ * kSearchQueue;
-    __syncthreads();
-    const int wave = threadIdx.x >> 6;
-    SearchState<L> st[NQ];
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) st[q].init();
-    const int64_t row_begin = (int64_t)blockIdx.x * rows_per_wg;
-    int64_t row_end = row_begin + rows_per_wg;
-    if (row_end > n) row_end = n;
-    const uintptr_t lo = reinterpret_cast<uintptr_t>(codes);
-    const uintptr_t hi = lo + (uintptr_t)((n - 1) * c_rs + M);      // one past the last code byte
-    bool bad = false;
-    for (int64_t base = row_begin; base < row_end; base += 1024) {  // wave-uniform trip count: the selection is wave-wide
-        const int64_t row = base + threadIdx.x;
-        const bool valid = row < row_end;
-        float neg[NQ];                                              // -score per query
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) neg[q] = 0.f;
-        if (valid) {
-            const float sc = scales ? scales[row] : 1.f;
-            const uintptr_t a = lo + (uintptr_t)(row * c_rs);
-            unsigned w[NW];
-            adc_fetch_row<NW>(a, lo, hi, M, w);
-            const unsigned sh = (unsigned)(a & 3);
-            if constexpr (NQ == 1) {
-                neg[0] = -fmul(adc_row_sum<NV>(w, sh, lds_s, M, K, bad), sc);
-            } else {
-                f32x2 s[NH][2];
-#pragma unroll
-                for (int hq = 0; hq < NH; ++hq) { s[hq][0] = (f32x2){0.f, 0.f}; s[hq][1] = (f32x2){0.f, 0.f}; }
-                adc_row_sum_mq<NV, NH>(w, sh, lds_s, M, K, MK, bad, s);
-#pragma unroll
-                for (int hq = 0; hq < NH; ++hq) {
-                    neg[4 * hq + 0] = -fmul(s[hq][0][0], sc);
-                    neg[4 * hq + 1] = -fmul(s[hq][0][1], sc);
-                    neg[4 * hq + 2] = -fmul(s[hq][1][0], sc);
-                    neg[4 * hq + 3] = -fmul(s[hq][1][1], sc);
-                }
-            }
-        }
-        const unsigned off = (unsigned)(row - row_begin);
-#pragma unroll
-        for (int q = 0; q < NQ; ++q)
-            st[q].offer(neg[q], off, valid, qk + (wave * NQ + q) * kSearchQueue, qi + (wave * NQ + q) * kSearchQueue, kk);
-    }
-    if (bad) atomicOr(err, 1);
-    search_finish<NQ, L>(st, qk, qi, reinterpret_cast<unsigned*>(lds_s), row_begin, part_k, part_i);
-}
-
-// k_adc_search_any in similarity form: any code width, the table in LDS when TAB_LDS, else read through L2
-template <typename IdxT, int L, bool TAB_LDS>
-__global__ __launch_bounds__(1024) void k_adc_ip_search_any(const IdxT* __restrict__ codes, int64_t n, int64_t c_rs,
-                                                            const float* __restrict__ lut,
-                                                            const float* __restrict__ scales /* [n] or null */, int M, int K,
-                                                            int kk, int64_t rows_per_wg, unsigned* __restrict__ part_k,
-                                                            uint64_t* __restrict__ part_i, int* __restrict__ err)
-{
-    extern __shared__ __attribute__((aligned(16))) float lds_a[];
-    const int MK = M * K;
-    const float* tab = lut;
-    unsigned* qk = reinterpret_cast<unsigned*>(lds_a);
-    if (TAB_LDS) {
-        for (int i = threadIdx.x; i < MK; i += 1024) lds_a[i] = lut[i];
-        tab = lds_a;
-        qk = reinterpret_cast<unsigned*>(lds_a + MK);
-    }
-    unsigned* qi = qk + kSearchWaves * kSearchQueue;
-    __syncthreads();
-    const int wave = threadIdx.x >> 6;
-    SearchState<L> st[1];
-    st[0].init();
-    const int64_t row_begin = (int64_t)blockIdx.x * rows_per_wg;
-    int64_t row_end = row_begin + rows_per_wg;
-    if (row_end > n) row_end = n;
-    bool bad = false;
-    for (int64_t base = row_begin; base < row_end; base += 1024) {
-        const int64_t row = base + threadIdx.x;
-        const bool valid = row < row_end;
-        float neg = 0.f;
-        if (valid) {
-            const IdxT* cr = codes + row * c_rs;
-            float s = 0.f;
-            for (int m = 0; m < M; ++m) {
-                uint64_t c = (uint64_t)cr[m];
-                if (c >= (uint64_t)K) { bad = true; c = 0; }
-                s = fadd(s, tab[(int64_t)m * K + (int64_t)c]);
-            }
-            neg = -fmul(s, scales ? scales[row] : 1.f);
-        }
-        st[0].offer(neg, (unsigned)(row - row_begin), valid, qk + wave * kSearchQueue, qi + wave * kSearchQueue, kk);
-    }
-    if (bad) atomicOr(err, 1);
-    search_finish<1, L>(st, qk, qi, reinterpret_cast<unsigned*>(lds_a), row_begin, part_k, part_i);
-}
-
-// k_adc_search_merge in similarity form: the same list merge; writes the scores of the first kk entries, and past the
-// last row index -1 and -Inf.
-template <int L>
-__global__ __launch_bounds__(512) void k_adc_ip_search_merge(const unsigned* __restrict__ part_k,
-                                                             const uint64_t* __restrict__ part_i, int n_lists, int kk,
-                                                             float* __restrict__ score, int64_t s_rs,
-                                                             int64_t* __restrict__ idx, int64_t i_rs)
-{
-    constexpr int LK = 64 * L;
-    extern __shared__ __attribute__((aligned(16))) unsigned lds_m[];
-    unsigned* ck = lds_m;                                                    // [8][LK]
-    uint64_t* ci = reinterpret_cast<uint64_t*>(lds_m + kSearchMergeWaves * LK);   // [8][LK]
-    const int q = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    WaveList<L, uint64_t> lst;
-    lst.clear();
-    for (int g = wave; g < n_lists; g += kSearchMergeWaves) {
-        const size_t base = ((size_t)q * n_lists + g) * LK;
-        lst.merge_sorted(part_k + base, part_i + base);
-    }
-    lst.store(ck + wave * LK, ci + wave * LK);
-    __syncthreads();
-    for (int h = kSearchMergeWaves / 2; h >= 1; h >>= 1) {
-        if (wave < h) {
-            lst.merge_sorted(ck + (wave + h) * LK, ci + (wave + h) * LK);
-            lst.store(ck + wave * LK, ci + wave * LK);
-        }
-        __syncthreads();
-    }
-    if (wave == 0) {
-#pragma unroll
-        for (int r = 0; r < L; ++r) {
-            const int e = r * 64 + lane;
-            if (e < kk) {
-                const bool pad = lst.i[r] == ~0ull;
-                score[(int64_t)q * s_rs + e] = pad ? __uint_as_float(0xff800000u) : adc_ip_key_score(lst.k[r]);
+                const float v = IP ? adc_ip_key_score(lst.k[r]) : adc_key_value(lst.k[r]);
+                val[(int64_t)q * v_rs + e] = pad ? __uint_as_float(IP ? 0xff800000u : 0x7f800000u) : v;
                 idx[(int64_t)q * i_rs + e] = pad ? (int64_t)-1 : (int64_t)lst.i[r];
             }
         }

@@ -1,6 +1,7 @@
-// kernels_adc_search_lists.hip.h -- ADC search over a partitioned code matrix (IVFADC without residuals): the fused scan +
-// exact top-k of kernels_adc_search.hip.h restricted, per query, to the rows of the lists that the query probes.
-// (Launched from exactly one translation unit, pqhip_adc.hip.)
+// kernels_adc_search_lists.hip.h -- ADC search over a partitioned code matrix (IVFADC, with or without residual
+// encoding): the fused scan + exact top-k of kernels_adc_search.hip.h restricted, per query, to the rows of the lists
+// that the query probes.  (pqhip_adc.hip instantiates the plan kernel and the producers without a row mask,
+// pqhip_adc_masked.hip those with one.)
 //
 // List l is rows [list_off[l], list_off[l + 1]) of the code matrix; probe row q names the lists of query q.  S_q is the
 // set of rows of those lists, and the result of query q is the first k rows of S_q under the order of the exhaustive
@@ -13,18 +14,27 @@
 // checks them: -1 is padding, any other id outside [0, n_lists) is skipped and raises the range flag, a range is
 // clamped to [0, n_codes] and an inverted one is empty (both raise the flag).  The producer therefore never forms a
 // row outside the matrix.  k_adc_search_lists_u8 (grid (G, queries), 1,024 threads) loads its query's [M][K] table
-// into LDS, takes the slice [ceil(T / G) b, ceil(T / G) (b + 1)) of the T concatenated probed rows and walks it 1,024
-// rows at a time: the trip count depends on the slice alone (wave-uniform, as SearchState::offer is wave-wide), every
-// lane maps its place in the concatenation to a row by stepping through the segments (monotone: one compare per row
-// while it stays inside a list), so short lists cost no idle lanes.  Row sum, score, selection, queue and the merge of
-// the 16 waves are those of k_adc_search_u8 with NQ = 1; the tie-break value offered with a row is its position
-// (32 bits: n_codes <= 2^32 - 2, 0xffffffff stays "empty").  The G partial lists of a query are merged by
-// k_adc_search_merge / k_adc_ip_search_merge, unchanged.
+// into LDS, takes its slice of the T concatenated probed rows (adc_lists_wg_slice) and walks it 1,024 rows at a time:
+// the trip count depends on the slice alone (wave-uniform, as SearchState::offer is wave-wide), every lane maps its
+// place in the concatenation to a row by stepping through the segments (adc_segment_start / adc_segment_seek: monotone,
+// one compare per row while it stays inside a list), so short lists cost no idle lanes.  Row sum, selection, queue and
+// the merge of the 16 waves are those of k_adc_search_u8 with NQ = 1; the tie-break value offered with a row is its
+// position (32 bits: n_codes <= 2^32 - 2, 0xffffffff stays "empty").  The G partial lists of a query are merged by
+// k_adc_search_merge.
+//
+// Residual codes (RESIDUAL; the codes encode x - c_list(x)).  One table per query, no table per list.  With r^_i the
+// reconstruction of row i's residual code, l its list and c_l the coarse centroid,
+//   |q - c_l - r^_i|^2 = |q - c_l|^2 + (|r^_i|^2 + 2 <c_l, r^_i>) - 2 <q, r^_i>         <q, c_l + r^_i> = <q, c_l> + <q, r^_i>
+// so both searches are the inner-product list scan plus one f32 per (query, probe slot), the probe bias, and for the
+// distance one f32 per row, the row term, stored beside the codes as the scales are.  A lane holds the bias of the
+// segment it stands in (SegmentPos::bias) and reloads it where it reloads delta, on a segment change; segments it only
+// steps over (skipped probes and empty lists) are never read, so the bias of a skipped probe cannot reach a result.
 #pragma once
 #include "kernels_adc_search.hip.h"
 
 namespace pqhip {
 
+#ifndef PQHIP_ADC_TEMPLATES_ONLY   // not a template: it belongs to one translation unit, pqhip_adc.hip
 // seg_begin [nq][n_probe]: first row of the probe's list (clamped); seg_cum [nq][n_probe + 1]: probed rows before the
 // probe, seg_cum[q][n_probe] = T_q.  A skipped probe is an empty segment.
 __global__ __launch_bounds__(1024) void k_adc_lists_plan(const int64_t* __restrict__ list_off, int64_t n_lists,
@@ -76,47 +86,43 @@ __global__ __launch_bounds__(1024) void k_adc_lists_plan(const int64_t* __restri
     if (threadIdx.x == 0) sc[n_probe] = carry;
     if (bad) atomicOr(err, 1);
 }
+#endif  // PQHIP_ADC_TEMPLATES_ONLY
 
-// IP = false: distances (lut = distance tables, scales unused); IP = true: -fl(s * scale) is offered, as in
-// k_adc_ip_search_u8.  lut [queries of the launch][M][K]; part_* [queries][G][64 L].
-template <bool IP, int NV, int L>
-__global__ __launch_bounds__(1024) void k_adc_search_lists_u8(const uint8_t* __restrict__ codes, int64_t n, int64_t c_rs,
-                                                              const float* __restrict__ lut,
-                                                              const float* __restrict__ scales /* IP: [n] or null */,
-                                                              int M, int K, int kk, const int64_t* __restrict__ seg_begin,
-                                                              const int64_t* __restrict__ seg_cum, int n_probe,
-                                                              unsigned* __restrict__ part_k, uint64_t* __restrict__ part_i,
-                                                              int* __restrict__ err)
+// The value offered for a row: s the row sum over the query's table (sequential f32 over m from +0), x = extra[row],
+// b the bias of the probe slot through which the row is reached, every operation one rounded f32 operation:
+//   plain:     IP = false: s                                         IP = true: -fl(s * x)           (x = 1 when extra == null)
+//   RESIDUAL:  IP = false: fl(fl(b + x) - fl(s + s))   (x: row terms, never null)
+//              IP = true:  -fl(fl(b + s) * x)          (x: scales, 1 when extra == null)          s over inner-product tables
+// MASKED: the row's bit of `allow` (the mask in position order) is tested before the fetch, as in k_adc_search_u8 -- the
+// row term / scale of a disallowed row is not loaded (a NaN there reaches nothing); the bias is per segment and is
+// loaded as without a mask.  A flag that is off leaves no instruction and no argument load behind.
+// lut [queries of the launch][M][K]; bias [queries of the launch][b_rs], b_rs >= n_probe; part_* [queries][G][64 L].
+template <bool IP, bool RESIDUAL, bool MASKED, int NV, int L>
+__global__ __launch_bounds__(1024) void k_adc_search_lists_u8(
+    const uint8_t* __restrict__ codes, int64_t n, int64_t c_rs, const float* __restrict__ lut,
+    const float* __restrict__ extra /* [n]: scales (IP) or row terms (RESIDUAL, !IP), or null */, int M, int K, int kk,
+    const int64_t* __restrict__ seg_begin, const int64_t* __restrict__ seg_cum, int n_probe, unsigned* __restrict__ part_k,
+    uint64_t* __restrict__ part_i, int* __restrict__ err, const float* __restrict__ bias /* RESIDUAL */, int64_t b_rs,
+    const uint32_t* __restrict__ allow /* MASKED */)
 {
     constexpr int NW = NV + 1;
     extern __shared__ __attribute__((aligned(16))) float lds_s[];
     const int MK = M * K;
-    const float* tab = lut + (size_t)blockIdx.y * MK;
-    for (int i = threadIdx.x; i < MK; i += 1024) lds_s[i] = tab[i];
+    adc_stage_tables<1>(lds_s, lut + (size_t)blockIdx.y * MK, MK);
     unsigned* qk = reinterpret_cast<unsigned*>(lds_s + MK);        // [16][kSearchQueue]
     unsigned* qi = qk + kSearchWaves * kSearchQueue;
     __syncthreads();
     const int wave = threadIdx.x >> 6;
     SearchState<L> st[1];
     st[0].init();
+    // (sb before sc, the slice after both: the scalar register allocation of these kernels follows the order)
     const int64_t* sb = seg_begin + (size_t)blockIdx.y * n_probe;
     const int64_t* sc = seg_cum + (size_t)blockIdx.y * ((size_t)n_probe + 1);
-    const int64_t total = sc[n_probe];
-    const int64_t per = (total + gridDim.x - 1) / gridDim.x;
-    const int64_t s0 = (int64_t)blockIdx.x * per < total ? (int64_t)blockIdx.x * per : total;
-    const int64_t s1 = s0 + per < total ? s0 + per : total;
-    // the segment that holds place s0: the first j with seg_cum[j + 1] > s0 (it exists while s0 < T)
-    int j = 0;
-    if (s0 < s1) {
-        int lo_j = 0, hi_j = n_probe - 1;
-        while (lo_j < hi_j) {
-            const int mid = (lo_j + hi_j) >> 1;
-            if (sc[mid + 1] > s0) hi_j = mid; else lo_j = mid + 1;
-        }
-        j = lo_j;
-    }
-    int64_t seg_end = sc[j + 1];
-    int64_t delta = sb[j] - sc[j];                                  // row = place + delta inside segment j
+    const float* pb = nullptr;
+    if constexpr (RESIDUAL) pb = bias + (int64_t)blockIdx.y * b_rs;
+    const ListsSlice slice = adc_lists_wg_slice(sc[n_probe]);
+    const int64_t s0 = slice.s0, s1 = slice.s1;
+    SegmentPos pos = adc_segment_start<RESIDUAL>(sb, sc, pb, n_probe, s0, s1);
     const uintptr_t lo = reinterpret_cast<uintptr_t>(codes);
     const uintptr_t hi = lo + (uintptr_t)((n - 1) * c_rs + M);      // one past the last code byte
     bool bad = false;
@@ -126,23 +132,23 @@ __global__ __launch_bounds__(1024) void k_adc_search_lists_u8(const uint8_t* __r
         float v = 0.f;
         int64_t row = 0;
         if (valid) {
-            while (c >= seg_end && j + 1 < n_probe) {               // places < T end inside some segment
-                ++j;
-                seg_end = sc[j + 1];
-                delta = sb[j] - sc[j];
-            }
-            row = c + delta;
+            pos = adc_segment_seek<!RESIDUAL, RESIDUAL>(pos, c, sb, sc, pb, n_probe);
+            row = c + pos.delta;
             valid = (uint64_t)row < (uint64_t)n;                    // holds by construction of the plan
         }
+        if constexpr (MASKED) {
+            if (valid) valid = adc_mask_bit(allow, row);            // before the fetch: a disallowed row is not read
+        }
         if (valid) {
-            float sc = 1.f;
-            if constexpr (IP) sc = scales ? scales[row] : 1.f;      // issued with the row's code words
+            float x = 1.f;
+            if constexpr (IP) x = extra ? extra[row] : 1.f;         // issued with the row's code words
+            else if constexpr (RESIDUAL) x = extra[row];
             const uintptr_t a = lo + (uintptr_t)(row * c_rs);
             unsigned w[NW];
             adc_fetch_row<NW>(a, lo, hi, M, w);
-            const unsigned sh = (unsigned)(a & 3);
-            v = adc_row_sum<NV>(w, sh, lds_s, M, K, bad);
-            if constexpr (IP) v = -fmul(v, sc);
+            const float s = adc_row_sum<NV>(w, (unsigned)(a & 3), lds_s, M, K, bad);
+            if constexpr (RESIDUAL) v = IP ? -fmul(fadd(pos.bias, s), x) : fsub(fadd(pos.bias, x), fadd(s, s));
+            else v = IP ? -fmul(s, x) : s;
         }
         st[0].offer(v, (unsigned)row, valid, qk + wave * kSearchQueue, qi + wave * kSearchQueue, kk);
     }

@@ -1,11 +1,6 @@
 // pqhip_adc.hip -- asymmetric distance computation over a resident code matrix ("next" row):
 // per-query lookup tables (linalg.rs:118-148 applied to the sub-vectors of the query) and the table-sum scans.
-#include "adc_search_launch.h"
-
-#include "kernels_adc.hip.h"
-#include "kernels_adc_search.hip.h"
-#include "kernels_adc_search_lists.hip.h"
-#include "kernels_adc_search_lists_residual.hip.h"
+#include "adc_search_u8_launch.hip.h"
 
 using namespace pqhip;
 
@@ -65,7 +60,8 @@ int search_nv_bucket(int nv)
     return 0;
 }
 
-// SearchLaunch: adc_search_launch.h (shared with the masked producers of pqhip_adc_masked.hip)
+// SearchLaunch, SearchRoute, ListsRoute and the drivers' contract: adc_search_launch.h; the u8 producers' launchers:
+// adc_search_u8_launch.hip.h (shared with the masked producers of pqhip_adc_masked.hip)
 
 // the producer's dynamic LDS: max(table image + queues, combine lists)
 size_t search_lds(size_t table_bytes, int nq, int L)
@@ -75,123 +71,60 @@ size_t search_lds(size_t table_bytes, int nq, int L)
     return std::max(table_bytes + queues, comb);
 }
 
-// IP = false: the distance search (k_adc_search_*); IP = true: the similarity search (k_adc_ip_search_*)
-template <bool IP, int NV, int NQ, int L>
-int32_t launch_search_u8(const SearchLaunch& a, const uint8_t* codes, const float* lut, size_t lds)
+// The generic producer, a SearchProducer for one query per pass: any code width, the table in LDS when it fits there
+// beside the queues (names "..._wide"), else read through L2 ("..._any").  It sizes its own LDS from that choice: the
+// driver's `lds`, like the queries per pass and the NV bucket, is for the u8 and packed producers and is not used here.
+template <typename IdxT>
+int32_t launch_search_any(bool ip, int, int L, int, const SearchLaunch& a, const void* codes, const float* lut, size_t)
 {
-    if constexpr (NQ * L > 16) {
-        return PQHIP_EUNSUPPORTED;
-    } else {
-        const void* kern = IP ? (const void*)k_adc_ip_search_u8<NV, NQ, L> : (const void*)k_adc_search_u8<NV, NQ, L>;
-        HIPCHK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        if constexpr (IP) {
-            hipLaunchKernelGGL((k_adc_ip_search_u8<NV, NQ, L>), dim3(a.grid), dim3(1024), lds, a.st, codes, a.n, a.c_rs, lut,
-                               a.scales, a.M, a.K, a.k, a.rows_per_wg, a.part_k, a.part_i, a.err);
-            note_kernel(NQ == 8 ? "k_adc_ip_search_u8_mq<8 queries>" : NQ == 4 ? "k_adc_ip_search_u8_mq<4 queries>" : "k_adc_ip_search_u8");
-        } else {
-            hipLaunchKernelGGL((k_adc_search_u8<NV, NQ, L>), dim3(a.grid), dim3(1024), lds, a.st, codes, a.n, a.c_rs, lut, a.M, a.K,
-                               a.k, a.rows_per_wg, a.part_k, a.part_i, a.err);
-            note_kernel(NQ == 8 ? "k_adc_search_u8_mq<8 queries>" : NQ == 4 ? "k_adc_search_u8_mq<4 queries>" : "k_adc_search_u8");
-        }
-        return PQHIP_OK;
-    }
-}
-
-template <bool IP, int NQ, int L>
-int32_t launch_search_u8_nv(int nvb, const SearchLaunch& a, const uint8_t* codes, const float* lut, size_t lds)
-{
-    switch (nvb) {
-    case 1: return launch_search_u8<IP, 1, NQ, L>(a, codes, lut, lds);
-    case 2: return launch_search_u8<IP, 2, NQ, L>(a, codes, lut, lds);
-    case 4: return launch_search_u8<IP, 4, NQ, L>(a, codes, lut, lds);
-    case 8: return launch_search_u8<IP, 8, NQ, L>(a, codes, lut, lds);
-    case 13: return launch_search_u8<IP, 13, NQ, L>(a, codes, lut, lds);
-    case kAdcMaxValueWords: return launch_search_u8<IP, kAdcMaxValueWords, NQ, L>(a, codes, lut, lds);
-    default: return PQHIP_EUNSUPPORTED;
-    }
-}
-
-template <bool IP, int NQ>
-int32_t launch_search_u8_l(int L, int nvb, const SearchLaunch& a, const uint8_t* codes, const float* lut, size_t lds)
-{
-    switch (L) {
-    case 1: return launch_search_u8_nv<IP, NQ, 1>(nvb, a, codes, lut, lds);
-    case 2: return launch_search_u8_nv<IP, NQ, 2>(nvb, a, codes, lut, lds);
-    case 4: return launch_search_u8_nv<IP, NQ, 4>(nvb, a, codes, lut, lds);
-    case 8: return launch_search_u8_nv<IP, NQ, 8>(nvb, a, codes, lut, lds);
-    case 16: return launch_search_u8_nv<IP, NQ, 16>(nvb, a, codes, lut, lds);
-    default: return PQHIP_EUNSUPPORTED;
-    }
-}
-
-template <bool IP, typename IdxT, int L, bool TAB_LDS>
-void launch_search_any_t(const SearchLaunch& a, const IdxT* codes, const float* lut, size_t lds)
-{
-    if constexpr (IP)
-        hipLaunchKernelGGL((k_adc_ip_search_any<IdxT, L, TAB_LDS>), dim3(a.grid), dim3(1024), lds, a.st, codes, a.n, a.c_rs,
-                           lut, a.scales, a.M, a.K, a.k, a.rows_per_wg, a.part_k, a.part_i, a.err);
-    else
-        hipLaunchKernelGGL((k_adc_search_any<IdxT, L, TAB_LDS>), dim3(a.grid), dim3(1024), lds, a.st, codes, a.n, a.c_rs, lut,
-                           a.M, a.K, a.k, a.rows_per_wg, a.part_k, a.part_i, a.err);
-}
-
-template <bool IP, typename IdxT, int L>
-int32_t launch_search_any(const SearchLaunch& a, const IdxT* codes, const float* lut, bool tab_lds)
-{
-    const size_t table = tab_lds ? (size_t)a.M * a.K * sizeof(float) : 0;
-    const size_t lds = search_lds(table, 1, L);
-    const void* kern = IP ? (tab_lds ? (const void*)k_adc_ip_search_any<IdxT, L, true> : (const void*)k_adc_ip_search_any<IdxT, L, false>)
-                          : (tab_lds ? (const void*)k_adc_search_any<IdxT, L, true> : (const void*)k_adc_search_any<IdxT, L, false>);
-    HIPCHK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    if (tab_lds) launch_search_any_t<IP, IdxT, L, true>(a, codes, lut, lds);
-    else launch_search_any_t<IP, IdxT, L, false>(a, codes, lut, lds);
-    if (IP) note_kernel(tab_lds ? "k_adc_ip_search_wide" : "k_adc_ip_search_any");
+    const bool tab_lds = !diag().adc_any && search_lds((size_t)a.M * a.K * sizeof(float), 1, L) <= 160 * 1024;
+    const size_t lds = search_lds(tab_lds ? (size_t)a.M * a.K * sizeof(float) : 0, 1, L);
+    const int32_t status = dispatch_int<0, 1>(ip, [&](auto ip_c) {
+        return dispatch_int<0, 1>(tab_lds, [&](auto tab_c) {
+            return dispatch_list_regs(L, [&](auto l_c) -> int32_t {
+                auto kern = k_adc_search_any<decltype(ip_c)::value != 0, IdxT, decltype(l_c)::value, decltype(tab_c)::value != 0>;
+                HIPCHK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+                hipLaunchKernelGGL(kern, dim3(a.grid), dim3(1024), lds, a.st, (const IdxT*)codes, a.n, a.c_rs, lut, a.scales, a.M,
+                                   a.K, a.k, a.rows_per_wg, a.part_k, a.part_i, a.err);
+                return PQHIP_OK;
+            });
+        });
+    });
+    if (status != PQHIP_OK) return status;
+    if (ip) note_kernel(tab_lds ? "k_adc_ip_search_wide" : "k_adc_ip_search_any");
     else note_kernel(tab_lds ? "k_adc_search_wide" : "k_adc_search_any");
     return PQHIP_OK;
 }
 
-template <bool IP, typename IdxT>
-int32_t launch_search_any_l(int L, const SearchLaunch& a, const IdxT* codes, const float* lut, bool tab_lds)
+// k_adc_search_merge over the partial lists of nq queries; n_lists == 0 writes the padding only
+int32_t launch_search_merge(bool ip, int L, int nq, int n_lists, int k, const unsigned* part_k, const uint64_t* part_i, float* d_val,
+                            int64_t v_rs, int64_t* d_idx, int64_t i_rs, hipStream_t st)
 {
-    switch (L) {
-    case 1: return launch_search_any<IP, IdxT, 1>(a, codes, lut, tab_lds);
-    case 2: return launch_search_any<IP, IdxT, 2>(a, codes, lut, tab_lds);
-    case 4: return launch_search_any<IP, IdxT, 4>(a, codes, lut, tab_lds);
-    case 8: return launch_search_any<IP, IdxT, 8>(a, codes, lut, tab_lds);
-    case 16: return launch_search_any<IP, IdxT, 16>(a, codes, lut, tab_lds);
-    default: return PQHIP_EUNSUPPORTED;
-    }
-}
-
-template <bool IP, int L>
-int32_t launch_search_merge_t(int nq, int n_lists, int k, const unsigned* part_k, const uint64_t* part_i, float* dist, int64_t d_rs,
-                              int64_t* idx, int64_t i_rs, hipStream_t st)
-{
-    const size_t lds = (size_t)kSearchMergeWaves * 64 * L * (sizeof(unsigned) + sizeof(uint64_t));
-    const void* kern = IP ? (const void*)k_adc_ip_search_merge<L> : (const void*)k_adc_search_merge<L>;
-    HIPCHK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    if constexpr (IP)
-        hipLaunchKernelGGL((k_adc_ip_search_merge<L>), dim3((unsigned)nq), dim3(64 * kSearchMergeWaves), lds, st, part_k, part_i,
-                           n_lists, k, dist, d_rs, idx, i_rs);
-    else
-        hipLaunchKernelGGL((k_adc_search_merge<L>), dim3((unsigned)nq), dim3(64 * kSearchMergeWaves), lds, st, part_k, part_i,
-                           n_lists, k, dist, d_rs, idx, i_rs);
-    note_kernel(IP ? "k_adc_ip_search_merge" : "k_adc_search_merge");
+    const int32_t status = dispatch_int<0, 1>(ip, [&](auto ip_c) {
+        return dispatch_list_regs(L, [&](auto l_c) -> int32_t {
+            constexpr int LL = decltype(l_c)::value;
+            auto kern = k_adc_search_merge<decltype(ip_c)::value != 0, LL>;
+            const size_t lds = (size_t)kSearchMergeWaves * 64 * LL * (sizeof(unsigned) + sizeof(uint64_t));
+            HIPCHK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            hipLaunchKernelGGL(kern, dim3((unsigned)nq), dim3(64 * kSearchMergeWaves), lds, st, part_k, part_i, n_lists, k, d_val, v_rs,
+                               d_idx, i_rs);
+            return PQHIP_OK;
+        });
+    });
+    if (status != PQHIP_OK) return status;
+    note_kernel(ip ? "k_adc_ip_search_merge" : "k_adc_search_merge");
+    HIPCHK(hipGetLastError());
     return PQHIP_OK;
 }
 
-template <bool IP>
-int32_t launch_search_merge(int L, int nq, int n_lists, int k, const unsigned* part_k, const uint64_t* part_i, float* dist,
-                            int64_t d_rs, int64_t* idx, int64_t i_rs, hipStream_t st)
+// no row to search: index -1 and +Inf resp. -Inf for every query
+int32_t search_padding_only(bool ip, int L, int64_t nq, int k, float* d_val, int64_t v_rs, int64_t* d_idx, int64_t i_rs, hipStream_t st)
 {
-    switch (L) {
-    case 1: return launch_search_merge_t<IP, 1>(nq, n_lists, k, part_k, part_i, dist, d_rs, idx, i_rs, st);
-    case 2: return launch_search_merge_t<IP, 2>(nq, n_lists, k, part_k, part_i, dist, d_rs, idx, i_rs, st);
-    case 4: return launch_search_merge_t<IP, 4>(nq, n_lists, k, part_k, part_i, dist, d_rs, idx, i_rs, st);
-    case 8: return launch_search_merge_t<IP, 8>(nq, n_lists, k, part_k, part_i, dist, d_rs, idx, i_rs, st);
-    case 16: return launch_search_merge_t<IP, 16>(nq, n_lists, k, part_k, part_i, dist, d_rs, idx, i_rs, st);
-    default: return PQHIP_EUNSUPPORTED;
+    for (int64_t q = 0; q < nq; q += 65535) {
+        const int nqp = (int)std::min<int64_t>(nq - q, 65535);
+        PQCHK(launch_search_merge(ip, L, nqp, 0, k, nullptr, nullptr, d_val + q * v_rs, v_rs, d_idx + q * i_rs, i_rs, st));
     }
+    return PQHIP_OK;
 }
 
 // Lookup tables for both searches: the query is rotated first for an OPQ codebook (pq.rs:293), then one thread per
@@ -233,59 +166,39 @@ int32_t adc_tables(bool ip, pqhip_codebook* cb, int32_t slot, const float* d_q, 
     return PQHIP_OK;
 }
 
-// The fused scan + exact top-k of both searches, one policy: argument checks, queries per pass (NQ L <= 16 and the
-// 160 KB of LDS, option "adc_single_query"), the u8 fast path or the generic kernel, the partial lists in the
-// codebook's scratch, one merge per pass.  IP: similarity (k_adc_ip_search_*, d_scales may be null); else distance.
-// d_allow != null: the same choices with the masked producer in the place of the u8 one; a call that the u8 route does
-// not serve (4-byte codes, a table beyond LDS) is PQHIP_EUNSUPPORTED -- never another path.
-template <bool IP>
-int32_t adc_search(pqhip_codebook* cb, int32_t slot, const float* d_tables, int64_t nq, const void* d_codes, int32_t code_bytes,
-                   int64_t n, int64_t c_rs, const float* d_scales, int32_t k, float* d_dist, int64_t d_rs, int64_t* d_idx,
-                   int64_t i_rs, void* stream, const RowMask* mask = nullptr)
+// The fused scan + exact top-k of every exhaustive search, one policy: the checks that follow the caller's, queries per
+// pass (NQ L <= 16 and the 160 KB of LDS, option "adc_single_query"), the partial lists in the codebook's scratch, one
+// merge per pass.  ip: similarity (d_scales may be null); else distance.
+int32_t adc_search_run(bool ip, pqhip_codebook* cb, int32_t slot, const SearchRoute& r, const float* d_tables, int64_t nq,
+                       const void* d_codes, int64_t n, int64_t c_rs, const uint32_t* d_allow, const float* d_scales, int32_t k,
+                       float* d_val, int64_t v_rs, int64_t* d_idx, int64_t i_rs, void* stream)
 {
-    const uint32_t* d_allow = mask ? mask->words : nullptr;
-    if (!cb || nq < 0 || n < 0 || k < 1) return PQHIP_EINVAL;
-    if (slot < 0 || slot >= (int)cb->dev.size()) return PQHIP_ENODEV;
-    if (code_bytes != 1 && code_bytes != 4) return PQHIP_EUNSUPPORTED;
-    if (k > kSearchMaxK) return PQHIP_EUNSUPPORTED;
-    if (d_allow && (code_bytes != 1 || search_nv_bucket(((int)cb->M + 3) / 4) == 0 ||
-                    search_lds((size_t)cb->M * cb->K * sizeof(float), 1, search_list_regs(k)) > 160 * 1024))
-        return PQHIP_EUNSUPPORTED;                                  // a mask: the u8 route or nothing
     if (nq == 0) return PQHIP_OK;
-    if (!d_dist || !d_idx || (n > 0 && (!d_tables || !d_codes))) return PQHIP_EINVAL;
-    if ((n > 0 && c_rs < cb->M) || d_rs < k || i_rs < k) return PQHIP_ESHAPE;
+    if (!d_val || !d_idx || (n > 0 && (!d_tables || !d_codes))) return PQHIP_EINVAL;
+    if ((n > 0 && c_rs < r.row_len) || v_rs < k || i_rs < k) return PQHIP_ESHAPE;
     SET_DEVICE(cb->ctx->devs[slot]->ordinal);
     hipStream_t st = (hipStream_t)stream;
     const int L = search_list_regs(k);
-    if (n == 0) {      // padding only
-        for (int64_t q = 0; q < nq; q += 65535) {
-            const int nqp = (int)std::min<int64_t>(nq - q, 65535);
-            PQCHK(launch_search_merge<IP>(L, nqp, 0, k, nullptr, nullptr, d_dist + q * d_rs, d_rs, d_idx + q * i_rs, i_rs, st));
-            HIPCHK(hipGetLastError());
-        }
-        return PQHIP_OK;
-    }
+    if (n == 0) return search_padding_only(ip, L, nq, k, d_val, v_rs, d_idx, i_rs, st);
     ErrFlag ef(cb, slot, st);
     const int M = (int)cb->M, K = (int)cb->K;
-    const size_t table = (size_t)M * K * sizeof(float);
-    const int nv = (M + 3) / 4;
-    const int nvb = search_nv_bucket(nv);
-    const bool fast = code_bytes == 1 && nvb != 0 && search_lds(table, 1, L) <= 160 * 1024;
-    // Queries per pass on the fast path: every query of a pass keeps a list of 64 L entries (2 L VGPRs) per wave, so
-    // NQ L <= 16 (at most 32 list VGPRs beside the row sum; 1,024-thread workgroups leave 128 VGPRs per lane): 8 queries
-    // up to k = 128, 4 up to k = 256, one beyond -- and only while NQ table images plus the queues fit the 160 KB of LDS.
+    const size_t table = r.table_bytes;
+    // Queries per pass: every query of a pass keeps a list of 64 L entries (2 L VGPRs) per wave, so NQ L <= 16 (at most
+    // 32 list VGPRs beside the row sum; 1,024-thread workgroups leave 128 VGPRs per lane): 8 queries up to k = 128, 4 up
+    // to k = 256, one beyond -- and only while NQ table images plus the queues fit the 160 KB of LDS.
     // Option "adc_single_query" = 1 keeps one query per pass, as for the scan.
-    const bool mq_on = cb->ctx->opt.adc_single_query.load(std::memory_order_relaxed) == 0;
+    const bool mq_on = r.multi_query && cb->ctx->opt.adc_single_query.load(std::memory_order_relaxed) == 0;
+    auto pass_fits = [&](int c) { return mq_on && c * L <= 16 && search_lds(table * c, c, L) <= 160 * 1024; };
     int nqp_first = 1;
-    if (fast && mq_on) {
-        for (int c : {8, 4}) {
-            if (c * L <= 16 && search_lds(table * c, c, L) <= 160 * 1024 && nq >= c) { nqp_first = c; break; }
-        }
+    for (int c : {8, 4}) {
+        if (pass_fits(c) && nq >= c) { nqp_first = c; break; }
     }
-    const int n_cus = cb->ctx->devs[slot]->n_cus;
-    // one 1,024-thread workgroup per CU, a contiguous row range each (offsets within it are 32-bit: < 2^31 rows)
-    int64_t rows_per_wg = round_up((n + n_cus - 1) / n_cus, 1024);
-    rows_per_wg = std::max<int64_t>(rows_per_wg, 4096);
+    // one 1,024-thread workgroup per CU, a contiguous row range each (offsets within it are 32-bit: < 2^31 rows) of at
+    // least 4,096 rows; a forced number of workgroups keeps the rows per workgroup a multiple of 1,024 (a wave's rows
+    // share two mask words)
+    const int64_t wgs = r.forced_wgs > 0 ? std::min<int64_t>(r.forced_wgs, 65536) : cb->ctx->devs[slot]->n_cus;
+    int64_t rows_per_wg = round_up((n + wgs - 1) / wgs, 1024);
+    if (r.forced_wgs <= 0) rows_per_wg = std::max<int64_t>(rows_per_wg, 4096);
     rows_per_wg = std::min<int64_t>(rows_per_wg, (int64_t)1 << 30);
     const int64_t grid = (n + rows_per_wg - 1) / rows_per_wg;
     const size_t list_entries = (size_t)nqp_first * grid * 64 * L;
@@ -293,32 +206,39 @@ int32_t adc_search(pqhip_codebook* cb, int32_t slot, const float* d_tables, int6
     PQCHK(part.acquire(list_entries * (sizeof(unsigned) + sizeof(uint64_t))));
     uint64_t* part_i = (uint64_t*)part.ptr();
     unsigned* part_k = (unsigned*)(part_i + list_entries);
-    SearchLaunch a{n, c_rs, rows_per_wg, (unsigned)grid, M, K, k, d_scales, part_k, part_i, ef.flag, st, d_allow};
-    const bool adc_any = diag().adc_any;
+    SearchLaunch a{n, c_rs, rows_per_wg, (unsigned)grid, M, K, k, ip ? d_scales : nullptr, part_k, part_i, ef.flag, st, d_allow};
     int64_t q = 0;
     for (int nqp : {8, 4, 1}) {
         if (nqp > nqp_first) continue;
-        if (nqp == 4 && !(fast && mq_on && 4 * L <= 16 && search_lds(table * 4, 4, L) <= 160 * 1024)) continue;
+        if (nqp == 4 && !pass_fits(4)) continue;
         for (; q + nqp <= nq; q += nqp) {
-            const float* lut = d_tables + q * (int64_t)M * K;
-            if (fast && d_allow) {
-                PQCHK(mask->search(IP, nqp, L, nvb, a, (const uint8_t*)d_codes, lut, search_lds(table * nqp, nqp, L)));
-            } else if (fast) {
-                const size_t lds = search_lds(table * nqp, nqp, L);
-                if (nqp == 8) PQCHK((launch_search_u8_l<IP, 8>(L, nvb, a, (const uint8_t*)d_codes, lut, lds)));
-                else if (nqp == 4) PQCHK((launch_search_u8_l<IP, 4>(L, nvb, a, (const uint8_t*)d_codes, lut, lds)));
-                else PQCHK((launch_search_u8_l<IP, 1>(L, nvb, a, (const uint8_t*)d_codes, lut, lds)));
-            } else {
-                const bool tab_lds = !adc_any && search_lds(table, 1, L) <= 160 * 1024;
-                if (code_bytes == 1) PQCHK((launch_search_any_l<IP, uint8_t>(L, a, (const uint8_t*)d_codes, lut, tab_lds)));
-                else PQCHK((launch_search_any_l<IP, uint32_t>(L, a, (const uint32_t*)d_codes, lut, tab_lds)));
-            }
+            PQCHK(r.launch(ip, nqp, L, r.nvb, a, d_codes, d_tables + q * (int64_t)M * K, search_lds(table * nqp, nqp, L)));
             HIPCHK(hipGetLastError());
-            PQCHK(launch_search_merge<IP>(L, nqp, (int)grid, k, part_k, part_i, d_dist + q * d_rs, d_rs, d_idx + q * i_rs, i_rs, st));
-            HIPCHK(hipGetLastError());
+            PQCHK(launch_search_merge(ip, L, nqp, (int)grid, k, part_k, part_i, d_val + q * v_rs, v_rs, d_idx + q * i_rs, i_rs, st));
         }
     }
     return PQHIP_OK;
+}
+
+// The exhaustive searches over u8 / 32-bit codes: the u8 producer when the codes are bytes and the table fits LDS beside
+// the queues, else the generic kernel.  mask != null: the masked producer in the place of the u8 one; a call that the
+// u8 route does not serve (4-byte codes, a table beyond LDS) is PQHIP_EUNSUPPORTED -- never another path.
+int32_t adc_search(bool ip, pqhip_codebook* cb, int32_t slot, const float* d_tables, int64_t nq, const void* d_codes, int32_t code_bytes,
+                   int64_t n, int64_t c_rs, const float* d_scales, int32_t k, float* d_val, int64_t v_rs, int64_t* d_idx,
+                   int64_t i_rs, void* stream, const RowMask* mask = nullptr)
+{
+    if (!cb || nq < 0 || n < 0 || k < 1) return PQHIP_EINVAL;
+    if (slot < 0 || slot >= (int)cb->dev.size()) return PQHIP_ENODEV;
+    if ((code_bytes != 1 && code_bytes != 4) || k > kSearchMaxK) return PQHIP_EUNSUPPORTED;
+    const size_t table = (size_t)cb->M * cb->K * sizeof(float);
+    const int nvb = search_nv_bucket(((int)cb->M + 3) / 4);
+    const bool fast = code_bytes == 1 && nvb != 0 && search_lds(table, 1, search_list_regs(k)) <= 160 * 1024;
+    if (mask && !fast) return PQHIP_EUNSUPPORTED;                   // a mask: the u8 route or nothing
+    const SearchProducer producer = mask ? mask->search : fast ? launch_search_u8<false>
+                                    : code_bytes == 1 ? launch_search_any<uint8_t> : launch_search_any<uint32_t>;
+    const SearchRoute r{cb->M, table, nvb, fast, 0, producer};
+    return adc_search_run(ip, cb, slot, r, d_tables, nq, d_codes, n, c_rs, mask ? mask->words : nullptr, d_scales, k, d_val, v_rs, d_idx,
+                          i_rs, stream);
 }
 
 // ---- ADC search over probed lists (kernels_adc_search_lists.hip.h) ----------------------------------------------------
@@ -330,48 +250,6 @@ int lists_nv_bucket(int nv)
     for (int b : {4, 8, 13, kAdcMaxValueWords})
         if (nv <= b) return b;
     return 0;
-}
-
-template <bool IP, int NV, int L>
-int32_t launch_lists_u8(const ListsLaunch& a, const uint8_t* codes, const float* lut, size_t lds)
-{
-    if (a.bias) {   // the residual producer
-        HIPCHK(hipFuncSetAttribute((const void*)k_adc_search_lists_residual_u8<IP, NV, L>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        hipLaunchKernelGGL((k_adc_search_lists_residual_u8<IP, NV, L>), dim3(a.G, a.nq), dim3(1024), lds, a.st, codes, a.n, a.c_rs, lut,
-                           a.bias, a.b_rs, a.scales, a.M, a.K, a.k, a.seg_begin, a.seg_cum, a.n_probe, a.part_k, a.part_i, a.err);
-        note_kernel(IP ? "k_adc_ip_search_lists_residual_u8" : "k_adc_search_lists_residual_u8");
-        return PQHIP_OK;
-    }
-    HIPCHK(hipFuncSetAttribute((const void*)k_adc_search_lists_u8<IP, NV, L>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    hipLaunchKernelGGL((k_adc_search_lists_u8<IP, NV, L>), dim3(a.G, a.nq), dim3(1024), lds, a.st, codes, a.n, a.c_rs, lut,
-                       a.scales, a.M, a.K, a.k, a.seg_begin, a.seg_cum, a.n_probe, a.part_k, a.part_i, a.err);
-    note_kernel(IP ? "k_adc_ip_search_lists_u8" : "k_adc_search_lists_u8");
-    return PQHIP_OK;
-}
-
-template <bool IP, int L>
-int32_t launch_lists_u8_nv(int nvb, const ListsLaunch& a, const uint8_t* codes, const float* lut, size_t lds)
-{
-    switch (nvb) {
-    case 4: return launch_lists_u8<IP, 4, L>(a, codes, lut, lds);
-    case 8: return launch_lists_u8<IP, 8, L>(a, codes, lut, lds);
-    case 13: return launch_lists_u8<IP, 13, L>(a, codes, lut, lds);
-    case kAdcMaxValueWords: return launch_lists_u8<IP, kAdcMaxValueWords, L>(a, codes, lut, lds);
-    default: return PQHIP_EUNSUPPORTED;
-    }
-}
-
-template <bool IP>
-int32_t launch_lists_u8_l(int L, int nvb, const ListsLaunch& a, const uint8_t* codes, const float* lut, size_t lds)
-{
-    switch (L) {
-    case 1: return launch_lists_u8_nv<IP, 1>(nvb, a, codes, lut, lds);
-    case 2: return launch_lists_u8_nv<IP, 2>(nvb, a, codes, lut, lds);
-    case 4: return launch_lists_u8_nv<IP, 4>(nvb, a, codes, lut, lds);
-    case 8: return launch_lists_u8_nv<IP, 8>(nvb, a, codes, lut, lds);
-    case 16: return launch_lists_u8_nv<IP, 16>(nvb, a, codes, lut, lds);
-    default: return PQHIP_EUNSUPPORTED;
-    }
 }
 
 // Workgroups per query, from what the host knows: the expected number of probed rows (lists of average size) in units
@@ -400,44 +278,27 @@ int32_t launch_lists_plan(const int64_t* d_list_off, int64_t n_lists, const int6
 
 // ListsResidual (probe bias rows; the row terms travel in the place of the scales): adc_search_launch.h
 
-// All list searches: argument checks in the order of adc_search, the plan kernel (the only reader of the offsets and
-// probes), the producer over a (G, queries) grid and one merge, per chunk of queries that fits the scratch lease.
-// res != null: the residual producer; d_scales then holds the row terms of the distance search (required).
-// d_allow != null: the masked producers (pqhip_adc_masked.hip) behind the same plan, before the same merge.
-template <bool IP>
-int32_t adc_search_lists(pqhip_codebook* cb, int32_t slot, const float* d_tables, int64_t nq, const void* d_codes,
-                         int32_t code_bytes, int64_t n, int64_t c_rs, const int64_t* d_list_off, int64_t n_lists,
-                         const int64_t* d_probes, int32_t n_probe, int64_t p_rs, const float* d_scales, int32_t k,
-                         float* d_val, int64_t v_rs, int64_t* d_idx, int64_t i_rs, void* stream,
-                         const ListsResidual* res = nullptr, const RowMask* mask = nullptr)
+// All list searches: the checks that follow the caller's in the order of adc_search_run, the plan kernel (the only
+// reader of the offsets and probes), the producer over a (G, queries) grid and one merge, per chunk of queries that fits
+// the scratch lease.
+int32_t adc_search_lists_run(bool ip, pqhip_codebook* cb, int32_t slot, const ListsRoute& r, const float* d_tables, int64_t nq,
+                             const void* d_codes, int64_t n, int64_t c_rs, const uint32_t* d_allow, const int64_t* d_list_off,
+                             int64_t n_lists, const int64_t* d_probes, int32_t n_probe, int64_t p_rs, const float* d_scales,
+                             int32_t k, float* d_val, int64_t v_rs, int64_t* d_idx, int64_t i_rs, void* stream,
+                             const ListsResidual* res)
 {
-    const uint32_t* d_allow = mask ? mask->words : nullptr;
-    if (!cb || nq < 0 || n < 0 || k < 1 || n_lists < 0 || n_probe < 1) return PQHIP_EINVAL;
-    if (slot < 0 || slot >= (int)cb->dev.size()) return PQHIP_ENODEV;
-    const int M = (int)cb->M, K = (int)cb->K;
-    const size_t table = (size_t)M * K * sizeof(float);
-    const int nvb = lists_nv_bucket((M + 3) / 4);
-    if (code_bytes != 1 || k > kSearchMaxK) return PQHIP_EUNSUPPORTED;
-    const int L = search_list_regs(k);
-    if (nvb == 0 || search_lds(table, 1, L) > 160 * 1024) return PQHIP_EUNSUPPORTED;   // the table must fit LDS beside the queues
     if (n > (int64_t)0xfffffffell) return PQHIP_EUNSUPPORTED;                          // positions are offered as 32-bit values
     const size_t plan_q = ((size_t)n_probe * 2 + 1) * sizeof(int64_t);
     if (plan_q > kListsScratchBytes / 2) return PQHIP_EUNSUPPORTED;
     if (nq == 0) return PQHIP_OK;
     if (!d_val || !d_idx || !d_list_off || !d_probes || (n > 0 && (!d_tables || !d_codes))) return PQHIP_EINVAL;
-    if (res && (!res->bias || (!IP && !d_scales))) return PQHIP_EINVAL;
-    if ((n > 0 && c_rs < cb->M) || v_rs < k || i_rs < k || p_rs < n_probe) return PQHIP_ESHAPE;
+    if (res && (!res->bias || (!ip && !d_scales))) return PQHIP_EINVAL;
+    if ((n > 0 && c_rs < r.row_len) || v_rs < k || i_rs < k || p_rs < n_probe) return PQHIP_ESHAPE;
     if (res && res->b_rs < n_probe) return PQHIP_ESHAPE;
     SET_DEVICE(cb->ctx->devs[slot]->ordinal);
     hipStream_t st = (hipStream_t)stream;
-    if (n == 0 || n_lists == 0) {      // padding only
-        for (int64_t q = 0; q < nq; q += 65535) {
-            const int nqp = (int)std::min<int64_t>(nq - q, 65535);
-            PQCHK(launch_search_merge<IP>(L, nqp, 0, k, nullptr, nullptr, d_val + q * v_rs, v_rs, d_idx + q * i_rs, i_rs, st));
-            HIPCHK(hipGetLastError());
-        }
-        return PQHIP_OK;
-    }
+    const int M = (int)cb->M, K = (int)cb->K, L = search_list_regs(k);
+    if (n == 0 || n_lists == 0) return search_padding_only(ip, L, nq, k, d_val, v_rs, d_idx, i_rs, st);
     ErrFlag ef(cb, slot, st);
     const int64_t forced = cb->ctx->opt.adc_lists_wgs_per_query.load(std::memory_order_relaxed);
     const int64_t G = forced > 0 ? std::min<int64_t>(forced, 4096)
@@ -451,27 +312,37 @@ int32_t adc_search_lists(pqhip_codebook* cb, int32_t slot, const float* d_tables
     int64_t* seg_begin = (int64_t*)(part_i + (size_t)chunk * G * 64 * L);
     int64_t* seg_cum = seg_begin + (size_t)chunk * n_probe;
     unsigned* part_k = (unsigned*)(seg_cum + (size_t)chunk * ((size_t)n_probe + 1));
-    const size_t lds = search_lds(table, 1, L);
+    const size_t lds = search_lds(r.table_bytes, 1, L);
     for (int64_t q = 0; q < nq; q += chunk) {
         const unsigned nqc = (unsigned)std::min<int64_t>(chunk, nq - q);
         PQCHK(launch_lists_plan(d_list_off, n_lists, d_probes + q * p_rs, (int)n_probe, p_rs, n, seg_begin, seg_cum, nqc, ef.flag, st));
-        ListsLaunch a{n, c_rs, (unsigned)G, nqc, M, K, k, (int)n_probe, d_scales, res ? res->bias + q * res->b_rs : nullptr,
-                      res ? res->b_rs : 0, seg_begin, seg_cum, part_k, part_i, ef.flag, st, d_allow};
-        if (d_allow) PQCHK(mask->lists(IP, L, nvb, a, (const uint8_t*)d_codes, d_tables + q * (int64_t)M * K, lds));
-        else PQCHK((launch_lists_u8_l<IP>(L, nvb, a, (const uint8_t*)d_codes, d_tables + q * (int64_t)M * K, lds)));
+        ListsLaunch a{n, c_rs, (unsigned)G, nqc, M, K, k, (int)n_probe, (ip || res) ? d_scales : nullptr,
+                      res ? res->bias + q * res->b_rs : nullptr, res ? res->b_rs : 0, seg_begin, seg_cum, part_k, part_i, ef.flag, st,
+                      d_allow};
+        PQCHK(r.launch(ip, L, r.nvb, a, d_codes, d_tables + q * (int64_t)M * K, lds));
         HIPCHK(hipGetLastError());
-        PQCHK(launch_search_merge<IP>(L, (int)nqc, (int)G, k, part_k, part_i, d_val + q * v_rs, v_rs, d_idx + q * i_rs, i_rs, st));
-        HIPCHK(hipGetLastError());
+        PQCHK(launch_search_merge(ip, L, (int)nqc, (int)G, k, part_k, part_i, d_val + q * v_rs, v_rs, d_idx + q * i_rs, i_rs, st));
     }
     return PQHIP_OK;
 }
 
-// The merge of both searches for the units that bring producers of their own (pqhip_adc_packed4.hip)
-int32_t adc_search_merge(bool ip, int L, int nq, int n_lists, int k, const unsigned* part_k, const uint64_t* part_i, float* d_val,
-                         int64_t v_rs, int64_t* d_idx, int64_t i_rs, hipStream_t st)
+// The list searches over u8 codes.  mask != null: the masked producers (pqhip_adc_masked.hip) behind the same plan,
+// before the same merge.
+int32_t adc_search_lists(bool ip, pqhip_codebook* cb, int32_t slot, const float* d_tables, int64_t nq, const void* d_codes,
+                         int32_t code_bytes, int64_t n, int64_t c_rs, const int64_t* d_list_off, int64_t n_lists,
+                         const int64_t* d_probes, int32_t n_probe, int64_t p_rs, const float* d_scales, int32_t k, float* d_val,
+                         int64_t v_rs, int64_t* d_idx, int64_t i_rs, void* stream, const ListsResidual* res = nullptr,
+                         const RowMask* mask = nullptr)
 {
-    if (ip) return launch_search_merge<true>(L, nq, n_lists, k, part_k, part_i, d_val, v_rs, d_idx, i_rs, st);
-    return launch_search_merge<false>(L, nq, n_lists, k, part_k, part_i, d_val, v_rs, d_idx, i_rs, st);
+    if (!cb || nq < 0 || n < 0 || k < 1 || n_lists < 0 || n_probe < 1) return PQHIP_EINVAL;
+    if (slot < 0 || slot >= (int)cb->dev.size()) return PQHIP_ENODEV;
+    if (code_bytes != 1 || k > kSearchMaxK) return PQHIP_EUNSUPPORTED;
+    const size_t table = (size_t)cb->M * cb->K * sizeof(float);
+    const int nvb = lists_nv_bucket(((int)cb->M + 3) / 4);
+    if (nvb == 0 || search_lds(table, 1, search_list_regs(k)) > 160 * 1024) return PQHIP_EUNSUPPORTED;   // the table must fit LDS beside the queues
+    const ListsRoute r{cb->M, table, nvb, mask ? mask->lists : launch_lists_u8<false>};
+    return adc_search_lists_run(ip, cb, slot, r, d_tables, nq, d_codes, n, c_rs, mask ? mask->words : nullptr, d_list_off, n_lists,
+                                d_probes, n_probe, p_rs, d_scales, k, d_val, v_rs, d_idx, i_rs, stream, res);
 }
 
 // The doors of pqhip_adc_masked.hip into the two routines above
@@ -479,8 +350,7 @@ int32_t adc_search_masked(bool ip, pqhip_codebook* cb, int32_t slot, const float
                           int32_t code_bytes, int64_t n, int64_t c_rs, const float* d_scales, int32_t k, float* d_val, int64_t v_rs,
                           int64_t* d_idx, int64_t i_rs, void* stream, const RowMask& mask)
 {
-    if (ip) return adc_search<true>(cb, slot, d_tables, nq, d_codes, code_bytes, n, c_rs, d_scales, k, d_val, v_rs, d_idx, i_rs, stream, &mask);
-    return adc_search<false>(cb, slot, d_tables, nq, d_codes, code_bytes, n, c_rs, nullptr, k, d_val, v_rs, d_idx, i_rs, stream, &mask);
+    return adc_search(ip, cb, slot, d_tables, nq, d_codes, code_bytes, n, c_rs, d_scales, k, d_val, v_rs, d_idx, i_rs, stream, &mask);
 }
 
 int32_t adc_search_lists_masked(bool ip, pqhip_codebook* cb, int32_t slot, const float* d_tables, int64_t nq, const void* d_codes,
@@ -489,13 +359,9 @@ int32_t adc_search_lists_masked(bool ip, pqhip_codebook* cb, int32_t slot, const
                                 float* d_val, int64_t v_rs, int64_t* d_idx, int64_t i_rs, void* stream, const ListsResidual* res,
                                 const RowMask& mask)
 {
-    if (ip)
-        return adc_search_lists<true>(cb, slot, d_tables, nq, d_codes, code_bytes, n, c_rs, d_list_off, n_lists, d_probes, n_probe,
-                                      p_rs, d_scales, k, d_val, v_rs, d_idx, i_rs, stream, res, &mask);
-    return adc_search_lists<false>(cb, slot, d_tables, nq, d_codes, code_bytes, n, c_rs, d_list_off, n_lists, d_probes, n_probe,
-                                   p_rs, d_scales, k, d_val, v_rs, d_idx, i_rs, stream, res, &mask);
+    return adc_search_lists(ip, cb, slot, d_tables, nq, d_codes, code_bytes, n, c_rs, d_list_off, n_lists, d_probes, n_probe, p_rs,
+                            d_scales, k, d_val, v_rs, d_idx, i_rs, stream, res, &mask);
 }
-
 }  // namespace pqh
 
 using namespace pqh;
@@ -582,14 +448,14 @@ int32_t pqhip_adc_search_f32_dev(pqhip_codebook* cb, int32_t slot, const float* 
                                  int32_t code_bytes, int64_t n, int64_t c_rs, int32_t k, float* d_dist, int64_t d_rs,
                                  int64_t* d_idx, int64_t i_rs, void* stream)
 {
-    return adc_search<false>(cb, slot, d_tables, nq, d_codes, code_bytes, n, c_rs, nullptr, k, d_dist, d_rs, d_idx, i_rs, stream);
+    return adc_search(false, cb, slot, d_tables, nq, d_codes, code_bytes, n, c_rs, nullptr, k, d_dist, d_rs, d_idx, i_rs, stream);
 }
 
 int32_t pqhip_adc_ip_search_f32_dev(pqhip_codebook* cb, int32_t slot, const float* d_tables, int64_t nq, const void* d_codes,
                                     int32_t code_bytes, int64_t n, int64_t c_rs, const float* d_scales, int32_t k,
                                     float* d_score, int64_t s_rs, int64_t* d_idx, int64_t i_rs, void* stream)
 {
-    return adc_search<true>(cb, slot, d_tables, nq, d_codes, code_bytes, n, c_rs, d_scales, k, d_score, s_rs, d_idx, i_rs, stream);
+    return adc_search(true, cb, slot, d_tables, nq, d_codes, code_bytes, n, c_rs, d_scales, k, d_score, s_rs, d_idx, i_rs, stream);
 }
 
 int32_t pqhip_adc_search_lists_f32_dev(pqhip_codebook* cb, int32_t slot, const float* d_tables, int64_t nq, const void* d_codes,
@@ -597,7 +463,7 @@ int32_t pqhip_adc_search_lists_f32_dev(pqhip_codebook* cb, int32_t slot, const f
                                        const int64_t* d_probes, int32_t n_probe, int64_t p_rs, int32_t k, float* d_dist,
                                        int64_t d_rs, int64_t* d_idx, int64_t i_rs, void* stream)
 {
-    return adc_search_lists<false>(cb, slot, d_tables, nq, d_codes, code_bytes, n, c_rs, d_list_off, n_lists, d_probes, n_probe,
+    return adc_search_lists(false, cb, slot, d_tables, nq, d_codes, code_bytes, n, c_rs, d_list_off, n_lists, d_probes, n_probe,
                                    p_rs, nullptr, k, d_dist, d_rs, d_idx, i_rs, stream);
 }
 
@@ -607,7 +473,7 @@ int32_t pqhip_adc_ip_search_lists_f32_dev(pqhip_codebook* cb, int32_t slot, cons
                                           int64_t p_rs, const float* d_scales, int32_t k, float* d_score, int64_t s_rs,
                                           int64_t* d_idx, int64_t i_rs, void* stream)
 {
-    return adc_search_lists<true>(cb, slot, d_tables, nq, d_codes, code_bytes, n, c_rs, d_list_off, n_lists, d_probes, n_probe,
+    return adc_search_lists(true, cb, slot, d_tables, nq, d_codes, code_bytes, n, c_rs, d_list_off, n_lists, d_probes, n_probe,
                                   p_rs, d_scales, k, d_score, s_rs, d_idx, i_rs, stream);
 }
 
@@ -619,7 +485,7 @@ int32_t pqhip_adc_search_lists_residual_f32_dev(pqhip_codebook* cb, int32_t slot
                                                 int64_t* d_idx, int64_t i_rs, void* stream)
 {
     const ListsResidual res{d_probe_bias, b_rs};
-    return adc_search_lists<false>(cb, slot, d_tables, nq, d_codes, code_bytes, n, c_rs, d_list_off, n_lists, d_probes, n_probe,
+    return adc_search_lists(false, cb, slot, d_tables, nq, d_codes, code_bytes, n, c_rs, d_list_off, n_lists, d_probes, n_probe,
                                    p_rs, d_row_terms, k, d_dist, d_rs, d_idx, i_rs, stream, &res);
 }
 
@@ -631,7 +497,7 @@ int32_t pqhip_adc_ip_search_lists_residual_f32_dev(pqhip_codebook* cb, int32_t s
                                                    int64_t* d_idx, int64_t i_rs, void* stream)
 {
     const ListsResidual res{d_probe_bias, b_rs};
-    return adc_search_lists<true>(cb, slot, d_tables, nq, d_codes, code_bytes, n, c_rs, d_list_off, n_lists, d_probes, n_probe,
+    return adc_search_lists(true, cb, slot, d_tables, nq, d_codes, code_bytes, n, c_rs, d_list_off, n_lists, d_probes, n_probe,
                                   p_rs, d_scales, k, d_score, s_rs, d_idx, i_rs, stream, &res);
 }
 

@@ -1,141 +1,20 @@
 // pqhip_adc_masked.hip -- the ADC searches restricted to an allowed set of rows (include/pqhip.h:
 // pqhip_adc_*search*_masked_f32_dev, pqhip_pack_row_mask_dev).  The policy of a search is pqhip_adc.hip's, the same
 // routines with the mask as one more field (adc_search_launch.h); this unit holds the entry points, the instantiations
-// of the masked producers (kernels_adc_search_masked.hip.h) with their launchers, and packs a mask.  A unit of its own
-// so that the build compiles it beside pqhip_adc.hip; nothing in pqhip_adc.hip refers to it.
-#include "adc_search_launch.h"
-
-#define PQHIP_ADC_TEMPLATES_ONLY   // kernels_adc.hip.h: its non-template kernels belong to pqhip_adc.hip
+// of the u8 producers with their MASKED flag (through the launchers of adc_search_u8_launch.hip.h), and packs a mask.
+// A unit of its own so that the build compiles it beside pqhip_adc.hip; nothing in pqhip_adc.hip refers to it.
+#define PQHIP_ADC_TEMPLATES_ONLY   // the non-template kernels of the headers below belong to pqhip_adc.hip
+#include "adc_search_u8_launch.hip.h"
 #include "kernels_adc_search_masked.hip.h"
 
 using namespace pqhip;
-
-namespace pqh {
-
-template <bool IP, int NV, int NQ, int L>
-int32_t launch_search_masked(const SearchLaunch& a, const uint8_t* codes, const float* lut, size_t lds)
-{
-    if constexpr (NQ * L > 16) {
-        return PQHIP_EUNSUPPORTED;
-    } else {
-        const void* kern = IP ? (const void*)k_adc_ip_search_masked_u8<NV, NQ, L> : (const void*)k_adc_search_masked_u8<NV, NQ, L>;
-        HIPCHK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        if constexpr (IP) {
-            hipLaunchKernelGGL((k_adc_ip_search_masked_u8<NV, NQ, L>), dim3(a.grid), dim3(1024), lds, a.st, codes, a.n, a.c_rs,
-                               a.allow, lut, a.scales, a.M, a.K, a.k, a.rows_per_wg, a.part_k, a.part_i, a.err);
-            note_kernel(NQ == 8 ? "k_adc_ip_search_masked_u8_mq<8 queries>"
-                                : NQ == 4 ? "k_adc_ip_search_masked_u8_mq<4 queries>" : "k_adc_ip_search_masked_u8");
-        } else {
-            hipLaunchKernelGGL((k_adc_search_masked_u8<NV, NQ, L>), dim3(a.grid), dim3(1024), lds, a.st, codes, a.n, a.c_rs,
-                               a.allow, lut, a.M, a.K, a.k, a.rows_per_wg, a.part_k, a.part_i, a.err);
-            note_kernel(NQ == 8 ? "k_adc_search_masked_u8_mq<8 queries>"
-                                : NQ == 4 ? "k_adc_search_masked_u8_mq<4 queries>" : "k_adc_search_masked_u8");
-        }
-        return PQHIP_OK;
-    }
-}
-
-template <bool IP, int NQ, int L>
-int32_t launch_search_masked_nv(int nvb, const SearchLaunch& a, const uint8_t* codes, const float* lut, size_t lds)
-{
-    switch (nvb) {
-    case 1: return launch_search_masked<IP, 1, NQ, L>(a, codes, lut, lds);
-    case 2: return launch_search_masked<IP, 2, NQ, L>(a, codes, lut, lds);
-    case 4: return launch_search_masked<IP, 4, NQ, L>(a, codes, lut, lds);
-    case 8: return launch_search_masked<IP, 8, NQ, L>(a, codes, lut, lds);
-    case 13: return launch_search_masked<IP, 13, NQ, L>(a, codes, lut, lds);
-    case kAdcMaxValueWords: return launch_search_masked<IP, kAdcMaxValueWords, NQ, L>(a, codes, lut, lds);
-    default: return PQHIP_EUNSUPPORTED;
-    }
-}
-
-template <bool IP, int NQ>
-int32_t launch_search_masked_l(int L, int nvb, const SearchLaunch& a, const uint8_t* codes, const float* lut, size_t lds)
-{
-    switch (L) {
-    case 1: return launch_search_masked_nv<IP, NQ, 1>(nvb, a, codes, lut, lds);
-    case 2: return launch_search_masked_nv<IP, NQ, 2>(nvb, a, codes, lut, lds);
-    case 4: return launch_search_masked_nv<IP, NQ, 4>(nvb, a, codes, lut, lds);
-    case 8: return launch_search_masked_nv<IP, NQ, 8>(nvb, a, codes, lut, lds);
-    case 16: return launch_search_masked_nv<IP, NQ, 16>(nvb, a, codes, lut, lds);
-    default: return PQHIP_EUNSUPPORTED;
-    }
-}
-
-template <bool IP>
-int32_t launch_search_masked_q(int nq_pass, int L, int nvb, const SearchLaunch& a, const uint8_t* codes, const float* lut, size_t lds)
-{
-    switch (nq_pass) {
-    case 8: return launch_search_masked_l<IP, 8>(L, nvb, a, codes, lut, lds);
-    case 4: return launch_search_masked_l<IP, 4>(L, nvb, a, codes, lut, lds);
-    case 1: return launch_search_masked_l<IP, 1>(L, nvb, a, codes, lut, lds);
-    default: return PQHIP_EUNSUPPORTED;
-    }
-}
-
-int32_t launch_search_masked_u8(bool ip, int nq_pass, int L, int nvb, const SearchLaunch& a, const uint8_t* codes,
-                                const float* lut, size_t lds)
-{
-    return ip ? launch_search_masked_q<true>(nq_pass, L, nvb, a, codes, lut, lds)
-              : launch_search_masked_q<false>(nq_pass, L, nvb, a, codes, lut, lds);
-}
-
-template <bool IP, int NV, int L>
-int32_t launch_lists_masked(const ListsLaunch& a, const uint8_t* codes, const float* lut, size_t lds)
-{
-    if (a.bias) {   // the residual producer
-        HIPCHK(hipFuncSetAttribute((const void*)k_adc_search_lists_residual_masked_u8<IP, NV, L>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        hipLaunchKernelGGL((k_adc_search_lists_residual_masked_u8<IP, NV, L>), dim3(a.G, a.nq), dim3(1024), lds, a.st, codes, a.n,
-                           a.c_rs, a.allow, lut, a.bias, a.b_rs, a.scales, a.M, a.K, a.k, a.seg_begin, a.seg_cum, a.n_probe,
-                           a.part_k, a.part_i, a.err);
-        note_kernel(IP ? "k_adc_ip_search_lists_residual_masked_u8" : "k_adc_search_lists_residual_masked_u8");
-        return PQHIP_OK;
-    }
-    HIPCHK(hipFuncSetAttribute((const void*)k_adc_search_lists_masked_u8<IP, NV, L>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    hipLaunchKernelGGL((k_adc_search_lists_masked_u8<IP, NV, L>), dim3(a.G, a.nq), dim3(1024), lds, a.st, codes, a.n, a.c_rs,
-                       a.allow, lut, a.scales, a.M, a.K, a.k, a.seg_begin, a.seg_cum, a.n_probe, a.part_k, a.part_i, a.err);
-    note_kernel(IP ? "k_adc_ip_search_lists_masked_u8" : "k_adc_search_lists_masked_u8");
-    return PQHIP_OK;
-}
-
-template <bool IP, int L>
-int32_t launch_lists_masked_nv(int nvb, const ListsLaunch& a, const uint8_t* codes, const float* lut, size_t lds)
-{
-    switch (nvb) {
-    case 4: return launch_lists_masked<IP, 4, L>(a, codes, lut, lds);
-    case 8: return launch_lists_masked<IP, 8, L>(a, codes, lut, lds);
-    case 13: return launch_lists_masked<IP, 13, L>(a, codes, lut, lds);
-    case kAdcMaxValueWords: return launch_lists_masked<IP, kAdcMaxValueWords, L>(a, codes, lut, lds);
-    default: return PQHIP_EUNSUPPORTED;
-    }
-}
-
-template <bool IP>
-int32_t launch_lists_masked_l(int L, int nvb, const ListsLaunch& a, const uint8_t* codes, const float* lut, size_t lds)
-{
-    switch (L) {
-    case 1: return launch_lists_masked_nv<IP, 1>(nvb, a, codes, lut, lds);
-    case 2: return launch_lists_masked_nv<IP, 2>(nvb, a, codes, lut, lds);
-    case 4: return launch_lists_masked_nv<IP, 4>(nvb, a, codes, lut, lds);
-    case 8: return launch_lists_masked_nv<IP, 8>(nvb, a, codes, lut, lds);
-    case 16: return launch_lists_masked_nv<IP, 16>(nvb, a, codes, lut, lds);
-    default: return PQHIP_EUNSUPPORTED;
-    }
-}
-
-int32_t launch_lists_masked_u8(bool ip, int L, int nvb, const ListsLaunch& a, const uint8_t* codes, const float* lut, size_t lds)
-{
-    return ip ? launch_lists_masked_l<true>(L, nvb, a, codes, lut, lds) : launch_lists_masked_l<false>(L, nvb, a, codes, lut, lds);
-}
-
-}  // namespace pqh
 
 using namespace pqh;
 
 extern "C" {
 
 // In all six: d_allow == NULL is the unmasked call itself.
-static RowMask row_mask(const uint32_t* d_allow) { return RowMask{d_allow, launch_search_masked_u8, launch_lists_masked_u8}; }
+static RowMask row_mask(const uint32_t* d_allow) { return RowMask{d_allow, launch_search_u8<true>, launch_lists_u8<true>}; }
 
 int32_t pqhip_adc_search_masked_f32_dev(pqhip_codebook* cb, int32_t slot, const float* d_tables, int64_t nq, const void* d_codes,
                                         int32_t code_bytes, int64_t n, int64_t c_rs, const uint32_t* d_allow, int32_t k,

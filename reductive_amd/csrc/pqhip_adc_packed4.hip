@@ -1,8 +1,7 @@
 // pqhip_adc_packed4.hip -- 4-bit packed codes (include/pqhip.h: pqhip_pack_codes4_dev, pqhip_unpack_codes4_dev and the
-// six pqhip_adc_*search*_packed4_f32_dev).  The unit holds the entry points, the policy of the packed searches -- the
-// choices of adc_search / adc_search_lists of pqhip_adc.hip restated for packed rows: queries per pass, list length,
-// grid, scratch, the plan and the merge, which it reaches through adc_search_launch.h -- and the instantiations of the
-// exhaustive producers and of the pack / unpack kernels (kernels_adc_packed4.hip.h).  The list producers are
+// six pqhip_adc_*search*_packed4_f32_dev).  The unit holds the entry points, the route on which the packed searches
+// enter the drivers of pqhip_adc.hip (adc_search_launch.h: the policy of a search is theirs), and the instantiations of
+// the exhaustive producers and of the pack / unpack kernels (kernels_adc_packed4.hip.h).  The list producers are
 // instantiated in pqhip_adc_packed4_lists.hip.  Nothing in pqhip_adc.hip refers to this unit.
 #include "adc_search_launch.h"
 
@@ -44,109 +43,45 @@ int32_t launch_search_p4(const SearchLaunch& a, const uint8_t* packed, const flo
     }
 }
 
-template <bool IP, int NQ, int L>
-int32_t launch_search_p4_nv(int nvb, const SearchLaunch& a, const uint8_t* packed, const float* lut, size_t lds)
+int32_t launch_search_packed4(bool ip, int nq_pass, int L, int nvb, const SearchLaunch& a, const void* packed, const float* lut,
+                              size_t lds)
 {
-    switch (nvb) {
-    case 1: return launch_search_p4<IP, 1, NQ, L>(a, packed, lut, lds);
-    case 2: return launch_search_p4<IP, 2, NQ, L>(a, packed, lut, lds);
-    case 4: return launch_search_p4<IP, 4, NQ, L>(a, packed, lut, lds);
-    case 8: return launch_search_p4<IP, 8, NQ, L>(a, packed, lut, lds);
-    case kPacked4MaxValueWords: return launch_search_p4<IP, kPacked4MaxValueWords, NQ, L>(a, packed, lut, lds);
-    default: return PQHIP_EUNSUPPORTED;
-    }
+    return dispatch_int<0, 1>(ip, [&](auto ip_c) {
+        return dispatch_queries_per_pass(nq_pass, [&](auto nq_c) {
+            return dispatch_list_regs(L, [&](auto l_c) {
+                return dispatch_int<1, 2, 4, 8, kPacked4MaxValueWords>(nvb, [&](auto nv_c) {
+                    return launch_search_p4<decltype(ip_c)::value != 0, decltype(nv_c)::value, decltype(nq_c)::value,
+                                            decltype(l_c)::value>(a, (const uint8_t*)packed, lut, lds);
+                });
+            });
+        });
+    });
 }
 
-template <bool IP, int NQ>
-int32_t launch_search_p4_l(int L, int nvb, const SearchLaunch& a, const uint8_t* packed, const float* lut, size_t lds)
+// The packed searches enter the drivers of pqhip_adc.hip with their own routes: rows of PB = ceil(M / 2) bytes, a table
+// image of M x 16 entries per query whatever K is (kernels_adc_packed4.hip.h) -- which is what the queries per pass are
+// chosen from -- packed dwords per row, and the packed producers.  First the checks that need the format, in the order
+// of every search: EINVAL (the caller's `bad_args`: negative counts), ENODEV, EUNSUPPORTED.
+static int32_t packed4_checks(const pqhip_codebook* cb, int32_t slot, bool bad_args, int32_t k)
 {
-    switch (L) {
-    case 1: return launch_search_p4_nv<IP, NQ, 1>(nvb, a, packed, lut, lds);
-    case 2: return launch_search_p4_nv<IP, NQ, 2>(nvb, a, packed, lut, lds);
-    case 4: return launch_search_p4_nv<IP, NQ, 4>(nvb, a, packed, lut, lds);
-    case 8: return launch_search_p4_nv<IP, NQ, 8>(nvb, a, packed, lut, lds);
-    case 16: return launch_search_p4_nv<IP, NQ, 16>(nvb, a, packed, lut, lds);
-    default: return PQHIP_EUNSUPPORTED;
-    }
+    if (!cb || bad_args) return PQHIP_EINVAL;
+    if (slot < 0 || slot >= (int)cb->dev.size()) return PQHIP_ENODEV;
+    if (cb->K > 16 || cb->M > 100 || k > kSearchMaxK) return PQHIP_EUNSUPPORTED;
+    return PQHIP_OK;
 }
 
-template <bool IP>
-int32_t launch_search_p4_q(int nqp, int L, int nvb, const SearchLaunch& a, const uint8_t* packed, const float* lut, size_t lds)
-{
-    switch (nqp) {
-    case 8: return launch_search_p4_l<IP, 8>(L, nvb, a, packed, lut, lds);
-    case 4: return launch_search_p4_l<IP, 4>(L, nvb, a, packed, lut, lds);
-    case 1: return launch_search_p4_l<IP, 1>(L, nvb, a, packed, lut, lds);
-    default: return PQHIP_EUNSUPPORTED;
-    }
-}
-
-// The exhaustive packed searches: adc_search's policy on its u8 route.  The table image in LDS is M x 16 entries per
-// query whatever K is (kernels_adc_packed4.hip.h), which is what the queries per pass are chosen from.
+// Option "adc_packed4_wgs" forces the number of producer workgroups.
 static int32_t adc_search_packed4(bool ip, pqhip_codebook* cb, int32_t slot, const float* d_tables, int64_t nq, const uint8_t* d_packed,
                                   int64_t n, int64_t c_rs, const uint32_t* d_allow, const float* d_scales, int32_t k, float* d_val,
                                   int64_t v_rs, int64_t* d_idx, int64_t i_rs, void* stream)
 {
-    if (!cb || nq < 0 || n < 0 || k < 1) return PQHIP_EINVAL;
-    if (slot < 0 || slot >= (int)cb->dev.size()) return PQHIP_ENODEV;
-    if (cb->K > 16 || cb->M > 100 || k > kSearchMaxK) return PQHIP_EUNSUPPORTED;
-    if (nq == 0) return PQHIP_OK;
-    if (!d_val || !d_idx || (n > 0 && (!d_tables || !d_packed))) return PQHIP_EINVAL;
-    const int M = (int)cb->M, K = (int)cb->K, PB = (M + 1) / 2;
-    if ((n > 0 && c_rs < PB) || v_rs < k || i_rs < k) return PQHIP_ESHAPE;
-    SET_DEVICE(cb->ctx->devs[slot]->ordinal);
-    hipStream_t st = (hipStream_t)stream;
-    const int L = search_list_regs(k);
-    if (n == 0) {      // padding only
-        for (int64_t q = 0; q < nq; q += 65535) {
-            const int nqp = (int)std::min<int64_t>(nq - q, 65535);
-            PQCHK(adc_search_merge(ip, L, nqp, 0, k, nullptr, nullptr, d_val + q * v_rs, v_rs, d_idx + q * i_rs, i_rs, st));
-            HIPCHK(hipGetLastError());
-        }
-        return PQHIP_OK;
-    }
-    ErrFlag ef(cb, slot, st);
-    const size_t table = (size_t)M * 16 * sizeof(float);
-    const int nvb = packed4_nv_bucket((PB + 3) / 4);
-    const bool mq_on = cb->ctx->opt.adc_single_query.load(std::memory_order_relaxed) == 0;
-    int nqp_first = 1;
-    if (mq_on) {
-        for (int c : {8, 4}) {
-            if (c * L <= 16 && search_lds(table * c, c, L) <= 160 * 1024 && nq >= c) { nqp_first = c; break; }
-        }
-    }
-    // one 1,024-thread workgroup per CU over a contiguous row range, at least 4,096 rows each; option "adc_packed4_wgs"
-    // forces the number of workgroups (rows per workgroup stay a multiple of 1,024: a wave's rows share two mask words)
-    const int64_t forced = cb->ctx->opt.adc_packed4_wgs.load(std::memory_order_relaxed);
-    const int64_t wgs = forced > 0 ? std::min<int64_t>(forced, 65536) : cb->ctx->devs[slot]->n_cus;
-    int64_t rows_per_wg = round_up((n + wgs - 1) / wgs, 1024);
-    if (forced <= 0) rows_per_wg = std::max<int64_t>(rows_per_wg, 4096);
-    rows_per_wg = std::min<int64_t>(rows_per_wg, (int64_t)1 << 30);
-    const int64_t grid = (n + rows_per_wg - 1) / rows_per_wg;
-    const size_t list_entries = (size_t)nqp_first * grid * 64 * L;
-    ScratchLease part(cb, slot, st);
-    PQCHK(part.acquire(list_entries * (sizeof(unsigned) + sizeof(uint64_t))));
-    uint64_t* part_i = (uint64_t*)part.ptr();
-    unsigned* part_k = (unsigned*)(part_i + list_entries);
-    SearchLaunch a{n, c_rs, rows_per_wg, (unsigned)grid, M, K, k, ip ? d_scales : nullptr, part_k, part_i, ef.flag, st, d_allow};
-    int64_t q = 0;
-    for (int nqp : {8, 4, 1}) {
-        if (nqp > nqp_first) continue;
-        if (nqp == 4 && !(mq_on && 4 * L <= 16 && search_lds(table * 4, 4, L) <= 160 * 1024)) continue;
-        for (; q + nqp <= nq; q += nqp) {
-            const float* lut = d_tables + q * (int64_t)M * K;
-            const size_t lds = search_lds(table * nqp, nqp, L);
-            if (ip) PQCHK(launch_search_p4_q<true>(nqp, L, nvb, a, d_packed, lut, lds));
-            else PQCHK(launch_search_p4_q<false>(nqp, L, nvb, a, d_packed, lut, lds));
-            HIPCHK(hipGetLastError());
-            PQCHK(adc_search_merge(ip, L, nqp, (int)grid, k, part_k, part_i, d_val + q * v_rs, v_rs, d_idx + q * i_rs, i_rs, st));
-            HIPCHK(hipGetLastError());
-        }
-    }
-    return PQHIP_OK;
+    PQCHK(packed4_checks(cb, slot, nq < 0 || n < 0 || k < 1, k));
+    const int PB = ((int)cb->M + 1) / 2;
+    const SearchRoute r{PB, (size_t)cb->M * 16 * sizeof(float), packed4_nv_bucket((PB + 3) / 4), true,
+                        cb->ctx->opt.adc_packed4_wgs.load(std::memory_order_relaxed), launch_search_packed4};
+    return adc_search_run(ip, cb, slot, r, d_tables, nq, d_packed, n, c_rs, d_allow, d_scales, k, d_val, v_rs, d_idx, i_rs, stream);
 }
 
-// The packed list searches: adc_search_lists' checks, plan, chunking and merge around the packed producer.
 // res != null: the residual searches; d_scales then holds the row terms of the distance search (required).
 static int32_t adc_search_lists_packed4(bool ip, pqhip_codebook* cb, int32_t slot, const float* d_tables, int64_t nq,
                                         const uint8_t* d_packed, int64_t n, int64_t c_rs, const uint32_t* d_allow,
@@ -154,57 +89,11 @@ static int32_t adc_search_lists_packed4(bool ip, pqhip_codebook* cb, int32_t slo
                                         int64_t p_rs, const float* d_scales, int32_t k, float* d_val, int64_t v_rs, int64_t* d_idx,
                                         int64_t i_rs, void* stream, const ListsResidual* res)
 {
-    if (!cb || nq < 0 || n < 0 || k < 1 || n_lists < 0 || n_probe < 1) return PQHIP_EINVAL;
-    if (slot < 0 || slot >= (int)cb->dev.size()) return PQHIP_ENODEV;
-    if (cb->K > 16 || cb->M > 100 || k > kSearchMaxK) return PQHIP_EUNSUPPORTED;
-    const int M = (int)cb->M, K = (int)cb->K, PB = (M + 1) / 2;
-    const int L = search_list_regs(k);
-    if (n > (int64_t)0xfffffffell) return PQHIP_EUNSUPPORTED;                          // positions are offered as 32-bit values
-    const size_t plan_q = ((size_t)n_probe * 2 + 1) * sizeof(int64_t);
-    if (plan_q > kListsScratchBytes / 2) return PQHIP_EUNSUPPORTED;
-    if (nq == 0) return PQHIP_OK;
-    if (!d_val || !d_idx || !d_list_off || !d_probes || (n > 0 && (!d_tables || !d_packed))) return PQHIP_EINVAL;
-    if (res && (!res->bias || (!ip && !d_scales))) return PQHIP_EINVAL;
-    if ((n > 0 && c_rs < PB) || v_rs < k || i_rs < k || p_rs < n_probe) return PQHIP_ESHAPE;
-    if (res && res->b_rs < n_probe) return PQHIP_ESHAPE;
-    SET_DEVICE(cb->ctx->devs[slot]->ordinal);
-    hipStream_t st = (hipStream_t)stream;
-    if (n == 0 || n_lists == 0) {      // padding only
-        for (int64_t q = 0; q < nq; q += 65535) {
-            const int nqp = (int)std::min<int64_t>(nq - q, 65535);
-            PQCHK(adc_search_merge(ip, L, nqp, 0, k, nullptr, nullptr, d_val + q * v_rs, v_rs, d_idx + q * i_rs, i_rs, st));
-            HIPCHK(hipGetLastError());
-        }
-        return PQHIP_OK;
-    }
-    ErrFlag ef(cb, slot, st);
-    const size_t table = (size_t)M * 16 * sizeof(float);
-    const int nvb = packed4_lists_nv_bucket((PB + 3) / 4);
-    const int64_t forced = cb->ctx->opt.adc_lists_wgs_per_query.load(std::memory_order_relaxed);
-    const int64_t G = forced > 0 ? std::min<int64_t>(forced, 4096)
-                                 : lists_wgs_per_query(n, n_lists, n_probe, std::min<int64_t>(nq, 65535), cb->ctx->devs[slot]->n_cus);
-    const size_t lists_q = (size_t)G * 64 * L * (sizeof(unsigned) + sizeof(uint64_t));
-    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>({nq, (int64_t)65535, (int64_t)(kListsScratchBytes / (plan_q + lists_q))}));
-    ScratchLease lease(cb, slot, st);
-    PQCHK(lease.acquire((size_t)chunk * (plan_q + lists_q)));
-    // 8-byte items first: part_i [chunk][G][64 L], seg_begin [chunk][n_probe], seg_cum [chunk][n_probe + 1]; then the keys
-    uint64_t* part_i = (uint64_t*)lease.ptr();
-    int64_t* seg_begin = (int64_t*)(part_i + (size_t)chunk * G * 64 * L);
-    int64_t* seg_cum = seg_begin + (size_t)chunk * n_probe;
-    unsigned* part_k = (unsigned*)(seg_cum + (size_t)chunk * ((size_t)n_probe + 1));
-    const size_t lds = search_lds(table, 1, L);
-    for (int64_t q = 0; q < nq; q += chunk) {
-        const unsigned nqc = (unsigned)std::min<int64_t>(chunk, nq - q);
-        PQCHK(launch_lists_plan(d_list_off, n_lists, d_probes + q * p_rs, (int)n_probe, p_rs, n, seg_begin, seg_cum, nqc, ef.flag, st));
-        ListsLaunch a{n, c_rs, (unsigned)G, nqc, M, K, k, (int)n_probe, (ip || res) ? d_scales : nullptr,
-                      res ? res->bias + q * res->b_rs : nullptr, res ? res->b_rs : 0, seg_begin, seg_cum, part_k, part_i, ef.flag, st,
-                      d_allow};
-        PQCHK(launch_lists_packed4(ip, L, nvb, a, d_packed, d_tables + q * (int64_t)M * K, lds));
-        HIPCHK(hipGetLastError());
-        PQCHK(adc_search_merge(ip, L, (int)nqc, (int)G, k, part_k, part_i, d_val + q * v_rs, v_rs, d_idx + q * i_rs, i_rs, st));
-        HIPCHK(hipGetLastError());
-    }
-    return PQHIP_OK;
+    PQCHK(packed4_checks(cb, slot, nq < 0 || n < 0 || k < 1 || n_lists < 0 || n_probe < 1, k));
+    const int PB = ((int)cb->M + 1) / 2;
+    const ListsRoute r{PB, (size_t)cb->M * 16 * sizeof(float), packed4_lists_nv_bucket((PB + 3) / 4), launch_lists_packed4};
+    return adc_search_lists_run(ip, cb, slot, r, d_tables, nq, d_packed, n, c_rs, d_allow, d_list_off, n_lists, d_probes, n_probe, p_rs,
+                                d_scales, k, d_val, v_rs, d_idx, i_rs, stream, res);
 }
 
 // one lane per aligned dword of the span [p, p + bytes)

@@ -22,33 +22,16 @@ int32_t launch_lists_p4(const ListsLaunch& a, const uint8_t* packed, const float
     return PQHIP_OK;
 }
 
-template <bool IP, int L>
-int32_t launch_lists_p4_nv(int nvb, const ListsLaunch& a, const uint8_t* packed, const float* lut, size_t lds)
+int32_t launch_lists_packed4(bool ip, int L, int nvb, const ListsLaunch& a, const void* packed, const float* lut, size_t lds)
 {
-    switch (nvb) {
-    case 2: return launch_lists_p4<IP, 2, L>(a, packed, lut, lds);
-    case 8: return launch_lists_p4<IP, 8, L>(a, packed, lut, lds);
-    case kPacked4MaxValueWords: return launch_lists_p4<IP, kPacked4MaxValueWords, L>(a, packed, lut, lds);
-    default: return PQHIP_EUNSUPPORTED;
-    }
-}
-
-template <bool IP>
-int32_t launch_lists_p4_l(int L, int nvb, const ListsLaunch& a, const uint8_t* packed, const float* lut, size_t lds)
-{
-    switch (L) {
-    case 1: return launch_lists_p4_nv<IP, 1>(nvb, a, packed, lut, lds);
-    case 2: return launch_lists_p4_nv<IP, 2>(nvb, a, packed, lut, lds);
-    case 4: return launch_lists_p4_nv<IP, 4>(nvb, a, packed, lut, lds);
-    case 8: return launch_lists_p4_nv<IP, 8>(nvb, a, packed, lut, lds);
-    case 16: return launch_lists_p4_nv<IP, 16>(nvb, a, packed, lut, lds);
-    default: return PQHIP_EUNSUPPORTED;
-    }
-}
-
-int32_t launch_lists_packed4(bool ip, int L, int nvb, const ListsLaunch& a, const uint8_t* packed, const float* lut, size_t lds)
-{
-    return ip ? launch_lists_p4_l<true>(L, nvb, a, packed, lut, lds) : launch_lists_p4_l<false>(L, nvb, a, packed, lut, lds);
+    return dispatch_int<0, 1>(ip, [&](auto ip_c) {
+        return dispatch_list_regs(L, [&](auto l_c) {
+            return dispatch_int<2, 8, kPacked4MaxValueWords>(nvb, [&](auto nv_c) {
+                return launch_lists_p4<decltype(ip_c)::value != 0, decltype(nv_c)::value, decltype(l_c)::value>(
+                    a, (const uint8_t*)packed, lut, lds);
+            });
+        });
+    });
 }
 
 }  // namespace pqh

@@ -39,29 +39,15 @@ int32_t launch_range(const RangeLaunch& a, const uint8_t* codes, const float* lu
     return PQHIP_OK;
 }
 
-template <bool IP, int NQ>
-int32_t launch_range_nv(int nvb, const RangeLaunch& a, const uint8_t* codes, const float* lut, size_t lds, int fill)
+int32_t launch_range_u8(bool ip, int nq_pass, int nvb, const RangeLaunch& a, const uint8_t* codes, const float* lut, size_t lds, int fill)
 {
-    switch (nvb) {
-    case 1: return launch_range<IP, 1, NQ>(a, codes, lut, lds, fill);
-    case 2: return launch_range<IP, 2, NQ>(a, codes, lut, lds, fill);
-    case 4: return launch_range<IP, 4, NQ>(a, codes, lut, lds, fill);
-    case 8: return launch_range<IP, 8, NQ>(a, codes, lut, lds, fill);
-    case 13: return launch_range<IP, 13, NQ>(a, codes, lut, lds, fill);
-    case kAdcMaxValueWords: return launch_range<IP, kAdcMaxValueWords, NQ>(a, codes, lut, lds, fill);
-    default: return PQHIP_EUNSUPPORTED;
-    }
-}
-
-template <bool IP>
-int32_t launch_range_q(int nqp, int nvb, const RangeLaunch& a, const uint8_t* codes, const float* lut, size_t lds, int fill)
-{
-    switch (nqp) {
-    case 8: return launch_range_nv<IP, 8>(nvb, a, codes, lut, lds, fill);
-    case 4: return launch_range_nv<IP, 4>(nvb, a, codes, lut, lds, fill);
-    case 1: return launch_range_nv<IP, 1>(nvb, a, codes, lut, lds, fill);
-    default: return PQHIP_EUNSUPPORTED;
-    }
+    return dispatch_int<0, 1>(ip, [&](auto ip_c) {
+        return dispatch_queries_per_pass(nq_pass, [&](auto nq_c) {
+            return dispatch_int<1, 2, 4, 8, 13, kAdcMaxValueWords>(nvb, [&](auto nv_c) {
+                return launch_range<decltype(ip_c)::value != 0, decltype(nv_c)::value, decltype(nq_c)::value>(a, codes, lut, lds, fill);
+            });
+        });
+    });
 }
 
 constexpr int64_t kRangeScanMax = 1 << 20;   // partial counts of one pass / chunk of queries: what one scan launch sums
@@ -133,11 +119,11 @@ int32_t adc_range(pqhip_codebook* cb, int32_t slot, const float* d_tables, int64
         for (; q + nqp <= nq; q += nqp) {
             const float* lut = d_tables + q * (int64_t)M * K;
             a.thr = d_thr + q;
-            PQCHK((launch_range_q<IP>(nqp, nvb, a, (const uint8_t*)d_codes, lut, table * nqp, 0)));
+            PQCHK((launch_range_u8(IP, nqp, nvb, a, (const uint8_t*)d_codes, lut, table * nqp, 0)));
             HIPCHK(hipGetLastError());
             PQCHK(launch_range_scan(a.part, units, nqp, d_lims + q, st));
             if (capacity > 0) {     // capacity == 0: a pure count call
-                PQCHK((launch_range_q<IP>(nqp, nvb, a, (const uint8_t*)d_codes, lut, table * nqp, 1)));
+                PQCHK((launch_range_u8(IP, nqp, nvb, a, (const uint8_t*)d_codes, lut, table * nqp, 1)));
                 HIPCHK(hipGetLastError());
             }
         }
@@ -175,27 +161,13 @@ int32_t launch_range_lists(const RangeListsLaunch& a, const uint8_t* codes, cons
     return PQHIP_OK;
 }
 
-template <int POL>
-int32_t launch_range_lists_nv(int nvb, const RangeListsLaunch& a, const uint8_t* codes, const float* lut, size_t lds, int fill)
-{
-    switch (nvb) {
-    case 4: return launch_range_lists<POL, 4>(a, codes, lut, lds, fill);
-    case 8: return launch_range_lists<POL, 8>(a, codes, lut, lds, fill);
-    case 13: return launch_range_lists<POL, 13>(a, codes, lut, lds, fill);
-    case kAdcMaxValueWords: return launch_range_lists<POL, kAdcMaxValueWords>(a, codes, lut, lds, fill);
-    default: return PQHIP_EUNSUPPORTED;
-    }
-}
-
 int32_t launch_range_lists_p(int pol, int nvb, const RangeListsLaunch& a, const uint8_t* codes, const float* lut, size_t lds, int fill)
 {
-    switch (pol) {
-    case kRangeL2: return launch_range_lists_nv<kRangeL2>(nvb, a, codes, lut, lds, fill);
-    case kRangeIP: return launch_range_lists_nv<kRangeIP>(nvb, a, codes, lut, lds, fill);
-    case kRangeResL2: return launch_range_lists_nv<kRangeResL2>(nvb, a, codes, lut, lds, fill);
-    case kRangeResIP: return launch_range_lists_nv<kRangeResIP>(nvb, a, codes, lut, lds, fill);
-    default: return PQHIP_EUNSUPPORTED;
-    }
+    return dispatch_int<kRangeL2, kRangeIP, kRangeResL2, kRangeResIP>(pol, [&](auto pol_c) {
+        return dispatch_int<4, 8, 13, kAdcMaxValueWords>(nvb, [&](auto nv_c) {
+            return launch_range_lists<decltype(pol_c)::value, decltype(nv_c)::value>(a, codes, lut, lds, fill);
+        });
+    });
 }
 
 // All four list range calls: the checks of adc_search_lists, its plan kernel (unchanged: the only reader of the offsets
