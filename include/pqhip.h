@@ -184,6 +184,9 @@ int32_t pqhip_adc_scan_f32_dev(pqhip_codebook *cb, int32_t device_slot, const fl
  * A code >= K reads entry 0 and raises the stream's range flag (pqhip_check_codes_dev -> PQHIP_ECODE_RANGE).
  * Asynchronous on `stream`; per-workgroup partial lists live in the codebook's scratch, the caller allocates only the
  * outputs.
+ * Host policy: one producer workgroup per CU with at least 4,096 rows each; option "adc_search_wgs" forces the number of
+ * producer workgroups of this call, of pqhip_adc_ip_search_f32_dev and of their _masked forms (rows per workgroup stay a
+ * multiple of 1,024).  The results do not depend on it.
  */
 int32_t pqhip_adc_search_f32_dev(pqhip_codebook *cb, int32_t device_slot, const float *d_tables, int64_t n_queries,
                                  const void *d_codes, int32_t code_bytes, int64_t n_codes, int64_t codes_row_stride,
@@ -820,6 +823,8 @@ int32_t pqhip_set_rotation_variant(int32_t variant);
  *                          so that the one-workgroup prefix scan of a pass sums at most 2^20 counts)
  *   "adc_range_wgs_per_query"  workgroups that share one query of the list range searches (0 = chosen from the shape; at
  *                          most 4096, as "adc_lists_wgs_per_query")
+ *   "adc_search_wgs"       producer workgroups of the exhaustive searches over 1- and 4-byte codes, masked or not (0 = one
+ *                          per CU with at least 4,096 rows; at most 65536; rows per workgroup stay a multiple of 1,024)
  *   "adc_packed4_wgs"      producer workgroups of the exhaustive searches over 4-bit packed codes (0 = chosen from the shape,
  *                          as for the u8 searches; at most 65536; rows per workgroup stay a multiple of 1,024)
  *   "lists_merge_wgs"      workgroups of the mover of pqhip_lists_merge_dev (0 = chosen from the size and the CU count; at

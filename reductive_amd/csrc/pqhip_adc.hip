@@ -223,6 +223,7 @@ int32_t adc_search_run(bool ip, pqhip_codebook* cb, int32_t slot, const SearchRo
 // The exhaustive searches over u8 / 32-bit codes: the u8 producer when the codes are bytes and the table fits LDS beside
 // the queues, else the generic kernel.  mask != null: the masked producer in the place of the u8 one; a call that the
 // u8 route does not serve (4-byte codes, a table beyond LDS) is PQHIP_EUNSUPPORTED -- never another path.
+// Option "adc_search_wgs" forces the number of producer workgroups, whichever producer runs.
 int32_t adc_search(bool ip, pqhip_codebook* cb, int32_t slot, const float* d_tables, int64_t nq, const void* d_codes, int32_t code_bytes,
                    int64_t n, int64_t c_rs, const float* d_scales, int32_t k, float* d_val, int64_t v_rs, int64_t* d_idx,
                    int64_t i_rs, void* stream, const RowMask* mask = nullptr)
@@ -236,7 +237,7 @@ int32_t adc_search(bool ip, pqhip_codebook* cb, int32_t slot, const float* d_tab
     if (mask && !fast) return PQHIP_EUNSUPPORTED;                   // a mask: the u8 route or nothing
     const SearchProducer producer = mask ? mask->search : fast ? launch_search_u8<false>
                                     : code_bytes == 1 ? launch_search_any<uint8_t> : launch_search_any<uint32_t>;
-    const SearchRoute r{cb->M, table, nvb, fast, 0, producer};
+    const SearchRoute r{cb->M, table, nvb, fast, cb->ctx->opt.adc_search_wgs.load(std::memory_order_relaxed), producer};
     return adc_search_run(ip, cb, slot, r, d_tables, nq, d_codes, n, c_rs, mask ? mask->words : nullptr, d_scales, k, d_val, v_rs, d_idx,
                           i_rs, stream);
 }

@@ -98,6 +98,7 @@ struct Options {
     std::atomic<int64_t> adc_range_wgs_per_query{0};   // list range searches: workgroups per query (0: chosen from the shape)
     std::atomic<int64_t> lists_merge_wgs{0};        // list merge: workgroups of the mover (0: chosen from the size)
     std::atomic<int64_t> adc_packed4_wgs{0};        // exhaustive searches over 4-bit packed codes: producer workgroups (0: chosen from the shape)
+    std::atomic<int64_t> adc_search_wgs{0};         // exhaustive u8 / masked / generic searches: producer workgroups (0: chosen from the shape)
     std::atomic<int64_t> lists_layout_wgs{0};       // list layout: workgroups, one row slice each (0: chosen from the size)
 };
 

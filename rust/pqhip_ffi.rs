@@ -82,7 +82,8 @@ extern "C" {
         d_probe_bias: *const f32, bias_row_stride: i64, d_scales: *const f32, k: i32, d_score: *mut f32,
         score_row_stride: i64, d_idx: *mut i64, idx_row_stride: i64, stream: *mut c_void) -> i32;
     // the six searches restricted to an allowed set of rows: d_allow holds ceil(n_codes / 32) words in the row order of
-    // d_codes, bit i & 31 of word i >> 5 set = row i may be returned; NULL = the unmasked call itself
+    // d_codes, bit i & 31 of word i >> 5 set = row i may be returned; NULL = the unmasked call itself; option
+    // "adc_search_wgs" forces the producer workgroups of the two exhaustive calls, as of their unmasked forms
     pub fn pqhip_adc_search_masked_f32_dev(cb: *mut pqhip_codebook, device_slot: i32, d_tables: *const f32,
         n_queries: i64, d_codes: *const c_void, code_bytes: i32, n_codes: i64, codes_row_stride: i64,
         d_allow: *const u32, k: i32, d_dist: *mut f32, dist_row_stride: i64, d_idx: *mut i64, idx_row_stride: i64,
