@@ -14,13 +14,11 @@ import threading
 
 import numpy as np
 
-from . import _lib
+from . import _lib, _marshal
+from ._lib import PanicError
+from ._marshal import ptr_or_none, row_stride
 
 _INDEX_TYPES = (np.uint8, np.uint16, np.uint32, np.uint64)
-
-
-class PanicError(AssertionError):
-    """A Rust `panic!` / failed `assert!` of the reference surfaced as an exception."""
 
 
 class ReductiveError(ValueError):
@@ -33,18 +31,12 @@ _ctx_lock = threading.Lock()
 
 class _Ctx:
     def __init__(self, devices=None):
-        L = _lib.lib()
         h = ctypes.c_void_p()
-        if devices:
-            arr = (ctypes.c_int32 * len(devices))(*devices)
-            rc = L.pqhip_ctx_create(arr, len(devices), ctypes.byref(h))
-        else:
-            rc = L.pqhip_ctx_create(None, 0, ctypes.byref(h))
-        if rc != _lib.OK:
-            raise _lib.PqHipError(rc, "pqhip_ctx_create")
+        arr = (ctypes.c_int32 * len(devices))(*devices) if devices else None
+        _marshal.run("pqhip_ctx_create", arr, len(devices) if devices else 0, ctypes.byref(h))
         self.handle = h
         self.devices = list(devices) if devices else None
-        self.n_devices = L.pqhip_ctx_n_devices(h)
+        self.n_devices = _lib.lib().pqhip_ctx_n_devices(h)
 
     def close(self):
         if self.handle:
@@ -89,9 +81,8 @@ def vor2_tables(quantizers):
     if rc != _lib.OK:
         raise _lib.PqHipError(rc, "pqhip_vor2_tables_host")
     words = np.zeros(n.value, dtype=np.uint32)
-    rc = L.pqhip_vor2_tables_host(q.ctypes.data, M, K, dsub, words.ctypes.data, words.size, off.ctypes.data, ctypes.byref(n))
-    if rc != _lib.OK:
-        raise _lib.PqHipError(rc, "pqhip_vor2_tables_host")
+    _marshal.run("pqhip_vor2_tables_host", q.ctypes.data, M, K, dsub, words.ctypes.data, words.size, off.ctypes.data,
+                 ctypes.byref(n))
     return words, off
 
 
@@ -150,12 +141,8 @@ def cluster_assignments(centroids, instances, dtype=np.uint64, ctx=None):
     rs, cs = _estrides(x)
     ctx = ctx or default_ctx()
     fp = ctypes.POINTER(ctypes.c_float)
-    rc = _lib.lib().pqhip_cluster_assignments_f32(ctx.handle, centroids.ctypes.data_as(fp),
-                                                  centroids.shape[0], centroids.shape[1],
-                                                  x.ctypes.data, x.shape[0], rs, cs,
-                                                  out.ctypes.data, out.itemsize)
-    if rc != _lib.OK:
-        raise _lib.PqHipError(rc, "pqhip_cluster_assignments_f32")
+    _marshal.run("pqhip_cluster_assignments_f32", ctx.handle, centroids.ctypes.data_as(fp), centroids.shape[0],
+                 centroids.shape[1], x.ctypes.data, x.shape[0], rs, cs, out.ctypes.data, out.itemsize)
     return out
 
 
@@ -192,7 +179,7 @@ def kmeans_iterations(quantizers, instances, n_iterations=1, want_loss=True, ctx
         dev = x.device.index or 0
         slot = dev if ctx.devices is None else ctx.devices.index(dev)
         stream = torch.cuda.current_stream(x.device).cuda_stream
-        rs = x.stride(0) if x.shape[0] > 1 else max(x.stride(0), x.shape[1])
+        rs = row_stride(x, x.shape[0], x.shape[1])
         rc = L.pqhip_kmeans_iterations_f32_dev(ctx.handle, slot, q.ctypes.data_as(fp), M, K, dsub,
                                                x.data_ptr(), x.shape[0], rs, n_iterations, lp,
                                                ctypes.c_void_p(stream))
@@ -258,12 +245,10 @@ def at_dot_b(a, b, ctx=None):
     dev = a.device.index or 0
     slot = dev if ctx.devices is None else ctx.devices.index(dev)
     out = np.zeros((a.shape[1], b.shape[1]), np.float32)
-    rs = lambda t: t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
-    rc = _lib.lib().pqhip_at_dot_b_f32_dev(ctx.handle, slot, a.data_ptr(), rs(a), a.shape[1], b.data_ptr(), rs(b),
-                                           b.shape[1], a.shape[0], out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
-                                           ctypes.c_void_p(torch.cuda.current_stream(a.device).cuda_stream))
-    if rc != _lib.OK:
-        raise _lib.PqHipError(rc, "pqhip_at_dot_b_f32_dev")
+    rs = lambda t: row_stride(t, t.shape[0], t.shape[1])
+    _marshal.run("pqhip_at_dot_b_f32_dev", ctx.handle, slot, a.data_ptr(), rs(a), a.shape[1], b.data_ptr(), rs(b),
+                 b.shape[1], a.shape[0], out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+                 ctypes.c_void_p(torch.cuda.current_stream(a.device).cuda_stream))
     return out
 
 
@@ -292,12 +277,9 @@ def opq_train_step(quantizers, projection, instances, ctx=None):
     slot = dev if ctx.devices is None else ctx.devices.index(dev)
     cross = np.zeros((d, d), np.float32)
     fp = ctypes.POINTER(ctypes.c_float)
-    rc = _lib.lib().pqhip_opq_train_step_f32_dev(
-        ctx.handle, slot, q.ctypes.data_as(fp), M, K, dsub, P.ctypes.data_as(fp), x.data_ptr(), x.shape[0],
-        x.stride(0) if x.shape[0] > 1 else max(x.stride(0), d), cross.ctypes.data_as(fp),
-        ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
-    if rc != _lib.OK:
-        raise _lib.PqHipError(rc, "pqhip_opq_train_step_f32_dev")
+    _marshal.run("pqhip_opq_train_step_f32_dev", ctx.handle, slot, q.ctypes.data_as(fp), M, K, dsub, P.ctypes.data_as(fp),
+                 x.data_ptr(), x.shape[0], row_stride(x, x.shape[0], d), cross.ctypes.data_as(fp),
+                 ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
     return q, cross
 
 
@@ -347,9 +329,7 @@ def create_projection_matrix(instances, n_subquantizers):
 
 def set_rotation_variant(variant):
     """test knob (include/pqhip.h: pqhip_set_rotation_variant), process-wide: 0 auto, 8 / 9 force that rotation kernel."""
-    rc = _lib.lib().pqhip_set_rotation_variant(variant)
-    if rc != _lib.OK:
-        raise _lib.PqHipError(rc, "pqhip_set_rotation_variant")
+    _marshal.run("pqhip_set_rotation_variant", variant)
 
 
 def rotate(instances, projection, ctx=None):
@@ -368,12 +348,9 @@ def rotate(instances, projection, ctx=None):
     dev = x.device.index or 0
     slot = dev if ctx.devices is None else ctx.devices.index(dev)
     out = torch.empty((x.shape[0], d), dtype=torch.float32, device=x.device)
-    rc = _lib.lib().pqhip_rotate_f32_dev(ctx.handle, slot, x.data_ptr(), x.shape[0],
-                                         x.stride(0) if x.shape[0] > 1 else max(x.stride(0), d), d,
-                                         P.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), out.data_ptr(), d,
-                                         ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
-    if rc != _lib.OK:
-        raise _lib.PqHipError(rc, "pqhip_rotate_f32_dev")
+    _marshal.run("pqhip_rotate_f32_dev", ctx.handle, slot, x.data_ptr(), x.shape[0], row_stride(x, x.shape[0], d), d,
+                 P.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), out.data_ptr(), d,
+                 ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
     return out
 
 
@@ -518,16 +495,13 @@ class Pq:
     def _cb(self):
         with self._lock:
             if self._handle is None:
-                L = _lib.lib()
                 ctx = self._ctx or default_ctx()
                 M, K, dsub = self._quantizers.shape
                 fp = ctypes.POINTER(ctypes.c_float)
                 h = ctypes.c_void_p()
                 proj = self._projection.ctypes.data_as(fp) if self._projection is not None else None
-                rc = L.pqhip_codebook_create(ctx.handle, self._quantizers.ctypes.data_as(fp), M, K,
-                                             dsub, proj, ctypes.byref(h))
-                if rc != _lib.OK:
-                    raise _lib.PqHipError(rc, "pqhip_codebook_create")
+                _marshal.run("pqhip_codebook_create", ctx.handle, self._quantizers.ctypes.data_as(fp), M, K, dsub, proj,
+                             ctypes.byref(h))
                 self._handle = h
                 self._ctx = ctx
             return self._handle
@@ -679,12 +653,26 @@ class Pq:
         return rec.astype(np.float32)
 
     # ---- device-resident variants (torch tensors in HBM; used by bench.py and the GPU tests) ----
+    # Every wrapper below: normalise the arguments, allocate, call, optionally check the range flag, shape the result.
+    # The marshalling they share is reductive_amd/_marshal.py.
     def _slot_for(self, tensor):
         ctx = self._ctx or default_ctx()
         dev = tensor.device.index or 0
         if ctx.devices is None:
             return dev
         return ctx.devices.index(dev)
+
+    def _reconstructions(self, out, n, device):
+        """The float32 [n, d] output of the three reconstruct calls, allocated unless given."""
+        import torch
+        d = self.reconstructed_len()
+        if out is None:
+            out = torch.empty((n, d), dtype=torch.float32, device=device)
+        assert out.is_cuda and out.dtype == torch.float32 and out.stride(1) == 1
+        if tuple(out.shape) != (n, d):
+            raise PanicError("Reconstructions matrix has incorrect shape, expected: (%d, %d), got: (%d, %d)"
+                             % (n, d, out.shape[0], out.shape[1]))
+        return out, row_stride(out, n, d)
 
     def quantize_batch_device(self, x, out=None, stream=None):
         """x: CUDA float32 tensor [n, d] (unit column stride) -> codes tensor [n, M] (uint8; int32 when K > 256).
@@ -693,31 +681,21 @@ class Pq:
         assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2
         if x.shape[1] != self.reconstructed_len():
             raise PanicError("Quantizer and vector length mismatch")
-        if x.stride(1) != 1:
-            x = x.contiguous()
+        x = _marshal.unit_columns(x)
+        n, M = x.shape[0], self.quantized_len()
         if out is None:
             # u8 codes, or 32-bit codes (int32 tensor, values < 2^31) when K > 256
             dt = torch.uint8 if self.n_quantizer_centroids() <= 256 else torch.int32
-            out = torch.empty((x.shape[0], self.quantized_len()), dtype=dt, device=x.device)
-        if tuple(out.shape) != (x.shape[0], self.quantized_len()):
+            out = torch.empty((n, M), dtype=dt, device=x.device)
+        if tuple(out.shape) != (n, M):
             raise PanicError("Quantized matrix has incorrect shape, expected: (%d, %d), got: (%d, %d)"
-                             % (x.shape[0], self.quantized_len(), out.shape[0], out.shape[1]))
+                             % (n, M, out.shape[0], out.shape[1]))
         # index type I of quantize_batch::<I, _>: uint8, or int16 / int32 / int64 tensors as 2- / 4- / 8-byte containers
         # (u16 / u32 / u64 bit patterns)
         assert out.is_cuda and out.dtype in (torch.uint8, torch.int16, torch.int32, torch.int64) and out.stride(1) == 1
-        code_bytes = out.element_size()
-        cb = self._cb()
-        if stream is None:
-            stream = torch.cuda.current_stream(x.device).cuda_stream
-        rc = _lib.lib().pqhip_quantize_batch_f32_dev(cb, self._slot_for(x), x.data_ptr(), x.shape[0],
-                                                    x.stride(0) if x.shape[0] > 1 else max(x.stride(0), x.shape[1]),
-                                                    out.data_ptr(), code_bytes,
-                                                    out.stride(0) if out.shape[0] > 1 else max(out.stride(0), out.shape[1]),
-                                                    ctypes.c_void_p(stream))
-        if rc == _lib.EINDEX_WIDTH:
-            raise PanicError("Cannot store centroids in quantizer index type")
-        if rc != _lib.OK:
-            raise _lib.PqHipError(rc, "pqhip_quantize_batch_f32_dev")
+        cb, slot, sp = _marshal.launch(self, x, stream)
+        _marshal.run("pqhip_quantize_batch_f32_dev", cb, slot, x.data_ptr(), n, row_stride(x, n, x.shape[1]),
+                     out.data_ptr(), out.element_size(), row_stride(out, n, M), sp, panics=_marshal.WIDTH_PANIC)
         return out
 
     def reconstruct_batch_device(self, codes, out=None, stream=None, check=True):
@@ -727,34 +705,13 @@ class Pq:
         violation pending on the stream's flag (a later check=True call on that stream reports it)."""
         import torch
         assert codes.is_cuda and codes.dtype in (torch.uint8, torch.int16, torch.int32, torch.int64) and codes.dim() == 2
-        if codes.shape[1] != self.quantized_len():
-            raise PanicError("Quantization length does not match number of subquantizers")
-        if codes.stride(1) != 1:
-            codes = codes.contiguous()
-        if out is None:
-            out = torch.empty((codes.shape[0], self.reconstructed_len()), dtype=torch.float32,
-                              device=codes.device)
-        assert out.is_cuda and out.dtype == torch.float32 and out.stride(1) == 1
-        if tuple(out.shape) != (codes.shape[0], self.reconstructed_len()):
-            raise PanicError("Reconstructions matrix has incorrect shape, expected: (%d, %d), got: (%d, %d)"
-                             % (codes.shape[0], self.reconstructed_len(), out.shape[0], out.shape[1]))
-        cb = self._cb()
-        if stream is None:
-            stream = torch.cuda.current_stream(codes.device).cuda_stream
-        slot = self._slot_for(codes)
-        rc = _lib.lib().pqhip_reconstruct_batch_f32_dev(
-            cb, slot, codes.data_ptr(), codes.element_size(), codes.shape[0],
-            codes.stride(0) if codes.shape[0] > 1 else max(codes.stride(0), codes.shape[1]),
-            out.data_ptr(), out.stride(0) if out.shape[0] > 1 else max(out.stride(0), out.shape[1]),
-            ctypes.c_void_p(stream))
-        if rc != _lib.OK:
-            raise _lib.PqHipError(rc, "pqhip_reconstruct_batch_f32_dev")
+        codes, n, c_rs = _marshal.codes_arg(codes, _marshal.code_width(codes, self.quantized_len()))
+        out, o_rs = self._reconstructions(out, n, codes.device)
+        cb, slot, sp = _marshal.launch(self, codes, stream)
+        _marshal.run("pqhip_reconstruct_batch_f32_dev", cb, slot, codes.data_ptr(), codes.element_size(), n, c_rs,
+                     out.data_ptr(), o_rs, sp)
         if check:
-            rc = _lib.lib().pqhip_check_codes_dev(cb, slot, ctypes.c_void_p(stream))
-            if rc == _lib.ECODE_RANGE:
-                raise PanicError("ndarray: index out of bounds")
-            if rc != _lib.OK:
-                raise _lib.PqHipError(rc, "pqhip_check_codes_dev")
+            _marshal.check_range(cb, slot, sp)
         return out
 
     def reconstruct_rows_device(self, codes, rows, scales=None, out=None, stream=None, check=True):
@@ -764,41 +721,15 @@ class Pq:
         import torch
         assert codes.is_cuda and codes.dtype == torch.uint8 and codes.dim() == 2
         assert rows.is_cuda and rows.dtype == torch.int64 and rows.dim() == 1 and rows.is_contiguous()
-        if codes.shape[1] != self.quantized_len():
-            raise PanicError("Quantization length does not match number of subquantizers")
-        if codes.stride(1) != 1:
-            codes = codes.contiguous()
-        if scales is not None:
-            assert scales.is_cuda and scales.dtype == torch.float32 and scales.is_contiguous()
-            if scales.shape != (codes.shape[0],):
-                raise PanicError("scales must hold one value per code row")
+        codes, N, c_rs = _marshal.codes_arg(codes, _marshal.code_width(codes, self.quantized_len()))
+        _marshal.per_row_arg(scales, N, "scales")
         n = rows.shape[0]
-        if out is None:
-            out = torch.empty((n, self.reconstructed_len()), dtype=torch.float32, device=codes.device)
-        assert out.is_cuda and out.dtype == torch.float32 and out.stride(1) == 1
-        if tuple(out.shape) != (n, self.reconstructed_len()):
-            raise PanicError("Reconstructions matrix has incorrect shape, expected: (%d, %d), got: (%d, %d)"
-                             % (n, self.reconstructed_len(), out.shape[0], out.shape[1]))
-        cb = self._cb()
-        if stream is None:
-            stream = torch.cuda.current_stream(codes.device).cuda_stream
-        slot = self._slot_for(codes)
-        rc = _lib.lib().pqhip_reconstruct_rows_f32_dev(
-            cb, slot, codes.data_ptr(), 1, codes.shape[0],
-            codes.stride(0) if codes.shape[0] > 1 else max(codes.stride(0), codes.shape[1]),
-            rows.data_ptr(), n, scales.data_ptr() if scales is not None else None,
-            out.data_ptr(), out.stride(0) if n > 1 else max(out.stride(0), out.shape[1]),
-            ctypes.c_void_p(stream))
-        if rc == _lib.ECODE_RANGE:
-            raise PanicError("ndarray: index out of bounds")
-        if rc != _lib.OK:
-            raise _lib.PqHipError(rc, "pqhip_reconstruct_rows_f32_dev")
+        out, o_rs = self._reconstructions(out, n, codes.device)
+        cb, slot, sp = _marshal.launch(self, codes, stream)
+        _marshal.run("pqhip_reconstruct_rows_f32_dev", cb, slot, codes.data_ptr(), 1, N, c_rs, rows.data_ptr(), n,
+                     ptr_or_none(scales), out.data_ptr(), o_rs, sp, panics=_marshal.RANGE_PANIC)
         if check:
-            rc = _lib.lib().pqhip_check_codes_dev(cb, slot, ctypes.c_void_p(stream))
-            if rc == _lib.ECODE_RANGE:
-                raise PanicError("ndarray: index out of bounds")
-            if rc != _lib.OK:
-                raise _lib.PqHipError(rc, "pqhip_check_codes_dev")
+            _marshal.check_range(cb, slot, sp)
         return out
 
     @staticmethod
@@ -825,55 +756,37 @@ class Pq:
         assert records.is_cuda and records.dtype == torch.uint8 and records.dim() == 2 and records.is_contiguous()
         assert rows.is_cuda and rows.dtype == torch.int64 and rows.dim() == 1 and rows.is_contiguous()
         n = rows.shape[0]
-        if out is None:
-            out = torch.empty((n, self.reconstructed_len()), dtype=torch.float32, device=records.device)
-        assert out.is_cuda and out.dtype == torch.float32 and out.stride(1) == 1
-        if tuple(out.shape) != (n, self.reconstructed_len()):
-            raise PanicError("Reconstructions matrix has incorrect shape, expected: (%d, %d), got: (%d, %d)"
-                             % (n, self.reconstructed_len(), out.shape[0], out.shape[1]))
-        cb = self._cb()
-        if stream is None:
-            stream = torch.cuda.current_stream(records.device).cuda_stream
-        slot = self._slot_for(records)
-        rc = _lib.lib().pqhip_reconstruct_rows_records_f32_dev(
-            cb, slot, records.data_ptr(), 1, records.shape[0], records.shape[1], scale_offset, rows.data_ptr(), n,
-            out.data_ptr(), out.stride(0) if n > 1 else max(out.stride(0), out.shape[1]), ctypes.c_void_p(stream))
-        if rc == _lib.ECODE_RANGE:
-            raise PanicError("ndarray: index out of bounds")
-        if rc != _lib.OK:
-            raise _lib.PqHipError(rc, "pqhip_reconstruct_rows_records_f32_dev")
+        out, o_rs = self._reconstructions(out, n, records.device)
+        cb, slot, sp = _marshal.launch(self, records, stream)
+        _marshal.run("pqhip_reconstruct_rows_records_f32_dev", cb, slot, records.data_ptr(), 1, records.shape[0],
+                     records.shape[1], scale_offset, rows.data_ptr(), n, out.data_ptr(), o_rs, sp,
+                     panics=_marshal.RANGE_PANIC)
         if check:
-            rc = _lib.lib().pqhip_check_codes_dev(cb, slot, ctypes.c_void_p(stream))
-            if rc == _lib.ECODE_RANGE:
-                raise PanicError("ndarray: index out of bounds")
-            if rc != _lib.OK:
-                raise _lib.PqHipError(rc, "pqhip_check_codes_dev")
+            _marshal.check_range(cb, slot, sp)
         return out
 
     # ---- "next" row: asymmetric distance computation over resident codes -----
-    def adc_tables_device(self, queries, stream=None):
-        """queries: CUDA float32 [d] or [nq, d] -> tables [M, K] or [nq, M, K] with
-        tables[q, m, j] = `y_q[m].squared_euclidean_distance(quantizers[m])[j]` (linalg.rs:118-148;
-        y = query.dot(projection) first for OPQ, pq.rs:293)."""
+    def _adc_tables(self, name, queries, stream):
+        """Both table builders."""
         import torch
         assert queries.is_cuda and queries.dtype == torch.float32 and queries.dim() in (1, 2)
         single = queries.dim() == 1
         q2 = queries[None] if single else queries
         if q2.shape[1] != self.reconstructed_len():
             raise PanicError("Quantizer and vector length mismatch")
-        if q2.stride(1) != 1:
-            q2 = q2.contiguous()
-        M, K = self.quantized_len(), self.n_quantizer_centroids()
-        out = torch.empty((q2.shape[0], M, K), dtype=torch.float32, device=queries.device)
-        cb = self._cb()
-        if stream is None:
-            stream = torch.cuda.current_stream(queries.device).cuda_stream
-        rc = _lib.lib().pqhip_adc_tables_f32_dev(cb, self._slot_for(queries), q2.data_ptr(), q2.shape[0],
-                                                q2.stride(0) if q2.shape[0] > 1 else max(q2.stride(0), q2.shape[1]),
-                                                out.data_ptr(), ctypes.c_void_p(stream))
-        if rc != _lib.OK:
-            raise _lib.PqHipError(rc, "pqhip_adc_tables_f32_dev")
+        q2 = _marshal.unit_columns(q2)
+        nq = q2.shape[0]
+        out = torch.empty((nq, self.quantized_len(), self.n_quantizer_centroids()), dtype=torch.float32,
+                          device=queries.device)
+        cb, slot, sp = _marshal.launch(self, queries, stream)
+        _marshal.run(name, cb, slot, q2.data_ptr(), nq, row_stride(q2, nq, q2.shape[1]), out.data_ptr(), sp)
         return out[0] if single else out
+
+    def adc_tables_device(self, queries, stream=None):
+        """queries: CUDA float32 [d] or [nq, d] -> tables [M, K] or [nq, M, K] with
+        tables[q, m, j] = `y_q[m].squared_euclidean_distance(quantizers[m])[j]` (linalg.rs:118-148;
+        y = query.dot(projection) first for OPQ, pq.rs:293)."""
+        return self._adc_tables("pqhip_adc_tables_f32_dev", queries, stream)
 
     def adc_scan_device(self, codes, tables, out=None, stream=None, check=False):
         """codes: CUDA uint8 (or int32 when K > 256) [n, M]; tables: [M, K] or [nq, M, K] from
@@ -883,51 +796,23 @@ class Pq:
         assert codes.is_cuda and codes.dtype in (torch.uint8, torch.int32) and codes.dim() == 2
         assert tables.is_cuda and tables.dtype == torch.float32 and tables.is_contiguous()
         M, K = self.quantized_len(), self.n_quantizer_centroids()
-        if codes.shape[1] != M:
-            raise PanicError("Quantization length does not match number of subquantizers")
-        single = tables.dim() == 2
-        if tuple(tables.shape[-2:]) != (M, K):
-            raise PanicError("lookup tables must be [.., %d, %d]" % (M, K))
-        nq = 1 if single else tables.shape[0]
-        if codes.stride(1) != 1:
-            codes = codes.contiguous()
-        n = codes.shape[0]
+        W = _marshal.code_width(codes, M)
+        single, nq = _marshal.tables_arg(tables, M, K)
+        codes, n, c_rs = _marshal.codes_arg(codes, W)
         if out is None:
             out = torch.empty((n,) if single else (nq, n), dtype=torch.float32, device=codes.device)
         assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == nq * n
-        cb = self._cb()
-        if stream is None:
-            stream = torch.cuda.current_stream(codes.device).cuda_stream
-        slot = self._slot_for(codes)
-        rc = _lib.lib().pqhip_adc_scan_f32_dev(cb, slot, tables.data_ptr(), nq, codes.data_ptr(), codes.element_size(), n,
-                                              codes.stride(0) if n > 1 else max(codes.stride(0), M),
-                                              out.data_ptr(), n, ctypes.c_void_p(stream))
-        if rc != _lib.OK:
-            raise _lib.PqHipError(rc, "pqhip_adc_scan_f32_dev")
+        cb, slot, sp = _marshal.launch(self, codes, stream)
+        _marshal.run("pqhip_adc_scan_f32_dev", cb, slot, tables.data_ptr(), nq, codes.data_ptr(), codes.element_size(), n,
+                     c_rs, out.data_ptr(), n, sp)
         if check:
-            rc = _lib.lib().pqhip_check_codes_dev(cb, slot, ctypes.c_void_p(stream))
-            if rc == _lib.ECODE_RANGE:
-                raise PanicError("ndarray: index out of bounds")
-            if rc != _lib.OK:
-                raise _lib.PqHipError(rc, "pqhip_check_codes_dev")
+            _marshal.check_range(cb, slot, sp)
         return out
 
     # ---- 4-bit packed codes: two codes per byte for K <= 16 ----------------------------------------------------------
     def _packed4_served(self):
         if self.n_quantizer_centroids() > 16:
             raise PanicError("4-bit packed codes need a quantizer of at most 16 centroids")
-
-    def _code_row_bytes(self, codes, packed4):
-        """The row width the searches expect of `codes`: M elements, or ceil(M / 2) bytes of 4-bit packed rows."""
-        import torch
-        M = self.quantized_len()
-        if not packed4:
-            if codes.shape[1] != M:
-                raise PanicError("Quantization length does not match number of subquantizers")
-            return M
-        if codes.dtype != torch.uint8 or codes.shape[1] != (M + 1) // 2:
-            raise PanicError("4-bit packed codes must be uint8 [n, ceil(n_subquantizers / 2)]")
-        return (M + 1) // 2
 
     def pack_codes4_device(self, codes, out=None, stream=None, check=False):
         """codes: CUDA uint8 or int32 [n, M] of a quantizer with K <= 16 -> 4-bit packed rows, CUDA uint8
@@ -938,31 +823,17 @@ class Pq:
         assert codes.is_cuda and codes.dtype in (torch.uint8, torch.int32) and codes.dim() == 2
         M = self.quantized_len()
         PB = (M + 1) // 2
-        if codes.shape[1] != M:
-            raise PanicError("Quantization length does not match number of subquantizers")
-        if codes.stride(1) != 1:
-            codes = codes.contiguous()
-        n = codes.shape[0]
+        codes, n, c_rs = _marshal.codes_arg(codes, _marshal.code_width(codes, M))
         if out is None:
             out = torch.empty((n, PB), dtype=torch.uint8, device=codes.device)
         assert out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == (n, PB) and (PB == 1 or out.stride(1) == 1)
         if n == 0:
             return out
-        cb = self._cb()
-        if stream is None:
-            stream = torch.cuda.current_stream(codes.device).cuda_stream
-        slot = self._slot_for(codes)
-        rc = _lib.lib().pqhip_pack_codes4_dev(cb, slot, codes.data_ptr(), codes.element_size(), n,
-                                             codes.stride(0) if n > 1 else max(codes.stride(0), M), out.data_ptr(),
-                                             out.stride(0) if n > 1 else max(out.stride(0), PB), ctypes.c_void_p(stream))
-        if rc != _lib.OK:
-            raise _lib.PqHipError(rc, "pqhip_pack_codes4_dev")
+        cb, slot, sp = _marshal.launch(self, codes, stream)
+        _marshal.run("pqhip_pack_codes4_dev", cb, slot, codes.data_ptr(), codes.element_size(), n, c_rs, out.data_ptr(),
+                     row_stride(out, n, PB), sp)
         if check:
-            rc = _lib.lib().pqhip_check_codes_dev(cb, slot, ctypes.c_void_p(stream))
-            if rc == _lib.ECODE_RANGE:
-                raise PanicError("ndarray: index out of bounds")
-            if rc != _lib.OK:
-                raise _lib.PqHipError(rc, "pqhip_check_codes_dev")
+            _marshal.check_range(cb, slot, sp)
         return out
 
     def unpack_codes4_device(self, packed, rows=None, out=None, stream=None, check=False):
@@ -973,9 +844,8 @@ class Pq:
         self._packed4_served()
         assert packed.is_cuda and packed.dim() == 2
         M = self.quantized_len()
-        PB = self._code_row_bytes(packed, True)
-        if packed.stride(1) != 1:
-            packed = packed.contiguous()
+        PB = _marshal.code_width(packed, M, True)
+        packed = _marshal.unit_columns(packed)
         n = packed.shape[0]
         n_out = n
         if rows is not None:
@@ -987,23 +857,13 @@ class Pq:
         assert out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == (n_out, M) and (M == 1 or out.stride(1) == 1)
         if n_out == 0:
             return out
-        # an empty tensor may have no address: every row id is then out of range and no packed byte is read
-        src = packed if n > 0 else torch.zeros((1, PB), dtype=torch.uint8, device=packed.device)
-        cb = self._cb()
-        if stream is None:
-            stream = torch.cuda.current_stream(packed.device).cuda_stream
-        slot = self._slot_for(packed)
-        rc = _lib.lib().pqhip_unpack_codes4_dev(cb, slot, src.data_ptr(), n, src.stride(0) if n > 1 else max(src.stride(0), PB),
-                                               rows.data_ptr() if rows is not None else None, n_out, out.data_ptr(),
-                                               out.stride(0) if n_out > 1 else max(out.stride(0), M), ctypes.c_void_p(stream))
-        if rc != _lib.OK:
-            raise _lib.PqHipError(rc, "pqhip_unpack_codes4_dev")
+        # with n = 0 every row id is out of range and no packed byte is read
+        src = _marshal.stand_in(packed, n, packed.device, PB)
+        cb, slot, sp = _marshal.launch(self, packed, stream)
+        _marshal.run("pqhip_unpack_codes4_dev", cb, slot, src.data_ptr(), n, row_stride(src, n, PB), ptr_or_none(rows),
+                     n_out, out.data_ptr(), row_stride(out, n_out, M), sp)
         if check:
-            rc = _lib.lib().pqhip_check_codes_dev(cb, slot, ctypes.c_void_p(stream))
-            if rc == _lib.ECODE_RANGE:
-                raise PanicError("ndarray: index out of bounds")
-            if rc != _lib.OK:
-                raise _lib.PqHipError(rc, "pqhip_check_codes_dev")
+            _marshal.check_range(cb, slot, sp)
         return out
 
     # ---- row masks: restrict a search to an allowed set of rows ------------------------------------------------------
@@ -1026,33 +886,37 @@ class Pq:
         words = torch.empty(((n + 31) // 32,), dtype=torch.int32, device=allow.device)
         if n == 0:
             return words
-        if n_src == 0:      # an empty tensor may have no address
-            ab = torch.zeros(1, dtype=torch.uint8, device=allow.device)
-        cb = self._cb()
-        if stream is None:
-            stream = torch.cuda.current_stream(allow.device).cuda_stream
-        slot = self._slot_for(allow)
-        rc = _lib.lib().pqhip_pack_row_mask_dev(cb, slot, ab.data_ptr(), n_src, perm.data_ptr() if perm is not None else None,
-                                               n, words.data_ptr(), ctypes.c_void_p(stream))
-        if rc != _lib.OK:
-            raise _lib.PqHipError(rc, "pqhip_pack_row_mask_dev")
+        ab = _marshal.stand_in(ab, n_src, allow.device)
+        cb, slot, sp = _marshal.launch(self, allow, stream)
+        _marshal.run("pqhip_pack_row_mask_dev", cb, slot, ab.data_ptr(), n_src, ptr_or_none(perm), n, words.data_ptr(), sp)
         if check:
-            rc = _lib.lib().pqhip_check_codes_dev(cb, slot, ctypes.c_void_p(stream))
-            if rc == _lib.ECODE_RANGE:
-                raise PanicError("ndarray: index out of bounds")
-            if rc != _lib.OK:
-                raise _lib.PqHipError(rc, "pqhip_check_codes_dev")
+            _marshal.check_range(cb, slot, sp)
         return words
 
-    @staticmethod
-    def _mask_words(allow, codes):
-        """The words tensor of a search's `allow=`: CUDA int32 [ceil(n / 32)] on the device of the codes."""
+    def _adc_search(self, ip, codes, tables, k, scales, stream, check, allow, packed4):
+        """Both exhaustive searches; allow given: their masked forms; packed4: their forms over 4-bit packed rows (a mask
+        or none)."""
         import torch
-        assert allow.is_cuda and allow.dtype == torch.int32 and allow.dim() == 1 and allow.is_contiguous()
-        if allow.device != codes.device or allow.shape[0] != (codes.shape[0] + 31) // 32:
-            raise PanicError("the row mask must hold ceil(n / 32) words for the n code rows")
-        # an empty tensor may have no address; a non-NULL mask must stay a mask (n = 0 reads no word)
-        return allow if allow.shape[0] > 0 else torch.zeros(1, dtype=torch.int32, device=codes.device)
+        if packed4:
+            self._packed4_served()
+        name = "pqhip_adc_%ssearch_%sf32_dev" % ("ip_" if ip else "",
+                                                 "packed4_" if packed4 else "masked_" if allow is not None else "")
+        assert codes.is_cuda and codes.dtype in (torch.uint8, torch.int32) and codes.dim() == 2
+        assert tables.is_cuda and tables.dtype == torch.float32 and tables.is_contiguous()
+        M, K = self.quantized_len(), self.n_quantizer_centroids()
+        W = _marshal.code_width(codes, M, packed4)
+        single, nq = _marshal.tables_arg(tables, M, K)
+        codes, n, c_rs = _marshal.codes_arg(codes, W)
+        _marshal.per_row_arg(scales, n, "scales")
+        val = torch.empty((nq, k), dtype=torch.float32, device=codes.device)
+        idx = torch.empty((nq, k), dtype=torch.int64, device=codes.device)
+        cb, slot, sp = _marshal.launch(self, codes, stream)
+        head = _marshal.search_head(cb, slot, tables, nq, codes, n, c_rs, packed4, _marshal.mask_arg(allow, codes, packed4),
+                                    last=(ptr_or_none(scales),) if ip else ())
+        _marshal.run(name, *head, k, val.data_ptr(), k, idx.data_ptr(), k, sp)
+        if check:
+            _marshal.check_range(cb, slot, sp)
+        return (val[0], idx[0]) if single else (val, idx)
 
     def adc_search_device(self, codes, tables, k, stream=None, check=False, allow=None, packed4=False):
         """The k nearest rows per query without the distance matrix: codes and tables as for adc_scan_device ->
@@ -1062,76 +926,14 @@ class Pq:
         ranks the allowed rows only, as if the others were not in the matrix (pqhip_adc_search_masked_f32_dev).
         packed4=True: codes are 4-bit packed rows, CUDA uint8 [n, ceil(M / 2)] (pack_codes4_device; K <= 16), and the
         result is bit for bit that of the unpacked codes (pqhip_adc_search_packed4_f32_dev)."""
-        import torch
-        if packed4:
-            self._packed4_served()
-        assert codes.is_cuda and codes.dtype in (torch.uint8, torch.int32) and codes.dim() == 2
-        assert tables.is_cuda and tables.dtype == torch.float32 and tables.is_contiguous()
-        M, K = self.quantized_len(), self.n_quantizer_centroids()
-        W = self._code_row_bytes(codes, packed4)
-        single = tables.dim() == 2
-        if tuple(tables.shape[-2:]) != (M, K):
-            raise PanicError("lookup tables must be [.., %d, %d]" % (M, K))
-        nq = 1 if single else tables.shape[0]
-        if codes.stride(1) != 1:
-            codes = codes.contiguous()
-        n = codes.shape[0]
-        dist = torch.empty((nq, k), dtype=torch.float32, device=codes.device)
-        idx = torch.empty((nq, k), dtype=torch.int64, device=codes.device)
-        cb = self._cb()
-        if stream is None:
-            stream = torch.cuda.current_stream(codes.device).cuda_stream
-        slot = self._slot_for(codes)
-        c_rs = codes.stride(0) if n > 1 else max(codes.stride(0), W)
-        if packed4:
-            name = "pqhip_adc_search_packed4_f32_dev"
-            rc = _lib.lib().pqhip_adc_search_packed4_f32_dev(cb, slot, tables.data_ptr(), nq, codes.data_ptr(), n, c_rs,
-                                                            self._mask_words(allow, codes).data_ptr() if allow is not None else None,
-                                                            k, dist.data_ptr(), k, idx.data_ptr(), k, ctypes.c_void_p(stream))
-        elif allow is not None:
-            name = "pqhip_adc_search_masked_f32_dev"
-            rc = _lib.lib().pqhip_adc_search_masked_f32_dev(cb, slot, tables.data_ptr(), nq, codes.data_ptr(),
-                                                           codes.element_size(), n, c_rs,
-                                                           self._mask_words(allow, codes).data_ptr(), k,
-                                                           dist.data_ptr(), k, idx.data_ptr(), k, ctypes.c_void_p(stream))
-        else:
-            name = "pqhip_adc_search_f32_dev"
-            rc = _lib.lib().pqhip_adc_search_f32_dev(cb, slot, tables.data_ptr(), nq, codes.data_ptr(), codes.element_size(), n,
-                                                    c_rs, k, dist.data_ptr(), k, idx.data_ptr(), k, ctypes.c_void_p(stream))
-        if rc != _lib.OK:
-            raise _lib.PqHipError(rc, name)
-        if check:
-            rc = _lib.lib().pqhip_check_codes_dev(cb, slot, ctypes.c_void_p(stream))
-            if rc == _lib.ECODE_RANGE:
-                raise PanicError("ndarray: index out of bounds")
-            if rc != _lib.OK:
-                raise _lib.PqHipError(rc, "pqhip_check_codes_dev")
-        return (dist[0], idx[0]) if single else (dist, idx)
+        return self._adc_search(False, codes, tables, k, None, stream, check, allow, packed4)
 
     # ---- ADC similarity search: inner products over resident codes --------------------------------------------------
     def adc_ip_tables_device(self, queries, stream=None):
         """queries: CUDA float32 [d] or [nq, d] -> inner-product tables [M, K] or [nq, M, K]:
         tables[q, m, j] = unrolled_dot(quantizers[m, j], y_q[m]), the dp term of adc_tables_device (y = query.dot(projection)
         first for OPQ).  sum_m tables[q, m, codes[i, m]] is <query_q, reconstruct(codes[i])> (pqhip_adc_ip_tables_f32_dev)."""
-        import torch
-        assert queries.is_cuda and queries.dtype == torch.float32 and queries.dim() in (1, 2)
-        single = queries.dim() == 1
-        q2 = queries[None] if single else queries
-        if q2.shape[1] != self.reconstructed_len():
-            raise PanicError("Quantizer and vector length mismatch")
-        if q2.stride(1) != 1:
-            q2 = q2.contiguous()
-        M, K = self.quantized_len(), self.n_quantizer_centroids()
-        out = torch.empty((q2.shape[0], M, K), dtype=torch.float32, device=queries.device)
-        cb = self._cb()
-        if stream is None:
-            stream = torch.cuda.current_stream(queries.device).cuda_stream
-        rc = _lib.lib().pqhip_adc_ip_tables_f32_dev(cb, self._slot_for(queries), q2.data_ptr(), q2.shape[0],
-                                                   q2.stride(0) if q2.shape[0] > 1 else max(q2.stride(0), q2.shape[1]),
-                                                   out.data_ptr(), ctypes.c_void_p(stream))
-        if rc != _lib.OK:
-            raise _lib.PqHipError(rc, "pqhip_adc_ip_tables_f32_dev")
-        return out[0] if single else out
+        return self._adc_tables("pqhip_adc_ip_tables_f32_dev", queries, stream)
 
     def adc_ip_search_device(self, codes, tables, k, scales=None, stream=None, check=False, allow=None, packed4=False):
         """The k most similar rows per query: codes as for adc_scan_device, tables from adc_ip_tables_device, scales None
@@ -1140,53 +942,7 @@ class Pq:
         descending score -- NaN after -Inf -- then by index (pqhip_adc_ip_search_f32_dev).  A zero score comes back as
         +0, a NaN as the canonical NaN.  Past the last row: index -1, score -Inf.  allow: as for adc_search_device
         (pqhip_adc_ip_search_masked_f32_dev).  packed4: as for adc_search_device (pqhip_adc_ip_search_packed4_f32_dev)."""
-        import torch
-        if packed4:
-            self._packed4_served()
-        assert codes.is_cuda and codes.dtype in (torch.uint8, torch.int32) and codes.dim() == 2
-        assert tables.is_cuda and tables.dtype == torch.float32 and tables.is_contiguous()
-        M, K = self.quantized_len(), self.n_quantizer_centroids()
-        W = self._code_row_bytes(codes, packed4)
-        single = tables.dim() == 2
-        if tuple(tables.shape[-2:]) != (M, K):
-            raise PanicError("lookup tables must be [.., %d, %d]" % (M, K))
-        nq = 1 if single else tables.shape[0]
-        if codes.stride(1) != 1:
-            codes = codes.contiguous()
-        n = codes.shape[0]
-        if scales is not None:
-            assert scales.is_cuda and scales.dtype == torch.float32 and scales.is_contiguous()
-            if tuple(scales.shape) != (n,):
-                raise PanicError("scales must hold one value per code row")
-        score = torch.empty((nq, k), dtype=torch.float32, device=codes.device)
-        idx = torch.empty((nq, k), dtype=torch.int64, device=codes.device)
-        cb = self._cb()
-        if stream is None:
-            stream = torch.cuda.current_stream(codes.device).cuda_stream
-        slot = self._slot_for(codes)
-        head = (cb, slot, tables.data_ptr(), nq, codes.data_ptr(), codes.element_size(), n,
-                codes.stride(0) if n > 1 else max(codes.stride(0), W))
-        tail = (scales.data_ptr() if scales is not None else None, k, score.data_ptr(), k, idx.data_ptr(), k,
-                ctypes.c_void_p(stream))
-        if packed4:
-            name = "pqhip_adc_ip_search_packed4_f32_dev"
-            rc = _lib.lib().pqhip_adc_ip_search_packed4_f32_dev(
-                *head[:5], *head[6:], self._mask_words(allow, codes).data_ptr() if allow is not None else None, *tail)
-        elif allow is not None:
-            name = "pqhip_adc_ip_search_masked_f32_dev"
-            rc = _lib.lib().pqhip_adc_ip_search_masked_f32_dev(*head, self._mask_words(allow, codes).data_ptr(), *tail)
-        else:
-            name = "pqhip_adc_ip_search_f32_dev"
-            rc = _lib.lib().pqhip_adc_ip_search_f32_dev(*head, *tail)
-        if rc != _lib.OK:
-            raise _lib.PqHipError(rc, name)
-        if check:
-            rc = _lib.lib().pqhip_check_codes_dev(cb, slot, ctypes.c_void_p(stream))
-            if rc == _lib.ECODE_RANGE:
-                raise PanicError("ndarray: index out of bounds")
-            if rc != _lib.OK:
-                raise _lib.PqHipError(rc, "pqhip_check_codes_dev")
-        return (score[0], idx[0]) if single else (score, idx)
+        return self._adc_search(True, codes, tables, k, scales, stream, check, allow, packed4)
 
     # ---- ADC search over a partitioned code matrix: exact top-k within the probed lists -----------------------------
     def _adc_search_lists(self, ip, codes, tables, list_off, probes, k, scales, stream, check, probe_bias=None,
@@ -1202,74 +958,31 @@ class Pq:
                                                         "packed4_" if packed4 else "masked_" if allow is not None else "")
         assert codes.is_cuda and codes.dtype == torch.uint8 and codes.dim() == 2
         assert tables.is_cuda and tables.dtype == torch.float32 and tables.is_contiguous()
-        assert list_off.is_cuda and list_off.dtype == torch.int64 and list_off.dim() == 1 and list_off.is_contiguous()
-        assert probes.is_cuda and probes.dtype == torch.int64 and probes.dim() in (1, 2)
+        _marshal.assert_lists(list_off, probes)
         M, K = self.quantized_len(), self.n_quantizer_centroids()
-        W = self._code_row_bytes(codes, packed4)
-        single = tables.dim() == 2
-        if tuple(tables.shape[-2:]) != (M, K):
-            raise PanicError("lookup tables must be [.., %d, %d]" % (M, K))
-        nq = 1 if single else tables.shape[0]
-        pr = probes[None] if probes.dim() == 1 else probes
-        if pr.shape[0] != nq or pr.shape[1] < 1 or list_off.shape[0] < 1:
-            raise PanicError("one probe row of at least one list id per query and n_lists + 1 offsets expected")
-        if pr.stride(1) != 1:
-            pr = pr.contiguous()
-        if codes.stride(1) != 1:
-            codes = codes.contiguous()
-        n = codes.shape[0]
-        if scales is not None:
-            assert scales.is_cuda and scales.dtype == torch.float32 and scales.is_contiguous()
-            if tuple(scales.shape) != (n,):
-                raise PanicError("scales must hold one value per code row")
-        n_probe = pr.shape[1]
+        W = _marshal.code_width(codes, M, packed4)
+        single, nq = _marshal.tables_arg(tables, M, K)
+        pr, n_probe, p_rs = _marshal.probes_arg(probes, list_off, nq)
+        codes, n, c_rs = _marshal.codes_arg(codes, W)
+        _marshal.per_row_arg(scales, n, "scales")
+        bias = ()
         if residual:
-            assert probe_bias.is_cuda and probe_bias.dtype == torch.float32 and probe_bias.dim() in (1, 2)
-            pb = probe_bias[None] if probe_bias.dim() == 1 else probe_bias
-            if tuple(pb.shape) != (nq, n_probe):
-                raise PanicError("one probe bias per query and probe slot expected")
-            if pb.stride(1) != 1:
-                pb = pb.contiguous()
+            bias = _marshal.bias_arg(probe_bias, nq, n_probe)
             if not ip:
-                assert row_terms.is_cuda and row_terms.dtype == torch.float32 and row_terms.is_contiguous()
-                if tuple(row_terms.shape) != (n,):
-                    raise PanicError("row_terms must hold one value per code row")
+                _marshal.per_row_arg(row_terms, n, "row_terms")
         val = torch.empty((nq, k), dtype=torch.float32, device=codes.device)
         idx = torch.empty((nq, k), dtype=torch.int64, device=codes.device)
-        cb = self._cb()
-        if stream is None:
-            stream = torch.cuda.current_stream(codes.device).cuda_stream
-        slot = self._slot_for(codes)
-        head = (cb, slot, tables.data_ptr(), nq, codes.data_ptr(), codes.element_size(), n,
-                codes.stride(0) if n > 1 else max(codes.stride(0), W))
-        if packed4:
-            head = head[:5] + head[6:] + (self._mask_words(allow, codes).data_ptr() if allow is not None else None,)
-        elif allow is not None:
-            head += (self._mask_words(allow, codes).data_ptr(),)
-        head += (list_off.data_ptr(), list_off.shape[0] - 1,
-                 pr.data_ptr(), n_probe, pr.stride(0) if nq > 1 else max(pr.stride(0), n_probe))
-        tail = (k, val.data_ptr(), k, idx.data_ptr(), k, ctypes.c_void_p(stream))
-        fn = getattr(_lib.lib(), name)
-        if residual:
-            head += (pb.data_ptr(), pb.stride(0) if nq > 1 else max(pb.stride(0), n_probe))
-            if ip:
-                rc = fn(*head, scales.data_ptr() if scales is not None else None, *tail)
-            else:
-                # an empty tensor may have no address, and the C call wants one even when there is no row to read
-                rt = row_terms if n > 0 else torch.zeros(1, dtype=torch.float32, device=codes.device)
-                rc = fn(*head, rt.data_ptr(), *tail)
-        elif ip:
-            rc = fn(*head, scales.data_ptr() if scales is not None else None, *tail)
-        else:
-            rc = fn(*head, *tail)
-        if rc != _lib.OK:
-            raise _lib.PqHipError(rc, name)
+        cb, slot, sp = _marshal.launch(self, codes, stream)
+        mask = _marshal.mask_arg(allow, codes, packed4)
+        last = (ptr_or_none(scales),) if ip else ()
+        if residual and not ip:
+            rt = _marshal.stand_in(row_terms, n, codes.device)      # the C call wants an address even without a row to read
+            last = (rt.data_ptr(),)
+        _marshal.run(name, *_marshal.search_head(cb, slot, tables, nq, codes, n, c_rs, packed4, mask,
+                                                 (list_off, pr, n_probe, p_rs), bias, last),
+                     k, val.data_ptr(), k, idx.data_ptr(), k, sp)
         if check:
-            rc = _lib.lib().pqhip_check_codes_dev(cb, slot, ctypes.c_void_p(stream))
-            if rc == _lib.ECODE_RANGE:
-                raise PanicError("ndarray: index out of bounds")
-            if rc != _lib.OK:
-                raise _lib.PqHipError(rc, "pqhip_check_codes_dev")
+            _marshal.check_range(cb, slot, sp)
         return (val[0], idx[0]) if single else (val, idx)
 
     def adc_search_lists_device(self, codes, tables, list_off, probes, k, stream=None, check=False, allow=None,
@@ -1333,70 +1046,29 @@ class Pq:
         assert codes.is_cuda and codes.dtype in (torch.uint8, torch.int32) and codes.dim() == 2
         assert tables.is_cuda and tables.dtype == torch.float32 and tables.is_contiguous()
         M, K = self.quantized_len(), self.n_quantizer_centroids()
-        if codes.shape[1] != M:
-            raise PanicError("Quantization length does not match number of subquantizers")
-        single = tables.dim() == 2
-        if tuple(tables.shape[-2:]) != (M, K):
-            raise PanicError("lookup tables must be [.., %d, %d]" % (M, K))
-        nq = 1 if single else tables.shape[0]
-        if codes.stride(1) != 1:
-            codes = codes.contiguous()
-        n, dev = codes.shape[0], codes.device
-        if hasattr(threshold, "is_cuda"):
-            thr = threshold.to(dev, torch.float32).reshape(-1)
-        else:
-            thr = torch.from_numpy(np.asarray(threshold, dtype=np.float32).reshape(-1).copy()).to(dev)
-        if thr.shape[0] == 1 and nq != 1:
-            thr = thr.expand(nq)
-        if thr.shape[0] != nq:
-            raise PanicError("one threshold, or one per query (%d), expected" % nq)
-        thr = thr.contiguous()
-        if scales is not None:
-            assert scales.is_cuda and scales.dtype == torch.float32 and scales.is_contiguous()
-            if tuple(scales.shape) != (n,):
-                raise PanicError("scales must hold one value per code row")
-        head = (tables.data_ptr(), nq, codes.data_ptr(), codes.element_size(), n,
-                codes.stride(0) if n > 1 else max(codes.stride(0), M),
-                self._mask_words(allow, codes).data_ptr() if allow is not None else None)
-        keep = []       # tensors made here that the call reads
+        W = _marshal.code_width(codes, M)
+        single, nq = _marshal.tables_arg(tables, M, K)
+        codes, n, c_rs = _marshal.codes_arg(codes, W)
+        dev = codes.device
+        thr = _marshal.threshold_arg(threshold, nq, dev)
+        _marshal.per_row_arg(scales, n, "scales")
+        mask = _marshal.mask_arg(allow, codes, True)
+        bias = ()
+        last = (ptr_or_none(scales),) if ip else ()
         if lists is not None:
             list_off, probes = lists
-            assert list_off.is_cuda and list_off.dtype == torch.int64 and list_off.dim() == 1 and list_off.is_contiguous()
-            assert probes.is_cuda and probes.dtype == torch.int64 and probes.dim() in (1, 2)
-            pr = probes[None] if probes.dim() == 1 else probes
-            if pr.shape[0] != nq or pr.shape[1] < 1 or list_off.shape[0] < 1:
-                raise PanicError("one probe row of at least one list id per query and n_lists + 1 offsets expected")
-            if pr.stride(1) != 1:
-                pr = pr.contiguous()
-            n_probe = pr.shape[1]
-            head += (list_off.data_ptr(), list_off.shape[0] - 1,
-                     pr.data_ptr(), n_probe, pr.stride(0) if nq > 1 else max(pr.stride(0), n_probe))
-            keep.append(pr)
+            _marshal.assert_lists(list_off, probes)
+            pr, n_probe, p_rs = _marshal.probes_arg(probes, list_off, nq)
+            lists = (list_off, pr, n_probe, p_rs)
             if residual:
-                assert probe_bias.is_cuda and probe_bias.dtype == torch.float32 and probe_bias.dim() in (1, 2)
-                pb = probe_bias[None] if probe_bias.dim() == 1 else probe_bias
-                if tuple(pb.shape) != (nq, n_probe):
-                    raise PanicError("one probe bias per query and probe slot expected")
-                if pb.stride(1) != 1:
-                    pb = pb.contiguous()
-                keep.append(pb)
-                head += (pb.data_ptr(), pb.stride(0) if nq > 1 else max(pb.stride(0), n_probe))
+                bias = _marshal.bias_arg(probe_bias, nq, n_probe)
                 if not ip:
-                    assert row_terms.is_cuda and row_terms.dtype == torch.float32 and row_terms.is_contiguous()
-                    if tuple(row_terms.shape) != (n,):
-                        raise PanicError("row_terms must hold one value per code row")
-                    # an empty tensor may have no address, and the C call wants one even when there is no row to read
-                    rt = row_terms if n > 0 else torch.zeros(1, dtype=torch.float32, device=dev)
-                    keep.append(rt)
-                    head += (rt.data_ptr(),)
-        if ip:
-            head += (scales.data_ptr() if scales is not None else None,)
-        cb = self._cb()
+                    _marshal.per_row_arg(row_terms, n, "row_terms")
+                    rt = _marshal.stand_in(row_terms, n, dev)       # the C call wants an address even without a row to read
+                    last = (rt.data_ptr(),)
         own_stream = stream is None
-        if own_stream:
-            stream = torch.cuda.current_stream(dev).cuda_stream
-        slot = self._slot_for(codes)
-        fn = getattr(_lib.lib(), name)
+        cb, slot, sp = _marshal.launch(self, codes, stream)
+        head = _marshal.search_head(cb, slot, tables, nq, codes, n, c_rs, False, mask, lists or (), bias, last)
         lims = torch.empty(nq + 1, dtype=torch.int64, device=dev)
         cap = (1 << 20) if capacity is None else int(capacity)
         if cap < 0:
@@ -1404,10 +1076,7 @@ class Pq:
         while True:
             val = torch.empty(cap, dtype=torch.float32, device=dev)
             idx = torch.empty(cap, dtype=torch.int64, device=dev)
-            rc = fn(cb, slot, *head, thr.data_ptr(), lims.data_ptr(), val.data_ptr() if cap else None,
-                    idx.data_ptr() if cap else None, cap, ctypes.c_void_p(stream))
-            if rc != _lib.OK:
-                raise _lib.PqHipError(rc, name)
+            _marshal.run(name, *head, thr.data_ptr(), lims.data_ptr(), ptr_or_none(val, cap), ptr_or_none(idx, cap), cap, sp)
             if not own_stream:
                 torch.cuda.ExternalStream(stream, device=dev).synchronize()
             total = int(lims[-1])
@@ -1415,12 +1084,7 @@ class Pq:
                 break
             cap = total             # the second call always suffices
         if check:
-            rc = _lib.lib().pqhip_check_codes_dev(cb, slot, ctypes.c_void_p(stream))
-            if rc == _lib.ECODE_RANGE:
-                raise PanicError("ndarray: index out of bounds")
-            if rc != _lib.OK:
-                raise _lib.PqHipError(rc, "pqhip_check_codes_dev")
-        del keep
+            _marshal.check_range(cb, slot, sp)
         return lims, val[:total], idx[:total]
 
     def adc_range_device(self, codes, tables, threshold, stream=None, check=False, allow=None, capacity=None):
@@ -1521,24 +1185,12 @@ class Pq:
             vectors = vectors.contiguous()
         val = torch.empty((nq, k), dtype=torch.float32, device=vectors.device)
         idx = torch.empty((nq, k), dtype=torch.int64, device=vectors.device)
-        cb = self._cb()
-        if stream is None:
-            stream = torch.cuda.current_stream(vectors.device).cuda_stream
-        slot = self._slot_for(vectors)
-        rc = _lib.lib().pqhip_rerank_f32_dev(
-            cb, slot, q2.data_ptr(), nq, q2.stride(0) if nq > 1 else max(q2.stride(0), d),
-            vectors.data_ptr() if N > 0 else None, vectors.element_size(), N, d,
-            vectors.stride(0) if N > 1 else max(vectors.stride(0), d),
-            c2.data_ptr(), n_cand, c2.stride(0) if nq > 1 else max(c2.stride(0), n_cand),
-            1 if ip else 0, k, val.data_ptr(), k, idx.data_ptr(), k, ctypes.c_void_p(stream))
-        if rc != _lib.OK:
-            raise _lib.PqHipError(rc, "pqhip_rerank_f32_dev")
+        cb, slot, sp = _marshal.launch(self, vectors, stream)
+        _marshal.run("pqhip_rerank_f32_dev", cb, slot, q2.data_ptr(), nq, row_stride(q2, nq, d),
+                     ptr_or_none(vectors, N), vectors.element_size(), N, d, row_stride(vectors, N, d),
+                     c2.data_ptr(), n_cand, row_stride(c2, nq, n_cand), 1 if ip else 0, k, val.data_ptr(), k, idx.data_ptr(), k, sp)
         if check:
-            rc = _lib.lib().pqhip_check_codes_dev(cb, slot, ctypes.c_void_p(stream))
-            if rc == _lib.ECODE_RANGE:
-                raise PanicError("ndarray: index out of bounds")
-            if rc != _lib.OK:
-                raise _lib.PqHipError(rc, "pqhip_check_codes_dev")
+            _marshal.check_range(cb, slot, sp)
         return (val[0], idx[0]) if single else (val, idx)
 
     # ---- growing a partitioned matrix: merge of two list-ordered arrays ------------------------------------------------
@@ -1581,32 +1233,14 @@ class Pq:
         if out is None:
             out = torch.empty(shape, dtype=a.dtype, device=a.device)
         off_out = torch.empty(n_lists + 1, dtype=torch.int64, device=a.device)
-        cb = self._cb()
-        if stream is None:
-            stream = torch.cuda.current_stream(a.device).cuda_stream
-        slot = self._slot_for(a)
-        rc = _lib.lib().pqhip_lists_merge_dev(
-            cb, slot, list_off_a.data_ptr(), n_a, list_off_b.data_ptr(), n_b, n_lists, row_bytes,
-            a.data_ptr() if n_a else None, b.data_ptr() if n_b else None, out.data_ptr() if n_a + n_b else None,
-            off_out.data_ptr(), ctypes.c_void_p(stream))
-        if rc != _lib.OK:
-            raise _lib.PqHipError(rc, "pqhip_lists_merge_dev")
+        cb, slot, sp = _marshal.launch(self, a, stream)
+        _marshal.run("pqhip_lists_merge_dev", cb, slot, list_off_a.data_ptr(), n_a, list_off_b.data_ptr(), n_b, n_lists,
+                     row_bytes, ptr_or_none(a, n_a), ptr_or_none(b, n_b), ptr_or_none(out, n_a + n_b), off_out.data_ptr(), sp)
         if check:
-            rc = _lib.lib().pqhip_check_codes_dev(cb, slot, ctypes.c_void_p(stream))
-            if rc == _lib.ECODE_RANGE:
-                raise PanicError("ndarray: index out of bounds")
-            if rc != _lib.OK:
-                raise _lib.PqHipError(rc, "pqhip_check_codes_dev")
+            _marshal.check_range(cb, slot, sp)
         return out, off_out
 
     # ---- building a partitioned matrix on the device: list layout, residuals, query-free row terms -----------------------
-    def _raise_range(self, cb, slot, stream):
-        rc = _lib.lib().pqhip_check_codes_dev(cb, slot, ctypes.c_void_p(stream))
-        if rc == _lib.ECODE_RANGE:
-            raise PanicError("ndarray: index out of bounds")
-        if rc != _lib.OK:
-            raise _lib.PqHipError(rc, "pqhip_check_codes_dev")
-
     def lists_layout_device(self, assign, n_lists, want_lists=False, stream=None, check=False):
         """assign: CUDA int32 or int64 vector [n] of list ids in [0, n_lists), contiguous -> (ids, list_off, positions) or,
         with want_lists, (ids, list_off, positions, lists), all CUDA int64: what qmatrix.ivf_layout defines, computed on
@@ -1632,18 +1266,11 @@ class Pq:
         positions = torch.empty(n, dtype=torch.int64, device=dev)
         lists = torch.empty(n, dtype=torch.int64, device=dev) if want_lists else None
         list_off = torch.empty(n_lists + 1, dtype=torch.int64, device=dev)
-        cb = self._cb()
-        if stream is None:
-            stream = torch.cuda.current_stream(dev).cuda_stream
-        slot = self._slot_for(assign)
-        rc = _lib.lib().pqhip_lists_layout_dev(
-            cb, slot, assign.data_ptr() if n else None, assign.element_size(), n, n_lists, list_off.data_ptr(),
-            ids.data_ptr() if n else None, positions.data_ptr() if n else None,
-            lists.data_ptr() if want_lists and n else None, ctypes.c_void_p(stream))
-        if rc != _lib.OK:
-            raise _lib.PqHipError(rc, "pqhip_lists_layout_dev")
+        cb, slot, sp = _marshal.launch(self, assign, stream)
+        _marshal.run("pqhip_lists_layout_dev", cb, slot, ptr_or_none(assign, n), assign.element_size(), n, n_lists,
+                     list_off.data_ptr(), ptr_or_none(ids, n), ptr_or_none(positions, n), ptr_or_none(lists, n), sp)
         if check:
-            self._raise_range(cb, slot, stream)
+            _marshal.check_range(cb, slot, sp)
         return (ids, list_off, positions, lists) if want_lists else (ids, list_off, positions)
 
     @staticmethod
@@ -1684,18 +1311,11 @@ class Pq:
             raise PanicError("all tensors of residuals_device must live on one device")
         if out is None:
             out = torch.empty((n, d), dtype=torch.float32, device=x.device)
-        cb = self._cb()
-        if stream is None:
-            stream = torch.cuda.current_stream(x.device).cuda_stream
-        slot = self._slot_for(x)
-        rc = _lib.lib().pqhip_residuals_f32_dev(
-            cb, slot, x.data_ptr() if n else None, n, d, x.stride(0) if n > 1 else max(x.stride(0), d),
-            assign.data_ptr() if n else None, centroids.data_ptr(), centroids.shape[0],
-            out.data_ptr() if n else None, out.stride(0) if n > 1 else max(out.stride(0), d), ctypes.c_void_p(stream))
-        if rc != _lib.OK:
-            raise _lib.PqHipError(rc, "pqhip_residuals_f32_dev")
+        cb, slot, sp = _marshal.launch(self, x, stream)
+        _marshal.run("pqhip_residuals_f32_dev", cb, slot, ptr_or_none(x, n), n, d, row_stride(x, n, d), ptr_or_none(assign, n),
+                     centroids.data_ptr(), centroids.shape[0], ptr_or_none(out, n), row_stride(out, n, d), sp)
         if check:
-            self._raise_range(cb, slot, stream)
+            _marshal.check_range(cb, slot, sp)
         return out
 
     def residual_terms_device(self, codes, assign, centroids, out=None, stream=None, check=False):
@@ -1730,17 +1350,10 @@ class Pq:
             raise PanicError("all tensors of residual_terms_device must live on one device")
         if out is None:
             out = torch.empty(n, dtype=torch.float32, device=codes.device)
-        cb = self._cb()
-        if stream is None:
-            stream = torch.cuda.current_stream(codes.device).cuda_stream
-        slot = self._slot_for(codes)
-        M = self.quantized_len()
-        rc = _lib.lib().pqhip_residual_terms_f32_dev(
-            cb, slot, codes.data_ptr() if n else None, n, codes.stride(0) if n > 1 else max(codes.stride(0), M),
-            assign.data_ptr() if n else None, centroids.data_ptr(), centroids.shape[0],
-            out.data_ptr() if n else None, ctypes.c_void_p(stream))
-        if rc != _lib.OK:
-            raise _lib.PqHipError(rc, "pqhip_residual_terms_f32_dev")
+        cb, slot, sp = _marshal.launch(self, codes, stream)
+        _marshal.run("pqhip_residual_terms_f32_dev", cb, slot, ptr_or_none(codes, n), n,
+                     row_stride(codes, n, self.quantized_len()), ptr_or_none(assign, n), centroids.data_ptr(),
+                     centroids.shape[0], ptr_or_none(out, n), sp)
         if check:
-            self._raise_range(cb, slot, stream)
+            _marshal.check_range(cb, slot, sp)
         return out
