@@ -551,6 +551,62 @@ int32_t pqhip_adc_ip_range_lists_residual_f32_dev(pqhip_codebook *cb, int32_t de
                                                   int64_t *d_idx, int64_t capacity, void *stream);
 
 /*
+ * ADC search among given rows: exact top-k over per-query lists of candidate ids -- "rank exactly these rows".  The
+ * searches above decide by themselves which rows they read (all rows, the rows of the probed lists, either under one
+ * mask shared by the queries of a call); here the caller names the rows of every query: a tenant's rows, what a range
+ * search has just returned (its lims and idx as they are), a graph's neighbour lists, a shortlist from another index,
+ * or the allowed rows of a very sparse filter.
+ * Candidate set.  C_q is the set of entries of d_ids[lims[q] .. lims[q + 1]) that lie in [0, n_codes); with d_lims ==
+ * NULL every query takes d_ids[0 .. n_ids).  -1 is padding and is skipped; any other value outside the range is skipped
+ * and raises the stream's range flag (pqhip_check_codes_dev -> PQHIP_ECODE_RANGE).  An id named twice is a caller error
+ * and may be returned twice (the wording of pqhip_rerank_f32_dev).  Ids need not be sorted.
+ * d_lims is device memory and is not trusted: both ends are clamped to [0, n_ids] and an inverted range is empty; both
+ * cases raise the flag.  No byte outside d_ids[0 .. n_ids) is read.
+ * Values.  With s the scan's sequential f32 row sum, the value of row i for query q is the list producers', operation
+ * for operation.  Plain (d_row_list == d_list_bias == NULL): s, resp. fl(s * scale[i]) (s alone with d_scales == NULL).
+ * Residual (both non-NULL): fl(fl(b + term[i]) - fl(s + s)), resp. fl(fl(b + s) * scale[i]), with b =
+ * d_list_bias[q][d_row_list[i]]; d_tables are the INNER-PRODUCT tables in both residual calls; d_row_list [n_codes]
+ * holds the list of every row and d_list_bias [n_queries][bias_row_stride] one value per (query, list), |q - c_l|^2
+ * resp. <q, c_l>.  A d_row_list[i] outside [0, n_lists) on a named row skips the row and raises the flag.
+ * Result.  Row q of the outputs receives the first min(k, |C_q|) members of C_q ordered by (key(value), row id), resp.
+ * (key(-score), row id); key, the canonical NaN, zero as +0 and the padding (-1 with +Inf / -Inf) are those of
+ * pqhip_adc_search_f32_dev / pqhip_adc_ip_search_f32_dev.  The order is strict, so the result does not depend on the
+ * order of the ids, the grid or the chunking.  Hence for distinct in-range ids the result equals, bit for bit, that of
+ * pqhip_adc_search_masked_f32_dev / pqhip_adc_ip_search_masked_f32_dev with the mask of C_q, run for that query alone,
+ * and in the residual form that of pqhip_adc_*search_lists_residual_masked_f32_dev probing every list once with
+ * bias[q][p] = d_list_bias[q][probe p] and the same mask.
+ * A row that is not named is not read: its codes are not interpreted (a code >= K there raises nothing) and its scale,
+ * term and list id enter nothing.  A named row's code >= K reads entry 0 and raises the flag.
+ * Status codes follow the precedence of pqhip_adc_search_lists_f32_dev.  PQHIP_EINVAL: cb == NULL, k < 1, a negative
+ * count; then PQHIP_ENODEV; then PQHIP_EUNSUPPORTED: code_bytes != 1, more than 100 subquantizers, a table that does not
+ * fit LDS beside the queues, k > 1024, n_codes > 2^32 - 2.  n_queries == 0 launches nothing and returns PQHIP_OK.  Then
+ * PQHIP_EINVAL: a NULL output, d_ids == NULL with n_ids > 0, NULL tables or codes with rows to read, only one of
+ * d_row_list / d_list_bias given, d_row_terms == NULL in the residual distance call; then PQHIP_ESHAPE: codes_row_stride
+ * below the row length, an output stride below k, bias_row_stride < n_lists.  n_ids == 0 or n_codes == 0 writes the
+ * padding only.  Anything not served is PQHIP_EUNSUPPORTED, never another path.
+ * Host policy: the workgroups that share a query are chosen from the mean number of ids per query (n_ids / n_queries,
+ * n_ids with d_lims == NULL) -- at least 4,096 places each, bounded by the CU count over the queries of a launch; option
+ * "adc_among_wgs_per_query" forces the number.  The partial lists live in the codebook's scratch; queries are processed
+ * in chunks that keep them within 512 MB.  One query per workgroup set, also for a shared list.
+ */
+int32_t pqhip_adc_among_f32_dev(pqhip_codebook *cb, int32_t device_slot, const float *d_tables, int64_t n_queries,
+                                const void *d_codes, int32_t code_bytes, int64_t n_codes, int64_t codes_row_stride,
+                                const int64_t *d_lims /* [n_queries + 1] or NULL */, const int64_t *d_ids, int64_t n_ids,
+                                const int64_t *d_row_list /* [n_codes] or NULL */, int64_t n_lists,
+                                const float *d_list_bias /* [n_queries][bias_row_stride] or NULL */, int64_t bias_row_stride,
+                                const float *d_row_terms /* [n_codes]; residual form only */,
+                                int32_t k, float *d_dist, int64_t dist_row_stride, int64_t *d_idx, int64_t idx_row_stride,
+                                void *stream);
+int32_t pqhip_adc_ip_among_f32_dev(pqhip_codebook *cb, int32_t device_slot, const float *d_tables, int64_t n_queries,
+                                   const void *d_codes, int32_t code_bytes, int64_t n_codes, int64_t codes_row_stride,
+                                   const int64_t *d_lims /* [n_queries + 1] or NULL */, const int64_t *d_ids, int64_t n_ids,
+                                   const int64_t *d_row_list /* [n_codes] or NULL */, int64_t n_lists,
+                                   const float *d_list_bias /* [n_queries][bias_row_stride] or NULL */, int64_t bias_row_stride,
+                                   const float *d_scales /* [n_codes] or NULL */,
+                                   int32_t k, float *d_score, int64_t score_row_stride, int64_t *d_idx, int64_t idx_row_stride,
+                                   void *stream);
+
+/*
  * Exact re-ranking of search candidates against resident vectors ("IVFADC+R", refine): the stage after an ADC search
  * that replaces the quantizer's estimate by the distance to the stored vector.  For query q, the first n_cand entries of
  * row q of d_cand [n_queries][cand_row_stride] int64 name rows of d_vectors [n_rows][vec_row_stride], vec_bytes = 4 (f32)
@@ -819,6 +875,8 @@ int32_t pqhip_set_rotation_variant(int32_t variant);
  *   "opq_gather_rotation"  0 = OPQ reconstruct as gather -> scratch -> rotation (default 1)
  *   "adc_single_query"     1 = one scan pass per query (default 0: 8 / 4 queries share a pass)
  *   "adc_lists_wgs_per_query"  workgroups that share one query of the list searches (0 = chosen from the shape; at most 4096)
+ *   "adc_among_wgs_per_query"  workgroups that share one query of the searches among given rows (0 = chosen from the
+ *                          mean number of ids per query; at most 4096)
  *   "adc_range_wgs"        producer workgroups of the exhaustive range searches (0 = chosen from the shape; at most 8192,
  *                          so that the one-workgroup prefix scan of a pass sums at most 2^20 counts)
  *   "adc_range_wgs_per_query"  workgroups that share one query of the list range searches (0 = chosen from the shape; at

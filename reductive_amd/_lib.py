@@ -136,6 +136,9 @@ def _signatures():
             sig[search + "_masked_f32_dev"] = (i32, [vp, i32, vp, i64, vp, i32, i64, i64, vp] + mid + topk)
             sig[search + "_packed4_f32_dev"] = (i32, [vp, i32, vp, i64, vp, i64, i64, vp] + mid + topk)
             sig[rng] = (i32, [vp, i32, vp, i64, vp, i32, i64, i64, vp] + mid + csr)
+    # The two searches among given rows: lims, ids, n_ids; row_list, n_lists; list_bias, its row stride; row terms / scales
+    for name in ("pqhip_adc_among_f32_dev", "pqhip_adc_ip_among_f32_dev"):
+        sig[name] = (i32, [vp, i32, vp, i64, vp, i32, i64, i64, vp, vp, i64, vp, i64, vp, i64, vp] + topk)
     return sig
 
 

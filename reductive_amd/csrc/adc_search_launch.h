@@ -128,6 +128,11 @@ constexpr size_t kListsScratchBytes = 512u << 20;   // plan + partial lists of o
 int32_t launch_lists_plan(const int64_t* d_list_off, int64_t n_lists, const int64_t* d_probes, int n_probe, int64_t p_rs, int64_t n,
                           int64_t* seg_begin, int64_t* seg_cum, unsigned nq, int* err, hipStream_t st);
 
+// pqhip_adc.hip: the door to k_adc_search_merge for a producer of another unit (pqhip_adc_among.hip): merges the G partial
+// lists [nq][G][64 L] of nq <= 65535 queries into the outputs; G == 0 writes the padding only, for any nq.
+int32_t adc_search_merge(bool ip, int L, int64_t nq, int G, int k, const unsigned* part_k, const uint64_t* part_i, float* d_val,
+                         int64_t v_rs, int64_t* d_idx, int64_t i_rs, hipStream_t st);
+
 // pqhip_adc_packed4_lists.hip: the list producers over 4-bit packed codes (kernels_adc_packed4.hip.h), a unit of their
 // own so that the build compiles them beside the exhaustive ones.  nvb in {2, 8, 13} packed dwords; a.allow and a.bias
 // may be null.

@@ -127,6 +127,14 @@ int32_t search_padding_only(bool ip, int L, int64_t nq, int k, float* d_val, int
     return PQHIP_OK;
 }
 
+// the door of adc_search_launch.h
+int32_t adc_search_merge(bool ip, int L, int64_t nq, int G, int k, const unsigned* part_k, const uint64_t* part_i, float* d_val,
+                         int64_t v_rs, int64_t* d_idx, int64_t i_rs, hipStream_t st)
+{
+    if (G == 0) return search_padding_only(ip, L, nq, k, d_val, v_rs, d_idx, i_rs, st);
+    return launch_search_merge(ip, L, (int)nq, G, k, part_k, part_i, d_val, v_rs, d_idx, i_rs, st);
+}
+
 // Lookup tables for both searches: the query is rotated first for an OPQ codebook (pq.rs:293), then one thread per
 // (q, m, j) writes the squared distance (k_adc_tables) or, IP, the inner product alone (k_adc_ip_tables).
 int32_t adc_tables(bool ip, pqhip_codebook* cb, int32_t slot, const float* d_q, int64_t nq, int64_t q_rs, float* d_tables,

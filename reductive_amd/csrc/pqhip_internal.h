@@ -10,6 +10,7 @@
 //     pqhip_adc.hip       asymmetric-distance tables and scans
 //     pqhip_adc_packed4.hip  4-bit packed codes: pack / unpack and the searches over packed rows (list producers:
 //                         pqhip_adc_packed4_lists.hip)
+//     pqhip_adc_among.hip ADC search among given rows: top-k over per-query candidate id lists
 //     pqhip_adc_range.hip ADC range search: every row within a radius, as CSR
 //     pqhip_rerank.hip    exact re-ranking of search candidates against resident vectors
 //     pqhip_lists_merge.hip  merge of two list-ordered row arrays (growing a partitioned matrix)
@@ -100,6 +101,7 @@ struct Options {
     std::atomic<int64_t> adc_packed4_wgs{0};        // exhaustive searches over 4-bit packed codes: producer workgroups (0: chosen from the shape)
     std::atomic<int64_t> adc_search_wgs{0};         // exhaustive u8 / masked / generic searches: producer workgroups (0: chosen from the shape)
     std::atomic<int64_t> lists_layout_wgs{0};       // list layout: workgroups, one row slice each (0: chosen from the size)
+    std::atomic<int64_t> adc_among_wgs_per_query{0};   // searches among given rows: workgroups per query (0: chosen from the mean number of ids)
 };
 
 struct Diag {

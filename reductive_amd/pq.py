@@ -1032,6 +1032,95 @@ class Pq:
         return self._adc_search_lists(True, codes, ip_tables, list_off, probes, k, scales, stream, check,
                                       probe_bias=probe_bias, allow=allow, packed4=packed4)
 
+    # ---- ADC search among given rows: exact top-k over per-query candidate id lists ------------------------------------
+    def _adc_among(self, ip, codes, tables, ids, k, lims, row_list, list_bias, extra, what, stream, check):
+        """Both candidate searches; row_list and list_bias given: the residual forms.  extra: the scales (ip) or the row
+        terms, named `what`."""
+        import torch
+        name = "pqhip_adc_%samong_f32_dev" % ("ip_" if ip else "")
+        M, K = self.quantized_len(), self.n_quantizer_centroids()
+
+        def vector(t, dtype, text):
+            if not (hasattr(t, "is_cuda") and t.dtype == dtype and t.dim() == 1 and t.is_contiguous()):
+                raise PanicError(text)
+
+        if not (hasattr(codes, "is_cuda") and codes.dtype == torch.uint8 and codes.dim() == 2):
+            raise PanicError("codes must be a uint8 [n, n_subquantizers] tensor (4-byte and packed codes are not served)")
+        if not (hasattr(tables, "is_cuda") and tables.dtype == torch.float32 and tables.dim() in (2, 3) and tables.is_contiguous()):
+            raise PanicError("lookup tables must be a contiguous float32 tensor")
+        W = _marshal.code_width(codes, M)
+        single, nq = _marshal.tables_arg(tables, M, K)
+        vector(ids, torch.int64, "candidate ids must be one contiguous int64 vector, shared or cut per query by lims")
+        if lims is not None:
+            vector(lims, torch.int64, "lims must be a contiguous int64 vector")
+            if lims.shape[0] != nq + 1:
+                raise PanicError("lims must hold one offset per query and the end (%d)" % (nq + 1))
+        if not isinstance(k, int) or k < 1:
+            raise PanicError("k must be a positive integer")
+        n = codes.shape[0]
+        if extra is not None:
+            vector(extra, torch.float32, "%s must be a contiguous float32 vector" % what)
+            if extra.shape[0] != n:
+                raise PanicError("%s must hold one value per code row" % what)
+        if (row_list is None) != (list_bias is None):
+            raise PanicError("the residual candidate search needs the list of every row and a bias per list")
+        residual = row_list is not None
+        n_lists, lb, b_rs = 0, None, 0
+        if residual:
+            vector(row_list, torch.int64, "row_list must be a contiguous int64 vector")
+            if row_list.shape[0] != n:
+                raise PanicError("row_list must hold one list id per code row")
+            if not (hasattr(list_bias, "is_cuda") and list_bias.dtype == torch.float32 and list_bias.dim() in (1, 2)):
+                raise PanicError("list_bias must be a float32 [nq, n_lists] tensor")
+            lb = list_bias[None] if list_bias.dim() == 1 else list_bias
+            if lb.shape[0] != nq:
+                raise PanicError("one row of list biases per query expected")
+            if not ip and extra is None:
+                raise PanicError("the residual distance search needs the row terms")
+        given = [t for t in (codes, tables, ids, lims, extra, row_list, list_bias) if t is not None]
+        if not all(t.is_cuda and t.device == codes.device for t in given):
+            raise PanicError("the candidate search expects CUDA tensors on one device")
+        codes, n, c_rs = _marshal.codes_arg(codes, W)
+        _marshal.per_row_arg(extra, n, what)
+        if residual:
+            n_lists = lb.shape[1]
+            lb = _marshal.stand_in(_marshal.unit_columns(lb), n_lists, codes.device, 1)
+            b_rs = _marshal.row_stride(lb, nq, max(n_lists, 1))
+            row_list = _marshal.stand_in(row_list, n, codes.device)      # the C call tells the residual form by the address
+            if not ip:
+                extra = _marshal.stand_in(extra, n, codes.device)
+        n_ids = ids.shape[0]
+        val = torch.empty((nq, k), dtype=torch.float32, device=codes.device)
+        idx = torch.empty((nq, k), dtype=torch.int64, device=codes.device)
+        cb, slot, sp = _marshal.launch(self, codes, stream)
+        _marshal.run(name, cb, slot, tables.data_ptr(), nq, codes.data_ptr(), codes.element_size(), n, c_rs, ptr_or_none(lims),
+                     ptr_or_none(ids, n_ids), n_ids, ptr_or_none(row_list), n_lists, ptr_or_none(lb), b_rs,
+                     ptr_or_none(extra, extra is not None and extra.shape[0]) if (ip or residual) else None,
+                     k, val.data_ptr(), k, idx.data_ptr(), k, sp)
+        if check:
+            _marshal.check_range(cb, slot, sp)
+        return (val[0], idx[0]) if single else (val, idx)
+
+    def adc_among_device(self, codes, tables, ids, k, lims=None, row_list=None, list_bias=None, row_terms=None,
+                         stream=None, check=False):
+        """adc_search_device among given rows: ids CUDA int64 [n_ids] names the candidates -- of every query (lims None),
+        or ids[lims[q] : lims[q + 1]] of query q (lims CUDA int64 [nq + 1], as a range search returns it) -> (dist, idx)
+        [nq, k] ([k] for 2-D tables), the first k candidates by (distance, row).  -1 is padding; any other id outside
+        [0, n) is skipped and, like a bad lims, raises the range flag (check=True); an id named twice may come back
+        twice.  A row that is not named is not read.  For distinct ids the result is adc_search_device's with the mask
+        of the candidates (pqhip_adc_among_f32_dev).  Residual codes: row_list CUDA int64 [n] (the list of every row),
+        list_bias CUDA float32 [nq, n_lists] (|q - c_l|^2 per list), row_terms CUDA float32 [n] and INNER-PRODUCT tables,
+        dist = fl(fl(bias + term) - fl(s + s)) as adc_search_lists_residual_device forms it."""
+        return self._adc_among(False, codes, tables, ids, k, lims, row_list, list_bias, row_terms, "row_terms", stream,
+                               check)
+
+    def adc_ip_among_device(self, codes, tables, ids, k, lims=None, row_list=None, list_bias=None, scales=None,
+                            stream=None, check=False):
+        """adc_ip_search_device among given rows (arguments as for adc_among_device, tables from adc_ip_tables_device,
+        scales None or CUDA float32 [n]) -> (score, idx), the first k candidates by (descending score, row).  Residual
+        codes: list_bias holds <q, c_l> per list, score = fl(fl(bias + s) * scale) (pqhip_adc_ip_among_f32_dev)."""
+        return self._adc_among(True, codes, tables, ids, k, lims, row_list, list_bias, scales, "scales", stream, check)
+
     # ---- ADC range search: every row within a radius / at or above a similarity, as CSR ------------------------------
     def _adc_range(self, ip, codes, tables, threshold, scales, stream, check, allow, capacity, lists=None, probe_bias=None,
                    row_terms=None):

@@ -309,7 +309,68 @@ class _Packed4:
         return self.pq.reconstruct_rows_device(codes, sel, scales=None if scales is None else scales[pos].contiguous(), out=out)
 
 
-class QuantizedMatrix(_Refine, _Filter, _Packed4):
+class _Among:
+    """Searches among given rows for all three matrix classes: nearest_among() / most_similar_among() rank exactly the
+    rows the caller names (Pq.adc_among_device / adc_ip_among_device) -- a tenant's rows, the result of a range search,
+    a shortlist from another index -- and read no other row.  Not served on a packed matrix: unpack4() first."""
+
+    def _among_rows(self, rows):
+        """rows= -> (lims or None, row numbers): one int64 vector shared by all queries, or the pair (lims, rows) that
+        within() / similar_above() return; numpy or torch, brought to the device of the codes"""
+        import torch
+        dev = self.codes.device
+
+        def vector(t, what):
+            if not hasattr(t, "is_cuda"):
+                t = np.asarray(t)
+                if t.dtype.kind not in "iu":
+                    raise PanicError("%s must be integers" % what)
+                t = torch.from_numpy(np.ascontiguousarray(t, dtype=np.int64))
+            if t.is_floating_point() or t.dtype == torch.bool or t.dim() != 1:
+                raise PanicError("%s must be a vector of integers" % what)
+            return t.to(dev, torch.int64).contiguous()
+
+        if isinstance(rows, tuple):
+            if len(rows) != 2:
+                raise PanicError("rows must be a vector of row numbers or the pair (lims, rows)")
+            return vector(rows[0], "lims"), vector(rows[1], "rows")
+        return None, vector(rows, "rows")
+
+    def _among_ids(self, rows):
+        """original row numbers -> what the kernel is given; the unpartitioned matrix stores rows under their numbers"""
+        return rows
+
+    def _among_result(self, queries, val, idx, k, refine, ip):
+        return (val, idx) if refine is None else self._refined(queries, idx, k, ip)
+
+    def _among(self, ip, queries, rows, k, use_norms, refine, check):
+        self._unpacked_only("most_similar_among" if ip else "nearest_among")
+        R = k if refine is None else self._check_refine(k, refine)
+        lims, rows = self._among_rows(rows)
+        tables = self.pq.adc_ip_tables_device(queries) if ip else self.pq.adc_tables_device(queries)
+        if ip:
+            val, idx = self.pq.adc_ip_among_device(self.codes, tables, self._among_ids(rows), R, lims=lims,
+                                                   scales=self.norms if use_norms else None, check=check)
+        else:
+            val, idx = self.pq.adc_among_device(self.codes, tables, self._among_ids(rows), R, lims=lims, check=check)
+        return self._among_result(queries, val, idx, k, refine, ip)
+
+    def nearest_among(self, queries, rows, k, refine=None, check=False):
+        """nearest() among the rows that `rows` names and no others: a vector of ORIGINAL row numbers shared by all
+        queries, or the pair (lims, rows) -- the rows of query q are rows[lims[q]:lims[q + 1]], exactly what within() /
+        similar_above() return -> (dist, idx) [k] or [nq, k], the k nearest of them, ties to the smaller row (a
+        partitioned matrix: to the smaller position in list order), index -1 and +Inf past the last.  -1 is padding; any
+        other number outside [0, N) is skipped (check=True: the reference's index panic); a row named twice may come
+        back twice.  For distinct rows the result is nearest(queries, k, allow=<flags of the rows>) -- with all lists
+        probed on a partitioned matrix -- at the cost of the named rows alone.  refine=R: as for nearest()."""
+        return self._among(False, queries, rows, k, True, refine, check)
+
+    def most_similar_among(self, queries, rows, k, use_norms=True, refine=None, check=False):
+        """most_similar() among the rows that `rows` names (as for nearest_among) -> (score, idx), largest first."""
+        return self._among(True, queries, rows, k, use_norms, refine, check)
+
+
+class QuantizedMatrix(_Refine, _Filter, _Packed4, _Among):
     """Codes (+ norms) resident in HBM next to the device codebook: the lookup, scan and similarity-search consumer."""
 
     def __init__(self, pq, codes, norms=None, device="cuda:0"):
@@ -582,7 +643,7 @@ def ivf_layout(assign, n_lists):
     return perm, list_off
 
 
-class _Lists(_Refine, _Filter, _Packed4):
+class _Lists(_Refine, _Filter, _Packed4, _Among):
     """What both partitioned forms share: the list layout, the coarse quantizer and the probe selection."""
 
     device_terms = False        # ResidualPartitionedMatrix: the row terms come from Pq.residual_terms_device
@@ -648,6 +709,19 @@ class _Lists(_Refine, _Filter, _Packed4):
     def _original_rows(self, pos):
         import torch
         return torch.where(pos < 0, pos, self.ids[pos.clamp(min=0)])
+
+    def _among_ids(self, rows):
+        """original row numbers -> positions, without an index out of bounds on the device: the gather is clamped, -1
+        stays -1 and any other number outside [0, N) becomes N, which the kernel skips and flags"""
+        import torch
+        n = len(self)
+        inside = (rows >= 0) & (rows < n)
+        pos = self.positions[rows.clamp(0, n - 1)] if n else torch.zeros_like(rows)
+        return torch.where(inside, pos, torch.where(rows == -1, rows, torch.full_like(rows, n))).contiguous()
+
+    def _among_result(self, queries, val, pos, k, refine, ip):
+        rows = self._original_rows(pos)
+        return (val, rows) if refine is None else self._refined(queries, rows, k, ip)
 
     # ---- growth: every method returns a NEW matrix and leaves self (and the row filters built for it) untouched ----
     def assign(self, vectors):
@@ -911,6 +985,23 @@ class ResidualPartitionedMatrix(_Lists):
         return lims, sc, rows
 
     _ROW_ARRAYS = ("codes", "norms", "row_terms", "lists")
+
+    def _among(self, ip, queries, rows, k, use_norms, refine, check):
+        """the residual forms: the list of every position, the row terms / norms and, as the bias of every list, the
+        full row of the coarse table -- |q - c_l|^2 resp. <q, c_l> -- so a candidate need not lie in a probed list"""
+        self._unpacked_only("most_similar_among" if ip else "nearest_among")
+        R = k if refine is None else self._check_refine(k, refine)
+        lims, rows = self._among_rows(rows)
+        ct = self.coarse.adc_ip_tables_device(queries) if ip else self.coarse.adc_tables_device(queries)
+        bias = ct[0] if queries.dim() == 1 else ct[:, 0, :]
+        tables = self.pq.adc_ip_tables_device(queries)
+        if ip:
+            val, pos = self.pq.adc_ip_among_device(self.codes, tables, self._among_ids(rows), R, lims=lims, row_list=self.lists,
+                                                   list_bias=bias, scales=self.norms if use_norms else None, check=check)
+        else:
+            val, pos = self.pq.adc_among_device(self.codes, tables, self._among_ids(rows), R, lims=lims, row_list=self.lists,
+                                                list_bias=bias, row_terms=self.row_terms, check=check)
+        return self._among_result(queries, val, pos, k, refine, ip)
 
     def encode(self, vectors):
         """What the matrix would store for `vectors` ([B, d] float32, numpy or CUDA) -> (lists int64 [B], codes u8 [B, M],

@@ -81,6 +81,19 @@ extern "C" {
         d_list_off: *const i64, n_lists: i64, d_probes: *const i64, n_probe: i32, probes_row_stride: i64,
         d_probe_bias: *const f32, bias_row_stride: i64, d_scales: *const f32, k: i32, d_score: *mut f32,
         score_row_stride: i64, d_idx: *mut i64, idx_row_stride: i64, stream: *mut c_void) -> i32;
+    // the searches among given rows: query q ranks the entries of d_ids[lims[q] .. lims[q + 1]) (d_ids[0 .. n_ids) with
+    // d_lims NULL) that lie in [0, n_codes); -1 = padding; d_row_list and d_list_bias both given = the residual forms;
+    // option "adc_among_wgs_per_query" forces the workgroups that share a query
+    pub fn pqhip_adc_among_f32_dev(cb: *mut pqhip_codebook, device_slot: i32, d_tables: *const f32, n_queries: i64,
+        d_codes: *const c_void, code_bytes: i32, n_codes: i64, codes_row_stride: i64, d_lims: *const i64,
+        d_ids: *const i64, n_ids: i64, d_row_list: *const i64, n_lists: i64, d_list_bias: *const f32,
+        bias_row_stride: i64, d_row_terms: *const f32, k: i32, d_dist: *mut f32, dist_row_stride: i64,
+        d_idx: *mut i64, idx_row_stride: i64, stream: *mut c_void) -> i32;
+    pub fn pqhip_adc_ip_among_f32_dev(cb: *mut pqhip_codebook, device_slot: i32, d_tables: *const f32, n_queries: i64,
+        d_codes: *const c_void, code_bytes: i32, n_codes: i64, codes_row_stride: i64, d_lims: *const i64,
+        d_ids: *const i64, n_ids: i64, d_row_list: *const i64, n_lists: i64, d_list_bias: *const f32,
+        bias_row_stride: i64, d_scales: *const f32, k: i32, d_score: *mut f32, score_row_stride: i64,
+        d_idx: *mut i64, idx_row_stride: i64, stream: *mut c_void) -> i32;
     // the six searches restricted to an allowed set of rows: d_allow holds ceil(n_codes / 32) words in the row order of
     // d_codes, bit i & 31 of word i >> 5 set = row i may be returned; NULL = the unmasked call itself; option
     // "adc_search_wgs" forces the producer workgroups of the two exhaustive calls, as of their unmasked forms
