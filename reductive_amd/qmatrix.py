@@ -112,14 +112,42 @@ def sort_ranges(lims, val, idx, descending=False):
     return val[order], idx[order]
 
 
+def _on_device(a, dev, dtype=None, host_dtype=None):
+    """a host array (anything numpy converts, read as host_dtype) or a torch tensor -> a contiguous tensor on `dev`, of
+    `dtype` if given"""
+    import torch
+    if not hasattr(a, "is_cuda"):
+        a = torch.from_numpy(np.ascontiguousarray(a, dtype=host_dtype))
+    return (a.to(dev) if dtype is None else a.to(dev, dtype)).contiguous()
+
+
+def _positions(ids):
+    """ids [N] (ids[p] = the original row stored at position p) -> positions [N], positions[ids[p]] = p"""
+    import torch
+    positions = torch.empty_like(ids)
+    positions[ids] = torch.arange(ids.shape[0], dtype=torch.int64, device=ids.device)
+    return positions
+
+
+def _chunks(n, chunk=1 << 20):
+    """the row ranges (r0, r1) the build steps work through: [0, n) in pieces of at most 2^20 rows"""
+    return ((r0, min(n, r0 + chunk)) for r0 in range(0, n, chunk))
+
+
+def _clone(matrix, names=None):
+    """a new matrix of the class of `matrix` that shares its attributes: all it has set, or those of `names` it has set"""
+    new = object.__new__(type(matrix))
+    have = vars(matrix)
+    new.__dict__.update(have if names is None else {name: have[name] for name in names if name in have})
+    return new
+
+
 def _device_rows(vectors, width, dev, what="vectors"):
     """vectors [B, width] (numpy or torch, any float dtype torch converts) -> float32 [B, width] on `dev`, contiguous"""
     import torch
     if len(vectors.shape) != 2 or vectors.shape[1] != width:
         raise PanicError("%s must be [B, %d]" % (what, width))
-    if not hasattr(vectors, "is_cuda"):
-        vectors = torch.from_numpy(np.ascontiguousarray(vectors, dtype=np.float32))
-    return vectors.to(dev, torch.float32).contiguous()
+    return _on_device(vectors, dev, torch.float32, np.float32)
 
 
 def _batch_norms(norms, has_norms, B, dev):
@@ -129,17 +157,16 @@ def _batch_norms(norms, has_norms, B, dev):
         raise PanicError("norms are required for a matrix with norms and forbidden for one without")
     if norms is None:
         return None
-    if not hasattr(norms, "is_cuda"):
-        norms = torch.from_numpy(np.ascontiguousarray(norms, dtype=np.float32))
+    norms = _on_device(norms, dev, torch.float32, np.float32)
     if tuple(norms.shape) != (B,):
         raise PanicError("one norm per added vector expected")
-    return norms.to(dev, torch.float32).contiguous()
+    return norms
 
 
 def _residual_codes_terms(residual_pq, rows, c, codes_out):
     """What a residual matrix stores for `rows` [n, d] f32 of the lists whose centroids are `c` [n, d] (device tensors):
     the codes of rows - c go to codes_out [n, M]; returns the query-free terms t_i = sum_j (r^_ij^2 + 2 c_ij r^_ij),
-    accumulated in float64 and rounded once to f32.  The loop body of partition_residual and of encode()."""
+    accumulated in float64 and rounded once to f32.  The default route of _encode_residuals."""
     residual_pq.quantize_batch_device(rows - c, out=codes_out)
     r = residual_pq.reconstruct_batch_device(codes_out).double()
     return (r * r + 2.0 * c.double() * r).sum(1).float()
@@ -165,11 +192,30 @@ def _assign_device(coarse, n, rows_of_range, dev):
     `coarse` with a 4-byte index, in chunks of 2^20 rows; rows_of_range(r0, r1) gives the float32 device rows [r0, r1)"""
     import torch
     out = torch.empty((n, 1), dtype=torch.int32, device=dev)
-    chunk = 1 << 20
-    for r0 in range(0, n, chunk):
-        r1 = min(n, r0 + chunk)
+    for r0, r1 in _chunks(n):
         coarse.quantize_batch_device(rows_of_range(r0, r1), out=out[r0:r1])
     return out[:, 0].long()
+
+
+def _encode_residuals(residual_pq, n, rows_of_range, lists, centroids, device_terms):
+    """What a residual matrix stores for n rows, in chunks of 2^20 rows -> (codes u8 [n, M], row terms f32 [n]) on the
+    device: rows_of_range(r0, r1) gives the float32 device rows [r0, r1), `lists` int64 [n] the list of each row and
+    `centroids` [n_lists, d] the device centroids; device_terms chooses _residual_codes_terms_device (through one
+    residual buffer of a chunk's size) over _residual_codes_terms.  The loop of partition_residual and of encode()."""
+    import torch
+    dev = centroids.device
+    codes = torch.empty((n, residual_pq.quantized_len()), dtype=torch.uint8, device=dev)
+    terms = torch.empty(n, dtype=torch.float32, device=dev)
+    buf = None
+    if device_terms and n:
+        buf = torch.empty((min(1 << 20, n), centroids.shape[1]), dtype=torch.float32, device=dev)
+    for r0, r1 in _chunks(n):
+        rows = rows_of_range(r0, r1)
+        if device_terms:
+            _residual_codes_terms_device(residual_pq, rows, lists[r0:r1], centroids, codes[r0:r1], terms[r0:r1], buf)
+        else:
+            terms[r0:r1] = _residual_codes_terms(residual_pq, rows, centroids[lists[r0:r1]], codes[r0:r1])
+    return codes, terms
 
 
 class _Refine:
@@ -189,9 +235,7 @@ class _Refine:
             raise PanicError("vectors are kept as float32 or float16")
         if tuple(vectors.shape) != (len(self), self.pq.reconstructed_len()):
             raise PanicError("vectors must be [%d, %d]" % (len(self), self.pq.reconstructed_len()))
-        if not hasattr(vectors, "is_cuda"):
-            vectors = torch.from_numpy(np.ascontiguousarray(vectors))
-        self.vectors = vectors.to(self.codes.device, dtype).contiguous()
+        self.vectors = _on_device(vectors, self.codes.device, dtype)
         return self
 
     def _check_refine(self, k, refine):
@@ -233,18 +277,16 @@ class _Filter:
         if (allow is None) == (rows is None):
             raise PanicError("give either the flags of all rows or a list of row numbers")
         if rows is not None:
-            r = torch.as_tensor(np.asarray(rows, dtype=np.int64) if not hasattr(rows, "is_cuda") else rows,
-                                dtype=torch.int64, device=dev).reshape(-1)
+            r = _on_device(rows, dev, torch.int64, np.int64).reshape(-1)
             if r.numel() and (int(r.min()) < 0 or int(r.max()) >= N):
                 raise PanicError("row numbers must lie in [0, %d)" % N)
             flags = torch.full((N,), 0 if allowed else 1, dtype=torch.uint8, device=dev)
             flags[r] = 1 if allowed else 0
         else:
-            if not hasattr(allow, "is_cuda"):
-                allow = torch.from_numpy(np.ascontiguousarray(allow))
+            allow = _on_device(allow, dev)
             if allow.dtype != torch.bool or tuple(allow.shape) != (N,):
                 raise PanicError("allow must be a bool array with one flag per row (%d)" % N)
-            flags = allow.to(dev).contiguous().view(torch.uint8)
+            flags = allow.view(torch.uint8)
         words = self.pq.pack_row_mask_device(flags, perm=getattr(self, "ids", None))
         return RowFilter(self, words, int(flags.count_nonzero()))
 
@@ -269,8 +311,7 @@ class _Packed4:
     packed4 = False
 
     def _with_codes(self, codes, packed4):
-        new = object.__new__(type(self))
-        new.__dict__.update(self.__dict__)      # norms, ids, positions, lists, row terms, centroids, vectors: shared
+        new = _clone(self)      # norms, ids, positions, lists, row terms, centroids, vectors: shared
         new.codes = codes
         new.packed4 = packed4
         return new
@@ -309,6 +350,38 @@ class _Packed4:
         return self.pq.reconstruct_rows_device(codes, sel, scales=None if scales is None else scales[pos].contiguous(), out=out)
 
 
+class _Search:
+    """The top-k and the range search of all three matrix classes: one body each.  A class says what is its own in one
+    hook, _search_terms(ip, ranged, queries, nprobe) -> (the Pq method that serves the call, the tables it reads, the
+    arguments it takes between the tables and k or the threshold: none, the lists and probes, or those with the bias
+    of every probe and the row terms), and in _original_rows, which turns what the kernel returns into row numbers."""
+
+    def _tables(self, ip, queries):
+        return self.pq.adc_ip_tables_device(queries) if ip else self.pq.adc_tables_device(queries)
+
+    def _original_rows(self, pos):
+        """the unpartitioned matrix stores rows under their numbers"""
+        return pos
+
+    def _topk(self, ip, queries, k, nprobe, use_norms, refine, allow):
+        R = k if refine is None else self._check_refine(k, refine)
+        fn, tables, more = self._search_terms(ip, False, queries, nprobe)
+        kw = {"scales": self.norms if use_norms else None} if ip else {}
+        val, pos = fn(self.codes, tables, *more, R, allow=self._allow_words(allow), packed4=self.packed4, **kw)
+        rows = self._original_rows(pos)
+        return (val, rows) if refine is None else self._refined(queries, rows, k, ip)
+
+    def _range(self, ip, queries, threshold, nprobe, use_norms, allow, sort):
+        self._unpacked_only("similar_above" if ip else "within")
+        fn, tables, more = self._search_terms(ip, True, queries, nprobe)
+        kw = {"scales": self.norms if use_norms else None} if ip else {}
+        lims, val, pos = fn(self.codes, tables, *more, threshold, allow=self._allow_words(allow), **kw)
+        rows = self._original_rows(pos)
+        if sort:
+            val, rows = sort_ranges(lims, val, rows, ip)
+        return lims, val, rows
+
+
 class _Among:
     """Searches among given rows for all three matrix classes: nearest_among() / most_similar_among() rank exactly the
     rows the caller names (Pq.adc_among_device / adc_ip_among_device) -- a tenant's rows, the result of a range search,
@@ -321,14 +394,14 @@ class _Among:
         dev = self.codes.device
 
         def vector(t, what):
-            if not hasattr(t, "is_cuda"):
+            host = not hasattr(t, "is_cuda")
+            if host:
                 t = np.asarray(t)
                 if t.dtype.kind not in "iu":
                     raise PanicError("%s must be integers" % what)
-                t = torch.from_numpy(np.ascontiguousarray(t, dtype=np.int64))
-            if t.is_floating_point() or t.dtype == torch.bool or t.dim() != 1:
+            if len(t.shape) != 1 or not host and (t.is_floating_point() or t.dtype == torch.bool):
                 raise PanicError("%s must be a vector of integers" % what)
-            return t.to(dev, torch.int64).contiguous()
+            return _on_device(t, dev, torch.int64, np.int64)
 
         if isinstance(rows, tuple):
             if len(rows) != 2:
@@ -340,20 +413,21 @@ class _Among:
         """original row numbers -> what the kernel is given; the unpartitioned matrix stores rows under their numbers"""
         return rows
 
-    def _among_result(self, queries, val, idx, k, refine, ip):
-        return (val, idx) if refine is None else self._refined(queries, idx, k, ip)
+    def _among_terms(self, ip, queries):
+        """-> (tables, the keyword arguments that place a row in a list); the residual class names its lists here"""
+        return self._tables(ip, queries), {}
 
     def _among(self, ip, queries, rows, k, use_norms, refine, check):
         self._unpacked_only("most_similar_among" if ip else "nearest_among")
         R = k if refine is None else self._check_refine(k, refine)
         lims, rows = self._among_rows(rows)
-        tables = self.pq.adc_ip_tables_device(queries) if ip else self.pq.adc_tables_device(queries)
+        tables, kw = self._among_terms(ip, queries)
         if ip:
-            val, idx = self.pq.adc_ip_among_device(self.codes, tables, self._among_ids(rows), R, lims=lims,
-                                                   scales=self.norms if use_norms else None, check=check)
-        else:
-            val, idx = self.pq.adc_among_device(self.codes, tables, self._among_ids(rows), R, lims=lims, check=check)
-        return self._among_result(queries, val, idx, k, refine, ip)
+            kw["scales"] = self.norms if use_norms else None
+        fn = self.pq.adc_ip_among_device if ip else self.pq.adc_among_device
+        val, pos = fn(self.codes, tables, self._among_ids(rows), R, lims=lims, check=check, **kw)
+        rows = self._original_rows(pos)
+        return (val, rows) if refine is None else self._refined(queries, rows, k, ip)
 
     def nearest_among(self, queries, rows, k, refine=None, check=False):
         """nearest() among the rows that `rows` names and no others: a vector of ORIGINAL row numbers shared by all
@@ -370,7 +444,7 @@ class _Among:
         return self._among(True, queries, rows, k, use_norms, refine, check)
 
 
-class QuantizedMatrix(_Refine, _Filter, _Packed4, _Among):
+class QuantizedMatrix(_Refine, _Filter, _Packed4, _Search, _Among):
     """Codes (+ norms) resident in HBM next to the device codebook: the lookup, scan and similarity-search consumer."""
 
     def __init__(self, pq, codes, norms=None, device="cuda:0"):
@@ -417,6 +491,14 @@ class QuantizedMatrix(_Refine, _Filter, _Packed4, _Among):
             ip = ip * self.norms
         return ip
 
+    def _search_terms(self, ip, ranged, queries, nprobe):
+        pq = self.pq
+        if ip:
+            fn = pq.adc_ip_range_device if ranged else pq.adc_ip_search_device
+        else:
+            fn = pq.adc_range_device if ranged else pq.adc_search_device
+        return fn, self._tables(ip, queries), ()
+
     def nearest(self, queries, k, refine=None, allow=None):
         """the k rows of smallest asymmetric squared distance (adc_search_device over all rows), ties to the smaller
         row -> (dist, idx) [k] or [nq, k].  refine=R (k <= R <= 1024, vectors attached): the R nearest rows by that
@@ -424,10 +506,7 @@ class QuantizedMatrix(_Refine, _Filter, _Packed4, _Among):
         device; dist are then the exact distances.  allow: None, a RowFilter of this matrix (row_filter) or a bool
         array [N] packed on the spot -- only allowed rows are ranked, exactly as if the others were not stored (index
         -1 past the last allowed row); with refine= the shortlist holds allowed rows only."""
-        R = k if refine is None else self._check_refine(k, refine)
-        d, idx = self.pq.adc_search_device(self.codes, self.pq.adc_tables_device(queries), R, allow=self._allow_words(allow),
-                                           packed4=self.packed4)
-        return (d, idx) if refine is None else self._refined(queries, idx, k, False)
+        return self._topk(False, queries, k, None, True, refine, allow)
 
     def most_similar(self, queries, k, use_norms=True, refine=None, allow=None):
         """the k rows of largest inner product with what embeddings() returns (the stored vectors, unscaled, with
@@ -435,11 +514,7 @@ class QuantizedMatrix(_Refine, _Filter, _Packed4, _Among):
         refine=R (k <= R <= 1024, vectors attached): the R most similar rows by that estimate are re-ranked by their
         exact inner product with the attached vectors as they are; use_norms then only affects the candidate stage.
         allow: as for nearest()."""
-        R = k if refine is None else self._check_refine(k, refine)
-        scales = self.norms if use_norms else None
-        s, idx = self.pq.adc_ip_search_device(self.codes, self.pq.adc_ip_tables_device(queries), R, scales=scales,
-                                              allow=self._allow_words(allow), packed4=self.packed4)
-        return (s, idx) if refine is None else self._refined(queries, idx, k, True)
+        return self._topk(True, queries, k, None, use_norms, refine, allow)
 
     def within(self, queries, radius, allow=None, sort=False):
         """EVERY row whose asymmetric squared distance to the query is <= radius (a scalar or one value per query) ->
@@ -448,25 +523,14 @@ class QuantizedMatrix(_Refine, _Filter, _Packed4, _Among):
         read of the count).  sort=True: each query's rows ascending in distance instead, ties in row order
         (sort_ranges).  allow: as for nearest().  There is no refine=: re-ranking is defined for at most 1,024
         candidates per query, and a range result has no such bound.  Not served on a packed matrix: unpack4() first."""
-        self._unpacked_only("within")
-        lims, d, idx = self.pq.adc_range_device(self.codes, self.pq.adc_tables_device(queries), radius,
-                                                allow=self._allow_words(allow))
-        if sort:
-            d, idx = sort_ranges(lims, d, idx, False)
-        return lims, d, idx
+        return self._range(False, queries, radius, None, True, allow, sort)
 
     def similar_above(self, queries, threshold, use_norms=True, allow=None, sort=False):
         """Every row whose inner product with the query, as most_similar() scores it, is >= threshold (a scalar or one
         value per query) -> (lims, score, idx), CSR as for within() (Pq.adc_ip_range_device).  sort=True: each query's
         rows descending in score, ties in row order.  No refine=, as for within().  Not served on a packed matrix:
         unpack4() first."""
-        self._unpacked_only("similar_above")
-        scales = self.norms if use_norms else None
-        lims, sc, idx = self.pq.adc_ip_range_device(self.codes, self.pq.adc_ip_tables_device(queries), threshold,
-                                                    scales=scales, allow=self._allow_words(allow))
-        if sort:
-            sc, idx = sort_ranges(lims, sc, idx, True)
-        return lims, sc, idx
+        return self._range(True, queries, threshold, None, use_norms, allow, sort)
 
     def add(self, vectors, norms=None):
         """The matrix with the rows of `vectors` ([B, d] float32, numpy or CUDA) appended as rows len(self) .. len(self) +
@@ -478,9 +542,7 @@ class QuantizedMatrix(_Refine, _Filter, _Packed4, _Among):
         dev = self.codes.device
         x = _device_rows(vectors, self.pq.reconstructed_len(), dev)
         nb = _batch_norms(norms, self.norms is not None, x.shape[0], dev)
-        new = object.__new__(type(self))
-        new.pq = self.pq
-        new.packed4 = self.packed4
+        new = _clone(self, ("pq", "packed4"))
         codes = self._stored_codes(self.pq.quantize_batch_device(x)) if x.shape[0] else self.codes[:0]
         if codes.dtype != self.codes.dtype:
             raise PanicError("the matrix holds 1-byte codes")
@@ -526,7 +588,6 @@ class QuantizedMatrix(_Refine, _Filter, _Packed4, _Among):
         N, d = len(self), self.pq.reconstructed_len()
         if not 1 <= n_lists <= 16384:
             raise ReductiveError("The number of lists must be between 1 and 16384, was %d" % n_lists)
-        chunk = 1 << 20
         if on_device and not self.codes.is_cuda:
             raise PanicError("on_device=True needs a matrix that is resident on a GPU")
 
@@ -536,10 +597,7 @@ class QuantizedMatrix(_Refine, _Filter, _Packed4, _Among):
                 if not isinstance(sel, slice):
                     sel = torch.as_tensor(sel, dtype=torch.int64, device=self.codes.device)
                 return self.pq.reconstruct_batch_device(self.codes[sel])
-            v = vectors[sel]
-            if not hasattr(v, "is_cuda"):
-                v = torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32))
-            return v.to(self.codes.device, torch.float32).contiguous()
+            return _on_device(vectors[sel], self.codes.device, torch.float32, np.float32)
 
         if vectors is not None and tuple(vectors.shape) != (N, d):
             raise PanicError("vectors must be [%d, %d]" % (N, d))
@@ -557,8 +615,7 @@ class QuantizedMatrix(_Refine, _Filter, _Packed4, _Among):
             assign = _assign_device(coarse, N, lambda r0, r1: rows_of(slice(r0, r1)), self.codes.device)
             return centroids, assign, rows_of, train_sel
         assign = np.empty(N, np.int64)
-        for r0 in range(0, N, chunk):
-            r1 = min(N, r0 + chunk)
+        for r0, r1 in _chunks(N):
             assign[r0:r1] = cluster_assignments(centroids, rows_of(slice(r0, r1)).cpu().numpy(), ctx=self.pq._ctx)
         return centroids, assign, rows_of, train_sel
 
@@ -612,16 +669,7 @@ class QuantizedMatrix(_Refine, _Filter, _Packed4, _Among):
                 resid = rows_of(train_sel) - cd[ad[sel]]
             residual_pq = train_pq(M, int(bits), pq_iterations, n_attempts, resid.cpu().numpy(), rng=rng, ctx=self.pq._ctx)
             del resid
-        codes = torch.empty((N, residual_pq.quantized_len()), dtype=torch.uint8, device=dev)
-        terms = torch.empty(N, dtype=torch.float32, device=dev)
-        chunk = 1 << 20
-        buf = torch.empty((min(chunk, N), d), dtype=torch.float32, device=dev) if on_device else None
-        for r0 in range(0, N, chunk):
-            r1 = min(N, r0 + chunk)
-            if on_device:
-                _residual_codes_terms_device(residual_pq, rows_of(slice(r0, r1)), ad[r0:r1], cd, codes[r0:r1], terms[r0:r1], buf)
-            else:
-                terms[r0:r1] = _residual_codes_terms(residual_pq, rows_of(slice(r0, r1)), cd[ad[r0:r1]], codes[r0:r1])
+        codes, terms = _encode_residuals(residual_pq, N, lambda r0, r1: rows_of(slice(r0, r1)), ad, cd, on_device)
         out = ResidualPartitionedMatrix(residual_pq, codes, self.norms, terms, centroids, assign)
         out.device_terms = bool(on_device)
         out.vectors = self.vectors
@@ -643,7 +691,16 @@ def ivf_layout(assign, n_lists):
     return perm, list_off
 
 
-class _Lists(_Refine, _Filter, _Packed4, _Among):
+def _ivf_layout_device(assign, n_lists):
+    """ivf_layout of an int64 device tensor of list ids, in torch -> (perm, list_off) on its device: a stable sort of the
+    list ids, bincount and cumsum (a batch that is being added; a whole matrix goes through Pq.lists_layout_device)"""
+    import torch
+    list_off = torch.zeros(n_lists + 1, dtype=torch.int64, device=assign.device)
+    list_off[1:] = torch.cumsum(torch.bincount(assign, minlength=n_lists), 0)
+    return torch.sort(assign, stable=True).indices, list_off
+
+
+class _Lists(_Refine, _Filter, _Packed4, _Search, _Among):
     """What both partitioned forms share: the list layout, the coarse quantizer and the probe selection."""
 
     device_terms = False        # ResidualPartitionedMatrix: the row terms come from Pq.residual_terms_device
@@ -655,26 +712,25 @@ class _Lists(_Refine, _Filter, _Packed4, _Among):
         import torch
         self.centroids = np.ascontiguousarray(centroids, dtype=np.float32)
         self.n_lists = self.centroids.shape[0]
-        if hasattr(assign, "is_cuda"):
+        on_device = hasattr(assign, "is_cuda")
+        if on_device:
             if not assign.is_cuda or assign.dtype != torch.int64 or assign.device != torch.device(dev):
                 raise PanicError("a device assignment must be an int64 CUDA tensor on the device of the codes")
             if tuple(assign.shape) != (n_rows,):
                 raise PanicError("one list id per row expected")
-            self.coarse = Pq(None, self.centroids[None], ctx=ctx)
-            laid = self.coarse.lists_layout_device(assign.contiguous(), self.n_lists, want_lists=want_lists, check=True)
-            self.ids, self.list_off, self.positions = laid[:3]
-            self._list_ids = torch.arange(self.n_lists, dtype=torch.int32, device=dev)[:, None].contiguous()
-            return laid[3] if want_lists else None
-        perm, list_off = ivf_layout(assign, self.n_lists)
-        if perm.size != n_rows:
-            raise PanicError("one list id per row expected")
-        self.ids = torch.from_numpy(perm).to(dev)
-        self.list_off = torch.from_numpy(list_off).to(dev)
-        self.positions = torch.empty_like(self.ids)
-        self.positions[self.ids] = torch.arange(perm.size, dtype=torch.int64, device=dev)
+        else:
+            perm, list_off = ivf_layout(assign, self.n_lists)
+            if perm.size != n_rows:
+                raise PanicError("one list id per row expected")
         # the coarse quantizer as a codebook of one subquantizer: its distance tables order the lists
         self.coarse = Pq(None, self.centroids[None], ctx=ctx)
         self._list_ids = torch.arange(self.n_lists, dtype=torch.int32, device=dev)[:, None].contiguous()
+        if on_device:
+            laid = self.coarse.lists_layout_device(assign.contiguous(), self.n_lists, want_lists=want_lists, check=True)
+            self.ids, self.list_off, self.positions = laid[:3]
+            return laid[3] if want_lists else None
+        self.ids, self.list_off = torch.from_numpy(perm).to(dev), torch.from_numpy(list_off).to(dev)
+        self.positions = _positions(self.ids)
 
     def __len__(self):
         return self.codes.shape[0]
@@ -719,10 +775,6 @@ class _Lists(_Refine, _Filter, _Packed4, _Among):
         pos = self.positions[rows.clamp(0, n - 1)] if n else torch.zeros_like(rows)
         return torch.where(inside, pos, torch.where(rows == -1, rows, torch.full_like(rows, n))).contiguous()
 
-    def _among_result(self, queries, val, pos, k, refine, ip):
-        rows = self._original_rows(pos)
-        return (val, rows) if refine is None else self._refined(queries, rows, k, ip)
-
     # ---- growth: every method returns a NEW matrix and leaves self (and the row filters built for it) untouched ----
     def assign(self, vectors):
         """the list of each vector ([B, d] float32, numpy or CUDA) -> int64 [B] on the device: the nearest centroid, as
@@ -735,24 +787,14 @@ class _Lists(_Refine, _Filter, _Packed4, _Among):
 
     def _shell(self):
         """a matrix of this class that shares what growth does not change: quantizers, centroids, probe selection"""
-        new = object.__new__(type(self))
-        for name in ("pq", "centroids", "n_lists", "coarse", "_list_ids", "_centroids_dev", "packed4", "device_terms"):
-            if hasattr(self, name):
-                setattr(new, name, getattr(self, name))
-        return new
+        return _clone(self, ("pq", "centroids", "n_lists", "coarse", "_list_ids", "_centroids_dev", "packed4", "device_terms"))
 
     def _piece(self, assign, vectors, **row_arrays):
         """A batch laid out as a matrix of this class over the same lists: `assign` int64 [B] on the device, row_arrays
-        the per-row arrays in batch order (None where the matrix has none).  B-sized torch operations only: a stable
-        sort of the list ids, bincount and cumsum -- ivf_layout on the device."""
-        import torch
-        dev = assign.device
+        the per-row arrays in batch order (None where the matrix has none).  B-sized torch operations only."""
         p = self._shell()
-        p.ids = torch.sort(assign, stable=True).indices
-        p.list_off = torch.zeros(self.n_lists + 1, dtype=torch.int64, device=dev)
-        p.list_off[1:] = torch.cumsum(torch.bincount(assign, minlength=self.n_lists), 0)
-        p.positions = torch.empty_like(p.ids)
-        p.positions[p.ids] = torch.arange(assign.shape[0], dtype=torch.int64, device=dev)
+        p.ids, p.list_off = _ivf_layout_device(assign, self.n_lists)
+        p.positions = _positions(p.ids)
         for name, t in row_arrays.items():
             setattr(p, name, None if t is None else t[p.ids].contiguous())
         p.vectors = vectors
@@ -786,8 +828,7 @@ class _Lists(_Refine, _Filter, _Packed4, _Among):
         for name in self._ROW_ARRAYS:
             mine = getattr(self, name)
             setattr(new, name, None if mine is None else merge(self.list_off, mine, other.list_off, getattr(other, name))[0])
-        new.positions = torch.empty_like(new.ids)
-        new.positions[new.ids] = torch.arange(new.ids.shape[0], dtype=torch.int64, device=new.ids.device)
+        new.positions = _positions(new.ids)
         if self.vectors is not None and other.vectors is not None:
             new.vectors = torch.cat([self.vectors, other.vectors.to(self.vectors.device, self.vectors.dtype)])
         return new
@@ -814,6 +855,14 @@ class PartitionedMatrix(_Lists):
         self.codes = qm.codes[self.ids].contiguous()
         self.norms = None if qm.norms is None else qm.norms[self.ids].contiguous()
 
+    def _search_terms(self, ip, ranged, queries, nprobe):
+        pq = self.pq
+        if ip:
+            fn = pq.adc_ip_range_lists_device if ranged else pq.adc_ip_search_lists_device
+        else:
+            fn = pq.adc_range_lists_device if ranged else pq.adc_search_lists_device
+        return fn, self._tables(ip, queries), (self.list_off, self.probes(queries, nprobe))
+
     def nearest(self, queries, k, nprobe, refine=None, allow=None):
         """the k rows of smallest asymmetric squared distance among the rows of the nprobe nearest lists, ties to the
         smaller position in list order -> (dist, idx) [k] or [nq, k]; idx are original row numbers, -1 past the last
@@ -821,52 +870,27 @@ class PartitionedMatrix(_Lists):
         re-ranked by their exact squared distance to the attached vectors (Pq.rerank_device), ties to the smaller
         original row number; dist are then the exact distances.  allow: None, a RowFilter of this matrix or a bool array
         [N] in ORIGINAL row order -- only allowed rows of the probed lists are ranked, as if the others were not stored."""
-        R = k if refine is None else self._check_refine(k, refine)
-        d, pos = self.pq.adc_search_lists_device(self.codes, self.pq.adc_tables_device(queries), self.list_off,
-                                                 self.probes(queries, nprobe), R, allow=self._allow_words(allow),
-                                                 packed4=self.packed4)
-        rows = self._original_rows(pos)
-        return (d, rows) if refine is None else self._refined(queries, rows, k, False)
+        return self._topk(False, queries, k, nprobe, True, refine, allow)
 
     def most_similar(self, queries, k, nprobe, use_norms=True, refine=None, allow=None):
         """QuantizedMatrix.most_similar among the rows of the nprobe nearest lists -> (score, idx), idx original row
         numbers, -1 past the last probed row (score -Inf).  refine=R: the R first rows are re-ranked by their exact
         inner product with the attached vectors as they are; use_norms then only affects the candidate stage.
         allow: as for nearest()."""
-        R = k if refine is None else self._check_refine(k, refine)
-        scales = self.norms if use_norms else None
-        s, pos = self.pq.adc_ip_search_lists_device(self.codes, self.pq.adc_ip_tables_device(queries), self.list_off,
-                                                    self.probes(queries, nprobe), R, scales=scales,
-                                                    allow=self._allow_words(allow), packed4=self.packed4)
-        rows = self._original_rows(pos)
-        return (s, rows) if refine is None else self._refined(queries, rows, k, True)
+        return self._topk(True, queries, k, nprobe, use_norms, refine, allow)
 
     def within(self, queries, radius, nprobe, allow=None, sort=False):
         """QuantizedMatrix.within among the rows of the nprobe nearest lists -> (lims, dist, idx), idx original row
         numbers; the rows of a query come list by list in probe order, inside a list in ascending original row number
         (Pq.adc_range_lists_device).  sort=True: ascending in distance, ties in that order.  No refine=: re-ranking is
         defined for at most 1,024 candidates per query.  Not served on a packed matrix: unpack4() first."""
-        self._unpacked_only("within")
-        lims, d, pos = self.pq.adc_range_lists_device(self.codes, self.pq.adc_tables_device(queries), self.list_off,
-                                                      self.probes(queries, nprobe), radius, allow=self._allow_words(allow))
-        rows = self._original_rows(pos)
-        if sort:
-            d, rows = sort_ranges(lims, d, rows, False)
-        return lims, d, rows
+        return self._range(False, queries, radius, nprobe, True, allow, sort)
 
     def similar_above(self, queries, threshold, nprobe, use_norms=True, allow=None, sort=False):
         """QuantizedMatrix.similar_above among the rows of the nprobe nearest lists -> (lims, score, idx), idx original
         row numbers, order as for within() (Pq.adc_ip_range_lists_device).  sort=True: descending in score.  Not served
         on a packed matrix: unpack4() first."""
-        self._unpacked_only("similar_above")
-        scales = self.norms if use_norms else None
-        lims, sc, pos = self.pq.adc_ip_range_lists_device(self.codes, self.pq.adc_ip_tables_device(queries), self.list_off,
-                                                          self.probes(queries, nprobe), threshold, scales=scales,
-                                                          allow=self._allow_words(allow))
-        rows = self._original_rows(pos)
-        if sort:
-            sc, rows = sort_ranges(lims, sc, rows, True)
-        return lims, sc, rows
+        return self._range(True, queries, threshold, nprobe, use_norms, allow, sort)
 
     def add(self, vectors, norms=None):
         """The matrix with `vectors` ([B, d] float32, numpy or CUDA) added as rows len(self) .. len(self) + B - 1 -> a NEW
@@ -913,6 +937,17 @@ class ResidualPartitionedMatrix(_Lists):
         self.lists = lists
         self._centroids_dev = torch.from_numpy(self.centroids).to(dev)
 
+    def _search_terms(self, ip, ranged, queries, nprobe):
+        """the probes with the bias of each -- |q - c_l|^2 for distances, <q, c_l> for inner products -- then the one
+        table per query, which is the inner-product table for both"""
+        pq = self.pq
+        pr, bias = self._probes_and_ips(queries, nprobe) if ip else self._probes_and_dists(queries, nprobe)
+        if ip:
+            fn = pq.adc_ip_range_lists_residual_device if ranged else pq.adc_ip_search_lists_residual_device
+        else:
+            fn = pq.adc_range_lists_residual_device if ranged else pq.adc_search_lists_residual_device
+        return fn, pq.adc_ip_tables_device(queries), (self.list_off, pr, bias) + (() if ip else (self.row_terms,))
+
     def nearest(self, queries, k, nprobe, refine=None, allow=None):
         """the k rows of smallest dist = fl(fl(bias + row_term) - fl(s + s)) among the rows of the nprobe nearest lists:
         s the row sum over the query's inner-product table, bias the coarse distance of the row's list as
@@ -921,13 +956,7 @@ class ResidualPartitionedMatrix(_Lists):
         refine=R (k <= R <= 1024, vectors attached): the R first rows of that search are re-ranked by their exact
         squared distance to the attached vectors (Pq.rerank_device); dist are then the exact distances.  allow: as for
         PartitionedMatrix.nearest."""
-        R = k if refine is None else self._check_refine(k, refine)
-        pr, bias = self._probes_and_dists(queries, nprobe)
-        d, pos = self.pq.adc_search_lists_residual_device(self.codes, self.pq.adc_ip_tables_device(queries), self.list_off,
-                                                          pr, bias, self.row_terms, R, allow=self._allow_words(allow),
-                                                          packed4=self.packed4)
-        rows = self._original_rows(pos)
-        return (d, rows) if refine is None else self._refined(queries, rows, k, False)
+        return self._topk(False, queries, k, nprobe, True, refine, allow)
 
     def _probes_and_ips(self, queries, nprobe):
         """(list ids as probes() defines them, <q, c_l> of each: the entry of the coarse inner-product table at the list;
@@ -944,64 +973,32 @@ class ResidualPartitionedMatrix(_Lists):
         the row's list, i.e. <q, c_l> -> (score, idx), idx original row numbers, -1 past the last probed row (-Inf).
         refine=R: the R first rows are re-ranked by their exact inner product with the attached vectors as they are;
         use_norms then only affects the candidate stage.  allow: as for PartitionedMatrix.nearest."""
-        R = k if refine is None else self._check_refine(k, refine)
-        pr, bias = self._probes_and_ips(queries, nprobe)
-        scales = self.norms if use_norms else None
-        s, pos = self.pq.adc_ip_search_lists_residual_device(self.codes, self.pq.adc_ip_tables_device(queries),
-                                                             self.list_off, pr, bias, R, scales=scales,
-                                                             allow=self._allow_words(allow), packed4=self.packed4)
-        rows = self._original_rows(pos)
-        return (s, rows) if refine is None else self._refined(queries, rows, k, True)
+        return self._topk(True, queries, k, nprobe, use_norms, refine, allow)
 
     def within(self, queries, radius, nprobe, allow=None, sort=False):
         """every row of the nprobe nearest lists with dist = fl(fl(bias + row_term) - fl(s + s)) <= radius, bias obtained
         exactly as nearest() obtains it -> (lims, dist, idx), idx original row numbers, rows list by list in probe order
         (Pq.adc_range_lists_residual_device).  sort=True: ascending in distance.  No refine=: re-ranking is defined for
         at most 1,024 candidates per query.  Not served on a packed matrix: unpack4() first."""
-        self._unpacked_only("within")
-        pr, bias = self._probes_and_dists(queries, nprobe)
-        lims, d, pos = self.pq.adc_range_lists_residual_device(self.codes, self.pq.adc_ip_tables_device(queries),
-                                                               self.list_off, pr, bias, self.row_terms, radius,
-                                                               allow=self._allow_words(allow))
-        rows = self._original_rows(pos)
-        if sort:
-            d, rows = sort_ranges(lims, d, rows, False)
-        return lims, d, rows
+        return self._range(False, queries, radius, nprobe, True, allow, sort)
 
     def similar_above(self, queries, threshold, nprobe, use_norms=True, allow=None, sort=False):
         """every row of the nprobe nearest lists with score = fl(fl(bias + s) * norm) >= threshold (fl(bias + s) with
         use_norms=False or without norms), bias obtained exactly as most_similar() obtains it -> (lims, score, idx)
         (Pq.adc_ip_range_lists_residual_device).  sort=True: descending in score.  Not served on a packed matrix:
         unpack4() first."""
-        self._unpacked_only("similar_above")
-        pr, bias = self._probes_and_ips(queries, nprobe)
-        scales = self.norms if use_norms else None
-        lims, sc, pos = self.pq.adc_ip_range_lists_residual_device(self.codes, self.pq.adc_ip_tables_device(queries),
-                                                                   self.list_off, pr, bias, threshold, scales=scales,
-                                                                   allow=self._allow_words(allow))
-        rows = self._original_rows(pos)
-        if sort:
-            sc, rows = sort_ranges(lims, sc, rows, True)
-        return lims, sc, rows
+        return self._range(True, queries, threshold, nprobe, use_norms, allow, sort)
 
     _ROW_ARRAYS = ("codes", "norms", "row_terms", "lists")
 
-    def _among(self, ip, queries, rows, k, use_norms, refine, check):
-        """the residual forms: the list of every position, the row terms / norms and, as the bias of every list, the
-        full row of the coarse table -- |q - c_l|^2 resp. <q, c_l> -- so a candidate need not lie in a probed list"""
-        self._unpacked_only("most_similar_among" if ip else "nearest_among")
-        R = k if refine is None else self._check_refine(k, refine)
-        lims, rows = self._among_rows(rows)
+    def _among_terms(self, ip, queries):
+        """the residual forms: the list of every position, the row terms and, as the bias of every list, the full row
+        of the coarse table -- |q - c_l|^2 resp. <q, c_l> -- so a candidate need not lie in a probed list"""
         ct = self.coarse.adc_ip_tables_device(queries) if ip else self.coarse.adc_tables_device(queries)
-        bias = ct[0] if queries.dim() == 1 else ct[:, 0, :]
-        tables = self.pq.adc_ip_tables_device(queries)
-        if ip:
-            val, pos = self.pq.adc_ip_among_device(self.codes, tables, self._among_ids(rows), R, lims=lims, row_list=self.lists,
-                                                   list_bias=bias, scales=self.norms if use_norms else None, check=check)
-        else:
-            val, pos = self.pq.adc_among_device(self.codes, tables, self._among_ids(rows), R, lims=lims, row_list=self.lists,
-                                                list_bias=bias, row_terms=self.row_terms, check=check)
-        return self._among_result(queries, val, pos, k, refine, ip)
+        kw = {"row_list": self.lists, "list_bias": ct[0] if queries.dim() == 1 else ct[:, 0, :]}
+        if not ip:
+            kw["row_terms"] = self.row_terms
+        return self.pq.adc_ip_tables_device(queries), kw
 
     def encode(self, vectors):
         """What the matrix would store for `vectors` ([B, d] float32, numpy or CUDA) -> (lists int64 [B], codes u8 [B, M],
@@ -1009,22 +1006,10 @@ class ResidualPartitionedMatrix(_Lists):
         centroid, and the row's query-free term -- the loop body of partition_residual, on the route the matrix was
         built by (device_terms: Pq.residuals_device and Pq.residual_terms_device), so add() stays the constructor
         applied to the concatenation."""
-        import torch
         x = _device_rows(vectors, self.pq.reconstructed_len(), self.codes.device)
         lists = self.assign(x)
-        codes = torch.empty((x.shape[0], self.pq.quantized_len()), dtype=torch.uint8, device=x.device)
-        terms = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
-        chunk = 1 << 20
-        buf = None
-        if self.device_terms and x.shape[0]:
-            buf = torch.empty((min(chunk, x.shape[0]), x.shape[1]), dtype=torch.float32, device=x.device)
-        for r0 in range(0, x.shape[0], chunk):
-            r1 = min(x.shape[0], r0 + chunk)
-            if self.device_terms:
-                _residual_codes_terms_device(self.pq, x[r0:r1], lists[r0:r1], self._centroids_dev, codes[r0:r1],
-                                             terms[r0:r1], buf)
-            else:
-                terms[r0:r1] = _residual_codes_terms(self.pq, x[r0:r1], self._centroids_dev[lists[r0:r1]], codes[r0:r1])
+        codes, terms = _encode_residuals(self.pq, x.shape[0], lambda r0, r1: x[r0:r1], lists, self._centroids_dev,
+                                         self.device_terms)
         return lists, codes, terms
 
     def add(self, vectors, norms=None):
