@@ -64,6 +64,17 @@ __device__ __forceinline__ void gather_groups(float v, float (&o)[4])
     o[0] = __uint_as_float(e[0]); o[1] = __uint_as_float(d[0]); o[2] = __uint_as_float(e[1]); o[3] = __uint_as_float(d[1]);
 }
 
+// 4 x 4 transpose over the lane groups: w[j] of lane group g becomes what w[g] of lane group j was (same i16).  Four
+// swaps on distinct registers, each replacing both of its operands, so the compiler needs no copies around them.
+__device__ __forceinline__ void transpose_groups(float (&w)[4])
+{
+    const auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(w[0]), __float_as_uint(w[1]), false, false);
+    const auto c = __builtin_amdgcn_permlane16_swap(__float_as_uint(w[2]), __float_as_uint(w[3]), false, false);
+    const auto e = __builtin_amdgcn_permlane32_swap(a[0], c[0], false, false);
+    const auto o = __builtin_amdgcn_permlane32_swap(a[1], c[1], false, false);
+    w[0] = __uint_as_float(e[0]); w[1] = __uint_as_float(o[0]); w[2] = __uint_as_float(e[1]); w[3] = __uint_as_float(o[1]);
+}
+
 // Order-preserving map of an f32 distance onto u32 under ordered-float's total order
 // (kmeans.rs:149-156): NaN greatest, -0 == +0.  Smaller key <=> smaller distance.
 __device__ __forceinline__ unsigned ord_key(float d)

@@ -11,8 +11,9 @@
 // The key of a value is its f32 bits with the low 6 mantissa bits replaced by the lane-local centroid number
 // 4 cb + v (that moves a value by < 2^-17 |A|, part of the bound).  Per (lane, row block) the loop keeps the smallest
 // key m and the second smallest s (v_min_f32 + v_med3_f32, three vector instructions per value); the four lane groups
-// of a row are merged after the 16 centroid blocks.  When the second smallest key S of the row exceeds the smallest
-// M by more than 2 E_r, the centroid of M is the first minimum of D and its code is stored: no FP32 arithmetic.
+// of a row are merged once per trip of two tiles, 64 rows, one row per lane.  When the second smallest key S of the row
+// exceeds the smallest M by more than 2 E_r, the centroid of M is the first minimum of D and its code is stored: no FP32
+// arithmetic.
 // Every other row is recorded in the loop and resolved after it, where nothing is live: rows with two or more candidates
 // (|M| tiny included) by encode_rows_cand_f16, 16 rows at a time, at a cost proportional to their candidates; rows whose
 // scaled norm is beyond f16's range, or under a bad codebook, by encode_rows_slow_v, as in the FP32 body.
@@ -25,7 +26,7 @@
 // group 3: zeros), loaded as two 4-float chunks, scaled and converted in registers (v_cvt_pk_f16_f32).
 // Schedule: the 16 centroid blocks are software-pipelined -- block cb + 1's two matrix instructions are issued before
 // the selection on block cb's accumulators, A fragments are read two blocks ahead, the next tile's rows are converted
-// into f16 operands in the middle of the current tile, and its first block is issued before the lane-group merge.
+// into f16 operands in the middle of the current tile, and its first block is issued before the trip's merge.
 #pragma once
 #include "kernels_mfma.hip.h"
 
@@ -244,28 +245,52 @@ __device__ __forceinline__ void encode_mfma16_screen(const EncodeArgs& a)
     int64_t row_end = row_begin + a.rows_per_item;
     if (row_end > a.n) row_end = a.n;
     const bool bad_codebook = a.bad_flag != nullptr && *a.bad_flag != 0;  // wave-uniform
-    const bool cb_ok = !bad_codebook && cc_range;                          // wave-uniform
+    // strides too long for the loop's 32-bit row offsets (below) send every row to the exact path, like a bad codebook
+    const bool near_rows = (uint64_t)a.x_rs < (1ull << 24) && (uint64_t)a.o_rs < (1ull << 24);   // wave-uniform
+    const bool cb_ok = !bad_codebook && cc_range && near_rows;            // wave-uniform
     const float maxcct = sc2 * maxcc;                                    // max cc~, exact
 
     // x chunks of lane (i16, q): 4 floats at c0 and at c1 (lane group 2 uses only c0, lane group 3 neither; every
     // chunk lies inside the sub-vector)
     const int c0 = (8 * q) % 20, c1 = (8 * q + 4) % 20;
     const float* const xsub = a.x + (int64_t)m * a.dsub;
-    const float* const plast = xsub + (a.n - 1) * a.x_rs;
+    // Addresses: a row block's base (tile_row0 + 16 rb) * x_rs is wave-uniform and stays in scalar registers; a lane adds
+    // the loop-invariant 32-bit byte offset of its row and chunk (global_load with a scalar base), and the trip's store
+    // adds lane * o_rs the same way: no 64-bit vector arithmetic in the steady state.
+    // Under strides too long for that (rows 64 MiB apart) every lane reads its row block's first row, the loop decides
+    // nothing, and encode_rows_slow_v, which addresses in 64 bits, encodes every row.
+    const unsigned xrs4 = near_rows ? (unsigned)a.x_rs * 4u : 0u;
+    const unsigned xoff0 = (unsigned)i16 * xrs4 + 4u * c0, xoff1 = (unsigned)i16 * xrs4 + 4u * c1;
+    const unsigned ooff = near_rows ? (unsigned)lane * (unsigned)a.o_rs * (unsigned)sizeof(IdxT) : 0u;
+    auto load_rows = [&](float (&v)[8], const char* base, unsigned o0, unsigned o1) {
+        // the offsets stay 32-bit values of this block, so that the loads take them next to the scalar base
+        asm volatile("" : "+v"(o0), "+v"(o1));
+        const f32x4 v0 = *reinterpret_cast<const f32x4_u*>(base + o0), v1 = *reinterpret_cast<const f32x4_u*>(base + o1);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { v[j] = v0[j]; v[4 + j] = v1[j]; }
+    };
     auto load_tile = [&](float (&v)[2][8], int64_t tile_row0) {
-        const int left = (int)((a.n - tile_row0 < 32) ? a.n - tile_row0 : 32);  // wave-uniform
+        if (tile_row0 + 32 <= a.n) {                                     // wave-uniform: every row of the tile exists
+            const char* base = reinterpret_cast<const char*>(xsub + tile_row0 * a.x_rs);
+            load_rows(v[0], base, xoff0, xoff1);
+            load_rows(v[1], base + 64 * a.x_rs, xoff0, xoff1);          // 16 rows on, still a scalar
+        } else {
+            // the ragged last tile, or one past the end: rows >= n read the last row instead (never stored or recorded)
+            const int64_t r0 = tile_row0 < a.n ? tile_row0 : a.n - 1;   // scalar
+            const int last = (int)(a.n - 1 - r0);                       // 0 .. 30
+            const char* base = reinterpret_cast<const char*>(xsub + r0 * a.x_rs);
 #pragma unroll
-        for (int rb = 0; rb < 2; ++rb) {
-            const float* p = (16 * rb + i16 < left) ? xsub + (tile_row0 + 16 * rb + i16) * a.x_rs : plast;
-            const f32x4 v0 = *reinterpret_cast<const f32x4_u*>(p + c0), v1 = *reinterpret_cast<const f32x4_u*>(p + c1);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { v[rb][j] = v0[j]; v[rb][4 + j] = v1[j]; }
+            for (int rb = 0; rb < 2; ++rb) {
+                const unsigned ro = (unsigned)(16 * rb + i16 < last ? 16 * rb + i16 : last) * xrs4;
+                load_rows(v[rb], base, ro + 4u * c0, ro + 4u * c1);
+            }
         }
     };
     // lane group 3 carries zeros (scale 0: a NaN or inf of the row gives NaN, which only that row's column sees)
     const float sl = q < 3 ? sc : 0.f;
     const bool tail = q == 2;
-    auto split = [&](const float (&v)[2][8], u32x4_t (&bop)[2], float (&xx)[2]) {
+    // own[rb]: the lane's part of ||x||^2 of its row; the trip's merge sums the four lane groups
+    auto split = [&](const float (&v)[2][8], u32x4_t (&bop)[2], float (&own)[2]) {
 #pragma unroll
         for (int rb = 0; rb < 2; ++rb) {
             unsigned w[4];
@@ -278,10 +303,7 @@ __device__ __forceinline__ void encode_mfma16_screen(const EncodeArgs& a)
             float s0 = 0.f, s1 = 0.f;
 #pragma unroll
             for (int j = 0; j < 4; ++j) { s0 = fmaf(v[rb][j], v[rb][j], s0); s1 = fmaf(v[rb][4 + j], v[rb][4 + j], s1); }
-            const float own = (q < 3 ? s0 : 0.f) + (q < 2 ? s1 : 0.f);
-            float u[4];
-            gather_groups(own, u);
-            xx[rb] = sc2 * ((u[0] + u[1]) + (u[2] + u[3]));
+            own[rb] = (q < 3 ? s0 : 0.f) + (q < 2 ? s1 : 0.f);
         }
     };
 
@@ -302,31 +324,30 @@ __device__ __forceinline__ void encode_mfma16_screen(const EncodeArgs& a)
     // prologue: the first tile's operands, A fragments of blocks 0 and 1, block 0
     float xv[2][8];
     u32x4_t bop[2];
-    float xx[2];
+    float own[2];
     load_tile(xv, row_begin);
-    split(xv, bop, xx);
+    split(xv, bop, own);
     u32x4_t af[2];
     f32x4 acc[2][2];
     load_a(0, af[0]);
     load_a(1, af[1]);
     screen(af[0], bop, acc[0]);
-    // one 32-row tile; bop / xx hold its split rows, bnext / xxn receive the next tile's.  The loop below alternates two
-    // operand sets, so no operand is copied at the seam.
-    auto tile = [&](int64_t row0, int tile_idx, const u32x4_t (&bop)[2], const float (&xx)[2], u32x4_t (&bnext)[2], float (&xxn)[2]) {
-        const unsigned long long st_a = a.stamps ? __builtin_amdgcn_s_memtime() : 0;
-        // row0 stays a scalar: the per-lane row addresses are formed where they are used instead of being carried
-        // from tile to tile in vector registers
+    // The selection of one 32-row tile; bop holds its split rows, bnext / ownn receive the next tile's, mk / sk the two
+    // smallest keys per (lane, row block).  A trip of the loop below is two tiles on alternating operand sets (no operand
+    // is copied at the seam) and ONE merge of its 64 rows, one row per lane.
+    auto tile = [&](int64_t row0, const u32x4_t (&bop)[2], u32x4_t (&bnext)[2], float (&ownn)[2], float (&mk)[2], float (&sk)[2]) {
+        // row0 stays a scalar: a row block's base address is formed from it in scalar registers
         asm("" : "+s"(row0));
         // the next tile's rows (past row_end the loads are clamped like a short tile's, and their result is never used)
         load_tile(xv, row0 + 32);
-        float mk[2] = {__builtin_inff(), __builtin_inff()}, sk[2] = {__builtin_inff(), __builtin_inff()};
+        mk[0] = mk[1] = sk[0] = sk[1] = __builtin_inff();
         // step cb: issue block cb + 1, read the A fragments of block cb + 2 (mod 16: the next tile's blocks 0, 1),
         // then select on block cb
 #pragma unroll
         for (int cb = 0; cb < 16; ++cb) {
             if (cb < 15) screen(af[(cb + 1) & 1], bop, acc[(cb + 1) & 1]);
             load_a((cb + 2) & 15, af[cb & 1]);
-            if (cb == 8) split(xv, bnext, xxn);                          // the loads have landed by now
+            if (cb == 8) split(xv, bnext, ownn);                        // the loads have landed by now
             auto key = [&](int rb, int v) { return __uint_as_float((__float_as_uint(acc[cb & 1][rb][v]) & kKeyMask) | (unsigned)(4 * cb + v)); };
 #pragma unroll
             for (int rb = 0; rb < 2; ++rb) {
@@ -334,54 +355,76 @@ __device__ __forceinline__ void encode_mfma16_screen(const EncodeArgs& a)
                 keep2(mk[rb], sk[rb], key(rb, 2), key(rb, 3));
             }
         }
-        // the next tile's block 0 runs under the merge
+        // the next tile's block 0 runs under what follows: the trip's second tile, or the merge
         screen(af[0], bnext, acc[0]);
-        // ---- merge the four lane groups of each row; store the decided rows, record the others
-        unsigned need = 0, cand = 0, few_rows = 0;
-#pragma unroll
-        for (int rb = 0; rb < 2; ++rb) {
-            float mq[4], sq[4];
-            gather_groups(mk[rb], mq);
-            gather_groups(sk[rb], sq);
-            const float lo01 = vmin(mq[0], mq[1]), hi01 = vmax(mq[0], mq[1]);
-            const float lo23 = vmin(mq[2], mq[3]), hi23 = vmax(mq[2], mq[3]);
-            const float M = vmin(lo01, lo23);
-            const float S2 = vmin(vmin(sq[0], sq[1]), vmin(sq[2], sq[3]));   // smallest second key of a lane group
-            const float S = vmin(vmin(vmax(lo01, lo23), vmin(hi01, hi23)), S2);
-            const float tau = M + (kScreenRel * (xx[rb] + maxcct) + kScreenAbs);
-            const int64_t row = row0 + 16 * rb + i16;
-            const bool valid = row < a.n;
-            const bool in_range = valid && cb_ok && xx[rb] < kScreenMaxXX; // the f16 operands are exact enough
-            const bool plain = in_range && __builtin_fabsf(M) > kScreenTiny;
-            const bool one = plain && S > tau;                           // a single candidate
-            if (one && mk[rb] == M) {                                    // the one lane group that holds M
-                const unsigned kb = __float_as_uint(M) & 63u;
-                reinterpret_cast<IdxT*>(a.out)[row * a.o_rs + m] = (IdxT)(16 * (kb >> 2) + 4 * q + (kb & 3));
-            }
-            need |= ((unsigned)__builtin_amdgcn_ballot_w64(q == 0 && valid && !in_range) & 0xffffu) << (16 * rb);
-            cand |= ((unsigned)__builtin_amdgcn_ballot_w64(q == 0 && in_range && !one) & 0xffffu) << (16 * rb);
-            // stamps: the rows with two to four candidates, at most one per lane group (every lane group's second key is
-            // above tau), which round 6 resolved in the loop
-            if (a.stamps) few_rows |= ((unsigned)__builtin_amdgcn_ballot_w64(q == 0 && plain && !one && S2 > tau) & 0xffffu) << (16 * rb);
-        }
-        if (need) {                                                     // wave-uniform
-            if (lane == 0) need_s[wave][tile_idx] = need;
-            flagged |= 1ull << tile_idx;
-        }
-        if (cand) {                                                     // wave-uniform
-            if (lane == 0) cand_s[wave][tile_idx] = cand;
-            flagged_c |= 1ull << tile_idx;
-        }
-        if (a.stamps) st_rows += (unsigned long long)__builtin_popcount(few_rows) | ((unsigned long long)(__builtin_popcount(need | cand) - __builtin_popcount(few_rows)) << 32);
-        if (a.stamps) { st_tiles += 1; st_steps += __builtin_amdgcn_s_memtime() - st_a; }
     };
     u32x4_t bop2[2];
-    float xx2[2];
-    for (int64_t row0 = row_begin, tile_idx = 0;; row0 += 64, tile_idx += 2) {
-        if (row0 >= row_end) break;
-        tile(row0, (int)tile_idx, bop, xx, bop2, xx2);
-        if (row0 + 32 >= row_end) break;
-        tile(row0 + 32, (int)tile_idx + 1, bop2, xx2, bop, xx);
+    float own2[2], ownn[2] = {0.f, 0.f};
+    float mk[2], sk[2], mk2[2], sk2[2];
+    for (int64_t row0 = row_begin, tile_idx = 0; row0 < row_end; row0 += 64, tile_idx += 2) {
+        const unsigned long long st_a = a.stamps ? __builtin_amdgcn_s_memtime() : 0;
+        tile(row0, bop, bop2, own2, mk, sk);
+        // rows_per_item is a multiple of 32, not of 64: a wave's last trip can be one tile.  Lanes 32 .. 63 then stand
+        // for rows of the next wave; their keys are set here and their rows are masked by row_end below.
+        const bool two = row0 + 32 < row_end;                            // wave-uniform
+        if (two) tile(row0 + 32, bop2, bop, ownn, mk2, sk2);
+        else mk2[0] = mk2[1] = sk2[0] = sk2[1] = __builtin_inff();
+        // ---- merge, once per trip: transpose (lane group q) x (row block b) so that lane 16 b + i16 holds the four
+        // lane-group values of row row0 + 16 b + i16 -- the row's offset in the trip is the lane number -- then decide
+        // the row in that one lane; store the decided rows, record the others
+        float mq[4] = {mk[0], mk[1], mk2[0], mk2[1]}, sq[4] = {sk[0], sk[1], sk2[0], sk2[1]};
+        float u[4] = {own[0], own[1], own2[0], own2[1]};
+        transpose_groups(mq);
+        transpose_groups(sq);
+        transpose_groups(u);
+        const float xx = sc2 * ((u[0] + u[1]) + (u[2] + u[3]));
+        const float lo01 = vmin(mq[0], mq[1]), hi01 = vmax(mq[0], mq[1]);
+        const float lo23 = vmin(mq[2], mq[3]), hi23 = vmax(mq[2], mq[3]);
+        const float M = vmin(lo01, lo23);
+        const float S2 = vmin(vmin(sq[0], sq[1]), vmin(sq[2], sq[3]));   // smallest second key of a lane group
+        const float S = vmin(vmin(vmax(lo01, lo23), vmin(hi01, hi23)), S2);
+        const float tau = M + (kScreenRel * (xx + maxcct) + kScreenAbs);
+        const bool valid = lane < (int)(row_end - row0 < 64 ? row_end - row0 : 64);   // scalar bound
+        const bool in_range = valid && cb_ok && xx < kScreenMaxXX;       // the f16 operands are exact enough
+        const bool plain = in_range && __builtin_fabsf(M) > kScreenTiny;
+        const bool one = plain && S > tau;                               // a single candidate
+        if (one) {
+            // the lane group that holds M: only one does, since a tie between two would make S = M
+            const unsigned Mb = __float_as_uint(M);
+            const unsigned qw = Mb == __float_as_uint(lo01) ? (Mb == __float_as_uint(mq[0]) ? 0u : 1u)
+                                                            : (Mb == __float_as_uint(mq[2]) ? 2u : 3u);
+            const unsigned kb = Mb & 63u;
+            char* ob = reinterpret_cast<char*>(reinterpret_cast<IdxT*>(a.out) + (row0 * a.o_rs + m));   // scalar
+            unsigned oo = ooff;
+            asm volatile("" : "+v"(oo));                                 // as in load_rows
+            *reinterpret_cast<IdxT*>(ob + oo) = (IdxT)(16 * (kb >> 2) + 4 * qw + (kb & 3));
+        }
+        // bit l of a ballot is row row0 + l: the low word is tile tile_idx's record, the high word the next tile's
+        const unsigned long long need = __builtin_amdgcn_ballot_w64(valid && !in_range);
+        const unsigned long long cand = __builtin_amdgcn_ballot_w64(in_range && !one);
+        auto record = [&](unsigned* rec, unsigned long long& tiles, unsigned long long rows) {
+            const unsigned lo = (unsigned)rows, hi = (unsigned)(rows >> 32);
+            if (lo) {                                                   // wave-uniform
+                if (lane == 0) rec[tile_idx] = lo;
+                tiles |= 1ull << tile_idx;
+            }
+            if (hi) {                                                   // wave-uniform
+                if (lane == 0) rec[tile_idx + 1] = hi;
+                tiles |= 2ull << tile_idx;
+            }
+        };
+        record(need_s[wave], flagged, need);
+        record(cand_s[wave], flagged_c, cand);
+        if (a.stamps) {
+            // the rows with two to four candidates, at most one per lane group (every lane group's second key is above
+            // tau), which round 6 resolved in the loop
+            const int few = __builtin_popcountll(__builtin_amdgcn_ballot_w64(plain && !one && S2 > tau));
+            st_rows += (unsigned long long)few | ((unsigned long long)(__builtin_popcountll(need | cand) - few) << 32);
+            st_tiles += two ? 2 : 1;
+            st_steps += __builtin_amdgcn_s_memtime() - st_a;
+        }
+        own[0] = ownn[0];
+        own[1] = ownn[1];
     }
     // ---- rows the screen does not decide (nothing is live here)
     if (flagged_c)                                                      // wave-uniform
