@@ -9,11 +9,20 @@
 // xx is the same for every centroid of a row and is left out.  |A(c) - s^2 (D(c) - xx)| <= E_r for every c, D the CANON-F32
 // distance, with E_r = kScreenRel / 2 * (xx~ + max cc~) + kScreenAbs / 2 (the proof and its terms: DESIGN.md §5).
 // The key of a value is its f32 bits with the low 6 mantissa bits replaced by the lane-local centroid number
-// 4 cb + v (that moves a value by < 2^-17 |A|, part of the bound).  Per (lane, row block) the loop keeps the smallest
-// key m and the second smallest s (v_min_f32 + v_med3_f32, three vector instructions per value); the four lane groups
-// of a row are merged once per trip of two tiles, 64 rows, one row per lane.  When the second smallest key S of the row
-// exceeds the smallest M by more than 2 E_r, the centroid of M is the first minimum of D and its code is stored: no FP32
-// arithmetic.
+// 4 cb + v (that moves a value by < 2^-17 |A|, part of the bound).  Per (lane, row block) a tile has 64 values a[cb][v];
+// the loop hands the merge the smallest key mk and a lower bound sk of every other value (less a key's perturbation),
+// without keying every value: 13 vector instructions per 8 values, two blocks at a time,
+//     block side    b[cb] = min_v a[cb][v], raw (v_min_f32 + v_min3_f32); kb[cb] = (bits(b[cb]) & ~15) | cb;
+//                   (mB, sB) = the two smallest kb (keep2 on the pair's two keys)
+//     column side   mv[v] = min_cb a[cb][v], raw: one v_min3_f32 per v folds both blocks of the pair
+//     end of tile   (mA, sA) = the two smallest mv, v* = the column of mA;
+//                   mk = (mB & ~63) | ((mB & 15) << 2) | v*,  sk = min(sA, sB)
+// Every value but the smallest differs from it in column (then sA is at or below it) or in block (then sB is, up to the
+// 4 index bits); exact ties give sk = mk up to those bits; and when sk exceeds mk by the margin below, the smallest value
+// is unique, mB is its block's key, v* its column, and mk is bit for bit its 6-bit key.  The four lane groups
+// of a row are merged once per trip of two tiles, 64 rows, one row per lane.  When the second smallest S of the row
+// exceeds the smallest key M by more than 2 E_r, the centroid of M is the first minimum of D and its code is stored: no
+// FP32 arithmetic.
 // Every other row is recorded in the loop and resolved after it, where nothing is live: rows with two or more candidates
 // (|M| tiny included) by encode_rows_cand_f16, 16 rows at a time, at a cost proportional to their candidates; rows whose
 // scaled norm is beyond f16's range, or under a bad codebook, by encode_rows_slow_v, as in the FP32 body.
@@ -24,9 +33,12 @@
 // which puts the 16 lanes of every ds_read_b128 lane group on 16 different 16-B bank slots.
 // The B operand of a lane is x[8q .. 8q + 7] of its row (lane group 2: x[16 .. 19] and the [1 1 65504 0] tail, lane
 // group 3: zeros), loaded as two 4-float chunks, scaled and converted in registers (v_cvt_pk_f16_f32).
-// Schedule: the 16 centroid blocks are software-pipelined -- block cb + 1's two matrix instructions are issued before
-// the selection on block cb's accumulators, A fragments are read two blocks ahead, the next tile's rows are converted
-// into f16 operands in the middle of the current tile, and its first block is issued before the trip's merge.
+// Schedule: a selection step works on the pair of blocks (2p, 2p + 1) of ONE row block, 8 values per lane.  The steps
+// are software-pipelined over two accumulator sets of two blocks each (16 registers, as one block of both row blocks
+// took): before the selection on the pair of row block 0 the same pair's two matrix instructions for row block 1 are
+// issued, before that one the next pair's for row block 0; the A fragments of the next pair are read as soon as both
+// row blocks of this one are issued, the next tile's rows are converted into f16 operands in the middle of the current
+// tile, and its first pair is issued before the selection on the last, so it runs under the trip's merge.
 #pragma once
 #include "kernels_mfma.hip.h"
 
@@ -72,6 +84,9 @@ __device__ __forceinline__ void keep2(float& m, float& s, float k1, float k2)
     asm("v_min_f32 %0, %0, %1" : "+v"(s) : "v"(t));
     asm("v_min3_f32 %0, %0, %1, %2" : "+v"(m) : "v"(k1), "v"(k2));
 }
+// raw screening values folded two at a time (accumulator bits as they are: no canonicalization, as for the keys)
+__device__ __forceinline__ float vmin3(float a, float b, float c) { float r; asm("v_min3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
+__device__ __forceinline__ void fold2(float& m, float a, float b) { asm("v_min3_f32 %0, %0, %1, %2" : "+v"(m) : "v"(a), "v"(b)); }
 
 // The rows the screen's loop does not decide, after it: 16 at a time from all of the wave's tiles, the
 // f16 screen again on them, then the CANON-F32 distance of every centroid whose value is within thr of the row's smallest
@@ -307,56 +322,97 @@ __device__ __forceinline__ void encode_mfma16_screen(const EncodeArgs& a)
         }
     };
 
-    const unsigned kKeyMask = 0xffffffc0u;
+    const unsigned kKeyMask = 0xffffffc0u, kBlockMask = 0xfffffff0u;
     unsigned long long flagged = 0, flagged_c = 0;                      // wave-uniform: tiles with rows for the two exact paths
     unsigned long long st_tiles = 0, st_steps = 0, st_rows = 0;   // st_rows: {other rows off the screen, 2-4-candidate rows}
     const unsigned long long st_t0 = a.stamps ? __builtin_amdgcn_s_memtime() : 0, st_r0 = a.stamps ? __builtin_amdgcn_s_memrealtime() : 0;
     // A fragment of block cb: row 16 cb + i16, chunk q (k = 8q .. 8q + 7), swizzled
     const unsigned short* const arow = &img_s[i16 * kRow + 8 * (q ^ ((i16 >> 2) & 3))];
     auto load_a = [&](int cb, u32x4_t& af) { af = *reinterpret_cast<const u32x4_t*>(arow + cb * 16 * kRow); };
-    auto screen = [&](const u32x4_t& af, const u32x4_t (&bop)[2], f32x4 (&acc)[2]) {
+    // blocks 2p and 2p + 1 of one row block: the pair a selection step works on
+    auto screen2 = [&](const u32x4_t (&af)[2], const u32x4_t& b, f32x4 (&acc)[2]) {
 #pragma unroll
-        for (int rb = 0; rb < 2; ++rb)
-            acc[rb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, af), __builtin_bit_cast(f16x8_t, bop[rb]),
-                                                             (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+        for (int j = 0; j < 2; ++j)
+            acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, af[j]), __builtin_bit_cast(f16x8_t, b),
+                                                            (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
     };
 
-    // prologue: the first tile's operands, A fragments of blocks 0 and 1, block 0
+    // prologue: the first tile's operands, A fragments of blocks 0 and 1, their values for row block 0
     float xv[2][8];
     u32x4_t bop[2];
     float own[2];
     load_tile(xv, row_begin);
     split(xv, bop, own);
     u32x4_t af[2];
-    f32x4 acc[2][2];
+    f32x4 acc[2][2];                                                    // [row block][block of the pair]
     load_a(0, af[0]);
     load_a(1, af[1]);
-    screen(af[0], bop, acc[0]);
-    // The selection of one 32-row tile; bop holds its split rows, bnext / ownn receive the next tile's, mk / sk the two
-    // smallest keys per (lane, row block).  A trip of the loop below is two tiles on alternating operand sets (no operand
-    // is copied at the seam) and ONE merge of its 64 rows, one row per lane.
+    screen2(af, bop[0], acc[0]);
+    // the first pair has no selection step between its issue and its read (see the fence in tile): wait it out, once
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7");
+    __builtin_amdgcn_sched_barrier(0);
+    // The selection of one 32-row tile; bop holds its split rows, bnext / ownn receive the next tile's, mk / sk the
+    // smallest key and a lower bound of every other value per (lane, row block).  A trip of the loop below is two tiles on
+    // alternating operand sets (no operand is copied at the seam) and ONE merge of its 64 rows, one row per lane.
     auto tile = [&](int64_t row0, const u32x4_t (&bop)[2], u32x4_t (&bnext)[2], float (&ownn)[2], float (&mk)[2], float (&sk)[2]) {
         // row0 stays a scalar: a row block's base address is formed from it in scalar registers
         asm("" : "+s"(row0));
         // the next tile's rows (past row_end the loads are clamped like a short tile's, and their result is never used)
         load_tile(xv, row0 + 32);
-        mk[0] = mk[1] = sk[0] = sk[1] = __builtin_inff();
-        // step cb: issue block cb + 1, read the A fragments of block cb + 2 (mod 16: the next tile's blocks 0, 1),
-        // then select on block cb
+        float mB[2], sB[2], mv[2][4];
+        // step (p, rb): the pair of blocks (2p, 2p + 1) on row block rb.  Issue the pair that is selected on next -- the
+        // same blocks on row block 1, or the next pair (mod 8: the next tile's first) on row block 0 -- read the A
+        // fragments of the next pair once both row blocks of this one are issued, then select on this step's 8 values
 #pragma unroll
-        for (int cb = 0; cb < 16; ++cb) {
-            if (cb < 15) screen(af[(cb + 1) & 1], bop, acc[(cb + 1) & 1]);
-            load_a((cb + 2) & 15, af[cb & 1]);
-            if (cb == 8) split(xv, bnext, ownn);                        // the loads have landed by now
-            auto key = [&](int rb, int v) { return __uint_as_float((__float_as_uint(acc[cb & 1][rb][v]) & kKeyMask) | (unsigned)(4 * cb + v)); };
+        for (int p = 0; p < 8; ++p) {
 #pragma unroll
             for (int rb = 0; rb < 2; ++rb) {
-                keep2(mk[rb], sk[rb], key(rb, 0), key(rb, 1));
-                keep2(mk[rb], sk[rb], key(rb, 2), key(rb, 3));
+                if (rb == 0) {
+                    screen2(af, bop[1], acc[1]);
+                    load_a((2 * p + 2) & 15, af[0]);
+                    load_a((2 * p + 3) & 15, af[1]);
+                    if (p == 4) split(xv, bnext, ownn);                 // the loads have landed by now
+                } else {
+                    screen2(af, p < 7 ? bop[0] : bnext[0], acc[0]);     // under the trip's second tile, or the merge
+                }
+                // The raw values go straight into inline assembly, and the compiler inserts the wait states between a
+                // matrix instruction and a vector read of its result only in front of instructions of its own.  Nothing
+                // crosses this fence, so a pair issued in one step is read a whole step's selection (26 vector
+                // instructions, 13 in a tile's first two) later, however the steps are scheduled inside
+                // (tools/mfma_read_distance.py checks the compiled kernel)
+                __builtin_amdgcn_sched_barrier(0);
+                const f32x4 d0 = acc[rb][0], d1 = acc[rb][1];
+                // block side: the block's raw minimum, keyed by the block number in 4 bits
+                const float b0 = vmin3(d0[0], d0[1], vmin(d0[2], d0[3])), b1 = vmin3(d1[0], d1[1], vmin(d1[2], d1[3]));
+                const float k0 = __uint_as_float((__float_as_uint(b0) & kBlockMask) | (unsigned)(2 * p));
+                const float k1 = __uint_as_float((__float_as_uint(b1) & kBlockMask) | (unsigned)(2 * p + 1));
+                // column side: the raw minimum of every v over the blocks
+                if (p == 0) {
+                    mB[rb] = vmin(k0, k1);
+                    sB[rb] = vmax(k0, k1);
+#pragma unroll
+                    for (int v = 0; v < 4; ++v) mv[rb][v] = vmin(d0[v], d1[v]);
+                } else {
+                    keep2(mB[rb], sB[rb], k0, k1);
+#pragma unroll
+                    for (int v = 0; v < 4; ++v) fold2(mv[rb][v], d0[v], d1[v]);
+                }
             }
         }
-        // the next tile's block 0 runs under what follows: the trip's second tile, or the merge
-        screen(af[0], bnext, acc[0]);
+        // end of tile: the smallest value is the smallest block minimum and the smallest column minimum at once, which
+        // names its block and its v; every other value lies in another column or in another block
+#pragma unroll
+        for (int rb = 0; rb < 2; ++rb) {
+            float mA = vmin(mv[rb][0], mv[rb][1]), sA = vmax(mv[rb][0], mv[rb][1]);
+            keep2(mA, sA, mv[rb][2], mv[rb][3]);
+            unsigned vs = mv[rb][1] == mA ? 1u : 0u;                    // a tie between columns makes sk = mA: any of them
+            vs = mv[rb][2] == mA ? 2u : vs;
+            vs = mv[rb][3] == mA ? 3u : vs;
+            const unsigned mb = __float_as_uint(mB[rb]);
+            mk[rb] = __uint_as_float((mb & kKeyMask) | (((mb & 15u) << 2) | vs));
+            sk[rb] = vmin(sA, sB[rb]);
+        }
     };
     u32x4_t bop2[2];
     float own2[2], ownn[2] = {0.f, 0.f};
