@@ -21,9 +21,10 @@ namespace pqhip {
 // that true with a wide margin below 2^100.
 constexpr float kBigNorm = 1.2676506e30f;  // 2^100
 // k_encode_mfma16 instantiations that take the bf16 screen body (kernels_mfma16_screen.hip.h); their diagnostic stamps
-// carry a sixth word per wave, the cycles of the codebook-image staging
+// carry three more words per wave: the cycles of the codebook-image staging, the few-candidate rows that found the wave's
+// list full, and the cycles from the end of the loop to the end of the wave
 constexpr bool mfma16_screen_shape(int T, int DP) { return T == 8 && DP == 20; }
-constexpr int kScreenStampWords = 6;
+constexpr int kScreenStampWords = 8;
 constexpr int kMfma16MaxTiles = 64;        // k_encode_mfma16: row tiles per wave (rows_per_item <= 2048), one bit each in a 64-bit mask
 
 struct EncodeArgs {
@@ -50,7 +51,8 @@ struct EncodeArgs {
     // without the host looking at the flag between iterations.  nullptr: the host has checked.
     const int* bad_flag;
     // diagnostics only (PQHIP_DEBUG_ENC_STAMP): per wave {tiles, step-loop cycles, seam cycles (k_encode_mfma16: row counts),
-    // wave cycles, realtime ticks}
+    // wave cycles, realtime ticks}; the screen body of k_encode_mfma16 adds {image staging cycles, few-candidate rows
+    // that found the list full, cycles after the loop}
     unsigned long long* stamps = nullptr;
 };
 

@@ -23,9 +23,11 @@
 // of a row are merged once per trip of two tiles, 64 rows, one row per lane.  When the second smallest S of the row
 // exceeds the smallest key M by more than 2 E_r, the centroid of M is the first minimum of D and its code is stored: no
 // FP32 arithmetic.
-// Every other row is recorded in the loop and resolved after it, where nothing is live: rows with two or more candidates
-// (|M| tiny included) by encode_rows_cand_f16, 16 rows at a time, at a cost proportional to their candidates; rows whose
-// scaled norm is beyond f16's range, or under a bad codebook, by encode_rows_slow_v, as in the FP32 body.
+// Every other row is recorded in the loop and resolved after it, where nothing is live: rows with at most one candidate
+// per lane group (every lane group's second value above tau) by encode_rows_few, one row per lane, from the merge's four
+// keys; the other rows with two or more candidates (|M| tiny included) by encode_rows_cand_f16,
+// 16 rows at a time, at a cost proportional to their candidates; rows whose scaled norm is beyond f16's range, or under
+// a bad codebook, by encode_rows_slow_v, as in the FP32 body.
 //
 // Layout (16x16x32 f16): lane (i16, q) supplies A[i16][k = 8q .. 8q + 7] and B[k = 8q .. 8q + 7][i16] and receives
 // D[4q + v][i16].  A = 16 centroids (block cb), B = 16 rows (block rb).  The f16 codebook image (256 rows of 32 f16 =
@@ -190,6 +192,52 @@ __device__ __noinline__ void encode_rows_cand_f16(const float* x, int64_t x_rs, 
     }
 }
 
+// The few-candidate rows of a wave: rows off the screen in which every lane group's second value
+// is above tau, so each lane group holds at most one candidate and its key mq[g] names it.  The trip's merge appends
+// {mq[0..3], tau, the row's offset in the wave} (three 8-byte words) to a list in LDS; a row that finds the list full
+// keeps its bit in the candidate record and is resolved by encode_rows_cand_f16.
+constexpr int kScreenFewCap = 96;           // rows per wave: 43.0 on average at the headline shape (sd 6.5)
+constexpr int kScreenFewWords = 3;          // uint2 per entry
+
+// The listed rows after the loop, 64 at a time, one row per lane and no cross-lane step: the candidates are the lane
+// groups g with mq[g] <= tau, centroid 16 (kb >> 2) + 4 g + (kb & 3) from the key's low 6 bits kb; their CANON-F32
+// distances with the operations of encode_rows_cand_f16, the first minimum of those (ties to the lower index).  That set
+// holds the first minimum of D; a key whose index bits are off names one centroid more, which
+// cannot win.  A lane group that is no candidate (or names a padding centroid) evaluates centroid 0 and drops the result.
+template <typename IdxT>
+__device__ __noinline__ void encode_rows_few(const float* x, int64_t x_rs, void* out, int64_t o_rs, const float* cbk,
+                                             const float* ccn, int K, int k_pad, int dsub, int m, int64_t row_begin,
+                                             const uint2* list, int count)
+{
+    constexpr int DP = 20;
+    const int lane = threadIdx.x & 63;
+    const float* const xsub = x + (int64_t)m * dsub;
+    const float* const cbm = cbk + (int64_t)m * K * DP;
+    const float* const ccm = ccn + (int64_t)m * k_pad;
+    for (int e0 = 0; e0 < count; e0 += 64) {                            // wave-uniform
+        const bool rv = e0 + lane < count;
+        const uint2* const en = list + kScreenFewWords * (rv ? e0 + lane : 0);   // entry 0 exists: count > 0
+        const uint2 w0 = en[0], w1 = en[1], w2 = en[2];
+        const unsigned key[4] = {w0.x, w0.y, w1.x, w1.y};
+        const float tau = __uint_as_float(w2.x);
+        const int64_t row = row_begin + w2.y;
+        const float* xs = xsub + row * x_rs;
+        const float xxe = norm_unrolled_global(xs, DP);
+        unsigned bh = 0xffffffffu, bl = 0xffffffffu;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const unsigned kb = key[g] & 63u;
+            const int j = (int)(16u * (kb >> 2) + 4u * g + (kb & 3u));
+            const bool cg = __uint_as_float(key[g]) <= tau && j < K;
+            const int jj = cg ? j : 0;
+            const float dp = chain_dot_global(xs, 1, cbm + (int64_t)jj * DP, 1, DP);
+            const unsigned kh = ord_key(fsub(fadd(xxe, ccm[jj]), fadd(dp, dp)));
+            if (cg && (kh < bh || (kh == bh && (unsigned)j < bl))) { bh = kh; bl = (unsigned)j; }
+        }
+        if (rv) reinterpret_cast<IdxT*>(out)[row * o_rs + m] = (IdxT)bl;
+    }
+}
+
 template <typename IdxT>
 __device__ __forceinline__ void encode_mfma16_screen(const EncodeArgs& a)
 {
@@ -198,6 +246,7 @@ __device__ __forceinline__ void encode_mfma16_screen(const EncodeArgs& a)
     __shared__ __attribute__((aligned(16))) unsigned short img_s[256 * kRow];
     __shared__ unsigned need_s[4][kMfma16MaxTiles];   // rows for encode_rows_slow_v
     __shared__ unsigned cand_s[4][kMfma16MaxTiles];   // rows for the candidate path
+    __shared__ uint2 few_s[4][kScreenFewCap * kScreenFewWords];   // rows for encode_rows_few
     __shared__ unsigned maxcc_s;
 
     const int lane = threadIdx.x & 63;
@@ -324,7 +373,10 @@ __device__ __forceinline__ void encode_mfma16_screen(const EncodeArgs& a)
 
     const unsigned kKeyMask = 0xffffffc0u, kBlockMask = 0xfffffff0u;
     unsigned long long flagged = 0, flagged_c = 0;                      // wave-uniform: tiles with rows for the two exact paths
+    uint2* few_w = few_s[wave];                                         // wave-uniform: the list's next entry
+    int few_room = kScreenFewCap;
     unsigned long long st_tiles = 0, st_steps = 0, st_rows = 0;   // st_rows: {other rows off the screen, 2-4-candidate rows}
+    unsigned long long st_full = 0;                               // few-candidate rows that found the list full
     const unsigned long long st_t0 = a.stamps ? __builtin_amdgcn_s_memtime() : 0, st_r0 = a.stamps ? __builtin_amdgcn_s_memrealtime() : 0;
     // A fragment of block cb: row 16 cb + i16, chunk q (k = 8q .. 8q + 7), swizzled
     const unsigned short* const arow = &img_s[i16 * kRow + 8 * (q ^ ((i16 >> 2) & 3))];
@@ -455,9 +507,29 @@ __device__ __forceinline__ void encode_mfma16_screen(const EncodeArgs& a)
             asm volatile("" : "+v"(oo));                                 // as in load_rows
             *reinterpret_cast<IdxT*>(ob + oo) = (IdxT)(16 * (kb >> 2) + 4 * qw + (kb & 3));
         }
+        // few-candidate rows go to the wave's list (encode_rows_few): every lane group's second value is above tau, so
+        // the candidates are the mq[g] <= tau.  None of them may be tiny (index bits in the subnormal range): they lie
+        // in [M, tau], which is clear of [-kScreenTiny, kScreenTiny] when tau is below it or M above it; a row this
+        // holds back only takes the other path.
+        const bool few = plain && !one && S2 > tau && (tau < -kScreenTiny || M > kScreenTiny);
+        const unsigned long long fewm = __builtin_amdgcn_ballot_w64(few);
+        // the list position: few_w points past the few-candidate rows met so far, few_room is what is left of the
+        // capacity; a row that does not fit keeps its cand bit (few_room is then zero or negative for the rest of the
+        // wave and few_w, past the list's end, is not used again)
+        const int pos = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(fewm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)fewm, 0u));
+        const bool listed = few && pos < few_room;
+        if (listed) {                                                   // skipped when no lane has one
+            uint2* const en = few_w + kScreenFewWords * pos;
+            en[0] = make_uint2(__float_as_uint(mq[0]), __float_as_uint(mq[1]));
+            en[1] = make_uint2(__float_as_uint(mq[2]), __float_as_uint(mq[3]));
+            en[2] = make_uint2(__float_as_uint(tau), (unsigned)(row0 - row_begin) + (unsigned)lane);
+        }
+        const int few_k = __builtin_popcountll(fewm);                   // scalar
+        few_w += kScreenFewWords * few_k;
+        few_room -= few_k;
         // bit l of a ballot is row row0 + l: the low word is tile tile_idx's record, the high word the next tile's
         const unsigned long long need = __builtin_amdgcn_ballot_w64(valid && !in_range);
-        const unsigned long long cand = __builtin_amdgcn_ballot_w64(in_range && !one);
+        const unsigned long long cand = __builtin_amdgcn_ballot_w64(in_range && !one && !listed);
         auto record = [&](unsigned* rec, unsigned long long& tiles, unsigned long long rows) {
             const unsigned lo = (unsigned)rows, hi = (unsigned)(rows >> 32);
             if (lo) {                                                   // wave-uniform
@@ -474,15 +546,22 @@ __device__ __forceinline__ void encode_mfma16_screen(const EncodeArgs& a)
         if (a.stamps) {
             // the rows with two to four candidates, at most one per lane group (every lane group's second key is above
             // tau), which round 6 resolved in the loop
-            const int few = __builtin_popcountll(__builtin_amdgcn_ballot_w64(plain && !one && S2 > tau));
-            st_rows += (unsigned long long)few | ((unsigned long long)(__builtin_popcountll(need | cand) - few) << 32);
+            const int nfew = __builtin_popcountll(__builtin_amdgcn_ballot_w64(plain && !one && S2 > tau));
+            const int off = __builtin_popcountll(need | __builtin_amdgcn_ballot_w64(in_range && !one));
+            st_rows += (unsigned long long)nfew | ((unsigned long long)(off - nfew) << 32);
+            st_full += (unsigned long long)__builtin_popcountll(__builtin_amdgcn_ballot_w64(few && !listed));
             st_tiles += two ? 2 : 1;
             st_steps += __builtin_amdgcn_s_memtime() - st_a;
         }
         own[0] = ownn[0];
         own[1] = ownn[1];
     }
-    // ---- rows the screen does not decide (nothing is live here)
+    const unsigned long long st_p0 = a.stamps ? __builtin_amdgcn_s_memtime() : 0;
+    // ---- rows the screen does not decide (nothing is live here): the listed few-candidate rows one per lane, the others
+    // 16 at a time
+    if (few_room < kScreenFewCap)                                       // wave-uniform
+        encode_rows_few<IdxT>(a.x, a.x_rs, a.out, a.o_rs, a.cb, a.cc, a.K, a.k_pad, a.dsub, m, row_begin, few_s[wave],
+                              kScreenFewCap - (few_room > 0 ? few_room : 0));
     if (flagged_c)                                                      // wave-uniform
         encode_rows_cand_f16<IdxT>(a.x, a.x_rs, a.out, a.o_rs, a.cb, a.cc, a.K, a.k_pad, a.dsub, a.n, m, row_begin,
                                    img_s, cand_s[wave], flagged_c, sc, sc2 * maxcc);
@@ -496,7 +575,9 @@ __device__ __forceinline__ void encode_mfma16_screen(const EncodeArgs& a)
     if (a.stamps && lane == 0) {
         unsigned long long* o = a.stamps + ((size_t)blockIdx.x * 4 + wave) * kScreenStampWords;
         o[0] = st_tiles; o[1] = st_steps; o[2] = st_rows;
-        o[3] = __builtin_amdgcn_s_memtime() - st_t0; o[4] = __builtin_amdgcn_s_memrealtime() - st_r0; o[5] = st_stage;
+        const unsigned long long st_end = __builtin_amdgcn_s_memtime();
+        o[3] = st_end - st_t0; o[4] = __builtin_amdgcn_s_memrealtime() - st_r0; o[5] = st_stage;
+        o[6] = st_full; o[7] = st_end - st_p0;
     }
 }
 

@@ -312,7 +312,8 @@ static int32_t launch_mfma(pqhip_codebook* cb, int slot, const EncodePlan& p, co
     // k_encode_mfma16 (kind 3) leaves row counts in word 2: of the rows the screen does not decide, those with two to four
     // candidates, one per lane group (round 6 resolved them in the loop), and all others (both zero in its FP32 body);
     // kinds 0 and 2 leave the seam cycles there.  The screen body adds the
-    // image-staging cycles as a sixth word.
+    // image-staging cycles as a sixth word, the few-candidate rows that found their wave's list full as a seventh and
+    // the cycles after the loop as an eighth.
     if (p.kind == 3) return stamps.report5(io.st, "encode", "steps", "2-4-candidate / other off-screen", true, stamp_words);
     return stamps.report5(io.st, "encode", "steps", "seam");
 }
