@@ -21,10 +21,11 @@ namespace pqhip {
 // that true with a wide margin below 2^100.
 constexpr float kBigNorm = 1.2676506e30f;  // 2^100
 // k_encode_mfma16 instantiations that take the bf16 screen body (kernels_mfma16_screen.hip.h); their diagnostic stamps
-// carry three more words per wave: the cycles of the codebook-image staging, the few-candidate rows that found the wave's
-// list full, and the cycles from the end of the loop to the end of the wave
+// carry five more words per wave: the cycles of the codebook-image staging, the few-candidate rows that found the wave's
+// list full, the cycles from the end of the loop to the end of the wave, and of those the cycles in encode_rows_few and
+// in encode_rows_cand_f16
 constexpr bool mfma16_screen_shape(int T, int DP) { return T == 8 && DP == 20; }
-constexpr int kScreenStampWords = 8;
+constexpr int kScreenStampWords = 10;
 constexpr int kMfma16MaxTiles = 64;        // k_encode_mfma16: row tiles per wave (rows_per_item <= 2048), one bit each in a 64-bit mask
 
 struct EncodeArgs {
@@ -54,6 +55,9 @@ struct EncodeArgs {
     // wave cycles, realtime ticks}; the screen body of k_encode_mfma16 adds {image staging cycles, few-candidate rows
     // that found the list full, cycles after the loop}
     unsigned long long* stamps = nullptr;
+    // the screen body of k_encode_mfma16 only: the f16 codebook images in LDS order, [M][16,384 bytes], and behind them
+    // the 16-byte headers [M] with the bits of max cc (k_build_screen_image)
+    const unsigned* screen_img = nullptr;
 };
 
 // value of lane groups 0..3 (same i16) in every lane

@@ -31,7 +31,8 @@
 //
 // Layout (16x16x32 f16): lane (i16, q) supplies A[i16][k = 8q .. 8q + 7] and B[k = 8q .. 8q + 7][i16] and receives
 // D[4q + v][i16].  A = 16 centroids (block cb), B = 16 rows (block rb).  The f16 codebook image (256 rows of 32 f16 =
-// 64 B, no padding) is built by the workgroup from cb / cc; chunk j (16 B) of row r is stored at chunk j ^ ((r >> 2) & 3),
+// 64 B, no padding) is built once per codebook from cb / cc (k_build_screen_image) and copied into LDS by the workgroup;
+// chunk j (16 B) of row r is stored at chunk j ^ ((r >> 2) & 3),
 // which puts the 16 lanes of every ds_read_b128 lane group on 16 different 16-B bank slots.
 // The B operand of a lane is x[8q .. 8q + 7] of its row (lane group 2: x[16 .. 19] and the [1 1 65504 0] tail, lane
 // group 3: zeros), loaded as two 4-float chunks, scaled and converted in registers (v_cvt_pk_f16_f32).
@@ -59,6 +60,30 @@ constexpr float kScreenMinCC = 0x1p-100f;
 
 // instantiations that take the screen body (the others keep the FP32 body of k_encode_mfma16)
 template <int T, int DP> constexpr bool mfma16_screens() { return mfma16_screen_shape(T, DP); }
+
+// The f16 codebook image of the screen, built once per codebook by k_build_screen_image (kernels_prep.hip.h) and copied
+// into LDS by every workgroup: per subquantizer kScreenImageBytes in LDS order (256 rows of 32 f16, chunk j of row r at
+// chunk j ^ ((r >> 2) & 3), padding rows included), and behind the M images one 16-byte header per subquantizer whose
+// first word holds the bits of max cc.
+constexpr int kScreenImageBytes = 256 * 32 * 2;
+constexpr int kScreenHeaderBytes = 16;
+constexpr size_t screen_image_bytes(int64_t M) { return (size_t)M * (kScreenImageBytes + kScreenHeaderBytes); }
+
+// max cc -> the scale, the one rule of the kernel that builds the image and the kernel that screens with it
+struct ScreenScale {
+    bool cc_range;   // max cc in [kScreenMinCC, kBigNorm): the screen applies (false for NaN)
+    float sc, sc2;   // s and s^2
+};
+__device__ __forceinline__ ScreenScale screen_scale(float maxcc)
+{
+    ScreenScale r;
+    r.cc_range = maxcc >= kScreenMinCC && maxcc < kBigNorm;
+    // s = 2^e with e = floor((kScreenScaleLo + 1 - log2 max cc) / 2): s^2 max cc in [2^12, 2^14), e in [-43, 56]
+    const int escale = r.cc_range ? (kScreenScaleLo + 1 - ((int)(__float_as_uint(maxcc) >> 23) - 127)) >> 1 : 0;
+    r.sc = __uint_as_float((unsigned)(127 + escale) << 23);
+    r.sc2 = __uint_as_float((unsigned)(127 + 2 * escale) << 23);
+    return r;
+}
 
 typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
@@ -90,13 +115,42 @@ __device__ __forceinline__ void keep2(float& m, float& s, float k1, float k2)
 __device__ __forceinline__ float vmin3(float a, float b, float c) { float r; asm("v_min3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
 __device__ __forceinline__ void fold2(float& m, float a, float b) { asm("v_min3_f32 %0, %0, %1, %2" : "+v"(m) : "v"(a), "v"(b)); }
 
+// The two functions below that resolve rows after the loop receive generic pointers, and an out-of-line one would load
+// and store through flat instructions, which also count against the LDS counter.  They address x, the codebook, the
+// norms and the codes through global-address-space pointers and their LDS records through LDS ones: global_load /
+// global_store / ds_read, same addresses, same values.
+#define PQHIP_GLOBAL_AS __attribute__((address_space(1)))
+#define PQHIP_LDS_AS __attribute__((address_space(3)))
+typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
+typedef f32x4_u PQHIP_GLOBAL_AS const* gf32x4_p;
+// a row or a centroid of 20 floats
+__device__ __forceinline__ void load20_global(const PQHIP_GLOBAL_AS float* p, float (&v)[20])
+{
+#pragma unroll
+    for (int e = 0; e < 20; e += 4) {
+        const f32x4 t = *reinterpret_cast<gf32x4_p>(p + e);
+        v[e] = t[0]; v[e + 1] = t[1]; v[e + 2] = t[2]; v[e + 3] = t[3];
+    }
+}
+// chain_dot_global (common.hip.h) of two register vectors of 20 floats: one chain (20 < kKC), the same operations in the
+// same order
+__device__ __forceinline__ float chain_dot20(const float (&a)[20], const float (&b)[20])
+{
+    float ab = 0.f;
+#pragma unroll
+    for (int k = 0; k < 20; ++k) ab = ffma(a[k], b[k], ab);
+    return ab;
+}
+
 // The rows the screen's loop does not decide, after it: 16 at a time from all of the wave's tiles, the
 // f16 screen again on them, then the CANON-F32 distance of every centroid whose value is within thr of the row's smallest
 // value -- that set holds the first minimum, since A(c*) <= A(c) + 2 E_r for every c -- and the first minimum of those
-// (ties to the lower index).  The cost is one pass of 32 matrix instructions per 16 rows plus one distance per candidate,
+// (ties to the lower index).  The cost is two passes of 16 matrix instructions per 16 rows plus one distance per candidate,
 // against K distances per row on encode_rows_slow_v.  img: the workgroup's f16 image; tiles[t]: the rows of tile t.
+// Inline: out of line it took more registers than a callee may use freely and saved 48 of them on the stack, its whole
+// 280-byte frame; in the kernel, behind the loop, nothing is live and nothing is saved.
 template <typename IdxT>
-__device__ __noinline__ void encode_rows_cand_f16(const float* x, int64_t x_rs, void* out, int64_t o_rs, const float* cbk,
+__device__ __forceinline__ void encode_rows_cand_f16(const float* x, int64_t x_rs, void* out, int64_t o_rs, const float* cbk,
                                                   const float* ccn, int K, int k_pad, int dsub, int64_t n, int m,
                                                   int64_t row_begin, const unsigned short* img, const unsigned* tiles,
                                                   unsigned long long flagged_c, float sc, float maxcct)
@@ -106,11 +160,14 @@ __device__ __noinline__ void encode_rows_cand_f16(const float* x, int64_t x_rs, 
     const int i16 = lane & 15;
     const int q = lane >> 4;
     const int c0 = (8 * q) % 20, c1 = (8 * q + 4) % 20;
-    const float* const xsub = x + (int64_t)m * dsub;
-    const float* const plast = xsub + (n - 1) * x_rs;
+    const PQHIP_GLOBAL_AS float* const xsub = (const PQHIP_GLOBAL_AS float*)x + (int64_t)m * dsub;
+    const PQHIP_GLOBAL_AS float* const plast = xsub + (n - 1) * x_rs;
+    const PQHIP_GLOBAL_AS float* const cbm = (const PQHIP_GLOBAL_AS float*)cbk + (int64_t)m * K * DP;
+    const PQHIP_GLOBAL_AS float* const ccm = (const PQHIP_GLOBAL_AS float*)ccn + (int64_t)m * k_pad;
+    const PQHIP_LDS_AS unsigned* const tiles_l = (const PQHIP_LDS_AS unsigned*)tiles;
     const float sl = q < 3 ? sc : 0.f;
     const float sc2 = sc * sc;
-    const unsigned short* const arow = &img[i16 * kRow + 8 * (q ^ ((i16 >> 2) & 3))];
+    const PQHIP_LDS_AS unsigned short* const arow = (const PQHIP_LDS_AS unsigned short*)img + (i16 * kRow + 8 * (q ^ ((i16 >> 2) & 3)));
     unsigned cur = 0;
     int cur_ti = 0;
     while (cur || flagged_c) {                                          // wave-uniform
@@ -119,7 +176,7 @@ __device__ __noinline__ void encode_rows_cand_f16(const float* x, int64_t x_rs, 
             while (!cur && flagged_c) {
                 cur_ti = __builtin_ctzll(flagged_c);
                 flagged_c &= flagged_c - 1;
-                cur = __builtin_amdgcn_readfirstlane(tiles[cur_ti]);
+                cur = __builtin_amdgcn_readfirstlane(tiles_l[cur_ti]);
             }
             if (!cur) break;
             const int r = 32 * cur_ti + __builtin_ctz(cur);
@@ -128,8 +185,8 @@ __device__ __noinline__ void encode_rows_cand_f16(const float* x, int64_t x_rs, 
         }
         const bool rv = rel >= 0;
         const int64_t row = row_begin + rel;
-        const float* p = rv ? xsub + row * x_rs : plast;
-        const f32x4 v0 = *reinterpret_cast<const f32x4_u*>(p + c0), v1 = *reinterpret_cast<const f32x4_u*>(p + c1);
+        const PQHIP_GLOBAL_AS float* p = rv ? xsub + row * x_rs : plast;
+        const f32x4 v0 = *reinterpret_cast<gf32x4_p>(p + c0), v1 = *reinterpret_cast<gf32x4_p>(p + c1);
         // the B operand and s^2 xx exactly as the loop builds them
         unsigned w[4] = {pk_f16(sl * v0[0], sl * v0[1]), pk_f16(sl * v0[2], sl * v0[3]), pk_f16(sl * v1[0], sl * v1[1]),
                          pk_f16(sl * v1[2], sl * v1[3])};
@@ -141,41 +198,71 @@ __device__ __noinline__ void encode_rows_cand_f16(const float* x, int64_t x_rs, 
         float u[4];
         gather_groups((q < 3 ? s0 : 0.f) + (q < 2 ? s1 : 0.f), u);
         const float xxs = sc2 * ((u[0] + u[1]) + (u[2] + u[3]));
-        auto block = [&](int cb) {
-            const u32x4_t af = *reinterpret_cast<const u32x4_t*>(arow + cb * 16 * kRow);
+        // Two passes of 16 matrix instructions, neither of which keeps the 64 values: the first folds every block into the
+        // lane's smallest value, the second computes the blocks again -- the same instruction on the same operands, the
+        // same bits -- and tests a block's four values against tau while they are live.  The second pass reads its A
+        // fragments through a pointer the compiler cannot see through, so that it does not merge the passes and carry
+        // the values (or the fragments) from one to the other.
+        auto block = [&](const PQHIP_LDS_AS unsigned short* ar, int cb) {
+            const u32x4_t af = *reinterpret_cast<const PQHIP_LDS_AS u32x4_t*>(ar + cb * 16 * kRow);
             return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, af), __builtin_bit_cast(f16x8_t, bo),
                                                           (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
         };
+        // the values are no NaN for a row that is resolved here (finite operands); the minimum of a lane with no row is not used
         float mn = __builtin_inff();
 #pragma unroll
         for (int cb = 0; cb < 16; ++cb) {
-            const f32x4 d = block(cb);
-            mn = fminf(mn, fminf(fminf(d[0], d[1]), fminf(d[2], d[3])));
+            // four blocks in flight at a time: all sixteen fragments read ahead are 64 registers more
+            if (cb % 4 == 0) __builtin_amdgcn_sched_barrier(0);
+            const f32x4 d = block(arow, cb);
+            mn = __builtin_elementwise_minimum(mn, __builtin_elementwise_minimum(__builtin_elementwise_minimum(d[0], d[1]),
+                                                                                 __builtin_elementwise_minimum(d[2], d[3])));
         }
         float mq[4];
         gather_groups(mn, mq);
-        const float tau = fminf(fminf(mq[0], mq[1]), fminf(mq[2], mq[3])) + (kScreenRel * (xxs + maxcct) + kScreenAbs);
-        unsigned long long cm = 0;                                      // bit 4 cb + v: centroid 16 cb + 4 q + v
+        // (a lane with no row tests against NaN: no candidate, and no branch around the tests for the compiler to sink
+        // them into, behind all sixteen blocks)
+        const float tau = rv ? fminf(fminf(mq[0], mq[1]), fminf(mq[2], mq[3])) + (kScreenRel * (xxs + maxcct) + kScreenAbs)
+                             : __builtin_nanf("");
+        const PQHIP_LDS_AS unsigned short* arow2 = arow;
+        asm volatile("" : "+v"(arow2) : "v"(tau));                     // (and not before tau is there to test against)
+        unsigned cw[2] = {0u, 0u};                                      // bit 4 cb + v of the two words: centroid 16 cb + 4 q + v
 #pragma unroll
         for (int cb = 0; cb < 16; ++cb) {
-            const f32x4 d = block(cb);
+            if (cb % 4 == 0) __builtin_amdgcn_sched_barrier(0);
+            const f32x4 d = block(arow2, cb);
 #pragma unroll
-            for (int v = 0; v < 4; ++v) cm |= (d[v] <= tau ? 1ull : 0ull) << (4 * cb + v);
+            for (int v = 0; v < 4; ++v) cw[cb >> 3] |= (d[v] <= tau ? 1u : 0u) << (4 * (cb & 7) + v);
+            // the four blocks' bits are there before the next four are issued (the tests would otherwise move down to
+            // the word's first use, after the last block)
+            if (cb % 4 == 3) asm volatile("" : "+v"(cw[cb >> 3]));
         }
-        if (!rv) cm = 0;
-        const float* xs = xsub + (rv ? row : 0) * x_rs;
-        const float xxe = rv ? norm_unrolled_global(xs, DP) : 0.f;
+        unsigned long long cm = ((unsigned long long)cw[1] << 32) | cw[0];
+        float xr[DP];
+        load20_global(xsub + (rv ? row : 0) * x_rs, xr);
+        const float xxe = rv ? norm_unrolled_static<DP>(xr) : 0.f;
         unsigned bh = 0xffffffffu, bl = 0xffffffffu;
+        // the candidates of a lane two at a time, lowest index first: a lane with one left (or none) evaluates centroid 0
+        // in the empty slot and drops the result
         while (__builtin_amdgcn_ballot_w64(cm != 0)) {                 // wave-uniform
-            if (cm) {
-                const int bit = __builtin_ctzll(cm);
+            int j[2];
+            bool cv[2];
+            float ce[2][DP], ccj[2];
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                const int bit = cm ? __builtin_ctzll(cm) : 0;
+                j[s] = 16 * (bit >> 2) + 4 * q + (bit & 3);
+                cv[s] = cm != 0 && j[s] < K;
                 cm &= cm - 1;
-                const int j = 16 * (bit >> 2) + 4 * q + (bit & 3);
-                if (j < K) {
-                    const float dp = chain_dot_global(xs, 1, cbk + ((int64_t)m * K + j) * DP, 1, DP);
-                    const unsigned kh = ord_key(fsub(fadd(xxe, ccn[(int64_t)m * k_pad + j]), fadd(dp, dp)));
-                    if (kh < bh || (kh == bh && (unsigned)j < bl)) { bh = kh; bl = (unsigned)j; }
-                }
+                const int jj = cv[s] ? j[s] : 0;
+                load20_global(cbm + (int64_t)jj * DP, ce[s]);
+                ccj[s] = ccm[jj];
+            }
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                const float dp = chain_dot20(xr, ce[s]);
+                const unsigned kh = ord_key(fsub(fadd(xxe, ccj[s]), fadd(dp, dp)));
+                if (cv[s] && (kh < bh || (kh == bh && (unsigned)j[s] < bl))) { bh = kh; bl = (unsigned)j[s]; }
             }
         }
         float hq[4], lq[4];
@@ -188,7 +275,7 @@ __device__ __noinline__ void encode_rows_cand_f16(const float* x, int64_t x_rs, 
             const unsigned h = __float_as_uint(hq[g]), l = __float_as_uint(lq[g]);
             if (h < bh || (h == bh && l < bl)) { bh = h; bl = l; }
         }
-        if (rv && q == 0) reinterpret_cast<IdxT*>(out)[row * o_rs + m] = (IdxT)bl;
+        if (rv && q == 0) ((PQHIP_GLOBAL_AS IdxT*)out)[row * o_rs + m] = (IdxT)bl;
     }
 }
 
@@ -211,18 +298,20 @@ __device__ __noinline__ void encode_rows_few(const float* x, int64_t x_rs, void*
 {
     constexpr int DP = 20;
     const int lane = threadIdx.x & 63;
-    const float* const xsub = x + (int64_t)m * dsub;
-    const float* const cbm = cbk + (int64_t)m * K * DP;
-    const float* const ccm = ccn + (int64_t)m * k_pad;
+    const PQHIP_GLOBAL_AS float* const xsub = (const PQHIP_GLOBAL_AS float*)x + (int64_t)m * dsub;
+    const PQHIP_GLOBAL_AS float* const cbm = (const PQHIP_GLOBAL_AS float*)cbk + (int64_t)m * K * DP;
+    const PQHIP_GLOBAL_AS float* const ccm = (const PQHIP_GLOBAL_AS float*)ccn + (int64_t)m * k_pad;
+    const PQHIP_LDS_AS u32x2_t* const list_l = (const PQHIP_LDS_AS u32x2_t*)list;
     for (int e0 = 0; e0 < count; e0 += 64) {                            // wave-uniform
         const bool rv = e0 + lane < count;
-        const uint2* const en = list + kScreenFewWords * (rv ? e0 + lane : 0);   // entry 0 exists: count > 0
-        const uint2 w0 = en[0], w1 = en[1], w2 = en[2];
-        const unsigned key[4] = {w0.x, w0.y, w1.x, w1.y};
-        const float tau = __uint_as_float(w2.x);
-        const int64_t row = row_begin + w2.y;
-        const float* xs = xsub + row * x_rs;
-        const float xxe = norm_unrolled_global(xs, DP);
+        const PQHIP_LDS_AS u32x2_t* const en = list_l + kScreenFewWords * (rv ? e0 + lane : 0);   // entry 0 exists: count > 0
+        const u32x2_t w0 = en[0], w1 = en[1], w2 = en[2];
+        const unsigned key[4] = {w0[0], w0[1], w1[0], w1[1]};
+        const float tau = __uint_as_float(w2[0]);
+        const int64_t row = row_begin + w2[1];
+        float xr[DP];
+        load20_global(xsub + row * x_rs, xr);
+        const float xxe = norm_unrolled_static<DP>(xr);
         unsigned bh = 0xffffffffu, bl = 0xffffffffu;
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
@@ -230,11 +319,13 @@ __device__ __noinline__ void encode_rows_few(const float* x, int64_t x_rs, void*
             const int j = (int)(16u * (kb >> 2) + 4u * g + (kb & 3u));
             const bool cg = __uint_as_float(key[g]) <= tau && j < K;
             const int jj = cg ? j : 0;
-            const float dp = chain_dot_global(xs, 1, cbm + (int64_t)jj * DP, 1, DP);
+            float ce[DP];
+            load20_global(cbm + (int64_t)jj * DP, ce);
+            const float dp = chain_dot20(xr, ce);
             const unsigned kh = ord_key(fsub(fadd(xxe, ccm[jj]), fadd(dp, dp)));
             if (cg && (kh < bh || (kh == bh && (unsigned)j < bl))) { bh = kh; bl = (unsigned)j; }
         }
-        if (rv) reinterpret_cast<IdxT*>(out)[row * o_rs + m] = (IdxT)bl;
+        if (rv) ((PQHIP_GLOBAL_AS IdxT*)out)[row * o_rs + m] = (IdxT)bl;
     }
 }
 
@@ -247,7 +338,6 @@ __device__ __forceinline__ void encode_mfma16_screen(const EncodeArgs& a)
     __shared__ unsigned need_s[4][kMfma16MaxTiles];   // rows for encode_rows_slow_v
     __shared__ unsigned cand_s[4][kMfma16MaxTiles];   // rows for the candidate path
     __shared__ uint2 few_s[4][kScreenFewCap * kScreenFewWords];   // rows for encode_rows_few
-    __shared__ unsigned maxcc_s;
 
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -264,44 +354,23 @@ __device__ __forceinline__ void encode_mfma16_screen(const EncodeArgs& a)
     const bool wg_active = (g_local < a.chunks_per_xcd) && (group < a.n_chunks);
 
     const unsigned long long st_s0 = a.stamps ? __builtin_amdgcn_s_memtime() : 0;
-    if (wg_active && threadIdx.x == 0) maxcc_s = 0u;
-    __syncthreads();
-    // one thread per centroid: the largest real ||c||^2 first (bits order = value order for cc >= +0; a NaN norm comes
-    // out above +inf), then the scale and the image row
-    const int c = threadIdx.x;
-    const float ccv = wg_active ? a.cc[(int64_t)m * a.k_pad + c] : 0.f;
-    if (wg_active && c < a.K) atomicMax(&maxcc_s, __float_as_uint(ccv));
-    __syncthreads();
-    const float maxcc = __uint_as_float(maxcc_s);
-    const bool cc_range = maxcc >= kScreenMinCC && maxcc < kBigNorm;    // false for NaN
-    // s = 2^e with e = floor((kScreenScaleLo + 1 - log2 max cc) / 2): s^2 max cc in [2^12, 2^14), e in [-43, 56]
-    const int escale = cc_range ? (kScreenScaleLo + 1 - ((int)(__float_as_uint(maxcc) >> 23) - 127)) >> 1 : 0;
-    const float sc = __uint_as_float((unsigned)(127 + escale) << 23);
-    const float sc2 = __uint_as_float((unsigned)(127 + 2 * escale) << 23);
+    // the subquantizer's image, as k_build_screen_image left it: thread t copies the 16-byte chunks t, t + 256, t + 512 and
+    // t + 768; max cc comes from the header with one wave-uniform load
+    unsigned maxcc_bits = 0u;
     if (wg_active) {
-        unsigned w[16];
-        if (c < a.K) {
-            const float* cp = a.cb + ((int64_t)m * a.K + c) * DP;
-            const float m2s = -2.f * sc;
+        const u32x4_t* src = reinterpret_cast<const u32x4_t*>(a.screen_img) + (int64_t)m * (kScreenImageBytes / 16) + threadIdx.x;
+        u32x4_t* dst = reinterpret_cast<u32x4_t*>(img_s) + threadIdx.x;
+        u32x4_t ch[4];
 #pragma unroll
-            for (int j = 0; j < DP / 2; ++j) w[j] = pk_f16(m2s * cp[2 * j], m2s * cp[2 * j + 1]);   // RNE(-2 s c)
-            const float cct = sc2 * ccv;                                 // exact, < 2^14
-            const unsigned hp = pk_f16(cct, 0.f);
-            w[10] = pk_f16(cct, cct - f16_lo(hp));                       // cct - hi is exact
-            w[11] = 0u;
-        } else {
-            // padding centroid: A = 65504^2 from the k = 22 slot, above every real value, never a candidate
+        for (int j = 0; j < 4; ++j) ch[j] = src[256 * j];
+        maxcc_bits = a.screen_img[(int64_t)a.M * (kScreenImageBytes / 4) + m * (kScreenHeaderBytes / 4)];
 #pragma unroll
-            for (int j = 0; j < 11; ++j) w[j] = 0u;
-            w[11] = 0x7bffu;
-        }
-#pragma unroll
-        for (int j = 12; j < 16; ++j) w[j] = 0u;
-        u32x4_t* dst = reinterpret_cast<u32x4_t*>(&img_s[c * kRow]);
-        const int swz = (c >> 2) & 3;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) dst[j ^ swz] = (u32x4_t){w[4 * j], w[4 * j + 1], w[4 * j + 2], w[4 * j + 3]};
+        for (int j = 0; j < 4; ++j) dst[256 * j] = ch[j];
     }
+    const float maxcc = __uint_as_float(maxcc_bits);
+    const ScreenScale scale = screen_scale(maxcc);
+    const bool cc_range = scale.cc_range;
+    const float sc = scale.sc, sc2 = scale.sc2;
     __syncthreads();
     const unsigned long long st_stage = a.stamps ? __builtin_amdgcn_s_memtime() - st_s0 : 0;   // image staging
     const int64_t row_begin = (group * 4 + wave) * a.rows_per_item;
@@ -562,9 +631,11 @@ __device__ __forceinline__ void encode_mfma16_screen(const EncodeArgs& a)
     if (few_room < kScreenFewCap)                                       // wave-uniform
         encode_rows_few<IdxT>(a.x, a.x_rs, a.out, a.o_rs, a.cb, a.cc, a.K, a.k_pad, a.dsub, m, row_begin, few_s[wave],
                               kScreenFewCap - (few_room > 0 ? few_room : 0));
+    const unsigned long long st_p1 = a.stamps ? __builtin_amdgcn_s_memtime() : 0;
     if (flagged_c)                                                      // wave-uniform
         encode_rows_cand_f16<IdxT>(a.x, a.x_rs, a.out, a.o_rs, a.cb, a.cc, a.K, a.k_pad, a.dsub, a.n, m, row_begin,
                                    img_s, cand_s[wave], flagged_c, sc, sc2 * maxcc);
+    const unsigned long long st_p2 = a.stamps ? __builtin_amdgcn_s_memtime() : 0;
     // ---- rows outside the f16 range or under a bad codebook: every centroid exactly
     while (flagged) {                                                   // wave-uniform
         const int ti = __builtin_ctzll(flagged);
@@ -578,6 +649,7 @@ __device__ __forceinline__ void encode_mfma16_screen(const EncodeArgs& a)
         const unsigned long long st_end = __builtin_amdgcn_s_memtime();
         o[3] = st_end - st_t0; o[4] = __builtin_amdgcn_s_memrealtime() - st_r0; o[5] = st_stage;
         o[6] = st_full; o[7] = st_end - st_p0;
+        o[8] = st_p1 - st_p0; o[9] = st_p2 - st_p1;                     // encode_rows_few, encode_rows_cand_f16
     }
 }
 

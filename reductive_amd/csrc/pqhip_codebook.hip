@@ -163,6 +163,24 @@ ErrFlag::~ErrFlag()
 }
 
 // ---- preparation ---------------------------------------------------------------------------------------------------
+// codebooks the screen body of k_encode_mfma16 can take (it needs whole 20-float sub-vectors: dsub == DP)
+static bool has_screen_image(const pqhip_codebook* cb)
+{
+    return mfma16_screen_shape(cb->T, cb->DP) && cb->dsub == cb->DP && cb->K <= 256;
+}
+
+// the f16 image and max cc of the screen body, from cd.cb and cd.cc as they are on st
+int32_t build_screen_image(pqhip_codebook* cb, int slot, hipStream_t st)
+{
+    CodebookDev& cd = cb->dev[slot];
+    hipLaunchKernelGGL(k_build_screen_image, dim3((unsigned)cb->M), dim3(256), 0, st, cd.cb, cd.cc, (int)cb->M, (int)cb->K, cb->k_pad,
+                       cd.screen_img);
+    HIPCHK(hipGetLastError());
+    note_kernel("k_build_screen_image");
+    cd.screen_img_stale = false;
+    return PQHIP_OK;
+}
+
 static int32_t launch_prepare(pqhip_codebook* cb, int slot, hipStream_t st)
 {
     CodebookDev& cd = cb->dev[slot];
@@ -182,6 +200,14 @@ static int32_t launch_prepare(pqhip_codebook* cb, int slot, hipStream_t st)
         hipLaunchKernelGGL(k_build_frags, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st,
                            cd.cb, (int)M, (int)K, (int)dsub, tiles, S, cd.frags);
         note_kernel("k_build_frags");
+    }
+    // A Pq handle is prepared once and gets its image here.  A training handle is prepared after every update of its
+    // centroids, and its assignment step runs on another kernel: its image is only marked stale, and the first launch that
+    // screens with it (launch_mfma: the encode of an OPQ training step) builds it on its own stream, behind this
+    // preparation in stream order like the encode itself.
+    if (has_screen_image(cb)) {
+        if (cb->training) cd.screen_img_stale = true;
+        else PQCHK(build_screen_image(cb, slot, st));
     }
     if (cb->KP) {
         const int64_t tot = M * dsub * cb->KP;
@@ -234,6 +260,7 @@ int32_t codebook_create_impl(pqhip_ctx* ctx, const float* quantizers, int64_t M,
     cb->ctx = ctx;
     cb->M = M; cb->K = K; cb->dsub = dsub; cb->d = M * dsub;
     cb->has_proj = projection != nullptr;
+    cb->training = only_slot >= 0;
     // MFMA geometry: K <= 256 padded to {1,2,4,8} tiles of 32; dsub <= 32 padded to an even
     // number of k (one MFMA consumes two); A fragments must fit (T * DP/2 <= 128).
     int T = 0, DP = 0, groups = 1;
@@ -307,6 +334,7 @@ int32_t codebook_create_impl(pqhip_ctx* ctx, const float* quantizers, int64_t M,
         HIPCHK(hipMalloc((void**)&cd.err, (2 + kErrSlots) * sizeof(int)));
         HIPCHK(hipMemsetAsync(cd.err, 0, (2 + kErrSlots) * sizeof(int), st));
         if (T) HIPCHK(hipMalloc((void**)&cd.frags, (size_t)(M * groups * T * S * 64) * sizeof(float)));
+        if (has_screen_image(cb)) HIPCHK(hipMalloc((void**)&cd.screen_img, screen_image_bytes(M)));
         if (cb->KP) HIPCHK(hipMalloc((void**)&cd.cbt, (size_t)(M * dsub * cb->KP) * sizeof(float)));
         if (cb->pair16) HIPCHK(hipMalloc((void**)&cd.fragp, (size_t)(((M + 1) / 2) * (dsub * 64 + 32)) * sizeof(float)));
         if (cb->vor2) {
@@ -354,6 +382,7 @@ void pqhip_codebook_destroy(pqhip_codebook* cb)
         (void)hipDeviceSynchronize();
         if (cd.cb) (void)hipFree(cd.cb);
         if (cd.frags) (void)hipFree(cd.frags);
+        if (cd.screen_img) (void)hipFree(cd.screen_img);
         if (cd.cc) (void)hipFree(cd.cc);
         if (cd.cbt) (void)hipFree(cd.cbt);
         if (cd.fragp) (void)hipFree(cd.fragp);

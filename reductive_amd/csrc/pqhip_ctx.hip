@@ -64,7 +64,7 @@ int32_t StampRun::report5(hipStream_t st, const char* what, const char* a_name, 
     if (!buf.p) return PQHIP_OK;
     std::vector<unsigned long long> h;
     PQCHK(fetch(st, h));
-    double tiles = 0, a = 0, b = 0, cyc = 0, rt = 0, b_lo = 0, b_hi = 0, setup = 0, full = 0, post = 0;
+    double tiles = 0, a = 0, b = 0, cyc = 0, rt = 0, b_lo = 0, b_hi = 0, setup = 0, full = 0, post = 0, few = 0, cand = 0;
     size_t waves = 0;
     for (size_t i = 0; i + words <= n; i += words)
         if (h[i]) {
@@ -72,8 +72,12 @@ int32_t StampRun::report5(hipStream_t st, const char* what, const char* a_name, 
             b_lo += (double)(h[i + 2] & 0xffffffffull); b_hi += (double)(h[i + 2] >> 32);
             if (words > 5) setup += (double)h[i + 5];
             if (words > 7) { full += (double)h[i + 6]; post += (double)h[i + 7]; }
+            if (words > 9) { few += (double)h[i + 8]; cand += (double)h[i + 9]; }
         }
-    if (tiles > 0 && b_counts && words > 7)
+    if (tiles > 0 && b_counts && words > 9)
+        fprintf(stderr, "[pqhip] %s stamps: %zu waves, %.1f tiles/wave, %s %.0f cyc/tile, %s %.0f / %.0f rows, list full for %.0f rows, image staging %.0f cyc, after the loop %.0f cyc (few-candidate rows %.0f, candidate rows %.0f), wave life %.0f cyc, clock %.0f MHz\n",
+                what, waves, tiles / waves, a_name, a / tiles, b_name, b_lo, b_hi, full, setup / waves, post / waves, few / waves, cand / waves, cyc / waves, rt > 0 ? cyc / rt * 100.0 : 0.0);
+    else if (tiles > 0 && b_counts && words > 7)
         fprintf(stderr, "[pqhip] %s stamps: %zu waves, %.1f tiles/wave, %s %.0f cyc/tile, %s %.0f / %.0f rows, list full for %.0f rows, image staging %.0f cyc, after the loop %.0f cyc, wave life %.0f cyc, clock %.0f MHz\n",
                 what, waves, tiles / waves, a_name, a / tiles, b_name, b_lo, b_hi, full, setup / waves, post / waves, cyc / waves, rt > 0 ? cyc / rt * 100.0 : 0.0);
     else if (tiles > 0 && b_counts && words > 5)

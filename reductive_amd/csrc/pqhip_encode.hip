@@ -284,6 +284,13 @@ static int32_t launch_mfma(pqhip_codebook* cb, int slot, const EncodePlan& p, co
     a.frags = cd.frags; a.cc = cd.cc; a.cb = cd.cb;
     a.M = (int)cb->M; a.K = (int)cb->K; a.dsub = (int)cb->dsub; a.k_pad = cb->k_pad;
     a.groups = 1; a.bad_flag = io.bad_flag;
+    a.screen_img = cd.screen_img;
+    // the screen body of k_encode_mfma16 reads the prepared image and nothing else: without one there is no launch
+    if (p.kind == 3 && mfma16_screen_shape(cb->T, cb->DP)) {
+        if (!a.screen_img) return no_instantiation("k_encode_mfma16 (no screen image)");
+        // a training handle whose centroids moved since its image was built: build it now, in front of the launch that reads it
+        if (cd.screen_img_stale) PQCHK(build_screen_image(cb, slot, io.st));
+    }
     dim3 grid;
     if (p.kind >= 2) {
         // one workgroup = one subquantizer x 4 row streams (one per wave)
@@ -312,8 +319,9 @@ static int32_t launch_mfma(pqhip_codebook* cb, int slot, const EncodePlan& p, co
     // k_encode_mfma16 (kind 3) leaves row counts in word 2: of the rows the screen does not decide, those with two to four
     // candidates, one per lane group (round 6 resolved them in the loop), and all others (both zero in its FP32 body);
     // kinds 0 and 2 leave the seam cycles there.  The screen body adds the
-    // image-staging cycles as a sixth word, the few-candidate rows that found their wave's list full as a seventh and
-    // the cycles after the loop as an eighth.
+    // image-staging cycles as a sixth word, the few-candidate rows that found their wave's list full as a seventh,
+    // the cycles after the loop as an eighth, and of those the cycles in encode_rows_few and in encode_rows_cand_f16
+    // as a ninth and a tenth.
     if (p.kind == 3) return stamps.report5(io.st, "encode", "steps", "2-4-candidate / other off-screen", true, stamp_words);
     return stamps.report5(io.st, "encode", "steps", "seam");
 }

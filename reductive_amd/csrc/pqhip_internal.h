@@ -276,6 +276,8 @@ struct ScratchBuf {
 struct CodebookDev {
     float* cb = nullptr;     // [M][K][dsub]
     float* frags = nullptr;  // [M][T][S][64]
+    unsigned* screen_img = nullptr;   // T = 8, DP = 20, K <= 256: f16 images [M][16,384 B] + headers [M][16 B] of k_encode_mfma16's screen
+    bool screen_img_stale = false;    // training handles: the centroids moved since the image was built (launch_mfma rebuilds it)
     float* cc = nullptr;     // [M][k_pad]
     float* cbt = nullptr;    // [M][dsub][KP] transposed image for the small-codebook kernel (K <= 64)
     float* fragp = nullptr;  // [NP][dsub][64] block-diagonal pair fragments + [NP][2][16] norms (K <= 16: kernels_pair16.hip.h)
@@ -310,6 +312,7 @@ struct pqhip_codebook {
     pqhip_ctx* ctx = nullptr;
     int64_t M = 0, K = 0, dsub = 0, d = 0;
     bool has_proj = false;
+    bool training = false;  // an internal single-device handle whose centroids move (k-means, OPQ training step); Pq handles never change
     // MFMA encode geometry (0 = shape not covered, anchor kernel is used)
     int T = 0, DP = 0, k_pad = 0;
     bool wide = false;      // 128 < dsub <= 1,024: groups of 32 T <= 128 centroids through k_encode_mfma_wide / _wide2 (kernels_mfma_wide.hip.h)
@@ -381,6 +384,7 @@ int32_t codebook_create_impl(pqhip_ctx* ctx, const float* quantizers, int64_t M,
                              const float* projection, int only_slot, pqhip_codebook** out);
 int32_t prepare_codebook_dev(pqhip_codebook* cb, int slot, hipStream_t st, bool* norms_ok);
 int32_t prepare_codebook_async(pqhip_codebook* cb, int slot, hipStream_t st);
+int32_t build_screen_image(pqhip_codebook* cb, int slot, hipStream_t st);   // (pqhip_codebook.hip; needs cd.screen_img)
 int32_t lease_scratch(pqhip_codebook* cb, int slot, size_t bytes, hipStream_t st, int* out_idx, void** out_p);
 void release_scratch(pqhip_codebook* cb, int slot, int idx, hipStream_t st);
 struct ScratchLease {
