@@ -6,19 +6,10 @@
 #pragma once
 #include "pqhip_internal.h"
 
-#include <type_traits>
+#include "launch_dispatch.h"   // dispatch_int: here Vs is the list of instantiated values
 
 namespace pqh {
 
-// f(std::integral_constant<int, V>{}) for the V among Vs that equals v; PQHIP_EUNSUPPORTED when v is none of them.
-// Vs is the list of instantiated values: the kernels that exist are the ones named at the call.
-template <int... Vs, typename F>
-int32_t dispatch_int(int v, F&& f)
-{
-    int32_t status = PQHIP_EUNSUPPORTED;
-    (void)((v == Vs && (status = f(std::integral_constant<int, Vs>{}), true)) || ...);
-    return status;
-}
 // the list lengths of the searches: 64 L entries per (wave, query)
 template <typename F>
 int32_t dispatch_list_regs(int L, F&& f) { return dispatch_int<1, 2, 4, 8, 16>(L, f); }

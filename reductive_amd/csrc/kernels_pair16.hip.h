@@ -37,6 +37,9 @@ struct Pair16Args {
 
 // (k_build_pair_frags, the kernel that writes fragp / ccp, is a preparation kernel: kernels_prep.hip.h)
 
+// the sub-vector lengths k_encode_pair16 is instantiated for: asked by the codebook set-up and by the launcher
+constexpr bool pair16_has(int dsub) { return dsub == 2 || dsub == 4 || dsub == 8 || dsub == 16; }
+
 template <int DSUB>
 __global__ __launch_bounds__(256, 3) void k_encode_pair16(Pair16Args a)
 {

@@ -4,6 +4,7 @@
 #include "pqhip_internal.h"
 
 #include "kernels_mfma.hip.h"     // kBigNorm
+#include "kernels_pair16.hip.h"   // pair16_has
 #include "kernels_prep.hip.h"
 #include "smallk_launch.h"        // smallk_has / smallk_kp
 #include "vor2_launch.h"         // vor2_has_lds
@@ -298,7 +299,7 @@ int32_t codebook_create_impl(pqhip_ctx* ctx, const float* quantizers, int64_t M,
     {   // pair kernel: K <= 16, power-of-two sub-vectors up to 16 floats, fragment image + slabs within 160 KB of LDS
         const int64_t NP = (M + 1) / 2;
         const size_t lds = ((size_t)NP * dsub * 64 + (size_t)NP * 32 + 4 * 2 * 32 * 36) * sizeof(float);
-        cb->pair16 = K <= 16 && (dsub == 2 || dsub == 4 || dsub == 8 || dsub == 16) && lds <= 160 * 1024;
+        cb->pair16 = K <= 16 && pair16_has((int)dsub) && lds <= 160 * 1024;
     }
     cb->k_pad = T ? T * 32 * groups : (int)round_up(K, 32);
     const int S = DP / 2;

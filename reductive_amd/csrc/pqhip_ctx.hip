@@ -92,6 +92,31 @@ int32_t StampRun::report5(hipStream_t st, const char* what, const char* a_name, 
     return PQHIP_OK;
 }
 
+int32_t StampRun::report_rotate(hipStream_t st, const char* file)
+{
+    if (!buf.p) return PQHIP_OK;
+    std::vector<unsigned long long> h;
+    PQCHK(fetch(st, h));
+    double tiles = 0, kc = 0, ec = 0, cyc = 0, rt = 0, cmax = 0, cmin = 1e30, wgmax = 0, first = 0, last = 0; size_t waves = 0, wgs = 0;
+    for (size_t w0 = 0; w0 < h.size(); w0 += 12 * 8) {
+        double m = 0;
+        for (size_t i = w0; i < w0 + 12 * 8; i += 8)
+            if (h[i]) {
+                tiles += (double)h[i]; kc += (double)h[i + 1]; ec += (double)h[i + 2]; cyc += (double)h[i + 3]; rt += (double)h[i + 4]; ++waves;
+                first += (double)h[i + 6]; last += (double)h[i + 7];
+                cmax = std::max(cmax, (double)h[i + 3]); cmin = std::min(cmin, (double)h[i + 3]); m = std::max(m, (double)h[i + 3]);
+            }
+        if (m > 0) { wgmax += m; ++wgs; }
+    }
+    if (tiles > 0)
+        fprintf(stderr, "[pqhip] rotate v8/v9 stamps: %zu waves, %.1f tiles/wave, tile %.0f cyc (first %.0f, last %.0f), P staging %.0f cyc/wave, wave life %.0f cyc (min %.0f, max %.0f; slowest wave of a workgroup %.0f), clock %.0f MHz\n",
+                waves, tiles / waves, kc / tiles, first / waves, last / waves, ec / waves, cyc / waves, cmin, cmax, wgmax / wgs, rt > 0 ? cyc / rt * 100.0 : 0.0);
+    if (file) {
+        if (FILE* fp = fopen(file, "ab")) { fwrite(h.data(), sizeof(unsigned long long), h.size(), fp); fclose(fp); }
+    }
+    return PQHIP_OK;
+}
+
 // ---- packing threads ---------------------------------------------------------------------------------------------
 RowPool::RowPool(int n_threads) : n_(std::max(1, n_threads))
 {

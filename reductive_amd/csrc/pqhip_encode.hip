@@ -145,6 +145,8 @@ EncodeCall encode_call(const pqhip_codebook* cb, int slot, const EncodeIo& io, i
 
 // ---- launch helpers: arguments and geometry of the planned kernel ---------------------------------------------------
 static int32_t no_instantiation(const char* kernel) { g_hip_err = std::string("no instantiation: ") + kernel; return PQHIP_EHIP; }
+// the answer of a family's launcher (launch_dispatch.h): a kernel the plan names and the launcher does not have is an error
+static int32_t launched(int32_t status, const char* kernel) { return status == PQHIP_OK ? PQHIP_OK : no_instantiation(kernel); }
 
 // wide and grouped: one 64-bit key {ordered distance, global index} per (row, group of <= 128 / 256 centroids), k_merge_keys ->
 // codes; the wide kernel takes squared norms from a pre-pass.  Keys and norms: one leased scratch buffer, rows chunked to <= 1 GiB.
@@ -175,9 +177,9 @@ static int32_t launch_keyed(pqhip_codebook* cb, int slot, const EncodePlan& p, c
         a.n_chunks = (rows + 4 * rpi - 1) / (4 * rpi);
         a.chunks_per_xcd = (a.n_chunks + 7) / 8;
         const dim3 grid((unsigned)(a.chunks_per_xcd * Mv * 8));
-        if (!(wide ? launch_encode_wide(cb->T, cb->DP, a, xx, grid, io.st)
-                   : launch_encode_mfma(2, 8, cb->DP, cb->DP == cb->dsub, 8, a, grid, io.st, diag().lds_pad)))
-            return no_instantiation(p.kernel);
+        PQCHK(launched(wide ? launch_encode_wide(cb->T, cb->DP, a, xx, grid, io.st)
+                            : launch_encode_mfma(2, 8, cb->DP, cb->DP == cb->dsub, 8, a, grid, io.st, diag().lds_pad),
+                       p.kernel));
         note_kernel(p.kernel);
         const unsigned mg = (unsigned)std::min<int64_t>((rows * cb->M + 255) / 256, 256 * 32);
         if (c.code_bytes == 4)
@@ -225,15 +227,19 @@ static int32_t launch_vor2_family(pqhip_codebook* cb, int slot, const EncodeCall
     const CodebookDev& cd = cb->dev[slot];
     const Vor2Launch l{io.x, c.n, io.x_rs, (uint8_t*)io.codes, io.o_rs, cd.cb, cd.cc, cd.vor2_tab, cd.vor2_off,
                        (int)cb->M, (int)cb->K, cb->k_pad, (int)cb->dsub, cb->vor2_max_region_words, c.n_cus};
-    return launch_vor2(l, io.st) ? PQHIP_OK : no_instantiation("k_encode_vor2");
+    return launched(launch_vor2(l, io.st), "k_encode_vor2");
 }
 
 template <int D>
 static int32_t pair16(const Pair16Args& a, unsigned grid, size_t lds, hipStream_t st)
 {
-    HIPCHK(hipFuncSetAttribute((const void*)k_encode_pair16<D>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    hipLaunchKernelGGL((k_encode_pair16<D>), dim3(grid), dim3(256), lds, st, a);
-    return PQHIP_OK;
+    if constexpr (!pair16_has(D)) {
+        return PQHIP_EUNSUPPORTED;
+    } else {
+        HIPCHK(hipFuncSetAttribute((const void*)k_encode_pair16<D>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        hipLaunchKernelGGL((k_encode_pair16<D>), dim3(grid), dim3(256), lds, st, a);
+        return PQHIP_OK;
+    }
 }
 
 static int32_t launch_pair16(pqhip_codebook* cb, int slot, const EncodeCall& c, const EncodeIo& io)
@@ -248,9 +254,9 @@ static int32_t launch_pair16(pqhip_codebook* cb, int slot, const EncodeCall& c, 
     const size_t lds = ((size_t)NP * cb->dsub * 64 + (size_t)NP * 32 + 4 * 2 * 32 * 36) * sizeof(float);
     const int per_cu = std::max<int>(1, std::min<int>(3, (int)(160 * 1024 / lds)));
     const unsigned grid = (unsigned)std::min<int64_t>((a.n_tiles + 3) / 4, (int64_t)c.n_cus * per_cu);
-    const int d = (int)cb->dsub;
-    return d == 2 ? pair16<2>(a, grid, lds, io.st) : d == 4 ? pair16<4>(a, grid, lds, io.st) : d == 8 ? pair16<8>(a, grid, lds, io.st)
-                                                                                                  : pair16<16>(a, grid, lds, io.st);
+    // candidates: the power-of-two sub-vector lengths up to 32 floats
+    const int32_t status = dispatch_int<1, 2, 4, 8, 16, 32>((int)cb->dsub, [&](auto d_c) { return pair16<decltype(d_c)::value>(a, grid, lds, io.st); });
+    return status == PQHIP_EUNSUPPORTED ? no_instantiation("k_encode_pair16") : status;
 }
 
 // the small-codebook kernels: k_encode_small16 (16x16x4, codebook image in LDS) and k_encode_smallk (VALU)
@@ -262,7 +268,7 @@ static int32_t launch_small(pqhip_codebook* cb, int slot, const EncodePlan& p, c
     a.cbt = cd.cbt; a.cc = cd.cc; a.cb = cd.cb;
     a.M = (int)cb->M; a.K = (int)cb->K; a.k_pad = cb->k_pad;
     if (p.family == EncodeFamily::smallk)
-        return launch_smallk(cb->KP, (int)cb->dsub, a, dim3((unsigned)((c.n + 255) / 256)), io.st) ? PQHIP_OK : no_instantiation(p.kernel);
+        return launched(launch_smallk(cb->KP, (int)cb->dsub, a, dim3((unsigned)((c.n + 255) / 256)), io.st), p.kernel);
     // consecutive 64-row tiles per wave: the codebook image is staged once per workgroup, so as many as leave about
     // eight rounds of workgroups for the launch
     const int64_t tile_rows = small16_tile_rows((int)cb->dsub);
@@ -272,7 +278,7 @@ static int32_t launch_small(pqhip_codebook* cb, int slot, const EncodePlan& p, c
     a.tiles_per_wave = (int)std::max<int64_t>(1, std::min<int64_t>(kSmall16TilesMax, n_tiles / (4 * wg_slots)));
     const size_t lds = small16_lds_bytes(a.M, (int)cb->dsub, cb->KP);
     const dim3 grid((unsigned)((n_tiles + 4 * a.tiles_per_wave - 1) / (4 * a.tiles_per_wave)));
-    return launch_small16(cb->KP, (int)cb->dsub, a, grid, lds, io.st) ? PQHIP_OK : no_instantiation(p.kernel);
+    return launched(launch_small16(cb->KP, (int)cb->dsub, a, grid, lds, io.st), p.kernel);
 }
 
 static int32_t launch_mfma(pqhip_codebook* cb, int slot, const EncodePlan& p, const EncodeCall& c, const EncodeIo& io)
@@ -315,7 +321,7 @@ static int32_t launch_mfma(pqhip_codebook* cb, int slot, const EncodePlan& p, co
     const int stamp_words = (p.kind == 3 && mfma16_screen_shape(cb->T, cb->DP)) ? kScreenStampWords : 5;
     PQCHK(stamps.begin(diag().enc_stamp && p.kind >= 2, (size_t)grid.x * 4 * stamp_words, io.st));
     a.stamps = stamps.ptr();
-    if (!launch_encode_mfma(p.kind, cb->T, cb->DP, p.vec, c.code_bytes, a, grid, io.st, diag().lds_pad)) return no_instantiation(p.kernel);
+    PQCHK(launched(launch_encode_mfma(p.kind, cb->T, cb->DP, p.vec, c.code_bytes, a, grid, io.st, diag().lds_pad), p.kernel));
     // k_encode_mfma16 (kind 3) leaves row counts in word 2: of the rows the screen does not decide, those with two to four
     // candidates, one per lane group (round 6 resolved them in the loop), and all others (both zero in its FP32 body);
     // kinds 0 and 2 leave the seam cycles there.  The screen body adds the

@@ -371,6 +371,9 @@ struct StampRun {
     // (b_counts: word 2 holds {low 32 bits, high 32 bits} row counts, printed as totals of the launch; words = 6: a sixth
     // word per wave holds set-up cycles before the first tile, printed per wave)
     int32_t report5(hipStream_t st, const char* what, const char* a_name, const char* b_name, bool b_counts = false, int words = 5);
+    // the eight-word-per-wave layout of the P-block rotation kernels, 12 waves per workgroup: {tiles, tile cycles, P staging
+    // cycles, wave life, real time, -, first tile, last tile}; file != null: the raw words are appended to it
+    int32_t report_rotate(hipStream_t st, const char* file);
 };
 
 // ---- pqhip_ctx.hip -------------------------------------------------------------------------------------------

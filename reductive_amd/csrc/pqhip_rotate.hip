@@ -7,12 +7,20 @@
 #include "kernels_rotate.hip.h"
 #include "kernels_rotate8.hip.h"
 #include "kernels_rotate9.hip.h"
+#include "launch_dispatch.h"
 
 using namespace pqhip;
 
 namespace pqh {
 
 static std::atomic<int> g_rotation_variant{0};   // pqhip_set_rotation_variant: 0 auto, 8 / 9 force k_rotate_pblock8 / 9 (test knob)
+
+// the four boolean template facts of a P-block kernel as one dispatch value: f(integral_constant 8 s + 4 o + 2 t + g)
+template <typename F>
+static int32_t dispatch_facts4(bool s, bool o, bool t, bool g, F&& f)
+{
+    return dispatch_int<0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15>(8 * s + 4 * o + 2 * t + g, f);
+}
 
 // out[n][d] = x[n][d] . Pm   on the device
 // ga != nullptr: the rows are gathered from the codebook inside the rotation kernel; returns PQHIP_EUNSUPPORTED when
@@ -59,67 +67,37 @@ int32_t rotate_dev(const float* d_x, int64_t n, int64_t x_rs, const float* Pm, i
             const dim3 grid((unsigned)(rg_per_xcd * ncb * 8));
             StampRun stamps;      // (diagnostic builds: in-kernel s_memtime summary of the launch)
             PQCHK(stamps.begin(diag().rot_stamp, (size_t)grid.x * 12 * 8, st));
+            const Rot8Gather gather = ga ? *ga : Rot8Gather{};
             if (v9) {
                 const size_t lds9 = (size_t)nb9 * (narrow9 ? 2048 : 4096);
                 // template facts: rule-2 split (d > 256), odd number of 16-k bursts, partial last burst
                 const bool splitk9 = d > kKC, odd9 = (nb9 & 1) != 0, tail9 = (d & 15) != 0;
-#define LAUNCH_ROT9W(W, S, O, T, G)                                                                                 \
-                do {                                                                                                \
-                    HIPCHK(hipFuncSetAttribute((const void*)k_rotate_pblock9<W, S, O, T, G>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
-                    hipLaunchKernelGGL((k_rotate_pblock9<W, S, O, T, G>), grid, dim3(768), lds9, st, d_x, n, x_rs, Pm, d, d_out, o_rs, rows_per_wg, ncb, \
-                                       rg_per_xcd, ga ? *ga : Rot8Gather{}, stamps.ptr());                          \
-                } while (0)
-#define LAUNCH_ROT9G(S, O, T, G) do { if (narrow9) LAUNCH_ROT9W(2, S, O, T, G); else LAUNCH_ROT9W(4, S, O, T, G); } while (0)
-#define LAUNCH_ROT9(S, O, T) do { if (ga) LAUNCH_ROT9G(S, O, T, true); else LAUNCH_ROT9G(S, O, T, false); } while (0)
-                if (splitk9) { if (odd9) { if (tail9) LAUNCH_ROT9(true, true, true); else LAUNCH_ROT9(true, true, false); }
-                               else      { if (tail9) LAUNCH_ROT9(true, false, true); else LAUNCH_ROT9(true, false, false); } }
-                else         { if (odd9) { if (tail9) LAUNCH_ROT9(false, true, true); else LAUNCH_ROT9(false, true, false); }
-                               else      { if (tail9) LAUNCH_ROT9(false, false, true); else LAUNCH_ROT9(false, false, false); } }
-#undef LAUNCH_ROT9
-#undef LAUNCH_ROT9G
-#undef LAUNCH_ROT9W
+                PQCHK((dispatch_int<2, 4>(narrow9 ? 2 : 4, [&](auto w_c) {
+                    return dispatch_facts4(splitk9, odd9, tail9, ga != nullptr, [&](auto f_c) -> int32_t {
+                        constexpr int W = decltype(w_c)::value, F = decltype(f_c)::value;
+                        constexpr bool S = (F & 8) != 0, O = (F & 4) != 0, T = (F & 2) != 0, G = (F & 1) != 0;
+                        HIPCHK(hipFuncSetAttribute((const void*)k_rotate_pblock9<W, S, O, T, G>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+                        hipLaunchKernelGGL((k_rotate_pblock9<W, S, O, T, G>), grid, dim3(768), lds9, st, d_x, n, x_rs, Pm, d, d_out, o_rs, rows_per_wg, ncb,
+                                           rg_per_xcd, gather, stamps.ptr());
+                        return PQHIP_OK;
+                    });
+                })));
                 note_kernel(ga ? "k_rotate_pblock9<gather>" : "k_rotate_pblock9");
             } else {
                 // template facts: rule-2 split (d > 256), odd number of full 32-k bursts, partial last burst
                 const bool splitk = d > kKC, odd = ((d >> 5) & 1) != 0, tail = (d & 31) != 0;
-#define LAUNCH_ROT8G(S, O, T, G)                                                                                    \
-                do {                                                                                                \
-                    HIPCHK(hipFuncSetAttribute((const void*)k_rotate_pblock8<S, O, T, G>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
-                    hipLaunchKernelGGL((k_rotate_pblock8<S, O, T, G>), grid, dim3(G ? 512 : 768), lds8, st, d_x, n, x_rs, Pm, d, d_out, o_rs, rows_per_wg, ncb, \
-                                       rg_per_xcd, ga ? *ga : Rot8Gather{}, stamps.ptr());                          \
-                } while (0)
-#define LAUNCH_ROT8(S, O, T) do { if (ga) LAUNCH_ROT8G(S, O, T, true); else LAUNCH_ROT8G(S, O, T, false); } while (0)
-                if (splitk) { if (odd) { if (tail) LAUNCH_ROT8(true, true, true); else LAUNCH_ROT8(true, true, false); }
-                              else     { if (tail) LAUNCH_ROT8(true, false, true); else LAUNCH_ROT8(true, false, false); } }
-                else        { if (odd) { if (tail) LAUNCH_ROT8(false, true, true); else LAUNCH_ROT8(false, true, false); }
-                              else     { if (tail) LAUNCH_ROT8(false, false, true); else LAUNCH_ROT8(false, false, false); } }
-#undef LAUNCH_ROT8
-#undef LAUNCH_ROT8G
+                PQCHK(dispatch_facts4(splitk, odd, tail, ga != nullptr, [&](auto f_c) -> int32_t {
+                    constexpr int F = decltype(f_c)::value;
+                    constexpr bool S = (F & 8) != 0, O = (F & 4) != 0, T = (F & 2) != 0, G = (F & 1) != 0;
+                    HIPCHK(hipFuncSetAttribute((const void*)k_rotate_pblock8<S, O, T, G>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+                    hipLaunchKernelGGL((k_rotate_pblock8<S, O, T, G>), grid, dim3(G ? 512 : 768), lds8, st, d_x, n, x_rs, Pm, d, d_out, o_rs, rows_per_wg, ncb,
+                                       rg_per_xcd, gather, stamps.ptr());
+                    return PQHIP_OK;
+                }));
                 note_kernel(ga ? "k_rotate_pblock8<gather>" : "k_rotate_pblock8");
             }
             HIPCHK(hipGetLastError());
-            if (stamps.ptr()) {   // diagnostics: synchronous summary on stderr (8 words per wave)
-                std::vector<unsigned long long> h;
-                PQCHK(stamps.fetch(st, h));
-                double tiles = 0, kc = 0, ec = 0, cyc = 0, rt = 0, cmax = 0, cmin = 1e30, wgmax = 0, first = 0, last = 0; size_t waves = 0, wgs = 0;
-                for (size_t w0 = 0; w0 < h.size(); w0 += 12 * 8) {
-                    double m = 0;
-                    for (size_t i = w0; i < w0 + 12 * 8; i += 8)
-                        if (h[i]) {
-                            tiles += (double)h[i]; kc += (double)h[i + 1]; ec += (double)h[i + 2]; cyc += (double)h[i + 3]; rt += (double)h[i + 4]; ++waves;
-                            first += (double)h[i + 6]; last += (double)h[i + 7];
-                            cmax = std::max(cmax, (double)h[i + 3]); cmin = std::min(cmin, (double)h[i + 3]); m = std::max(m, (double)h[i + 3]);
-                        }
-                    if (m > 0) { wgmax += m; ++wgs; }
-                }
-                if (tiles > 0)
-                    fprintf(stderr, "[pqhip] rotate v8/v9 stamps: %zu waves, %.1f tiles/wave, tile %.0f cyc (first %.0f, last %.0f), P staging %.0f cyc/wave, wave life %.0f cyc (min %.0f, max %.0f; slowest wave of a workgroup %.0f), clock %.0f MHz\n",
-                            waves, tiles / waves, kc / tiles, first / waves, last / waves, ec / waves, cyc / waves, cmin, cmax, wgmax / wgs, rt > 0 ? cyc / rt * 100.0 : 0.0);
-                if (const char* f = diag().rot_stamp_file) {
-                    if (FILE* fp = fopen(f, "ab")) { fwrite(h.data(), sizeof(unsigned long long), h.size(), fp); fclose(fp); }
-                }
-            }
-            return PQHIP_OK;
+            return stamps.report_rotate(st, diag().rot_stamp_file);
         }
     }
     if (ga) return PQHIP_EUNSUPPORTED;           // only v8 / v9 gather inside the kernel
@@ -127,11 +105,13 @@ int32_t rotate_dev(const float* d_x, int64_t n, int64_t x_rs, const float* Pm, i
     const bool split = d > kKC;
     constexpr int CT = 5;                      // 320 columns per workgroup
     const dim3 grid((unsigned)((n + 63) / 64), (unsigned)((d + 2 * CT * 32 - 1) / (2 * CT * 32)));
-#define LAUNCH_ROT(SP, VE) \
-    hipLaunchKernelGGL((k_rotate_gemm<CT, SP, VE>), grid, dim3(256), 0, st, d_x, n, x_rs, Pm, d, d_out, o_rs)
-    if (split) { if (vec) LAUNCH_ROT(true, true); else LAUNCH_ROT(true, false); }
-    else { if (vec) LAUNCH_ROT(false, true); else LAUNCH_ROT(false, false); }
-#undef LAUNCH_ROT
+    PQCHK((dispatch_int<0, 1>(split, [&](auto split_c) {
+        return dispatch_int<0, 1>(vec, [&](auto vec_c) -> int32_t {
+            hipLaunchKernelGGL((k_rotate_gemm<CT, decltype(split_c)::value != 0, decltype(vec_c)::value != 0>), grid, dim3(256), 0, st, d_x, n,
+                               x_rs, Pm, d, d_out, o_rs);
+            return PQHIP_OK;
+        });
+    })));
     HIPCHK(hipGetLastError());
     note_kernel("k_rotate_gemm");
     return PQHIP_OK;

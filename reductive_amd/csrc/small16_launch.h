@@ -16,6 +16,6 @@ constexpr int small16_pieces_per_lane(int dsub) { return dsub <= 8 ? 2 : dsub / 
 constexpr int small16_tile_rows(int dsub) { return dsub <= 8 ? 64 : dsub <= 20 ? 32 : 16; }
 // dynamic LDS of a workgroup: the transposed codebook image and the centroid norms
 inline size_t small16_lds_bytes(int M, int dsub, int KP) { return ((size_t)M * dsub * KP + (size_t)M * KP) * sizeof(float); }
-// false: no instantiation for (KP, dsub)
-bool launch_small16(int KP, int dsub, const SmallKArgs& a, dim3 grid, size_t lds, hipStream_t st);
+// PQHIP_EUNSUPPORTED: no instantiation for (KP, dsub)
+int32_t launch_small16(int KP, int dsub, const SmallKArgs& a, dim3 grid, size_t lds, hipStream_t st);
 }  // namespace pqhip

@@ -3,16 +3,17 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "kernels_smallk.hip.h"
+#include "launch_dispatch.h"
 
 namespace pqhip {
-// returns false when (KP, dsub) has no instantiation
+// PQHIP_EUNSUPPORTED: no instantiation for dsub (smallk_has)
 template <int KP>
-bool launch_smallk_t(int dsub, const SmallKArgs& a, dim3 grid, hipStream_t st);
-extern template bool launch_smallk_t<16>(int, const SmallKArgs&, dim3, hipStream_t);
-extern template bool launch_smallk_t<32>(int, const SmallKArgs&, dim3, hipStream_t);
-extern template bool launch_smallk_t<64>(int, const SmallKArgs&, dim3, hipStream_t);
+int32_t launch_smallk_t(int dsub, const SmallKArgs& a, dim3 grid, hipStream_t st);
+extern template int32_t launch_smallk_t<16>(int, const SmallKArgs&, dim3, hipStream_t);
+extern template int32_t launch_smallk_t<32>(int, const SmallKArgs&, dim3, hipStream_t);
+extern template int32_t launch_smallk_t<64>(int, const SmallKArgs&, dim3, hipStream_t);
 
-inline bool smallk_has(int dsub)
+constexpr bool smallk_has(int dsub)
 {
     switch (dsub) {
     case 2: case 4: case 6: case 8: case 10: case 12: case 16: case 20: case 24: case 32: return true;
@@ -21,11 +22,8 @@ inline bool smallk_has(int dsub)
 }
 inline int smallk_kp(int64_t K) { return K <= 16 ? 16 : K <= 32 ? 32 : K <= 64 ? 64 : 0; }
 
-inline bool launch_smallk(int KP, int dsub, const SmallKArgs& a, dim3 grid, hipStream_t st)
+inline int32_t launch_smallk(int KP, int dsub, const SmallKArgs& a, dim3 grid, hipStream_t st)
 {
-    if (KP == 16) return launch_smallk_t<16>(dsub, a, grid, st);
-    if (KP == 32) return launch_smallk_t<32>(dsub, a, grid, st);
-    if (KP == 64) return launch_smallk_t<64>(dsub, a, grid, st);
-    return false;
+    return pqh::dispatch_int<16, 32, 64>(KP, [&](auto kp_c) { return launch_smallk_t<decltype(kp_c)::value>(dsub, a, grid, st); });
 }
 }  // namespace pqhip

@@ -18,6 +18,6 @@ inline size_t vor2_lds_per_m(uint32_t max_region_words, int K) { return ((size_t
 inline bool vor2_has_lds(uint32_t max_region_words, int K) { return vor2_lds_per_m(max_region_words, K) <= 150 * 1024; }
 // ... and the launch's workgroups must fit a one-dimensional grid (2^31 - 1), which depends on the row count
 bool vor2_has_grid(int M, int K, int dsub, uint32_t max_region_words, int64_t n, int n_cus);
-// false: no instantiation (vor2_has_lds / vor2_has_grid)
-bool launch_vor2(const Vor2Launch& l, hipStream_t st);
+// PQHIP_EUNSUPPORTED: no launch for the handle or the row count (vor2_has_lds / vor2_has_grid)
+int32_t launch_vor2(const Vor2Launch& l, hipStream_t st);
 }  // namespace pqhip

@@ -1,6 +1,7 @@
 // vor2_launch.hip -- k_encode_vor2 and its launch geometry.
 #include "vor2_launch.h"
 #include "kernels_vor2.hip.h"
+#include "launch_dispatch.h"
 
 #include <algorithm>
 
@@ -63,32 +64,25 @@ bool vor2_has_grid(int M, int K, int dsub, uint32_t max_region_words, int64_t n,
     return geometry(l).n_wg <= 0x7fffffffll;
 }
 
-bool launch_vor2(const Vor2Launch& l, hipStream_t st)
+int32_t launch_vor2(const Vor2Launch& l, hipStream_t st)
 {
     const Geometry g = geometry(l);
-    if (!vor2_has_lds(l.max_region_words, l.K) || g.n_wg > 0x7fffffffll) return false;
+    if (!vor2_has_lds(l.max_region_words, l.K) || g.n_wg > 0x7fffffffll) return PQHIP_EUNSUPPORTED;
     const Vor2Args& a = g.a;
     const size_t lds = g.lds;
     const int nt = g.nt, mg = a.mg;
     const dim3 grid((unsigned)g.n_wg);
-#define PQHIP_VOR2_NT(MGT, NTT)                                                                                          \
-    do {                                                                                                                 \
-        if (lds > 48 * 1024 &&                                                                                           \
-            hipFuncSetAttribute((const void*)k_encode_vor2<MGT, NTT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) \
-            return false;                                                                                                \
-        hipLaunchKernelGGL((k_encode_vor2<MGT, NTT>), grid, dim3(NTT), lds, st, a);                                      \
-    } while (0)
-#define PQHIP_VOR2(MGT)                                                                                                  \
-    do {                                                                                                                 \
-        if (nt == 512) PQHIP_VOR2_NT(MGT, 512);                                                                          \
-        else PQHIP_VOR2_NT(MGT, 256);                                                                                    \
-    } while (0)
-    if (mg <= 2) PQHIP_VOR2(2);
-    else if (mg <= 4) PQHIP_VOR2(4);
-    else PQHIP_VOR2(8);
-#undef PQHIP_VOR2
-#undef PQHIP_VOR2_NT
-    return true;
+    // the kernel of the next group size up: 2, 4 or 8 subquantizers
+    return pqh::dispatch_int<2, 4, 8>(mg <= 2 ? 2 : mg <= 4 ? 4 : 8, [&](auto mg_c) {
+        return pqh::dispatch_int<256, 512>(nt, [&](auto nt_c) -> int32_t {
+            constexpr int MG = decltype(mg_c)::value, NT = decltype(nt_c)::value;
+            if (lds > 48 * 1024 &&
+                hipFuncSetAttribute((const void*)k_encode_vor2<MG, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
+                return PQHIP_EHIP;
+            hipLaunchKernelGGL((k_encode_vor2<MG, NT>), grid, dim3(NT), lds, st, a);
+            return PQHIP_OK;
+        });
+    });
 }
 
 }  // namespace pqhip

@@ -12,8 +12,8 @@ constexpr bool wide_has(int T, int DP)
     if (DP > 256) return DP % 64 == 0 && DP >= 320 && DP <= 1024 && (T == 1 || (T == 2 && DP <= 512));
     return (T == 1 || T == 2 || T == 4) && DP % 16 == 0 && DP >= 144 && DP <= 256;
 }
-// false: no instantiation for (T, DP)
-bool launch_encode_wide(int T, int DP, const EncodeArgs& a, const float* xx, dim3 grid, hipStream_t st);
+// PQHIP_EUNSUPPORTED: no instantiation for (T, DP)
+int32_t launch_encode_wide(int T, int DP, const EncodeArgs& a, const float* xx, dim3 grid, hipStream_t st);
 // xx[n][M] = rule-1 squared norms of the sub-vectors (the wide kernel's pre-pass)
 void launch_row_norms(const float* x, int64_t n, int64_t x_rs, int M, int dsub, float* xx, hipStream_t st);
 }  // namespace pqhip

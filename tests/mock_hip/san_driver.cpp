@@ -339,6 +339,17 @@ static int dispatch_mode()
         for (int it : {1, 3}) PQCHK_RUN(kmeans(ctx, s[0], s[1], s[2], 5000, it, 0));
     PQCHK_RUN(kmeans(ctx, 15, 256, 20, 5000, 3, 1));
     PQCHK_RUN(kmeans(ctx, 2, 16, 4, (1 << 20) + 1, 3, 0));
+    // the rotation in front of the two-kernel OPQ path: one d for every instantiation that rotate_dev() chooses by itself for
+    // plain rows -- k_rotate_pblock8 (d <= 636) and k_rotate_pblock9 (64-column blocks execute >= 10 % more columns, or d > 640)
+    // by rule-2 split, odd burst count and partial last burst; k_rotate_gemm where no P block fits (d = 640) and, with
+    // x_off = 1, for unaligned rows.  (pblock8<false, true, false>, pblock9<2, false, ..> and gemm<5, false, true> have no
+    // such d; the gather forms and the forced variants are tests/test_gpu_parity.py's.)
+    for (int64_t d : {4, 20, 32, 36, 48, 52, 64, 260, 272, 276, 288, 292, 320, 340, 352, 640, 644, 656, 660, 672}) {
+        Call c{d / 4, 16, 4};
+        c.opq = true; c.fused = 0; c.n = 1000;
+        PQCHK_RUN(run(ctx, c));
+        if (d == 4 || d == 260) { c.x_off = 1; PQCHK_RUN(run(ctx, c)); }
+    }
     pqhip_ctx_destroy(ctx);
     CHECK(mock_hip_violations() == 0);
     return 0;
