@@ -682,6 +682,48 @@ int32_t pqhip_lists_merge_dev(pqhip_codebook *cb, int32_t device_slot,
                               int64_t *d_off_out /* or NULL */, void *stream);
 
 /*
+ * Stable compaction of a row array under a row mask: the primitive under removing rows from a resident matrix, the twin
+ * of pqhip_lists_merge_dev.  d_keep is a row mask in the format of the _masked searches and pqhip_pack_row_mask_dev:
+ * ceil(n / 32) words, bit i & 31 of word i >> 5 set = row i is kept; bits of the last word at or beyond n are ignored,
+ * whatever they hold, and no byte outside those words is read.  With K the set of kept rows, c = |K| and
+ * s_0 < s_1 < .. < s_(c-1) its members: d_count[0] = c, always.  If c <= out_capacity_rows, row j of d_out is row s_j of
+ * d_in, byte for byte, for j < c, and d_src_rows[j] = s_j if d_src_rows is given; no byte of d_out at or beyond
+ * c row_bytes and no element of d_src_rows at or beyond c is written.  If c > out_capacity_rows, no byte of d_out or
+ * d_src_rows is written and no flag is raised: the count is the answer, the caller allocates and calls again (the
+ * capacity rule of the range searches: never write past the caller's buffers).  d_in == NULL together with
+ * d_out == NULL moves no rows: the count, the offsets and the source rows only.  Rows are contiguous: the stride of both
+ * arrays is row_bytes.  No base pointer needs any alignment (stores are 16 bytes wide on the 16-byte grid of the
+ * destination address whatever it is; the source is read at the byte addresses it has).  d_out must not overlap d_in.
+ * Bytes of rows that are not kept may be read -- they lie inside the input and are never interpreted; no byte outside
+ * the n row_bytes input bytes is read.  cb supplies the device slot, the scratch and the stream's range flag, as for
+ * pqhip_lists_merge_dev; its quantizer is not read.
+ * List offsets.  With d_off_in given ([n_lists + 1], the list offsets of a list-ordered array), d_off_out[l] is the number
+ * of kept rows i < off_in[l], for l in [0, n_lists]: compaction is stable in position order, so list l of the output is
+ * exactly the kept rows of list l, in order.  The offsets are device memory and are NOT TRUSTED.  The array is
+ * valid iff off[0] == 0, it is non-decreasing and off[n_lists] == n.  If it is invalid, no byte of d_out or d_src_rows is
+ * written, no row is read, the stream's range flag is raised (pqhip_check_codes_dev -> PQHIP_ECODE_RANGE) and d_count
+ * and d_off_out are unspecified.  A mask can hold anything: every mask is valid.
+ * Three kernels in stream order, none of which waits for another workgroup: every workgroup counts the kept rows of a
+ * contiguous slice of source rows (a multiple of 1,024) and of each of its tiles of 1,024; one workgroup turns the
+ * counts into each slice's first output row and the total, checks the offsets, computes d_off_out and decides whether
+ * the mover runs (valid offsets, c <= out_capacity_rows); the mover walks the slices again.  The result is a function of
+ * the input alone: it does not depend on the number of workgroups (chosen from the size and the CU count; option
+ * "rows_compact_wgs" forces it).
+ * Status codes, in the precedence of pqhip_lists_merge_dev: a null cb, n < 0, row_bytes < 1, out_capacity_rows < 0, a null
+ * d_count, n_lists < 0, exactly one of d_in / d_out null, d_off_out given without d_off_in, a null d_keep with n > 0:
+ * PQHIP_EINVAL; then the slot (PQHIP_ENODEV); row_bytes > PQHIP_ROWS_COMPACT_MAX_ROW_BYTES, n_lists >
+ * PQHIP_LISTS_MERGE_MAX_LISTS, n > 2^49 or counts beyond the scratch limit (4 bytes per 1,024 rows): PQHIP_EUNSUPPORTED.
+ * n == 0 writes d_count[0] = 0 and an all-zero d_off_out (the offsets are not read) and launches no kernel.
+ * Asynchronous on `stream`; the counts live in the codebook's scratch.
+ */
+#define PQHIP_ROWS_COMPACT_MAX_ROW_BYTES 4096
+int32_t pqhip_rows_compact_dev(pqhip_codebook *cb, int32_t device_slot,
+                               const uint32_t *d_keep, int64_t n, int64_t row_bytes,
+                               const void *d_in /* or NULL */, void *d_out /* or NULL */, int64_t out_capacity_rows,
+                               const int64_t *d_off_in /* or NULL */, int64_t n_lists, int64_t *d_off_out /* or NULL */,
+                               int64_t *d_src_rows /* or NULL */, int64_t *d_count, void *stream);
+
+/*
  * Building a partitioned index on the device: the layout of the lists, the residuals and the query-free row terms.
  *
  * pqhip_lists_layout_dev: d_assign is [n] list ids, signed integers of idx_bytes (4 or 8) bytes each.  With `ids` the
@@ -889,6 +931,8 @@ int32_t pqhip_set_rotation_variant(int32_t variant);
  *                          most 2^20, and never more than one per 1,024 16-byte chunks of output)
  *   "lists_layout_wgs"     workgroups (row slices) of pqhip_lists_layout_dev (0 = chosen from the size, the number of lists and
  *                          the CU count; at most 65536, never more than one per 1,024 rows; the result does not depend on it)
+ *   "rows_compact_wgs"     workgroups (row slices) of pqhip_rows_compact_dev (0 = chosen from the size and the CU count; at most
+ *                          2^20, never more than one per 1,024 rows; the result does not depend on it)
  *   "rerank_wgs_per_query" workgroups that share one query in the distance stage of pqhip_rerank_f32_dev (0 = chosen from the
  *                          shape; at most 1024)
  *   "cross_product_exact"  0 = X^T.R of the OPQ training step / pqhip_at_dot_b_f32_dev as a plain split-K product:

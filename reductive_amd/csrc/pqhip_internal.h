@@ -15,6 +15,7 @@
 //     pqhip_rerank.hip    exact re-ranking of search candidates against resident vectors
 //     pqhip_lists_merge.hip  merge of two list-ordered row arrays (growing a partitioned matrix)
 //     pqhip_lists_layout.hip  building a partitioned index: layout of the lists, residuals, query-free row terms
+//     pqhip_rows_compact.hip  stable compaction of a row array under a row mask (removing rows from a resident matrix)
 //     pqhip_train.hip     k-means iterations, X^T.R, the OPQ training step, resident matrices
 //     pqhip_host.hip      host-resident entry points: row sharding over devices, pinned double-buffered staging
 // There is deliberately NO CPU compute fallback anywhere: without HIP or a gfx950 device every compute entry
@@ -102,6 +103,7 @@ struct Options {
     std::atomic<int64_t> adc_search_wgs{0};         // exhaustive u8 / masked / generic searches: producer workgroups (0: chosen from the shape)
     std::atomic<int64_t> lists_layout_wgs{0};       // list layout: workgroups, one row slice each (0: chosen from the size)
     std::atomic<int64_t> adc_among_wgs_per_query{0};   // searches among given rows: workgroups per query (0: chosen from the mean number of ids)
+    std::atomic<int64_t> rows_compact_wgs{0};       // row compaction: workgroups, one row slice each (0: chosen from the size)
 };
 
 struct Diag {

@@ -1329,6 +1329,97 @@ class Pq:
             _marshal.check_range(cb, slot, sp)
         return out, off_out
 
+    # ---- removing rows from a resident matrix: stable compaction under a row mask --------------------------------------
+    def compact_rows_device(self, keep_words, rows, list_off=None, want_src_rows=False, capacity=None, out=None, n=None,
+                            stream=None, check=False):
+        """The kept rows of `rows`, in order (pqhip_rows_compact_dev).  keep_words: the mask words of the searches' `allow=`
+        (pack_row_mask_device), CUDA int32 [ceil(n / 32)], bit set = the row is kept; tail bits of the last word are
+        ignored.  rows: a contiguous CUDA tensor [n] or [n, w] of any dtype whose rows have between 1 and 4,096 bytes, or
+        None for the plan-only call (n= is then required): the count, the offsets and the source rows, no row moved.
+        list_off: None or CUDA int64 [n_lists + 1], the list offsets of a list-ordered `rows`.
+        -> (out, list_off_out or None, src_rows or None, count): count the number of kept rows (an int: the stream is
+        synchronised to read it), out [count(, w)] row j = the j-th kept row byte for byte (None for the plan-only call),
+        list_off_out[l] = kept rows below list_off[l] (the offsets of the compacted lists), src_rows int64 [count] the
+        numbers of the kept rows (want_src_rows).
+        capacity=None: one plan-only call, the read of the count, an output allocated to its size, then the moving call.
+        capacity=c (or out= given, whose rows are the capacity): one call into c rows; if more rows are kept nothing is
+        written, out and src_rows come back as None and count tells the size to call again with.  out, if given, must
+        not overlap rows; no tensor needs any alignment.  The offsets are checked on the device: if they do not start
+        at 0, decrease somewhere or do not end at n, nothing is written, count is unspecified and the stream's range
+        flag is raised (check=True: raises PanicError).  The quantizer of self is not used."""
+        import torch
+        tensors = [(keep_words, "keep_words")] + [(t, what) for t, what in ((rows, "rows"), (list_off, "list_off"), (out, "out"))
+                                                  if t is not None]
+        for t, what in tensors:
+            if not hasattr(t, "is_cuda"):
+                raise PanicError("%s must be a torch tensor" % what)
+        if rows is None:
+            if n is None or out is not None:
+                raise PanicError("the plan-only call (rows=None) takes n= and no out=")
+            n, tail, row_bytes = int(n), (), 1
+        else:
+            if rows.dim() not in (1, 2):
+                raise PanicError("rows must be a vector or a matrix")
+            if n is not None and int(n) != rows.shape[0]:
+                raise PanicError("n must be the number of rows")
+            n, tail = rows.shape[0], tuple(rows.shape[1:])
+            row_bytes = rows.element_size() * (rows.shape[1] if rows.dim() == 2 else 1)
+            if not 1 <= row_bytes <= 4096:
+                raise PanicError("a row must have between 1 and 4096 bytes, has %d" % row_bytes)
+        if n < 0:
+            raise PanicError("n must not be negative")
+        if keep_words.dtype != torch.int32 or keep_words.dim() != 1 or keep_words.shape[0] != (n + 31) // 32:
+            raise PanicError("the row mask must hold ceil(n / 32) int32 words for the n rows")
+        if list_off is not None and (list_off.dtype != torch.int64 or list_off.dim() != 1 or list_off.shape[0] < 1):
+            raise PanicError("the list offsets must be an int64 vector of length n_lists + 1")
+        if capacity is not None and int(capacity) < 0:
+            raise PanicError("capacity must not be negative")
+        if out is not None:
+            if out.dtype != rows.dtype or out.dim() != rows.dim() or tuple(out.shape[1:]) != tail:
+                raise PanicError("out must be a %s tensor of shape %s" % (rows.dtype, ["capacity"] + list(tail)))
+            if capacity is not None and out.shape[0] < int(capacity):
+                raise PanicError("out holds fewer rows than the capacity")
+        for t, what in tensors:
+            if not t.is_contiguous():
+                raise PanicError("compact_rows_device takes contiguous tensors")
+        if not all(t.is_cuda for t, _ in tensors):
+            raise PanicError("compact_rows_device takes CUDA tensors")
+        dev = keep_words.device
+        if not all(t.device == dev for t, _ in tensors):
+            raise PanicError("all tensors of a compaction must live on one device")
+        n_lists = 0 if list_off is None else list_off.shape[0] - 1
+        off_out = None if list_off is None else torch.empty(n_lists + 1, dtype=torch.int64, device=dev)
+        count = torch.empty(1, dtype=torch.int64, device=dev)
+        own_stream = stream is None
+        cb, slot, sp = _marshal.launch(self, keep_words, stream)
+
+        def call(cap, dst, src):
+            """one call of the entry point -> the count, read after a synchronisation of the stream"""
+            moving = rows is not None and dst is not None
+            _marshal.run("pqhip_rows_compact_dev", cb, slot, ptr_or_none(keep_words, n), n, row_bytes,
+                         ptr_or_none(rows, n) if moving else None, ptr_or_none(dst, n) if moving else None, cap,
+                         ptr_or_none(list_off), n_lists, ptr_or_none(off_out), ptr_or_none(src, cap), count.data_ptr(), sp)
+            if not own_stream:
+                torch.cuda.ExternalStream(stream, device=dev).synchronize()
+            return int(count)
+
+        wants = rows is not None or want_src_rows
+        if capacity is None and out is None and wants:
+            capacity = min(max(call(0, None, None), 0), n)         # (an invalid offset array leaves any count)
+        cap = 0 if not wants else int(capacity) if capacity is not None else out.shape[0]
+        dst = None
+        if rows is not None:
+            # the entry point wants an address for the output whenever it has one for the input
+            dst = out if out is not None and out.numel() else torch.empty((max(cap, 1),) + tail, dtype=rows.dtype, device=dev)
+        src = torch.empty(cap, dtype=torch.int64, device=dev) if want_src_rows else None
+        total = call(cap, dst, src)
+        if check:
+            _marshal.check_range(cb, slot, sp)
+        fits = total <= cap
+        if rows is not None:
+            dst = (out if out is not None else dst)[:total] if fits else None
+        return dst, off_out, (src[:total] if fits else None) if want_src_rows else None, total
+
     # ---- building a partitioned matrix on the device: list layout, residuals, query-free row terms -----------------------
     def lists_layout_device(self, assign, n_lists, want_lists=False, stream=None, check=False):
         """assign: CUDA int32 or int64 vector [n] of list ids in [0, n_lists), contiguous -> (ids, list_off, positions) or,

@@ -301,6 +301,43 @@ class _Filter:
         return self.row_filter(allow).words
 
 
+def _compact_arrays(pq, words, n, arrays, list_off=None, want_src_rows=False):
+    """The kept rows of each of `arrays` (device tensors of n rows, or None) under the mask words `words`, through
+    Pq.compact_rows_device: one plan-only call for the count (the offsets of the compacted lists, the numbers of the kept
+    rows), then one moving call per array into exactly that many rows -> (outs, list_off_out or None, src_rows or None)"""
+    _, off, src, c = pq.compact_rows_device(words, None, list_off=list_off, want_src_rows=want_src_rows, n=n, check=True)
+    outs = [None if a is None else pq.compact_rows_device(words, a, capacity=c)[0] for a in arrays]
+    return outs, off, src
+
+
+class _Compact:
+    """Removing rows, for all three matrix classes: compact() / remove() return a NEW matrix that holds the kept rows
+    alone -- tensor for tensor what the class's constructor builds from them in their original order -- and the old
+    row number of every new row.  Every per-row array is compacted on the device (Pq.compact_rows_device); nothing of
+    length N goes to the host or through a sort.  Row filters are not carried over: `kept` is what a caller needs to
+    rebuild one.  self and its filters stay as they are.  A packed matrix moves its packed rows as they are."""
+
+    def _keep_words(self, allow):
+        words = self._allow_words(allow)
+        if words is None:
+            raise PanicError("compact() takes a row filter of this matrix or the flags of all rows")
+        return words
+
+    def _compact_vectors(self, words, kept):
+        """the attached vectors (original row order) under the original-order mask, in their dtype"""
+        v = self.vectors
+        if v is None:
+            return None
+        if v.shape[1] * v.element_size() > 4096:
+            return v[kept].contiguous()
+        return self.pq.compact_rows_device(words, v, capacity=kept.shape[0])[0]
+
+    def remove(self, rows):
+        """compact() of the filter that excludes the ORIGINAL row numbers `rows` (numpy or torch; a number outside
+        [0, N) raises PanicError, as row_filter(rows=.., allowed=False) does) -> (new_matrix, kept)."""
+        return self.compact(self.row_filter(rows=rows, allowed=False))
+
+
 class _Packed4:
     """4-bit packed codes for all three matrix classes (quantizers of at most 16 centroids): pack4() gives a matrix of
     the same class whose `codes` hold two codes per byte, [N, ceil(M / 2)] (include/pqhip.h, "4-bit packed codes"), at
@@ -444,7 +481,7 @@ class _Among:
         return self._among(True, queries, rows, k, use_norms, refine, check)
 
 
-class QuantizedMatrix(_Refine, _Filter, _Packed4, _Search, _Among):
+class QuantizedMatrix(_Refine, _Filter, _Packed4, _Search, _Among, _Compact):
     """Codes (+ norms) resident in HBM next to the device codebook: the lookup, scan and similarity-search consumer."""
 
     def __init__(self, pq, codes, norms=None, device="cuda:0"):
@@ -551,6 +588,18 @@ class QuantizedMatrix(_Refine, _Filter, _Packed4, _Search, _Among):
         if self.vectors is not None:
             new.vectors = torch.cat([self.vectors, x.to(self.vectors.dtype)])
         return new
+
+    def compact(self, allow):
+        """The matrix of the rows that `allow` keeps (a RowFilter of this matrix, or a bool array [N]) -> (new_matrix,
+        kept): a NEW QuantizedMatrix with codes[kept] and norms[kept], and kept, int64 [N'] on the device, the old row
+        number of new row i, ascending.  Attached vectors are compacted in their dtype.  For any search S,
+        new.S(q, ..) is self.S(q, .., allow=allow) with the indices mapped through kept."""
+        words = self._keep_words(allow)
+        new = _clone(self, ("pq", "packed4"))
+        (new.codes, new.norms), _, kept = _compact_arrays(self.pq, words, len(self), (self.codes, self.norms), want_src_rows=True)
+        if self.vectors is not None:
+            new.vectors = self._compact_vectors(words, kept)
+        return new, kept
 
     def partition(self, n_lists, n_iterations=10, vectors=None, train_rows=None, rng=None, on_device=False):
         """Partition the rows with a coarse k-means quantizer of n_lists centroids -> PartitionedMatrix (IVFADC without
@@ -700,7 +749,7 @@ def _ivf_layout_device(assign, n_lists):
     return torch.sort(assign, stable=True).indices, list_off
 
 
-class _Lists(_Refine, _Filter, _Packed4, _Search, _Among):
+class _Lists(_Refine, _Filter, _Packed4, _Search, _Among, _Compact):
     """What both partitioned forms share: the list layout, the coarse quantizer and the probe selection."""
 
     device_terms = False        # ResidualPartitionedMatrix: the row terms come from Pq.residual_terms_device
@@ -832,6 +881,40 @@ class _Lists(_Refine, _Filter, _Packed4, _Search, _Among):
         if self.vectors is not None and other.vectors is not None:
             new.vectors = torch.cat([self.vectors, other.vectors.to(self.vectors.device, self.vectors.dtype)])
         return new
+
+    def compact(self, allow):
+        """The matrix of the rows that `allow` keeps (a RowFilter of this matrix, or a bool array [N] in ORIGINAL row
+        order) -> (new_matrix, kept): a NEW matrix of this class over the same lists, and kept, int64 [N'] on the
+        device, the old row number of new row i, ascending; the kept rows are renumbered 0 .. N' - 1 in that order.
+        Compaction is stable in position order, so list l of the result is the kept rows of list l, in order -- what
+        the constructor builds from the kept rows and their assignments: every stored array is compacted under the
+        position-order mask (Pq.compact_rows_device, which also gives list_off), ids[p'] = rank[ids[p]] with rank the
+        running count of the original-order flags, positions are rebuilt by a scatter.  Attached vectors are compacted
+        under the original-order mask.  Centroids, coarse codebook, packed4 and device_terms are shared or carried."""
+        import torch
+        words = self._keep_words(allow)
+        N, dev = len(self), self.codes.device
+        if isinstance(allow, RowFilter):             # the filter keeps the words only: bit p = position p is kept
+            shifts = torch.arange(32, dtype=torch.int32, device=dev)
+            kept_pos = ((words[:, None] >> shifts) & 1).reshape(-1)[:N].to(torch.uint8)
+            flags = torch.empty(N, dtype=torch.uint8, device=dev)
+            flags[self.ids] = kept_pos
+        else:                                        # the flags themselves (row_filter has checked them)
+            flags = _on_device(allow, dev).view(torch.uint8)
+        rank = torch.cumsum(flags, 0, dtype=torch.int64) - 1
+        names = ("ids",) + self._ROW_ARRAYS
+        outs, list_off, _ = _compact_arrays(self.pq, words, N, [getattr(self, name) for name in names], list_off=self.list_off)
+        new = self._shell()
+        for name, t in zip(names, outs):
+            setattr(new, name, t)
+        new.ids = rank[new.ids]
+        new.list_off = list_off
+        new.positions = _positions(new.ids)
+        words_orig = self.pq.pack_row_mask_device(flags)
+        kept = self.pq.compact_rows_device(words_orig, None, want_src_rows=True, n=N)[2]
+        if self.vectors is not None:
+            new.vectors = self._compact_vectors(words_orig, kept)
+        return new, kept
 
     def _add_encoded(self, x, norms, assign, **row_arrays):
         """add() of both classes: extend() applied to the batch laid out as a piece"""

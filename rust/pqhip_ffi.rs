@@ -174,6 +174,14 @@ extern "C" {
     pub fn pqhip_lists_merge_dev(cb: *mut pqhip_codebook, device_slot: i32, d_off_a: *const i64, n_a: i64,
         d_off_b: *const i64, n_b: i64, n_lists: i64, row_bytes: i64, d_a: *const c_void, d_b: *const c_void,
         d_out: *mut c_void, d_off_out: *mut i64, stream: *mut c_void) -> i32;
+    // stable compaction of a row array under a row mask (d_keep: the words of the masked searches): row j of d_out = the
+    // j-th kept row of d_in, d_src_rows[j] its number, d_count[0] the number of kept rows; more than out_capacity_rows:
+    // nothing written but the count; d_in / d_out both NULL: count, offsets and source rows only; d_off_in NULL or
+    // [n_lists + 1], validated on the device (invalid: nothing written, the stream's range flag raised), d_off_out[l] = kept
+    // rows below off_in[l]; option "rows_compact_wgs" forces the grid, on which the result does not depend
+    pub fn pqhip_rows_compact_dev(cb: *mut pqhip_codebook, device_slot: i32, d_keep: *const u32, n: i64, row_bytes: i64,
+        d_in: *const c_void, d_out: *mut c_void, out_capacity_rows: i64, d_off_in: *const i64, n_lists: i64,
+        d_off_out: *mut i64, d_src_rows: *mut i64, d_count: *mut i64, stream: *mut c_void) -> i32;
     // building a partitioned index on the device.  Layout: d_assign [n] signed list ids of idx_bytes (4 / 8) bytes ->
     // d_list_off [n_lists + 1], d_ids [n] (the stable argsort), d_positions [n], d_lists NULL or [n]; the ids are validated
     // on the device (one out of range: ids / positions / lists untouched, the stream's range flag raised); n_lists <= 16384;
