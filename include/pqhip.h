@@ -724,6 +724,52 @@ int32_t pqhip_rows_compact_dev(pqhip_codebook *cb, int32_t device_slot,
                                int64_t *d_src_rows /* or NULL */, int64_t *d_count, void *stream);
 
 /*
+ * Exact merge of the top-k results of several searches: the primitive under searching several resident matrices as one
+ * (a main index plus a delta, more rows than one call takes, row shards on several devices gathered on one).
+ * d_val is f32 [n_parts][n_queries][k_in] and d_idx int64 of the same shape, each with a part stride and a row stride in
+ * elements and a column stride of one.  Row q of part p is what a search of part p returned for query q: first its real
+ * entries in that search's order, then padding with index -1.  d_offsets is int64 [n_parts] in device memory or NULL; it
+ * is added to every index >= 0 of its part.  largest is 0 for distances and 1 for scores.  d_out_val and d_out_idx are
+ * [n_queries][k] with row strides; d_out_part is int32 [n_queries][k] with a row stride, or NULL, and receives the part
+ * each result came from.
+ * Definition.  An entry with index < 0 is absent, whatever its value holds.  The present entries of query q are ordered by
+ * (key(v), part, rank within the part's row), ascending; with largest the key is key(-v).  key() is the order of every
+ * search of the library: -0 == +0, every NaN equal to every other and after every number.  The output row is the first
+ * min(k, count) of them; after them come index -1, value +Inf (largest: -Inf) and part -1.  Values come back as the
+ * searches return them: bit for bit, a NaN as the canonical quiet NaN and a zero as +0.  No element of an output row at or
+ * beyond k is written.
+ * The merge is stable and never compares ids.
+ *   - If the parts are consecutive row ranges of one matrix, given in order, and each row is a result of an exhaustive
+ *     search (plain, masked, packed or re-ranked), the output is bit for bit that search on the whole matrix for every
+ *     k <= k_in.
+ *   - For any parts the values are those of the union.  Ties go to the earlier part.
+ *   - A row whose present entries are not in that order gives an unspecified order, but nothing is read or written out
+ *     of bounds.
+ * k > n_parts k_in is allowed: the row is padded.  Only the first min(k_in, 64 L) entries of a part's row are read, with L
+ * the smallest power of two with 64 L >= k: later entries cannot reach the output.
+ * One kernel, one workgroup per query and one wave per part (at most eight waves; further parts go round): a wave reads a
+ * part's row with consecutive lanes on consecutive entries, the waves' sorted lists of 32-bit (key, part << 10 | rank)
+ * pairs are merged in a tree through at most 32 KB of LDS, and the id of each of the k winners is fetched once.  Queries
+ * are taken grid-stride: the result does not depend on the number of workgroups (min(n_queries, 2^20); option
+ * "topk_merge_wgs" forces it).  cb supplies the device slot and the stream's device, as for pqhip_rerank_f32_dev; its
+ * quantizer is not read.  The call needs no scratch.
+ * Status codes, in the precedence of pqhip_adc_search_f32_dev: a null cb, n_queries < 0, n_parts < 1, k < 1, k_in < 1, a
+ * `largest` other than 0 or 1: PQHIP_EINVAL; then the slot (PQHIP_ENODEV); k or k_in > PQHIP_TOPK_MERGE_MAX_K, n_parts >
+ * PQHIP_TOPK_MERGE_MAX_PARTS: PQHIP_EUNSUPPORTED; n_queries == 0 launches nothing; then a null d_val, d_idx, d_out_val or
+ * d_out_idx: PQHIP_EINVAL; an input row stride < k_in or an output row stride < k: PQHIP_ESHAPE.  Part strides are not
+ * constrained.  Asynchronous on `stream`.
+ */
+#define PQHIP_TOPK_MERGE_MAX_K 1024
+#define PQHIP_TOPK_MERGE_MAX_PARTS 65536
+int32_t pqhip_topk_merge_f32_dev(pqhip_codebook *cb, int32_t device_slot,
+                                 const float *d_val, int64_t val_part_stride, int64_t val_row_stride,
+                                 const int64_t *d_idx, int64_t idx_part_stride, int64_t idx_row_stride,
+                                 int64_t n_parts, int64_t n_queries, int32_t k_in,
+                                 const int64_t *d_offsets /* or NULL */, int32_t largest, int32_t k,
+                                 float *d_out_val, int64_t out_val_row_stride, int64_t *d_out_idx, int64_t out_idx_row_stride,
+                                 int32_t *d_out_part /* or NULL */, int64_t out_part_row_stride, void *stream);
+
+/*
  * Building a partitioned index on the device: the layout of the lists, the residuals and the query-free row terms.
  *
  * pqhip_lists_layout_dev: d_assign is [n] list ids, signed integers of idx_bytes (4 or 8) bytes each.  With `ids` the
@@ -933,6 +979,8 @@ int32_t pqhip_set_rotation_variant(int32_t variant);
  *                          the CU count; at most 65536, never more than one per 1,024 rows; the result does not depend on it)
  *   "rows_compact_wgs"     workgroups (row slices) of pqhip_rows_compact_dev (0 = chosen from the size and the CU count; at most
  *                          2^20, never more than one per 1,024 rows; the result does not depend on it)
+ *   "topk_merge_wgs"       workgroups of pqhip_topk_merge_f32_dev (0 = one per query up to 2^20; at most 2^20, never more than
+ *                          one per query; the result does not depend on it)
  *   "rerank_wgs_per_query" workgroups that share one query in the distance stage of pqhip_rerank_f32_dev (0 = chosen from the
  *                          shape; at most 1024)
  *   "cross_product_exact"  0 = X^T.R of the OPQ training step / pqhip_at_dot_b_f32_dev as a plain split-K product:

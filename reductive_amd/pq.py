@@ -1420,6 +1420,58 @@ class Pq:
             dst = (out if out is not None else dst)[:total] if fits else None
         return dst, off_out, (src[:total] if fits else None) if want_src_rows else None, total
 
+    # ---- searching several matrices as one: exact merge of the parts' top-k results ------------------------------------
+    def merge_topk_device(self, vals, ids, k, largest=False, offsets=None, want_parts=False, stream=None):
+        """The k best of each query over the results of P searches (pqhip_topk_merge_f32_dev).  vals CUDA float32 and ids
+        CUDA int64, both [P, nq, k_in]: row q of part p is what a search of part p returned for query q, real entries
+        first in that search's order, then padding with index -1.  They may be views with any part and row stride (a
+        column stride other than one is removed by a copy).  offsets: None or CUDA int64 [P], added to every id >= 0 of
+        its part.  largest=False merges distances, True scores.  -> (val, idx), CUDA float32 and int64 [nq, k], and with
+        want_parts a third tensor, int32 [nq, k]: the part of each result.  The entries of a query are ordered by (value
+        in the library's order: -0 == +0, NaN last; part; rank within the part's row): the merge is stable by part and
+        never compares ids, so parts that are consecutive row ranges of one matrix, in order, give that matrix's
+        exhaustive search bit for bit.  Past the last entry: index -1, +Inf (largest: -Inf), part -1.  1 <= k, k_in <=
+        1024, P <= 65536; k > P k_in is allowed.  The quantizer of self is not used."""
+        import torch
+        for t, what in ((vals, "vals"), (ids, "ids")) + (() if offsets is None else ((offsets, "offsets"),)):
+            if not hasattr(t, "is_cuda"):
+                raise PanicError("%s must be a torch tensor" % what)
+        if vals.dtype != torch.float32 or vals.dim() != 3:
+            raise PanicError("vals must be float32 [P, nq, k_in]")
+        if ids.dtype != torch.int64 or tuple(ids.shape) != tuple(vals.shape):
+            raise PanicError("ids must be int64 of the shape of vals")
+        P, nq, k_in = vals.shape
+        if not 1 <= P <= 65536:
+            raise PanicError("between 1 and 65536 parts expected, got %d" % P)
+        if not 1 <= k_in <= 1024:
+            raise PanicError("between 1 and 1024 entries per part and query expected, got %d" % k_in)
+        k = int(k)
+        if not 1 <= k <= 1024:
+            raise PanicError("k must be between 1 and 1024, was %d" % k)
+        if offsets is not None and (offsets.dtype != torch.int64 or tuple(offsets.shape) != (P,)):
+            raise PanicError("offsets must be int64 [P], one per part")
+        if not (vals.is_cuda and ids.is_cuda and (offsets is None or offsets.is_cuda)):
+            raise PanicError("merge_topk_device takes CUDA tensors")
+        dev = vals.device
+        if ids.device != dev or (offsets is not None and offsets.device != dev):
+            raise PanicError("all tensors of a merge must live on one device")
+        if vals.stride(2) != 1:
+            vals = vals.contiguous()
+        if ids.stride(2) != 1:
+            ids = ids.contiguous()
+        if offsets is not None:
+            offsets = offsets.contiguous()
+        val = torch.empty((nq, k), dtype=torch.float32, device=dev)
+        idx = torch.empty((nq, k), dtype=torch.int64, device=dev)
+        part = torch.empty((nq, k), dtype=torch.int32, device=dev) if want_parts else None
+        cb, slot, sp = _marshal.launch(self, vals, stream)
+        v_rs = vals.stride(1) if nq > 1 else max(vals.stride(1), k_in)
+        i_rs = ids.stride(1) if nq > 1 else max(ids.stride(1), k_in)
+        _marshal.run("pqhip_topk_merge_f32_dev", cb, slot, ptr_or_none(vals, nq), vals.stride(0), v_rs,
+                     ptr_or_none(ids, nq), ids.stride(0), i_rs, P, nq, k_in, ptr_or_none(offsets), 1 if largest else 0, k,
+                     ptr_or_none(val, nq), k, ptr_or_none(idx, nq), k, ptr_or_none(part, nq), k, sp)
+        return (val, idx, part) if want_parts else (val, idx)
+
     # ---- building a partitioned matrix on the device: list layout, residuals, query-free row terms -----------------------
     def lists_layout_device(self, assign, n_lists, want_lists=False, stream=None, check=False):
         """assign: CUDA int32 or int64 vector [n] of list ids in [0, n_lists), contiguous -> (ids, list_off, positions) or,

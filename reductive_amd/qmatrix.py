@@ -1114,6 +1114,232 @@ class ResidualPartitionedMatrix(_Lists):
         return e if self.norms is None else e * self.norms[pos][:, None]
 
 
+class GroupFilter:
+    """The set of rows a search of a MatrixGroup may return: one RowFilter per part (None for a part without rows), built
+    from flags or row numbers in GLOBAL row numbering (MatrixGroup.row_filter); `n_allowed` counts the allowed rows."""
+
+    def __init__(self, group, filters, n_allowed):
+        self.group = group
+        self.filters = filters
+        self.n_allowed = n_allowed
+
+
+class MatrixGroup:
+    """Several resident matrices searched as one.  `parts` is a sequence of QuantizedMatrix, PartitionedMatrix or
+    ResidualPartitionedMatrix -- of mixed classes, packed or not, on one device or several.  Global row = bases[p] + the
+    part's own row number, bases the running sum of len(part) (int64 [P] on the group's device: `device`, by default the
+    first part's).  Results come back on that device.
+
+    A top-k search sends the queries to every part's device, runs the part's own method, gathers the parts' rows into
+    one stacked buffer on the group's device and merges them there in one call of Pq.merge_topk_device with
+    offsets=bases: the order is (value, part, rank in the part's result), so ties go to the earlier part and ids are
+    never compared.  For parts that are consecutive row ranges of one QuantizedMatrix, in order, every search of the
+    group is that matrix's search bit for bit.  For partitioned parts (which break ties by position, not by row) it
+    is the merge of the parts' own results under that order.  With refine=R the R best rows of the GROUP by the
+    estimate are the shortlist -- as one matrix would form it -- and each part re-ranks its members of the shortlist
+    against its own attached vectors; the parts' exact results are merged again.
+
+    A range search joins the parts' CSR results per query in part order, ids plus base (Pq.merge_lists_device over
+    lims): ascending global row for exhaustive parts in row order, part-major and then each part's stated order for
+    list parts; sort=True applies sort_ranges afterwards.
+
+    add, compact, remove, the *_among searches, persistence and any folding of a small part into a large one stay with
+    the parts: MatrixGroup(new_parts) over a replaced part is the way to a changed group."""
+
+    def __init__(self, parts, device=None):
+        import torch
+        self.parts = list(parts)
+        if not self.parts:
+            raise PanicError("a group needs at least one part")
+        for part in self.parts:
+            if not isinstance(part, (QuantizedMatrix, _Lists)):
+                raise PanicError("a part must be a QuantizedMatrix, PartitionedMatrix or ResidualPartitionedMatrix")
+        if len({part.pq.reconstructed_len() for part in self.parts}) != 1:
+            raise PanicError("the parts of a group must hold vectors of one length")
+        self.device = self.parts[0].codes.device if device is None else torch.device(device)
+        self._bounds = [0]
+        for part in self.parts:
+            self._bounds.append(self._bounds[-1] + len(part))
+        self.bases = torch.tensor(self._bounds[:-1], dtype=torch.int64, device=self.device)
+        self._pq = self.parts[0].pq              # its quantizer is not used: the handle the group's own calls run on
+
+    def __len__(self):
+        return self._bounds[-1]
+
+    def locate(self, rows):
+        """global row numbers (numpy or torch) -> (part, local_row), int64 tensors on the group's device"""
+        import torch
+        rows = _on_device(rows, self.device, torch.int64, np.int64)
+        if rows.numel() and (int(rows.min()) < 0 or int(rows.max()) >= len(self)):
+            raise PanicError("row numbers must lie in [0, %d)" % len(self))
+        part = torch.bucketize(rows, self.bases, right=True) - 1
+        return part, rows - self.bases[part]
+
+    # ---- filters --------------------------------------------------------------------------------------------------------
+    def row_filter(self, allow=None, rows=None, allowed=True):
+        """allow: bool [len(self)] in global row numbering, True = the row may be returned; or rows=: global row numbers
+        with allowed=True (only these) or allowed=False (all but these) -> GroupFilter for `allow=` of the group's
+        searches: one row_filter per part, from the flags or rows split at `bases`."""
+        import torch
+        if (allow is None) == (rows is None):
+            raise PanicError("give either the flags of all rows or a list of row numbers")
+        filters, n_allowed = [], 0
+        if rows is not None:
+            part, local = self.locate(_on_device(rows, self.device, torch.int64, np.int64).reshape(-1))
+        else:
+            allow = _on_device(allow, self.device)
+            if allow.dtype != torch.bool or tuple(allow.shape) != (len(self),):
+                raise PanicError("allow must be a bool array with one flag per row (%d)" % len(self))
+        for p, m in enumerate(self.parts):
+            if len(m) == 0:
+                filters.append(None)
+                continue
+            if rows is not None:
+                f = m.row_filter(rows=local[part == p], allowed=allowed)
+            else:
+                f = m.row_filter(allow[self._bounds[p]:self._bounds[p + 1]])
+            filters.append(f)
+            n_allowed += f.n_allowed
+        return GroupFilter(self, filters, n_allowed)
+
+    def _part_filters(self, allow):
+        if allow is None:
+            return [None] * len(self.parts)
+        if isinstance(allow, GroupFilter):
+            if allow.group is not self:
+                raise PanicError("the row filter was built for another group")
+            return allow.filters
+        return self.row_filter(allow).filters
+
+    # ---- searches -------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _more(part, nprobe):
+        """the arguments a part's search takes besides the group's: nprobe for the classes that have lists"""
+        if not isinstance(part, _Lists):
+            return {}
+        if nprobe is None:
+            raise PanicError("a group with a partitioned part needs nprobe")
+        return {"nprobe": nprobe}
+
+    def _queries(self, queries):
+        import torch
+        q = _on_device(queries, self.device, torch.float32, np.float32)
+        if q.dim() not in (1, 2):
+            raise PanicError("queries must be [d] or [nq, d]")
+        return q.dim() == 1, (q[None] if q.dim() == 1 else q)
+
+    def _gather(self, width, per_part):
+        """per_part(p, part) -> (val, rows) [nq, width] on the part's device, or None for nothing; stacks them on the
+        group's device ([P, nq, width], absent = index -1)"""
+        import torch
+        vals = ids = None
+        for p, part in enumerate(self.parts):
+            got = per_part(p, part) if len(part) else None
+            if vals is None and got is not None:
+                nq = got[0].shape[0]
+                vals = torch.empty((len(self.parts), nq, width), dtype=torch.float32, device=self.device)
+                ids = torch.full((len(self.parts), nq, width), -1, dtype=torch.int64, device=self.device)
+            if got is not None:
+                vals[p].copy_(got[0])            # torch orders the streams of a copy between devices
+                ids[p].copy_(got[1])
+        return vals, ids
+
+    def _topk(self, ip, queries, k, nprobe, use_norms, refine, allow):
+        import torch
+        single, q = self._queries(queries)
+        k = int(k)
+        filters = self._part_filters(allow)
+        R = k
+        if refine is not None:
+            R = max([part._check_refine(k, refine) for part in self.parts if len(part)], default=int(refine))
+        kw = {"use_norms": use_norms} if ip else {}
+        qs = [q.to(part.codes.device) for part in self.parts]
+
+        def estimate(p, part):
+            fn = part.most_similar if ip else part.nearest
+            return fn(qs[p], R, allow=filters[p], **self._more(part, nprobe), **kw)
+
+        vals, ids = self._gather(R, estimate)
+        if vals is None:                         # no part holds a row
+            val = torch.full((q.shape[0], k), float("-inf") if ip else float("inf"), dtype=torch.float32, device=self.device)
+            idx = torch.full((q.shape[0], k), -1, dtype=torch.int64, device=self.device)
+            return (val[0], idx[0]) if single else (val, idx)
+        if refine is None:
+            val, idx = self._pq.merge_topk_device(vals, ids, k, largest=ip, offsets=self.bases)
+        else:
+            # the group's shortlist, as one matrix forms it; each part re-ranks its members against its own vectors
+            _, short, src = self._pq.merge_topk_device(vals, ids, R, largest=ip, offsets=self.bases, want_parts=True)
+
+            def exact(p, part):
+                cand = torch.where(src == p, short - self._bounds[p], torch.full_like(short, -1))
+                return part._refined(qs[p], cand.to(part.codes.device), k, ip)
+
+            vals, ids = self._gather(k, exact)
+            val, idx = self._pq.merge_topk_device(vals, ids, k, largest=ip, offsets=self.bases)
+        return (val[0], idx[0]) if single else (val, idx)
+
+    def nearest(self, queries, k, nprobe=None, refine=None, allow=None):
+        """the k rows of smallest asymmetric squared distance over all parts -> (dist, idx) [k] or [nq, k], idx global row
+        numbers, -1 past the last row (distance +Inf).  nprobe goes to the partitioned parts (required if there is one);
+        refine=R needs vectors attached to every part; allow: None, a GroupFilter of this group or a bool array
+        [len(self)] in global row numbering."""
+        return self._topk(False, queries, k, nprobe, True, refine, allow)
+
+    def most_similar(self, queries, k, nprobe=None, use_norms=True, refine=None, allow=None):
+        """the k rows of largest inner product over all parts, largest first -> (score, idx), as nearest()."""
+        return self._topk(True, queries, k, nprobe, use_norms, refine, allow)
+
+    def _range(self, ip, queries, threshold, nprobe, use_norms, allow, sort):
+        import torch
+        _, q = self._queries(queries)
+        filters = self._part_filters(allow)
+        kw = {"use_norms": use_norms} if ip else {}
+        lims = val = idx = None
+        for p, part in enumerate(self.parts):
+            if len(part) == 0:
+                continue
+            dev = part.codes.device
+            thr = threshold.to(dev) if hasattr(threshold, "is_cuda") else threshold
+            fn = part.similar_above if ip else part.within
+            l, v, r = fn(q.to(dev), thr, allow=filters[p], sort=False, **self._more(part, nprobe), **kw)
+            l, v, r = l.to(self.device), v.to(self.device), (r.to(self.device) + self._bounds[p])
+            if lims is None:
+                lims, val, idx = l, v, r
+            else:                                # the queries as lists: rows of query q so far, then this part's
+                val, _ = self._pq.merge_lists_device(lims, val.contiguous(), l, v.contiguous())
+                idx, lims = self._pq.merge_lists_device(lims, idx.contiguous(), l, r.contiguous())
+        if lims is None:
+            return (torch.zeros(q.shape[0] + 1, dtype=torch.int64, device=self.device),
+                    torch.empty(0, dtype=torch.float32, device=self.device), torch.empty(0, dtype=torch.int64, device=self.device))
+        if sort:
+            val, idx = sort_ranges(lims, val, idx, ip)
+        return lims, val, idx
+
+    def within(self, queries, radius, nprobe=None, allow=None, sort=False):
+        """every row of every part within `radius` (a scalar or one value per query) -> (lims, dist, idx), CSR over the
+        queries: the rows of a query part by part, inside a part in the part's own order (ascending row for a
+        QuantizedMatrix), idx global row numbers.  sort=True: ascending in distance, ties in that order."""
+        return self._range(False, queries, radius, nprobe, True, allow, sort)
+
+    def similar_above(self, queries, threshold, nprobe=None, use_norms=True, allow=None, sort=False):
+        """every row of every part whose inner product with the query is >= threshold -> (lims, score, idx), as within();
+        sort=True: descending in score."""
+        return self._range(True, queries, threshold, nprobe, use_norms, allow, sort)
+
+    # ---- lookups --------------------------------------------------------------------------------------------------------
+    def embeddings(self, rows):
+        """the embeddings of the global row numbers `rows`, in request order -> float32 [len(rows), d] on the group's
+        device: the rows are bucketed by part, looked up by each part and scattered back."""
+        import torch
+        part, local = self.locate(_on_device(rows, self.device, torch.int64, np.int64).reshape(-1))
+        out = torch.empty((part.shape[0], self.parts[0].pq.reconstructed_len()), dtype=torch.float32, device=self.device)
+        for p, m in enumerate(self.parts):
+            sel = torch.nonzero(part == p).reshape(-1)
+            if sel.numel():
+                out[sel] = m.embeddings(local[sel].to(m.codes.device)).to(self.device)
+        return out
+
+
 def dumps(pq, codes, norms=None):
     b = io.BytesIO()
     write_chunk(b, pq, codes, norms)

@@ -182,6 +182,16 @@ extern "C" {
     pub fn pqhip_rows_compact_dev(cb: *mut pqhip_codebook, device_slot: i32, d_keep: *const u32, n: i64, row_bytes: i64,
         d_in: *const c_void, d_out: *mut c_void, out_capacity_rows: i64, d_off_in: *const i64, n_lists: i64,
         d_off_out: *mut i64, d_src_rows: *mut i64, d_count: *mut i64, stream: *mut c_void) -> i32;
+    // exact merge of the top-k results of several searches: d_val f32 / d_idx i64 [n_parts][n_queries][k_in] (part and row
+    // strides in elements; index < 0 = absent) -> [n_queries][k] ordered by (key(v), part, rank), key(-v) with largest = 1;
+    // d_offsets NULL or [n_parts], added to the ids of its part; d_out_part NULL or i32 [n_queries][k]; stable by part,
+    // never compares ids; k, k_in <= 1024, n_parts <= 65536; no scratch; option "topk_merge_wgs" forces the grid, on which
+    // the result does not depend
+    pub fn pqhip_topk_merge_f32_dev(cb: *mut pqhip_codebook, device_slot: i32, d_val: *const f32, val_part_stride: i64,
+        val_row_stride: i64, d_idx: *const i64, idx_part_stride: i64, idx_row_stride: i64, n_parts: i64, n_queries: i64,
+        k_in: i32, d_offsets: *const i64, largest: i32, k: i32, d_out_val: *mut f32, out_val_row_stride: i64,
+        d_out_idx: *mut i64, out_idx_row_stride: i64, d_out_part: *mut i32, out_part_row_stride: i64,
+        stream: *mut c_void) -> i32;
     // building a partitioned index on the device.  Layout: d_assign [n] signed list ids of idx_bytes (4 / 8) bytes ->
     // d_list_off [n_lists + 1], d_ids [n] (the stable argsort), d_positions [n], d_lists NULL or [n]; the ids are validated
     // on the device (one out of range: ids / positions / lists untouched, the stream's range flag raised); n_lists <= 16384;
