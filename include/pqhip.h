@@ -649,6 +649,46 @@ int32_t pqhip_rerank_f32_dev(pqhip_codebook *cb, int32_t device_slot,
                              float *d_val, int64_t val_row_stride, int64_t *d_idx, int64_t idx_row_stride, void *stream);
 
 /*
+ * Exact search over resident vectors: the exhaustive top-k of every query by its true squared distance or inner product
+ * to ALL rows of d_vectors [n_rows][vec_row_stride], vec_bytes = 4 (f32) or 2 (IEEE f16, converted exactly); d_queries
+ * [n_queries][q_row_stride] f32; d is the width of both.  It is the ground truth of the quantized searches, the search of
+ * rows that are not encoded and the values that `refine` returns.  cb supplies the device slot and the scratch, as for
+ * pqhip_rerank_f32_dev; its quantizer is not read and d need not equal its width.
+ * Value of a row x for query q: the value pqhip_rerank_f32_dev defines, operation for operation -- the 64 lane chains from
+ * +0 over j = l, l + 64, .. with fl(p + fl(t * t)), t = fl(q_j - x_j) (metric 0) or fl(p + fl(q_j * x_j)) (metric 1),
+ * then the tree p_l <- fl(p_l + p_(l+s)), s = 32 .. 1; no contraction.
+ * A = all rows in [0, n_rows), or with d_allow != NULL those whose bit is set: d_allow is ceil(n_rows / 32) words in the
+ * format of the _masked searches (bit r & 31 of word r >> 5; bits beyond n_rows are ignored).  Row q of d_val
+ * [n_queries][val_row_stride] and d_idx [n_queries][idx_row_stride] receives the first min(k, |A|) rows of A ordered by
+ * (key(value), row) ascending -- inner product: (key(-score), row), the largest score first -- key as for
+ * pqhip_adc_search_f32_dev (-0 == +0, every NaN equal and last, ties to the smaller row).  A returned value is the row's
+ * value bit for bit, a zero as +0 and a NaN as the canonical quiet NaN; the padding is index -1 with +Inf (inner product:
+ * -Inf).  Consequence: for n_rows <= 1024 the call equals pqhip_rerank_f32_dev with the candidate list 0 .. n_rows - 1
+ * (or the allowed rows), bit for bit.
+ * The order is strict: the result does not depend on the number of workgroups, on the rows each takes or on how many
+ * queries share a pass.  A row whose bit is clear enters nothing and none of its bytes is loaded (a NaN in it changes
+ * nothing).  No byte outside [d_vectors, last row + d elements) is read, whatever the strides; rows may start at any
+ * multiple of the element size.
+ * Status codes, in the precedence of pqhip_rerank_f32_dev (EINVAL, ENODEV, EUNSUPPORTED, ESHAPE):
+ *   null cb, k < 1, d < 1, n_queries < 0, n_rows < 0, metric not 0 / 1: PQHIP_EINVAL;
+ *   vec_bytes not 2 / 4, k > 1024, d > 16384 (one query image is 64 KB of LDS): PQHIP_EUNSUPPORTED;
+ *   with n_queries > 0, a null d_queries, d_val or d_idx, or a null d_vectors with n_rows > 0: PQHIP_EINVAL;
+ *   q_row_stride < d, vec_row_stride < d (n_rows > 0), val_row_stride < k or idx_row_stride < k: PQHIP_ESHAPE.
+ * n_queries == 0 launches nothing; n_rows == 0 or an all-zero mask writes the padding only.
+ * Asynchronous on `stream`.  One 1,024-thread producer workgroup per CU over a contiguous range of rows (a multiple of
+ * 1,024, so mask words never straddle workgroups; option "flat_search_wgs" forces the number of workgroups) streams the
+ * rows once for all queries of a pass -- 4 queries while k <= 128 and d <= 9216, else one; further queries take further
+ * passes -- and keeps an exact top-k per wave; the workgroups' partial lists go to the codebook's scratch and one merge
+ * kernel per pass writes the outputs, as in pqhip_adc_search_f32_dev.
+ */
+int32_t pqhip_flat_search_f32_dev(pqhip_codebook *cb, int32_t device_slot,
+                                  const float *d_queries, int64_t n_queries, int64_t q_row_stride,
+                                  const void *d_vectors, int32_t vec_bytes, int64_t n_rows, int64_t d, int64_t vec_row_stride,
+                                  const uint32_t *d_allow /* ceil(n_rows / 32) words or NULL */,
+                                  int32_t metric /* 0 = squared L2, 1 = inner product */, int32_t k,
+                                  float *d_val, int64_t val_row_stride, int64_t *d_idx, int64_t idx_row_stride, void *stream);
+
+/*
  * Merge of two list-ordered row arrays: the primitive under growing a partitioned matrix (rows added to an index, two
  * indexes over the same lists joined).  d_a is [n_a] rows of row_bytes bytes in list order under d_off_a [n_lists + 1]
  * (list l = rows off_a[l] .. off_a[l + 1] - 1), d_b likewise [n_b] rows under d_off_b; d_out is [n_a + n_b] rows.  For
@@ -983,7 +1023,9 @@ int32_t pqhip_set_rotation_variant(int32_t variant);
  *                          one per query; the result does not depend on it)
  *   "rerank_wgs_per_query" workgroups that share one query in the distance stage of pqhip_rerank_f32_dev (0 = chosen from the
  *                          shape; at most 1024)
- *   "cross_product_exact"  0 = X^T.R of the OPQ training step / pqhip_at_dot_b_f32_dev as a plain split-K product:
+ *   "flat_search_wgs"      producer workgroups of pqhip_flat_search_f32_dev (0 = one per CU; at most 65536; rows per workgroup
+ *                          stay a multiple of 1,024; the result does not depend on it)
+ *   "cross_product_exact" 0 = X^T.R of the OPQ training step / pqhip_at_dot_b_f32_dev as a plain split-K product:
  *                          within 1e-5 relative of the exact rule-2 result, no per-block partial matrices (default 1)
  *   "cross_product_group_bytes"  workspace of partial matrices per launch group (0 = 4 GiB)
  *   "lookup_two_pass"      row lookups (pqhip_reconstruct_rows*): 0 = one kernel, 1 = select the code rows into a compact

@@ -117,6 +117,19 @@ def mask_arg(allow, codes, required):
     return (mask_words(allow, codes).data_ptr(),)
 
 
+def vector_mask_words(allow, n):
+    """The words tensor of flat_search_device's `allow=`: None, or int32 [ceil(n / 32)] for the n rows of the vectors.
+    Shape and dtype only: the wrapper checks devices after everything a host tensor can get wrong."""
+    if allow is None:
+        return None
+    import torch
+    if not hasattr(allow, "is_cuda") or allow.dtype != torch.int32 or allow.dim() != 1 or not allow.is_contiguous():
+        raise PanicError("allow must be the int32 mask words of pack_row_mask_device")
+    if allow.shape[0] != (n + 31) // 32:
+        raise PanicError("the row mask must hold ceil(n / 32) words for the n rows")
+    return allow
+
+
 def assert_lists(list_off, probes):
     import torch
     assert list_off.is_cuda and list_off.dtype == torch.int64 and list_off.dim() == 1 and list_off.is_contiguous()

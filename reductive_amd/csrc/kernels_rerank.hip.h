@@ -1,7 +1,8 @@
 // kernels_rerank.hip.h -- exact re-ranking of search candidates against resident vectors (pqhip_rerank_f32_dev): the
 // stage after an ADC search that replaces the quantizer's estimate by the distance (or inner product) to the stored
 // vector itself.  Per query: a gather of n_cand rows of d elements, a fixed-order f32 reduction per row, an exact top-k.
-// (Included from exactly one translation unit, pqhip_rerank.hip.)
+// (The kernels are instantiated in one translation unit, pqhip_rerank.hip; kernels_flat_search.hip.h takes rerank_elem
+// and rerank_step, the row value's element and chain step, so that both calls share one definition of the value.)
 //
 // Value of a row (include/pqhip.h has the definition): lane l of a wave owns the chain over j = l, l + 64, l + 128, ..
 // -- one coalesced 256-byte load per 64 f32 elements (128 bytes for f16) -- and the 64 partials are reduced by the fixed

@@ -105,6 +105,7 @@ struct Options {
     std::atomic<int64_t> adc_among_wgs_per_query{0};   // searches among given rows: workgroups per query (0: chosen from the mean number of ids)
     std::atomic<int64_t> rows_compact_wgs{0};       // row compaction: workgroups, one row slice each (0: chosen from the size)
     std::atomic<int64_t> topk_merge_wgs{0};         // merge of search results: workgroups, queries taken grid-stride (0: one per query)
+    std::atomic<int64_t> flat_search_wgs{0};        // exact search over resident vectors: producer workgroups (0: chosen from the shape)
 };
 
 struct Diag {

@@ -1282,6 +1282,56 @@ class Pq:
             _marshal.check_range(cb, slot, sp)
         return (val[0], idx[0]) if single else (val, idx)
 
+    # ---- exact search over resident vectors: the exhaustive top-k by true distance ------------------------------------
+    def flat_search_device(self, queries, vectors, k, ip=False, allow=None, stream=None, check=False):
+        """The k best of ALL rows of `vectors` per query by their exact value: queries CUDA float32 [d] or [nq, d];
+        vectors CUDA float32 or float16 [N, d] (f16 elements are converted exactly); allow None or the mask words of
+        pack_row_mask_device, CUDA int32 [ceil(N / 32)] -- then the allowed rows only are ranked, as if the others were
+        not in the matrix -> (value, idx), CUDA float32 and int64 [nq, k] ([k] for one query).  Value, order and padding
+        are those of rerank_device over the candidate list 0 .. N - 1 (pqhip_flat_search_f32_dev).  Row strides are
+        respected (unit column stride is made by a copy if needed).  The quantizer of self is not used: d is the width
+        of the vectors.  There is no range flag to raise; check=True only synchronises."""
+        import torch
+        for t, what in ((queries, "queries"), (vectors, "vectors")):
+            if not hasattr(t, "is_cuda"):
+                raise PanicError("%s must be a torch tensor" % what)
+        if queries.dtype != torch.float32 or queries.dim() not in (1, 2):
+            raise PanicError("queries must be float32 [d] or [nq, d]")
+        if vectors.dtype not in (torch.float32, torch.float16) or vectors.dim() != 2:
+            raise PanicError("vectors must be float32 or float16 [N, d]")
+        single = queries.dim() == 1
+        q2 = queries[None] if single else queries
+        nq, d = q2.shape
+        N = vectors.shape[0]
+        if d < 1 or vectors.shape[1] != d:
+            raise PanicError("Query and vector length mismatch")
+        if d > 16384:
+            raise PanicError("vectors of at most 16384 elements are searched, got %d" % d)
+        k = int(k)
+        if not 1 <= k <= 1024:
+            raise PanicError("k must be between 1 and 1024, was %d" % k)
+        allow = _marshal.vector_mask_words(allow, N)
+        tensors = (queries, vectors) if allow is None else (queries, vectors, allow)
+        if not all(t.is_cuda for t in tensors):
+            raise PanicError("queries, vectors and allow must be CUDA tensors")
+        if any(t.device != vectors.device for t in tensors):
+            raise PanicError("queries, vectors and allow must live on one device")
+        if q2.stride(1) != 1:
+            q2 = q2.contiguous()
+        if N > 0 and vectors.stride(1) != 1:
+            vectors = vectors.contiguous()
+        if allow is not None:
+            allow = _marshal.stand_in(allow, allow.shape[0], vectors.device)   # a mask stays a mask (N = 0 reads no word)
+        val = torch.empty((nq, k), dtype=torch.float32, device=vectors.device)
+        idx = torch.empty((nq, k), dtype=torch.int64, device=vectors.device)
+        cb, slot, sp = _marshal.launch(self, vectors, stream)
+        _marshal.run("pqhip_flat_search_f32_dev", cb, slot, q2.data_ptr(), nq, row_stride(q2, nq, d),
+                     ptr_or_none(vectors, N), vectors.element_size(), N, d, row_stride(vectors, N, d),
+                     None if allow is None else allow.data_ptr(), 1 if ip else 0, k, val.data_ptr(), k, idx.data_ptr(), k, sp)
+        if check:
+            _marshal.check_range(cb, slot, sp)
+        return (val[0], idx[0]) if single else (val, idx)
+
     # ---- growing a partitioned matrix: merge of two list-ordered arrays ------------------------------------------------
     def merge_lists_device(self, list_off_a, a, list_off_b, b, out=None, stream=None, check=False):
         """a, b: CUDA tensors of one dtype, [n_a] / [n_b] or [n_a, c] / [n_b, c], contiguous, their rows in list order

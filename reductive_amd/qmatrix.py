@@ -249,6 +249,42 @@ class _Refine:
         """rows: the original row numbers of the candidates ([R] or [nq, R], -1 = padding), on the device"""
         return self.pq.rerank_device(queries, self.vectors, rows, k, ip=ip)
 
+    def _exact_words(self, allow):
+        """`allow=` of an exact search -> the mask words in ORIGINAL row order (the order of `vectors`) or None"""
+        import torch
+        if allow is None:
+            return None
+        if isinstance(allow, RowFilter):
+            if allow.matrix is not self:
+                raise PanicError("the row filter was built for another matrix")
+            if getattr(self, "ids", None) is not None:
+                raise PanicError("the row filter of a partitioned matrix is in position order: give the flags of all rows")
+            return allow.words
+        allow = _on_device(allow, self.vectors.device)
+        if allow.dtype != torch.bool or tuple(allow.shape) != (len(self),):
+            raise PanicError("allow must be a bool array with one flag per row (%d)" % len(self))
+        return self.pq.pack_row_mask_device(allow.view(torch.uint8))
+
+    def _exact(self, ip, queries, k, allow):
+        import torch
+        if self.vectors is None:
+            raise PanicError("refine needs the original vectors: call attach_vectors first")
+        q = _on_device(queries, self.vectors.device, torch.float32, np.float32)
+        return self.pq.flat_search_device(q, self.vectors, k, ip=ip, allow=self._exact_words(allow))
+
+    def exact_nearest(self, queries, k, allow=None):
+        """The true k nearest rows: the exhaustive top-k of ALL attached vectors by their exact squared distance
+        (Pq.flat_search_device), in original row numbers, ties to the smaller row -> (dist, idx) [k] or [nq, k].  The
+        codes are not read: this is the ground truth the quantized searches are measured against, and dist are the
+        values refine= returns.  allow: None, bool flags [N] in original row order, or (QuantizedMatrix) a RowFilter of
+        this matrix; a partitioned matrix's RowFilter is in position order and is refused."""
+        return self._exact(False, queries, k, allow)
+
+    def exact_most_similar(self, queries, k, allow=None):
+        """The true k rows of largest inner product with the attached vectors as they are, largest first -> (score, idx),
+        as exact_nearest()."""
+        return self._exact(True, queries, k, allow)
+
 
 class RowFilter:
     """The set of rows a search may return, packed for one matrix: `words` is the device mask of the searches' `allow=`
@@ -1114,6 +1150,80 @@ class ResidualPartitionedMatrix(_Lists):
         return e if self.norms is None else e * self.norms[pos][:, None]
 
 
+class FlatMatrix(_Refine, _Filter, _Compact):
+    """Rows kept as they are, f32 or f16, and searched exactly: no quantizer, no codes.  Every search is the exhaustive
+    top-k by the true squared distance or inner product (Pq.flat_search_device), so rows are searchable the moment
+    they are added -- the delta of a MatrixGroup before it is encoded -- and a small collection needs no training.  Its
+    values are those `refine=` returns on the other classes.  `vectors` is the [N, d] device tensor; `pq` is a
+    one-centroid placeholder of width d that only lends its device slot and scratch to the calls."""
+
+    def __init__(self, vectors, device="cuda:0", dtype=None, ctx=None):
+        import torch
+        if len(vectors.shape) != 2 or vectors.shape[1] < 1:
+            raise PanicError("vectors must be [N, d]")
+        if dtype is None:
+            dtype = torch.float16 if str(vectors.dtype) in ("float16", "torch.float16") else torch.float32
+        if dtype not in (torch.float32, torch.float16):
+            raise PanicError("vectors are kept as float32 or float16")
+        self.vectors = _on_device(vectors, device, dtype)
+        self.pq = Pq(None, np.zeros((1, 1, vectors.shape[1]), np.float32), ctx=ctx)
+
+    @property
+    def codes(self):
+        """what the shared row-filter and compaction code asks for its device: the stored rows take the codes' place"""
+        return self.vectors
+
+    def __len__(self):
+        return self.vectors.shape[0]
+
+    def attach_vectors(self, vectors, dtype=None):
+        raise PanicError("a FlatMatrix holds its vectors already")
+
+    def _topk(self, ip, queries, k, refine, allow):
+        import torch
+        if refine is not None:
+            self._check_refine(k, refine)       # the estimate is exact already: refine changes nothing
+        q = _on_device(queries, self.vectors.device, torch.float32, np.float32)
+        return self.pq.flat_search_device(q, self.vectors, k, ip=ip, allow=self._allow_words(allow))
+
+    def nearest(self, queries, k, refine=None, allow=None):
+        """the k rows of smallest exact squared distance, ties to the smaller row -> (dist, idx) [k] or [nq, k]; index -1
+        and +Inf past the last (allowed) row.  refine is accepted and changes nothing; allow: None, a RowFilter of this
+        matrix or a bool array [N]."""
+        return self._topk(False, queries, k, refine, allow)
+
+    def most_similar(self, queries, k, use_norms=True, refine=None, allow=None):
+        """the k rows of largest exact inner product, largest first -> (score, idx); use_norms is accepted and ignored
+        (the rows are stored unscaled), refine and allow as for nearest()."""
+        return self._topk(True, queries, k, refine, allow)
+
+    def embeddings(self, rows):
+        """the stored rows `rows` as float32 [len(rows), d]"""
+        import torch
+        rows = _on_device(rows, self.vectors.device, torch.int64, np.int64).reshape(-1)
+        if rows.numel() and (int(rows.min()) < 0 or int(rows.max()) >= len(self)):
+            raise PanicError("row numbers must lie in [0, %d)" % len(self))
+        return self.vectors[rows].to(torch.float32)
+
+    def add(self, vectors):
+        """The matrix with the rows of `vectors` ([B, d]) appended, rounded to the stored dtype -> a NEW FlatMatrix; self
+        and its row filters stay as they are."""
+        import torch
+        x = _device_rows(vectors, self.vectors.shape[1], self.vectors.device)
+        new = _clone(self, ("pq",))
+        new.vectors = torch.cat([self.vectors, x.to(self.vectors.dtype)])
+        return new
+
+    def compact(self, allow):
+        """The matrix of the rows that `allow` keeps (a RowFilter of this matrix, or a bool array [N]) -> (new_matrix,
+        kept), kept the old row number of new row i, ascending (Pq.compact_rows_device)."""
+        words = self._keep_words(allow)
+        _, _, kept = _compact_arrays(self.pq, words, len(self), (), want_src_rows=True)
+        new = _clone(self, ("pq",))
+        new.vectors = self._compact_vectors(words, kept)
+        return new, kept
+
+
 class GroupFilter:
     """The set of rows a search of a MatrixGroup may return: one RowFilter per part (None for a part without rows), built
     from flags or row numbers in GLOBAL row numbering (MatrixGroup.row_filter); `n_allowed` counts the allowed rows."""
@@ -1143,6 +1253,10 @@ class MatrixGroup:
     lims): ascending global row for exhaustive parts in row order, part-major and then each part's stated order for
     list parts; sort=True applies sort_ranges afterwards.
 
+    A FlatMatrix part (rows that are not encoded: a fresh delta) contributes its exact values to a top-k search and to
+    the shortlist of refine=R, and re-ranks its members against its own rows, which gives the same numbers; a range
+    search of a group with a flat part raises PanicError.
+
     add, compact, remove, the *_among searches, persistence and any folding of a small part into a large one stay with
     the parts: MatrixGroup(new_parts) over a replaced part is the way to a changed group."""
 
@@ -1152,8 +1266,8 @@ class MatrixGroup:
         if not self.parts:
             raise PanicError("a group needs at least one part")
         for part in self.parts:
-            if not isinstance(part, (QuantizedMatrix, _Lists)):
-                raise PanicError("a part must be a QuantizedMatrix, PartitionedMatrix or ResidualPartitionedMatrix")
+            if not isinstance(part, (QuantizedMatrix, _Lists, FlatMatrix)):
+                raise PanicError("a part must be a QuantizedMatrix, PartitionedMatrix, ResidualPartitionedMatrix or FlatMatrix")
         if len({part.pq.reconstructed_len() for part in self.parts}) != 1:
             raise PanicError("the parts of a group must hold vectors of one length")
         self.device = self.parts[0].codes.device if device is None else torch.device(device)
@@ -1291,6 +1405,8 @@ class MatrixGroup:
 
     def _range(self, ip, queries, threshold, nprobe, use_norms, allow, sort):
         import torch
+        if any(isinstance(part, FlatMatrix) for part in self.parts):
+            raise PanicError("a range search over the raw vectors of a FlatMatrix part is not served")
         _, q = self._queries(queries)
         filters = self._part_filters(allow)
         kw = {"use_norms": use_norms} if ip else {}

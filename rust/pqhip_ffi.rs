@@ -168,6 +168,13 @@ extern "C" {
         q_row_stride: i64, d_vectors: *const c_void, vec_bytes: i32, n_rows: i64, d: i64, vec_row_stride: i64,
         d_cand: *const i64, n_cand: i32, cand_row_stride: i64, metric: i32, k: i32, d_val: *mut f32,
         val_row_stride: i64, d_idx: *mut i64, idx_row_stride: i64, stream: *mut c_void) -> i32;
+    // exact search over resident f32 / f16 vectors: the top-k of ALL rows (or those allowed by d_allow, the words of the
+    // masked searches, NULL = no mask) by the value of pqhip_rerank_f32_dev; option "flat_search_wgs" forces the grid,
+    // on which the result does not depend
+    pub fn pqhip_flat_search_f32_dev(cb: *mut pqhip_codebook, device_slot: i32, d_queries: *const f32, n_queries: i64,
+        q_row_stride: i64, d_vectors: *const c_void, vec_bytes: i32, n_rows: i64, d: i64, vec_row_stride: i64,
+        d_allow: *const u32, metric: i32, k: i32, d_val: *mut f32, val_row_stride: i64, d_idx: *mut i64,
+        idx_row_stride: i64, stream: *mut c_void) -> i32;
     // merge of two list-ordered row arrays: list l of d_out = list l of d_a, then list l of d_b (rows of row_bytes bytes,
     // any alignment); the offsets are validated on the device (invalid: nothing written, the stream's range flag raised);
     // d_off_out NULL or [n_lists + 1]; option "lists_merge_wgs" forces the grid
