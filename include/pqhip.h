@@ -689,6 +689,51 @@ int32_t pqhip_flat_search_f32_dev(pqhip_codebook *cb, int32_t device_slot,
                                   float *d_val, int64_t val_row_stride, int64_t *d_idx, int64_t idx_row_stride, void *stream);
 
 /*
+ * Exact search in probed lists (IVF-Flat): the search above restricted, per query, to the rows of the lists the query
+ * probes.  d_vectors [n_rows][vec_row_stride], f32 or f16 as above, holds the rows in LIST ORDER: with d_list_off
+ * [n_lists + 1] int64, list l is the rows [list_off[l], list_off[l + 1]).  d_probes [n_queries][probes_row_stride] int64:
+ * the first n_probe entries of row q are list ids; -1 is padding and is skipped; any other value outside [0, n_lists) is
+ * skipped and raises the stream's range flag; a range is clamped to [0, n_rows] and an inverted range is empty, and both
+ * raise the flag too (pqhip_check_codes_dev -> PQHIP_ECODE_RANGE) -- exactly as for pqhip_adc_search_lists_f32_dev, whose
+ * plan kernel reads them here as well.  A list named twice in one row is a caller error: its rows may be returned twice.
+ * S_q = the rows of the lists named by probe row q, and with d_allow != NULL those of them whose bit is set: d_allow is
+ * ceil(n_rows / 32) words in POSITION order (bit p & 31 of word p >> 5 for the row at position p of d_vectors).
+ * Value of a row: the value pqhip_rerank_f32_dev defines, operation for operation -- the 64 lane chains, then the fixed
+ * tree, no contraction -- as for pqhip_flat_search_f32_dev.  Row q of the outputs receives the first min(k, |S_q|) rows of
+ * S_q ordered by (key(value), position) ascending -- inner product: (key(-score), position) -- with the library's key
+ * (-0 == +0, every NaN equal and last); returned indices are positions in d_vectors; the padding is index -1 with +Inf
+ * (inner product: -Inf); a returned zero is +0 and a NaN the canonical quiet NaN.
+ * Consequences: the result of query q equals pqhip_flat_search_f32_dev on the same matrix with the mask of S_q, query by
+ * query, bit for bit.  With every list probed once, in any order, the result equals the unmasked exhaustive call.
+ * The order is strict: the result depends neither on the number of workgroups that share a query (chosen on the host
+ * from the expected probed bytes, n_queries and the CU count; option "flat_lists_wgs_per_query" forces it) nor on the
+ * order of the probes.  No byte outside [d_vectors, last row + d elements) is read, whatever the offsets, probes and
+ * strides hold.  No byte of a disallowed or unprobed row is loaded (a NaN in it changes nothing).
+ * Status codes, in the precedence EINVAL, ENODEV, EUNSUPPORTED, ESHAPE -- the union of the checks of
+ * pqhip_flat_search_f32_dev and pqhip_adc_search_lists_f32_dev:
+ *   null cb, k < 1, d < 1, n_queries < 0, n_rows < 0, metric not 0 / 1, n_lists < 0, n_probe < 1: PQHIP_EINVAL;
+ *   vec_bytes not 2 / 4, k > 1024, d > 16384, n_rows > 2^32 - 2 (positions are compared as 32-bit values) or
+ *   n_probe >= 2^24: PQHIP_EUNSUPPORTED;
+ *   with n_queries > 0, a null d_queries, d_val, d_idx, d_list_off or d_probes, or a null d_vectors with n_rows > 0:
+ *   PQHIP_EINVAL;
+ *   q_row_stride < d, vec_row_stride < d (n_rows > 0), val_row_stride < k, idx_row_stride < k or probes_row_stride <
+ *   n_probe: PQHIP_ESHAPE.
+ * n_queries == 0 launches nothing; n_rows == 0 or n_lists == 0 writes the padding only.  Asynchronous on `stream`.  One
+ * query per 1,024-thread workgroup, grid (workgroups per query, queries): a wave reduces tiles of 16 consecutive places of
+ * the query's concatenated probed rows, whatever lists they fall in; the per-query segment plan and the partial lists
+ * live in the codebook's scratch (queries are processed in chunks that keep them within 512 MB) and one merge kernel per
+ * chunk writes the outputs.
+ */
+int32_t pqhip_flat_search_lists_f32_dev(pqhip_codebook *cb, int32_t device_slot,
+                                        const float *d_queries, int64_t n_queries, int64_t q_row_stride,
+                                        const void *d_vectors, int32_t vec_bytes, int64_t n_rows, int64_t d, int64_t vec_row_stride,
+                                        const int64_t *d_list_off, int64_t n_lists,
+                                        const int64_t *d_probes, int32_t n_probe, int64_t probes_row_stride,
+                                        const uint32_t *d_allow /* ceil(n_rows / 32) words in POSITION order, or NULL */,
+                                        int32_t metric /* 0 = squared L2, 1 = inner product */, int32_t k,
+                                        float *d_val, int64_t val_row_stride, int64_t *d_idx, int64_t idx_row_stride, void *stream);
+
+/*
  * Merge of two list-ordered row arrays: the primitive under growing a partitioned matrix (rows added to an index, two
  * indexes over the same lists joined).  d_a is [n_a] rows of row_bytes bytes in list order under d_off_a [n_lists + 1]
  * (list l = rows off_a[l] .. off_a[l + 1] - 1), d_b likewise [n_b] rows under d_off_b; d_out is [n_a + n_b] rows.  For
@@ -1025,6 +1070,8 @@ int32_t pqhip_set_rotation_variant(int32_t variant);
  *                          shape; at most 1024)
  *   "flat_search_wgs"      producer workgroups of pqhip_flat_search_f32_dev (0 = one per CU; at most 65536; rows per workgroup
  *                          stay a multiple of 1,024; the result does not depend on it)
+ *   "flat_lists_wgs_per_query"  workgroups that share one query of pqhip_flat_search_lists_f32_dev (0 = chosen from the
+ *                          expected probed bytes; at most 4096; the result does not depend on it)
  *   "cross_product_exact" 0 = X^T.R of the OPQ training step / pqhip_at_dot_b_f32_dev as a plain split-K product:
  *                          within 1e-5 relative of the exact rule-2 result, no per-block partial matrices (default 1)
  *   "cross_product_group_bytes"  workspace of partial matrices per launch group (0 = 4 GiB)

@@ -130,6 +130,28 @@ def vector_mask_words(allow, n):
     return allow
 
 
+def vector_lists_arg(list_off, probes, nq):
+    """The lists of flat_search_lists_device: list_off int64 [n_lists + 1] contiguous, probes int64 [nq, n_probe]
+    ([n_probe] for one query) with at least one column -> (pr with unit column stride, n_lists, n_probe, row stride).
+    Shape and dtype only, as vector_mask_words: the wrapper checks devices afterwards."""
+    import torch
+    for t, what in ((list_off, "list_off"), (probes, "probes")):
+        if not hasattr(t, "is_cuda"):
+            raise PanicError("%s must be a torch tensor" % what)
+    if list_off.dtype != torch.int64 or list_off.dim() != 1 or list_off.shape[0] < 1 or not list_off.is_contiguous():
+        raise PanicError("list_off must be the int64 offsets of the lists, [n_lists + 1]")
+    if probes.dtype != torch.int64 or probes.dim() not in (1, 2):
+        raise PanicError("probes must be int64 list ids, [n_probe] or [nq, n_probe]")
+    pr = probes[None] if probes.dim() == 1 else probes
+    if pr.shape[0] != nq or pr.shape[1] < 1:
+        raise PanicError("one probe row of at least one list id per query expected")
+    if pr.shape[1] >= 1 << 24:
+        raise PanicError("fewer than 2^24 probes per query are served")
+    pr = unit_columns(pr)
+    n_probe = pr.shape[1]
+    return pr, list_off.shape[0] - 1, n_probe, row_stride(pr, nq, n_probe)
+
+
 def assert_lists(list_off, probes):
     import torch
     assert list_off.is_cuda and list_off.dtype == torch.int64 and list_off.dim() == 1 and list_off.is_contiguous()

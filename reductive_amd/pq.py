@@ -1332,6 +1332,62 @@ class Pq:
             _marshal.check_range(cb, slot, sp)
         return (val[0], idx[0]) if single else (val, idx)
 
+    # ---- exact search in probed lists: the flat search restricted, per query, to the lists it probes --------------------
+    def flat_search_lists_device(self, queries, vectors, list_off, probes, k, ip=False, allow=None, stream=None, check=False):
+        """flat_search_device restricted, per query, to the rows of the probed lists (IVF-Flat): vectors CUDA float32 or
+        float16 [N, d] in LIST ORDER, list l being rows [list_off[l], list_off[l + 1]); list_off CUDA int64 [n_lists + 1];
+        probes CUDA int64 [nq, n_probe] ([n_probe] for one query) of list ids, -1 = padding; allow None or the mask words of
+        pack_row_mask_device in position order, CUDA int32 [ceil(N / 32)] -> (value, idx), CUDA float32 and int64 [nq, k]
+        ([k] for one query), idx being positions in vectors; past the last probed (allowed) row: index -1 and +Inf (ip:
+        -Inf).  Query by query the result is flat_search_device with the mask of those rows, bit for bit; with every list
+        probed it is the unmasked call (pqhip_flat_search_lists_f32_dev).  Row strides are respected (unit column
+        stride is made by a copy if needed).  The quantizer of self is not used.  check=True synchronises and reports a
+        list id or an offset out of range (they are skipped resp. clamped either way)."""
+        import torch
+        for t, what in ((queries, "queries"), (vectors, "vectors")):
+            if not hasattr(t, "is_cuda"):
+                raise PanicError("%s must be a torch tensor" % what)
+        if queries.dtype != torch.float32 or queries.dim() not in (1, 2):
+            raise PanicError("queries must be float32 [d] or [nq, d]")
+        if vectors.dtype not in (torch.float32, torch.float16) or vectors.dim() != 2:
+            raise PanicError("vectors must be float32 or float16 [N, d]")
+        single = queries.dim() == 1
+        q2 = queries[None] if single else queries
+        nq, d = q2.shape
+        N = vectors.shape[0]
+        if d < 1 or vectors.shape[1] != d:
+            raise PanicError("Query and vector length mismatch")
+        if d > 16384:
+            raise PanicError("vectors of at most 16384 elements are searched, got %d" % d)
+        k = int(k)
+        if not 1 <= k <= 1024:
+            raise PanicError("k must be between 1 and 1024, was %d" % k)
+        if N > (1 << 32) - 2:
+            raise PanicError("at most 2^32 - 2 rows are searched in lists")
+        pr, n_lists, n_probe, p_rs = _marshal.vector_lists_arg(list_off, probes, nq)
+        allow = _marshal.vector_mask_words(allow, N)
+        tensors = (queries, vectors, list_off, probes) + (() if allow is None else (allow,))
+        if not all(t.is_cuda for t in tensors):
+            raise PanicError("queries, vectors, list_off, probes and allow must be CUDA tensors")
+        if any(t.device != vectors.device for t in tensors):
+            raise PanicError("queries, vectors, list_off, probes and allow must live on one device")
+        if q2.stride(1) != 1:
+            q2 = q2.contiguous()
+        if N > 0 and vectors.stride(1) != 1:
+            vectors = vectors.contiguous()
+        if allow is not None:
+            allow = _marshal.stand_in(allow, allow.shape[0], vectors.device)   # a mask stays a mask (N = 0 reads no word)
+        val = torch.empty((nq, k), dtype=torch.float32, device=vectors.device)
+        idx = torch.empty((nq, k), dtype=torch.int64, device=vectors.device)
+        cb, slot, sp = _marshal.launch(self, vectors, stream)
+        _marshal.run("pqhip_flat_search_lists_f32_dev", cb, slot, q2.data_ptr(), nq, row_stride(q2, nq, d),
+                     ptr_or_none(vectors, N), vectors.element_size(), N, d, row_stride(vectors, N, d),
+                     list_off.data_ptr(), n_lists, pr.data_ptr(), n_probe, p_rs,
+                     None if allow is None else allow.data_ptr(), 1 if ip else 0, k, val.data_ptr(), k, idx.data_ptr(), k, sp)
+        if check:
+            _marshal.check_range(cb, slot, sp)
+        return (val[0], idx[0]) if single else (val, idx)
+
     # ---- growing a partitioned matrix: merge of two list-ordered arrays ------------------------------------------------
     def merge_lists_device(self, list_off_a, a, list_off_b, b, out=None, stream=None, check=False):
         """a, b: CUDA tensors of one dtype, [n_a] / [n_b] or [n_a, c] / [n_b, c], contiguous, their rows in list order

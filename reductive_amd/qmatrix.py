@@ -785,10 +785,10 @@ def _ivf_layout_device(assign, n_lists):
     return torch.sort(assign, stable=True).indices, list_off
 
 
-class _Lists(_Refine, _Filter, _Packed4, _Search, _Among, _Compact):
-    """What both partitioned forms share: the list layout, the coarse quantizer and the probe selection."""
-
-    device_terms = False        # ResidualPartitionedMatrix: the row terms come from Pq.residual_terms_device
+class _ListLayout:
+    """What every partitioned class shares, over codes or over the vectors themselves: the list layout, the coarse
+    quantizer, the probe selection and the assignment of new rows.  `codes` is what the class stores per row, in list
+    order (it lends its device and its length)."""
 
     def _init_lists(self, centroids, assign, n_rows, dev, ctx, want_lists=False):
         """The layout of the lists from `assign`: a numpy array of list ids (ivf_layout on the host) or an int64 CUDA
@@ -860,7 +860,6 @@ class _Lists(_Refine, _Filter, _Packed4, _Search, _Among, _Compact):
         pos = self.positions[rows.clamp(0, n - 1)] if n else torch.zeros_like(rows)
         return torch.where(inside, pos, torch.where(rows == -1, rows, torch.full_like(rows, n))).contiguous()
 
-    # ---- growth: every method returns a NEW matrix and leaves self (and the row filters built for it) untouched ----
     def assign(self, vectors):
         """the list of each vector ([B, d] float32, numpy or CUDA) -> int64 [B] on the device: the nearest centroid, as
         cluster_assignments(self.centroids, vectors) gives it row for row (the encode kernels of the one-subquantizer
@@ -868,6 +867,26 @@ class _Lists(_Refine, _Filter, _Packed4, _Search, _Among, _Compact):
         x = _device_rows(vectors, self.centroids.shape[1], self.codes.device)
         return _assign_device(self.coarse, x.shape[0], lambda r0, r1: x[r0:r1], x.device)
 
+    def _kept_flags(self, allow, words):
+        """what compact() keeps, as uint8 flags [N] in ORIGINAL row order: from the flags themselves, or from a
+        RowFilter's words (bit p = position p is kept) through ids"""
+        import torch
+        N, dev = len(self), self.codes.device
+        if isinstance(allow, RowFilter):             # the filter keeps the words only: bit p = position p is kept
+            shifts = torch.arange(32, dtype=torch.int32, device=dev)
+            kept_pos = ((words[:, None] >> shifts) & 1).reshape(-1)[:N].to(torch.uint8)
+            flags = torch.empty(N, dtype=torch.uint8, device=dev)
+            flags[self.ids] = kept_pos
+            return flags
+        return _on_device(allow, dev).view(torch.uint8)      # the flags themselves (row_filter has checked them)
+
+
+class _Lists(_ListLayout, _Refine, _Filter, _Packed4, _Search, _Among, _Compact):
+    """What both partitioned forms over codes share beside the layout: growth and compaction of the stored arrays."""
+
+    device_terms = False        # ResidualPartitionedMatrix: the row terms come from Pq.residual_terms_device
+
+    # ---- growth: every method returns a NEW matrix and leaves self (and the row filters built for it) untouched ----
     _ROW_ARRAYS = ("codes", "norms")          # what a matrix stores per row, in list order, beside ids
 
     def _shell(self):
@@ -929,14 +948,8 @@ class _Lists(_Refine, _Filter, _Packed4, _Search, _Among, _Compact):
         under the original-order mask.  Centroids, coarse codebook, packed4 and device_terms are shared or carried."""
         import torch
         words = self._keep_words(allow)
-        N, dev = len(self), self.codes.device
-        if isinstance(allow, RowFilter):             # the filter keeps the words only: bit p = position p is kept
-            shifts = torch.arange(32, dtype=torch.int32, device=dev)
-            kept_pos = ((words[:, None] >> shifts) & 1).reshape(-1)[:N].to(torch.uint8)
-            flags = torch.empty(N, dtype=torch.uint8, device=dev)
-            flags[self.ids] = kept_pos
-        else:                                        # the flags themselves (row_filter has checked them)
-            flags = _on_device(allow, dev).view(torch.uint8)
+        N = len(self)
+        flags = self._kept_flags(allow, words)
         rank = torch.cumsum(flags, 0, dtype=torch.int64) - 1
         names = ("ids",) + self._ROW_ARRAYS
         outs, list_off, _ = _compact_arrays(self.pq, words, N, [getattr(self, name) for name in names], list_off=self.list_off)
@@ -1223,6 +1236,153 @@ class FlatMatrix(_Refine, _Filter, _Compact):
         new.vectors = self._compact_vectors(words, kept)
         return new, kept
 
+    # the coarse training and assignment of QuantizedMatrix.partition: it asks self for pq (width, context), codes
+    # (device) and len alone, which this class has, and reads the rows from the `vectors` it is given
+    _coarse_partition = QuantizedMatrix._coarse_partition
+
+    def partition(self, n_lists, n_iterations=10, train_rows=None, rng=None):
+        """Partition the rows with a coarse k-means quantizer of n_lists centroids -> PartitionedFlatMatrix (IVF-Flat:
+        the rows stay the vectors themselves, a search reads the probed lists only).  The quantizer is trained on the
+        stored rows (f16 rows converted to f32), on train_rows distinct rows drawn with `rng` if given, from n_lists
+        distinct training rows as initial centroids: the training and the draws from `rng` of QuantizedMatrix.partition
+        with these rows as `vectors`.  Every row is assigned by the coarse codebook's quantize_batch_device and laid out
+        by Pq.lists_layout_device: nothing of length N goes to the host.  Row filters are not carried over."""
+        rng = rng or np.random.default_rng(0)
+        centroids, assign, _, _ = self._coarse_partition(n_lists, n_iterations, self.vectors, train_rows, rng, on_device=True)
+        return PartitionedFlatMatrix(self.vectors, centroids, assign, device=self.vectors.device, dtype=self.vectors.dtype,
+                                     ctx=self.pq._ctx)
+
+
+class PartitionedFlatMatrix(_ListLayout, _Filter, _Compact):
+    """A FlatMatrix whose rows are grouped by a coarse quantizer (IVF-Flat): list l holds the rows nearest to centroid l,
+    stored contiguously, and a search reads only the `nprobe` lists nearest to the query -- by the exact value of
+    FlatMatrix, so a search is FlatMatrix's restricted to the rows of the probed lists, bit for bit; with nprobe = n_lists
+    it returns FlatMatrix's values.  Ties go to the smaller position in list order.  Row numbers given and returned are
+    those of `vectors` as it was given.
+
+    rows [N, d] f32 or f16 in list order; ids [N] (ids[p] = original row of position p), positions [N] and list_off
+    [n_lists + 1] int64 on the device; centroids [n_lists, d] float32 (host); coarse (also `pq`): the one-subquantizer
+    codebook of the centroids, which orders the lists, assigns new rows and lends its device slot and scratch."""
+
+    vectors = None              # nothing is attached: the rows are the vectors
+
+    def __init__(self, vectors, centroids, assign, device="cuda:0", dtype=None, ctx=None):
+        """vectors [N, d] (numpy or torch), centroids [n_lists, d], assign [N] the list of every row: a numpy array of
+        list ids or an int64 CUDA tensor on `device` (then nothing of length N touches the host)."""
+        import torch
+        if len(vectors.shape) != 2 or vectors.shape[1] < 1:
+            raise PanicError("vectors must be [N, d]")
+        if dtype is None:
+            dtype = torch.float16 if str(vectors.dtype) in ("float16", "torch.float16") else torch.float32
+        if dtype not in (torch.float32, torch.float16):
+            raise PanicError("vectors are kept as float32 or float16")
+        if len(np.shape(centroids)) != 2 or np.shape(centroids)[1] != vectors.shape[1]:
+            raise PanicError("centroids must be [n_lists, %d]" % vectors.shape[1])
+        v = _on_device(vectors, device, dtype)
+        self._init_lists(centroids, assign, v.shape[0], v.device, ctx)
+        self.pq = self.coarse
+        self.rows = v[self.ids].contiguous()
+
+    @property
+    def codes(self):
+        """what the shared layout, row-filter and compaction code asks for its device: the stored rows take the codes' place"""
+        return self.rows
+
+    def _shell(self):
+        """a matrix of this class that shares what growth and compaction do not change"""
+        return _clone(self, ("pq", "centroids", "n_lists", "coarse", "_list_ids"))
+
+    def _wide(self):
+        """rows beyond the 4,096 bytes that the device mover and the device compaction take: they go through torch"""
+        return self.rows.shape[1] * self.rows.element_size() > 4096
+
+    # ---- searches -------------------------------------------------------------------------------------------------------
+    def _check_refine(self, k, refine):
+        if not k <= int(refine) <= 1024:
+            raise PanicError("refine must lie between k and 1024, was %d (k = %d)" % (refine, k))
+        return int(refine)
+
+    def _refined(self, queries, rows, k, ip):
+        """the re-ranking a MatrixGroup asks of a part: the candidates' exact values against the stored rows, which are
+        the values the search itself returns; ties to the smaller position"""
+        val, pos = self.pq.rerank_device(queries, self.rows, self._among_ids(rows), k, ip=ip)
+        return val, self._original_rows(pos)
+
+    def _topk(self, ip, queries, k, nprobe, refine, allow):
+        import torch
+        if refine is not None:
+            self._check_refine(k, refine)       # the values are exact already: refine changes nothing
+        q = _on_device(queries, self.rows.device, torch.float32, np.float32)
+        val, pos = self.pq.flat_search_lists_device(q, self.rows, self.list_off, self.probes(q, nprobe), k, ip=ip,
+                                                    allow=self._allow_words(allow))
+        return val, self._original_rows(pos)
+
+    def nearest(self, queries, k, nprobe, refine=None, allow=None):
+        """the k rows of smallest exact squared distance among the rows of the nprobe nearest lists, ties to the smaller
+        position in list order -> (dist, idx) [k] or [nq, k]; idx are original row numbers, -1 past the last probed
+        (allowed) row (distance +Inf).  refine is accepted and changes nothing; allow: None, a RowFilter of this matrix
+        or a bool array [N] in ORIGINAL row order (Pq.flat_search_lists_device)."""
+        return self._topk(False, queries, k, nprobe, refine, allow)
+
+    def most_similar(self, queries, k, nprobe, use_norms=True, refine=None, allow=None):
+        """the k rows of largest exact inner product among the rows of the nprobe nearest lists, largest first ->
+        (score, idx), -1 and -Inf past the last probed row; use_norms is accepted and ignored (the rows are stored
+        unscaled), the rest as for nearest().  The lists are chosen by distance to the centroids, as for nearest()."""
+        return self._topk(True, queries, k, nprobe, refine, allow)
+
+    def embeddings(self, rows):
+        """the stored rows of the original row numbers `rows` as float32 [len(rows), d]"""
+        import torch
+        rows = _on_device(rows, self.rows.device, torch.int64, np.int64).reshape(-1)
+        if rows.numel() and (int(rows.min()) < 0 or int(rows.max()) >= len(self)):
+            raise PanicError("row numbers must lie in [0, %d)" % len(self))
+        return self.rows[self.positions[rows]].to(torch.float32)
+
+    # ---- growth and removal: every method returns a NEW matrix and leaves self and its row filters untouched ----------
+    def add(self, vectors):
+        """The matrix with `vectors` ([B, d], numpy or CUDA) added as rows len(self) .. len(self) + B - 1, rounded to the
+        stored dtype -> a NEW PartitionedFlatMatrix: each vector goes to the end of the list assign() names.  ids and
+        rows are merged list by list on the device (Pq.merge_lists_device; rows wider than 4,096 bytes are gathered by
+        torch instead).  The result is, tensor for tensor, the matrix the constructor builds from all rows in row order."""
+        import torch
+        N = len(self)
+        x = _device_rows(vectors, self.rows.shape[1], self.rows.device)
+        ids_b, off_b = _ivf_layout_device(self.assign(x), self.n_lists)
+        rows_b = x.to(self.rows.dtype)[ids_b].contiguous()
+        new = self._shell()
+        merge = self.pq.merge_lists_device
+        new.ids, new.list_off = merge(self.list_off, self.ids, off_b, ids_b + N)
+        if self._wide():
+            # where original row r is stored in [self.rows; rows_b], gathered in the merged order
+            stored = torch.cat([self.positions, _positions(ids_b) + N])
+            new.rows = torch.cat([self.rows, rows_b])[stored[new.ids]]
+        else:
+            new.rows = merge(self.list_off, self.rows, off_b, rows_b)[0]
+        new.positions = _positions(new.ids)
+        return new
+
+    def compact(self, allow):
+        """The matrix of the rows that `allow` keeps (a RowFilter of this matrix, or a bool array [N] in ORIGINAL row
+        order) -> (new_matrix, kept): a NEW PartitionedFlatMatrix over the same lists and kept, int64 [N'] on the device,
+        the old row number of new row i, ascending; the kept rows are renumbered 0 .. N' - 1 in that order.  Compaction
+        is stable in position order, so list l of the result is the kept rows of list l, in order -- tensor for tensor
+        what the constructor builds from the kept rows and their assignments (Pq.compact_rows_device under the
+        position-order mask; rows wider than 4,096 bytes are selected by torch instead)."""
+        import torch
+        words = self._keep_words(allow)
+        N = len(self)
+        flags = self._kept_flags(allow, words)
+        rank = torch.cumsum(flags, 0, dtype=torch.int64) - 1
+        wide = self._wide()
+        outs, list_off, _ = _compact_arrays(self.pq, words, N, [self.ids, None if wide else self.rows], list_off=self.list_off)
+        new = self._shell()
+        new.rows = self.rows[flags[self.ids].bool()] if wide else outs[1]
+        new.ids = rank[outs[0]]
+        new.list_off = list_off
+        new.positions = _positions(new.ids)
+        kept = self.pq.compact_rows_device(self.pq.pack_row_mask_device(flags), None, want_src_rows=True, n=N)[2]
+        return new, kept
+
 
 class GroupFilter:
     """The set of rows a search of a MatrixGroup may return: one RowFilter per part (None for a part without rows), built
@@ -1255,7 +1415,8 @@ class MatrixGroup:
 
     A FlatMatrix part (rows that are not encoded: a fresh delta) contributes its exact values to a top-k search and to
     the shortlist of refine=R, and re-ranks its members against its own rows, which gives the same numbers; a range
-    search of a group with a flat part raises PanicError.
+    search of a group with a flat part raises PanicError.  A PartitionedFlatMatrix part (a delta grown large enough to be
+    worth lists) does the same over the lists that `nprobe` names.
 
     add, compact, remove, the *_among searches, persistence and any folding of a small part into a large one stay with
     the parts: MatrixGroup(new_parts) over a replaced part is the way to a changed group."""
@@ -1266,8 +1427,9 @@ class MatrixGroup:
         if not self.parts:
             raise PanicError("a group needs at least one part")
         for part in self.parts:
-            if not isinstance(part, (QuantizedMatrix, _Lists, FlatMatrix)):
-                raise PanicError("a part must be a QuantizedMatrix, PartitionedMatrix, ResidualPartitionedMatrix or FlatMatrix")
+            if not isinstance(part, (QuantizedMatrix, _Lists, FlatMatrix, PartitionedFlatMatrix)):
+                raise PanicError("a part must be a QuantizedMatrix, PartitionedMatrix, ResidualPartitionedMatrix, FlatMatrix "
+                                 "or PartitionedFlatMatrix")
         if len({part.pq.reconstructed_len() for part in self.parts}) != 1:
             raise PanicError("the parts of a group must hold vectors of one length")
         self.device = self.parts[0].codes.device if device is None else torch.device(device)
@@ -1329,7 +1491,7 @@ class MatrixGroup:
     @staticmethod
     def _more(part, nprobe):
         """the arguments a part's search takes besides the group's: nprobe for the classes that have lists"""
-        if not isinstance(part, _Lists):
+        if not isinstance(part, _ListLayout):
             return {}
         if nprobe is None:
             raise PanicError("a group with a partitioned part needs nprobe")
@@ -1405,7 +1567,7 @@ class MatrixGroup:
 
     def _range(self, ip, queries, threshold, nprobe, use_norms, allow, sort):
         import torch
-        if any(isinstance(part, FlatMatrix) for part in self.parts):
+        if any(isinstance(part, (FlatMatrix, PartitionedFlatMatrix)) for part in self.parts):
             raise PanicError("a range search over the raw vectors of a FlatMatrix part is not served")
         _, q = self._queries(queries)
         filters = self._part_filters(allow)

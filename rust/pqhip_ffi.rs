@@ -175,6 +175,15 @@ extern "C" {
         q_row_stride: i64, d_vectors: *const c_void, vec_bytes: i32, n_rows: i64, d: i64, vec_row_stride: i64,
         d_allow: *const u32, metric: i32, k: i32, d_val: *mut f32, val_row_stride: i64, d_idx: *mut i64,
         idx_row_stride: i64, stream: *mut c_void) -> i32;
+    // exact search in probed lists (IVF-Flat): the call above restricted, per query, to the rows of the lists its probe
+    // row names (d_vectors in list order under d_list_off; -1 pads a probe row; d_allow in POSITION order or NULL);
+    // equals the exhaustive call with the mask of those rows, bit for bit; option "flat_lists_wgs_per_query" forces the
+    // workgroups per query, on which the result does not depend
+    pub fn pqhip_flat_search_lists_f32_dev(cb: *mut pqhip_codebook, device_slot: i32, d_queries: *const f32,
+        n_queries: i64, q_row_stride: i64, d_vectors: *const c_void, vec_bytes: i32, n_rows: i64, d: i64,
+        vec_row_stride: i64, d_list_off: *const i64, n_lists: i64, d_probes: *const i64, n_probe: i32,
+        probes_row_stride: i64, d_allow: *const u32, metric: i32, k: i32, d_val: *mut f32, val_row_stride: i64,
+        d_idx: *mut i64, idx_row_stride: i64, stream: *mut c_void) -> i32;
     // merge of two list-ordered row arrays: list l of d_out = list l of d_a, then list l of d_b (rows of row_bytes bytes,
     // any alignment); the offsets are validated on the device (invalid: nothing written, the stream's range flag raised);
     // d_off_out NULL or [n_lists + 1]; option "lists_merge_wgs" forces the grid
