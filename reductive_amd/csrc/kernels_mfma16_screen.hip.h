@@ -1,47 +1,54 @@
 // kernels_mfma16_screen.hip.h -- the body of k_encode_mfma16<8, 20, IdxT>: screen all 256 centroids on
-// v_mfma_f32_16x16x32_f16, then resolve the rows the screen cannot decide exactly.
+// v_mfma_f32_32x32x16_f16, then resolve the rows the screen cannot decide exactly.
 //
-// Screening value A(c, r) = s^2 (cc(c) - 2 c.x(r)), computed entirely in the accumulator by ONE f16 matrix instruction per
-// 16 x 16 block.  s = 2^e is one power of two per subquantizer, chosen from max cc so that s^2 max cc is in [2^12, 2^14);
+// Screening value A(c, r) = s^2 (cc(c) - 2 c.x(r)), computed entirely in the accumulator by f16 matrix
+// instructions.  s = 2^e is one power of two per subquantizer, chosen from max cc so that s^2 max cc is in [2^12, 2^14);
 // x and c are scaled by it (exact) and rounded to f16 (RNE), cc~ = s^2 cc is split into f16 hi + lo; along k:
 //     A operand (centroid):  [-2 c~ (20) | cc~_hi | cc~_lo | 0 | 0 ...]      (a padding centroid: [0 ... | 0 | 0 | 65504 | 0 ...])
 //     B operand (row):       [   x~ (20) |    1   |    1   | 65504 | 0 ...]
 // xx is the same for every centroid of a row and is left out.  |A(c) - s^2 (D(c) - xx)| <= E_r for every c, D the CANON-F32
 // distance, with E_r = kScreenRel / 2 * (xx~ + max cc~) + kScreenAbs / 2 (the proof and its terms: DESIGN.md §5).
-// The key of a value is its f32 bits with the low 6 mantissa bits replaced by the lane-local centroid number
-// 4 cb + v (that moves a value by < 2^-17 |A|, part of the bound).  Per (lane, row block) a tile has 64 values a[cb][v];
-// the loop hands the merge the smallest key mk and a lower bound sk of every other value (less a key's perturbation),
-// without keying every value: 13 vector instructions per 8 values, two blocks at a time,
-//     block side    b[cb] = min_v a[cb][v], raw (v_min_f32 + v_min3_f32); kb[cb] = (bits(b[cb]) & ~15) | cb;
-//                   (mB, sB) = the two smallest kb (keep2 on the pair's two keys)
-//     column side   mv[v] = min_cb a[cb][v], raw: one v_min3_f32 per v folds both blocks of the pair
-//     end of tile   (mA, sA) = the two smallest mv, v* = the column of mA;
-//                   mk = (mB & ~63) | ((mB & 15) << 2) | v*,  sk = min(sA, sB)
-// Every value but the smallest differs from it in column (then sA is at or below it) or in block (then sB is, up to the
-// 4 index bits); exact ties give sk = mk up to those bits; and when sk exceeds mk by the margin below, the smallest value
-// is unique, mB is its block's key, v* its column, and mk is bit for bit its 6-bit key.  The four lane groups
-// of a row are merged once per trip of two tiles, 64 rows, one row per lane.  When the second smallest S of the row
-// exceeds the smallest key M by more than 2 E_r, the centroid of M is the first minimum of D and its code is stored: no
-// FP32 arithmetic.
+// The loop screens on v_mfma_f32_32x32x16_f16 (round 12): a block is 32 centroids x the tile's 32 rows, its 32 k
+// positions are two instructions chained through the accumulator, and an instruction holds the vector issue as long as a
+// 16x16x32 one for four times the values.  The chain adds the second instruction's products to the first's sum: one
+// more f32 addition than a single instruction's, inside the bound's term for an arbitrary accumulation order.
+// The key of a value is its f32 bits with the low 7 mantissa bits replaced by the lane-local centroid number
+// half-block << 3 | column (that moves a value by < 2^-16 |A|, part of the bound).  Per lane a tile has 128 values
+// d[b][i], block b = 0..7, accumulator register i = 0..15; registers 0..7 and 8..15 of block b are half-blocks 2b and
+// 2b + 1, and i & 7 is the column.  The loop hands the merge the smallest key mk and a lower bound sk of every other
+// value (less a key's perturbation) without keying every value (rounds 9 and 12): 21 vector instructions
+// per 16 values,
+//     block side    hb[j] = min of half-block j, raw (three v_min3_f32 + one v_min_f32); kb[j] = (bits(hb[j]) & ~15) | j;
+//                   (mB, sB) = the two smallest kb (keep2 on the block's two keys)
+//     column side   mv[c] = min over the half-blocks of column c, raw: one v_min3_f32 per column folds both half-blocks
+//     end of tile   kv[c] = (bits(mv[c]) & ~7) | c; (mA, sA) = the two smallest kv;
+//                   mk = (mB & ~127) | ((mB & 15) << 3) | (mA & 7),  sk = min(sA, sB)
+// Every value but the smallest differs from it in column (then sA is at or below it, up to the 3 index bits) or in
+// half-block (then sB is, up to the 4 index bits); exact ties give sk = mk up to those bits; and when sk exceeds mk by the
+// margin below, the smallest value is unique, mB is its half-block's key, mA its column's, and mk is bit for bit its
+// 7-bit key.  The two lane halves of a row are merged once per trip of two tiles, 64 rows, one row per lane.  When the
+// second smallest S of the row exceeds the smallest key M by more than 2 E_r, the centroid of M is the first minimum of
+// D and its code is stored: no FP32 arithmetic.
 // Every other row is recorded in the loop and resolved after it, where nothing is live: rows with at most one candidate
-// per lane group (every lane group's second value above tau) by encode_rows_few, one row per lane, from the merge's four
-// keys; the other rows with two or more candidates (|M| tiny included) by encode_rows_cand_f16,
-// 16 rows at a time, at a cost proportional to their candidates; rows whose scaled norm is beyond f16's range, or under
-// a bad codebook, by encode_rows_slow_v, as in the FP32 body.
+// per lane half (both halves' second value above tau) by encode_rows_few, one row per lane, from the merge's two keys;
+// the other rows with two or more candidates (|M| tiny included) by encode_rows_cand_f16, 16 rows at a time on the
+// 16x16x32 instruction and the same image, at a cost proportional to their candidates; rows whose scaled norm is beyond
+// f16's range, or under a bad codebook, by encode_rows_slow_v, as in the FP32 body.
 //
-// Layout (16x16x32 f16): lane (i16, q) supplies A[i16][k = 8q .. 8q + 7] and B[k = 8q .. 8q + 7][i16] and receives
-// D[4q + v][i16].  A = 16 centroids (block cb), B = 16 rows (block rb).  The f16 codebook image (256 rows of 32 f16 =
-// 64 B, no padding) is built once per codebook from cb / cc (k_build_screen_image) and copied into LDS by the workgroup;
-// chunk j (16 B) of row r is stored at chunk j ^ ((r >> 2) & 3),
-// which puts the 16 lanes of every ds_read_b128 lane group on 16 different 16-B bank slots.
-// The B operand of a lane is x[8q .. 8q + 7] of its row (lane group 2: x[16 .. 19] and the [1 1 65504 0] tail, lane
-// group 3: zeros), loaded as two 4-float chunks, scaled and converted in registers (v_cvt_pk_f16_f32).
-// Schedule: a selection step works on the pair of blocks (2p, 2p + 1) of ONE row block, 8 values per lane.  The steps
-// are software-pipelined over two accumulator sets of two blocks each (16 registers, as one block of both row blocks
-// took): before the selection on the pair of row block 0 the same pair's two matrix instructions for row block 1 are
-// issued, before that one the next pair's for row block 0; the A fragments of the next pair are read as soon as both
-// row blocks of this one are issued, the next tile's rows are converted into f16 operands in the middle of the current
-// tile, and its first pair is issued before the selection on the last, so it runs under the trip's merge.
+// Layout (32x32x16 f16): lane (n32 = lane & 31, h = lane >> 5) supplies A[n32][k = 8h .. 8h + 7] and
+// B[k = 8h .. 8h + 7][n32] and receives D[8 (i >> 2) + 4h + (i & 3)][n32] in register i.  A = 32 centroids (block b),
+// B = the tile's 32 rows.  The f16 codebook image (256 rows of 32 f16 = 64 B, no padding) is built once per codebook from
+// cb / cc (k_build_screen_image) and copied into LDS by the workgroup; chunk j (16 B) of row r is stored at chunk
+// j ^ ((r >> 2) & 3).  k step ks of block b reads row 32 b + n32, chunk 2 ks + h: the 16 lanes of a quarter wave are 16
+// rows in a row and land on 16 different 16-B bank slots, as under the 16x16x32 reads.
+// The B operands of a lane are x[8h .. 8h + 7] of its row for k step 0 and, for k step 1, x[16 .. 19] and the
+// [1 1 65504 0] tail in half 0, zeros in half 1: three 4-float chunks, scaled and converted in registers
+// (v_cvt_pk_f16_f32).
+// Schedule: a selection step works on one block, 16 values per lane.  The steps are software-pipelined over two
+// accumulator sets of 16 registers: before the selection on block b the two matrix instructions of block b + 1 are
+// issued into the other set, their A fragments read in front of them; the next tile's rows are loaded and converted
+// into f16 operands in the middle of the current tile, and its first block is issued before the selection on the last,
+// so it runs under the trip's merge.
 #pragma once
 #include "kernels_mfma.hip.h"
 
@@ -49,7 +56,7 @@ namespace pqhip {
 
 // the screen's constants, on the scaled values (xx~ = s^2 xx, max cc~ = s^2 max cc, M): accept a row when
 // S > M + kScreenRel * (xx~ + max cc~) + kScreenAbs and |M| > kScreenTiny
-constexpr float kScreenRel = 0x1.2p-9f;   // >= 2 E_r + 2 key perturbation: (132.6 + 2.0) 2^-16 needed, 144 2^-16 taken
+constexpr float kScreenRel = 0x1.2p-9f;   // >= 2 E_r + 2 key perturbation: (132.6 + 4.04) 2^-16 needed, 144 2^-16 taken
 constexpr float kScreenAbs = 0x1p-100f;   // flushed f32 subnormal products and partial sums
 constexpr float kScreenTiny = 0x1p-100f;  // keeps the index bits of M out of the subnormal range
 // the scale: s^2 max cc in [2^kScreenScaleLo, 2^(kScreenScaleLo + 2)); rows with xx~ >= kScreenMaxXX take the exact path
@@ -57,6 +64,11 @@ constexpr float kScreenTiny = 0x1p-100f;  // keeps the index bits of M out of th
 constexpr int kScreenScaleLo = 12;
 constexpr float kScreenMaxXX = 0x1p30f;
 constexpr float kScreenMinCC = 0x1p-100f;
+// the key of a value: its f32 bits with the low 7 mantissa bits replaced by half-block << 3 | column (round 12).
+// kKeyMask is the 6-bit mask of the block / column rule of rounds 9 and 10 on the 16x16x32 instruction, which the 7-bit
+// rule extends; tests/test_screen_select_model.py and tests/test_screen_pairs_model.py state that rule with it
+constexpr unsigned kKey7Mask = 0xffffff80u;
+[[maybe_unused]] constexpr unsigned kKeyMask = 0xffffffc0u;
 
 // instantiations that take the screen body (the others keep the FP32 body of k_encode_mfma16)
 template <int T, int DP> constexpr bool mfma16_screens() { return mfma16_screen_shape(T, DP); }
@@ -279,18 +291,25 @@ __device__ __forceinline__ void encode_rows_cand_f16(const float* x, int64_t x_r
     }
 }
 
-// The few-candidate rows of a wave: rows off the screen in which every lane group's second value
-// is above tau, so each lane group holds at most one candidate and its key mq[g] names it.  The trip's merge appends
-// {mq[0..3], tau, the row's offset in the wave} (three 8-byte words) to a list in LDS; a row that finds the list full
-// keeps its bit in the candidate record and is resolved by encode_rows_cand_f16.
-constexpr int kScreenFewCap = 96;           // rows per wave: 43.0 on average at the headline shape (sd 6.5)
-constexpr int kScreenFewWords = 3;          // uint2 per entry
+// The few-candidate rows of a wave (rounds 10 and 12): rows off the screen in which the second value of
+// both lane halves is above tau, so each half holds at most one candidate and its key names it.  The trip's merge appends
+// {key of half 0, key of half 1, tau, the row's offset in the wave} (16 bytes) to a list in LDS; a row that finds the
+// list full keeps its bit in the candidate record and is resolved by encode_rows_cand_f16.
+constexpr int kScreenFewCap = 96;           // rows per wave
+constexpr int kScreenFewWords = 2;          // uint2 per entry
+
+// centroid of a 7-bit key kb = half-block << 3 | column in lane half h (accumulator register i = 8 (half-block & 1) +
+// column of block half-block >> 1 is centroid 32 b + 8 (i >> 2) + 4 h + (i & 3))
+__device__ __forceinline__ unsigned screen_key_centroid(unsigned kb, unsigned h)
+{
+    return 16u * (kb >> 3) + 8u * ((kb >> 2) & 1u) + 4u * h + (kb & 3u);
+}
 
 // The listed rows after the loop, 64 at a time, one row per lane and no cross-lane step: the candidates are the lane
-// groups g with mq[g] <= tau, centroid 16 (kb >> 2) + 4 g + (kb & 3) from the key's low 6 bits kb; their CANON-F32
-// distances with the operations of encode_rows_cand_f16, the first minimum of those (ties to the lower index).  That set
-// holds the first minimum of D; a key whose index bits are off names one centroid more, which
-// cannot win.  A lane group that is no candidate (or names a padding centroid) evaluates centroid 0 and drops the result.
+// halves g with key[g] <= tau, centroid screen_key_centroid(key & 127, g); their CANON-F32 distances with the operations
+// of encode_rows_cand_f16, the first minimum of those (ties to the lower index).  That set holds the first minimum of D
+// (DESIGN.md §5, round 10); a key whose index bits are off names one centroid more, which cannot win.  A half that is
+// no candidate (or names a padding centroid) evaluates centroid 0 and drops the result.
 template <typename IdxT>
 __device__ __noinline__ void encode_rows_few(const float* x, int64_t x_rs, void* out, int64_t o_rs, const float* cbk,
                                              const float* ccn, int K, int k_pad, int dsub, int m, int64_t row_begin,
@@ -301,22 +320,20 @@ __device__ __noinline__ void encode_rows_few(const float* x, int64_t x_rs, void*
     const PQHIP_GLOBAL_AS float* const xsub = (const PQHIP_GLOBAL_AS float*)x + (int64_t)m * dsub;
     const PQHIP_GLOBAL_AS float* const cbm = (const PQHIP_GLOBAL_AS float*)cbk + (int64_t)m * K * DP;
     const PQHIP_GLOBAL_AS float* const ccm = (const PQHIP_GLOBAL_AS float*)ccn + (int64_t)m * k_pad;
-    const PQHIP_LDS_AS u32x2_t* const list_l = (const PQHIP_LDS_AS u32x2_t*)list;
+    const PQHIP_LDS_AS u32x4_t* const list_l = (const PQHIP_LDS_AS u32x4_t*)list;
     for (int e0 = 0; e0 < count; e0 += 64) {                            // wave-uniform
         const bool rv = e0 + lane < count;
-        const PQHIP_LDS_AS u32x2_t* const en = list_l + kScreenFewWords * (rv ? e0 + lane : 0);   // entry 0 exists: count > 0
-        const u32x2_t w0 = en[0], w1 = en[1], w2 = en[2];
-        const unsigned key[4] = {w0[0], w0[1], w1[0], w1[1]};
-        const float tau = __uint_as_float(w2[0]);
-        const int64_t row = row_begin + w2[1];
+        const u32x4_t en = list_l[rv ? e0 + lane : 0];                  // entry 0 exists: count > 0
+        const unsigned key[2] = {en[0], en[1]};
+        const float tau = __uint_as_float(en[2]);
+        const int64_t row = row_begin + en[3];
         float xr[DP];
         load20_global(xsub + row * x_rs, xr);
         const float xxe = norm_unrolled_static<DP>(xr);
         unsigned bh = 0xffffffffu, bl = 0xffffffffu;
 #pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const unsigned kb = key[g] & 63u;
-            const int j = (int)(16u * (kb >> 2) + 4u * g + (kb & 3u));
+        for (int g = 0; g < 2; ++g) {
+            const int j = (int)screen_key_centroid(key[g] & 127u, (unsigned)g);
             const bool cg = __uint_as_float(key[g]) <= tau && j < K;
             const int jj = cg ? j : 0;
             float ce[DP];
@@ -337,12 +354,12 @@ __device__ __forceinline__ void encode_mfma16_screen(const EncodeArgs& a)
     __shared__ __attribute__((aligned(16))) unsigned short img_s[256 * kRow];
     __shared__ unsigned need_s[4][kMfma16MaxTiles];   // rows for encode_rows_slow_v
     __shared__ unsigned cand_s[4][kMfma16MaxTiles];   // rows for the candidate path
-    __shared__ uint2 few_s[4][kScreenFewCap * kScreenFewWords];   // rows for encode_rows_few
+    __shared__ __attribute__((aligned(16))) uint2 few_s[4][kScreenFewCap * kScreenFewWords];   // rows for encode_rows_few
 
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int i16 = lane & 15;
-    const int q = lane >> 4;
+    const int n32 = lane & 31;                // the lane's row in a tile
+    const int h = lane >> 5;                  // its half of the k range and of every block's centroids
 
     // ---- workgroup -> (row group, m), as the FP32 body
     const int64_t b = blockIdx.x;
@@ -383,161 +400,151 @@ __device__ __forceinline__ void encode_mfma16_screen(const EncodeArgs& a)
     const bool cb_ok = !bad_codebook && cc_range && near_rows;            // wave-uniform
     const float maxcct = sc2 * maxcc;                                    // max cc~, exact
 
-    // x chunks of lane (i16, q): 4 floats at c0 and at c1 (lane group 2 uses only c0, lane group 3 neither; every
-    // chunk lies inside the sub-vector)
-    const int c0 = (8 * q) % 20, c1 = (8 * q + 4) % 20;
+    // x chunks of lane (n32, h): x[8h .. 8h + 7] for the first k step and one chunk of 4 floats for the second, x[16 .. 19]
+    // in half 0; half 1 carries zeros there and reads x[8 .. 11] again, inside the sub-vector, to multiply it by zero
     const float* const xsub = a.x + (int64_t)m * a.dsub;
-    // Addresses: a row block's base (tile_row0 + 16 rb) * x_rs is wave-uniform and stays in scalar registers; a lane adds
-    // the loop-invariant 32-bit byte offset of its row and chunk (global_load with a scalar base), and the trip's store
+    // Addresses: a tile's base tile_row0 * x_rs is wave-uniform and stays in scalar registers; a lane adds the
+    // loop-invariant 32-bit byte offset of its row and chunk (global_load with a scalar base), and the trip's store
     // adds lane * o_rs the same way: no 64-bit vector arithmetic in the steady state.
-    // Under strides too long for that (rows 64 MiB apart) every lane reads its row block's first row, the loop decides
+    // Under strides too long for that (rows 64 MiB apart) every lane reads its tile's first row, the loop decides
     // nothing, and encode_rows_slow_v, which addresses in 64 bits, encodes every row.
+    // The loop keeps two sets of 16 accumulators, and few vector registers are left for values that stay the same from
+    // trip to trip: the lane number, the offset of its first chunk and its two LDS addresses.  Everything else that
+    // depends on the lane -- the third chunk's offset, the store's offset, the ragged tile's row -- is formed again
+    // where it is used, from values the compiler cannot hoist (the empty asm statements).
     const unsigned xrs4 = near_rows ? (unsigned)a.x_rs * 4u : 0u;
-    const unsigned xoff0 = (unsigned)i16 * xrs4 + 4u * c0, xoff1 = (unsigned)i16 * xrs4 + 4u * c1;
-    const unsigned ooff = near_rows ? (unsigned)lane * (unsigned)a.o_rs * (unsigned)sizeof(IdxT) : 0u;
-    auto load_rows = [&](float (&v)[8], const char* base, unsigned o0, unsigned o1) {
-        // the offsets stay 32-bit values of this block, so that the loads take them next to the scalar base
-        asm volatile("" : "+v"(o0), "+v"(o1));
-        const f32x4 v0 = *reinterpret_cast<const f32x4_u*>(base + o0), v1 = *reinterpret_cast<const f32x4_u*>(base + o1);
+    const unsigned ors = near_rows ? (unsigned)a.o_rs * (unsigned)sizeof(IdxT) : 0u;   // scalar
+    const unsigned xoff0 = (unsigned)n32 * xrs4 + 32u * (unsigned)h;
+    auto load_rows = [&](float (&v)[12], const char* base, unsigned o0) {
+        // the offset stays a 32-bit value of this block, so that the loads take it next to the scalar base
+        asm volatile("" : "+v"(o0));
+        const unsigned o1 = h ? o0 : o0 + 64u;                           // x[16 .. 19], or x[8 .. 11] again
+        const f32x4 v0 = *reinterpret_cast<const f32x4_u*>(base + o0), v1 = *reinterpret_cast<const f32x4_u*>(base + o0 + 16);
+        const f32x4 v2 = *reinterpret_cast<const f32x4_u*>(base + o1);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) { v[j] = v0[j]; v[4 + j] = v1[j]; }
+        for (int j = 0; j < 4; ++j) { v[j] = v0[j]; v[4 + j] = v1[j]; v[8 + j] = v2[j]; }
     };
-    auto load_tile = [&](float (&v)[2][8], int64_t tile_row0) {
+    auto load_tile = [&](float (&v)[12], int64_t tile_row0) {
         if (tile_row0 + 32 <= a.n) {                                     // wave-uniform: every row of the tile exists
-            const char* base = reinterpret_cast<const char*>(xsub + tile_row0 * a.x_rs);
-            load_rows(v[0], base, xoff0, xoff1);
-            load_rows(v[1], base + 64 * a.x_rs, xoff0, xoff1);          // 16 rows on, still a scalar
+            load_rows(v, reinterpret_cast<const char*>(xsub + tile_row0 * a.x_rs), xoff0);
         } else {
             // the ragged last tile, or one past the end: rows >= n read the last row instead (never stored or recorded)
             const int64_t r0 = tile_row0 < a.n ? tile_row0 : a.n - 1;   // scalar
-            const int last = (int)(a.n - 1 - r0);                       // 0 .. 30
-            const char* base = reinterpret_cast<const char*>(xsub + r0 * a.x_rs);
-#pragma unroll
-            for (int rb = 0; rb < 2; ++rb) {
-                const unsigned ro = (unsigned)(16 * rb + i16 < last ? 16 * rb + i16 : last) * xrs4;
-                load_rows(v[rb], base, ro + 4u * c0, ro + 4u * c1);
-            }
+            int last = (int)(a.n - 1 - r0);                             // 0 .. 30
+            asm volatile("" : "+s"(last));
+            const int nl = lane & 31;
+            load_rows(v, reinterpret_cast<const char*>(xsub + r0 * a.x_rs), (unsigned)(nl < last ? nl : last) * xrs4 + (h ? 32u : 0u));
         }
     };
-    // lane group 3 carries zeros (scale 0: a NaN or inf of the row gives NaN, which only that row's column sees)
-    const float sl = q < 3 ? sc : 0.f;
-    const bool tail = q == 2;
-    // own[rb]: the lane's part of ||x||^2 of its row; the trip's merge sums the four lane groups
-    auto split = [&](const float (&v)[2][8], u32x4_t (&bop)[2], float (&own)[2]) {
+    // own: the lane's part of ||x||^2 of its row; the trip's merge sums the two halves
+    auto split = [&](const float (&v)[12], u32x4_t (&bop)[2], float& own) {
+        unsigned w[4];
 #pragma unroll
-        for (int rb = 0; rb < 2; ++rb) {
-            unsigned w[4];
+        for (int j = 0; j < 4; ++j) w[j] = pk_f16(sc * v[2 * j], sc * v[2 * j + 1]);
+        bop[0] = (u32x4_t){w[0], w[1], w[2], w[3]};
+        // half 1 carries zeros in the second k step
+        const unsigned t0 = pk_f16(sc * v[8], sc * v[9]), t1 = pk_f16(sc * v[10], sc * v[11]);
+        bop[1] = (u32x4_t){h ? 0u : t0, h ? 0u : t1, h ? 0u : 0x3c003c00u, h ? 0u : 0x7bffu};
+        // s^2 ||x||^2 for the bound and the range test (not rule 1: any f32 sum will do): the two halves' first chunks
+        // and the third chunk of half 0 cover the row once
+        float s0 = 0.f, s1 = 0.f, s2 = 0.f;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) w[j] = pk_f16(sl * v[rb][2 * j], sl * v[rb][2 * j + 1]);
-            if (tail) { w[2] = 0x3c003c00u; w[3] = 0x7bffu; }
-            bop[rb] = (u32x4_t){w[0], w[1], w[2], w[3]};
-            // s^2 ||x||^2 for the bound and the range test (not rule 1: any f32 sum will do): lane groups 0, 1 and the
-            // first half of group 2 cover the row once
-            float s0 = 0.f, s1 = 0.f;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { s0 = fmaf(v[rb][j], v[rb][j], s0); s1 = fmaf(v[rb][4 + j], v[rb][4 + j], s1); }
-            own[rb] = (q < 3 ? s0 : 0.f) + (q < 2 ? s1 : 0.f);
-        }
+        for (int j = 0; j < 4; ++j) { s0 = fmaf(v[j], v[j], s0); s1 = fmaf(v[4 + j], v[4 + j], s1); s2 = fmaf(v[8 + j], v[8 + j], s2); }
+        own = (s0 + s1) + (h ? 0.f : s2);
     };
 
-    const unsigned kKeyMask = 0xffffffc0u, kBlockMask = 0xfffffff0u;
+    const unsigned kHalfMask = 0xfffffff0u, kColMask = 0xfffffff8u;
     unsigned long long flagged = 0, flagged_c = 0;                      // wave-uniform: tiles with rows for the two exact paths
     uint2* few_w = few_s[wave];                                         // wave-uniform: the list's next entry
     int few_room = kScreenFewCap;
-    unsigned long long st_tiles = 0, st_steps = 0, st_rows = 0;   // st_rows: {other rows off the screen, 2-4-candidate rows}
+    unsigned long long st_tiles = 0, st_steps = 0, st_rows = 0;   // st_rows: {other rows off the screen, two-candidate rows}
     unsigned long long st_full = 0;                               // few-candidate rows that found the list full
     const unsigned long long st_t0 = a.stamps ? __builtin_amdgcn_s_memtime() : 0, st_r0 = a.stamps ? __builtin_amdgcn_s_memrealtime() : 0;
-    // A fragment of block cb: row 16 cb + i16, chunk q (k = 8q .. 8q + 7), swizzled
-    const unsigned short* const arow = &img_s[i16 * kRow + 8 * (q ^ ((i16 >> 2) & 3))];
-    auto load_a = [&](int cb, u32x4_t& af) { af = *reinterpret_cast<const u32x4_t*>(arow + cb * 16 * kRow); };
-    // blocks 2p and 2p + 1 of one row block: the pair a selection step works on
-    auto screen2 = [&](const u32x4_t (&af)[2], const u32x4_t& b, f32x4 (&acc)[2]) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-            acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, af[j]), __builtin_bit_cast(f16x8_t, b),
-                                                            (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+    // A fragments of block b: row 32 b + n32, chunks h (k step 0) and 2 + h (k step 1), swizzled
+    const unsigned short* const arow0 = &img_s[n32 * kRow + 8 * (h ^ ((n32 >> 2) & 3))];
+    const unsigned short* const arow1 = &img_s[n32 * kRow + 8 * ((2 + h) ^ ((n32 >> 2) & 3))];
+    auto load_a = [&](int b, u32x4_t (&af)[2]) {
+        af[0] = *reinterpret_cast<const u32x4_t*>(arow0 + b * 32 * kRow);
+        af[1] = *reinterpret_cast<const u32x4_t*>(arow1 + b * 32 * kRow);
+    };
+    // one block of 32 centroids on the tile's 32 rows: two k steps chained through the accumulator
+    auto screen = [&](const u32x4_t (&af)[2], const u32x4_t (&b)[2], f32x16& acc) {
+        const f32x16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        const f32x16 t = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, af[0]), __builtin_bit_cast(f16x8_t, b[0]), z, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, af[1]), __builtin_bit_cast(f16x8_t, b[1]), t, 0, 0, 0);
     };
 
-    // prologue: the first tile's operands, A fragments of blocks 0 and 1, their values for row block 0
-    float xv[2][8];
+    // prologue: the first tile's operands, block 0's values, the A fragments of block 1
+    float xv[12];
     u32x4_t bop[2];
-    float own[2];
+    float own;
     load_tile(xv, row_begin);
     split(xv, bop, own);
     u32x4_t af[2];
-    f32x4 acc[2][2];                                                    // [row block][block of the pair]
-    load_a(0, af[0]);
-    load_a(1, af[1]);
-    screen2(af, bop[0], acc[0]);
-    // the first pair has no selection step between its issue and its read (see the fence in tile): wait it out, once
+    f32x16 acc[2];
+    load_a(0, af);
+    screen(af, bop, acc[0]);
+    // the first block has no selection step between its issue and its read (see the fence in tile): wait it out, once
     __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7");
+    asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7\n\ts_nop 7");
     __builtin_amdgcn_sched_barrier(0);
     // The selection of one 32-row tile; bop holds its split rows, bnext / ownn receive the next tile's, mk / sk the
-    // smallest key and a lower bound of every other value per (lane, row block).  A trip of the loop below is two tiles on
+    // smallest key and a lower bound of every other value of the lane.  A trip of the loop below is two tiles on
     // alternating operand sets (no operand is copied at the seam) and ONE merge of its 64 rows, one row per lane.
-    auto tile = [&](int64_t row0, const u32x4_t (&bop)[2], u32x4_t (&bnext)[2], float (&ownn)[2], float (&mk)[2], float (&sk)[2]) {
-        // row0 stays a scalar: a row block's base address is formed from it in scalar registers
+    auto tile = [&](int64_t row0, const u32x4_t (&bop)[2], u32x4_t (&bnext)[2], float& ownn, float& mk, float& sk) {
+        // row0 stays a scalar: the tile's base address is formed from it in scalar registers
         asm("" : "+s"(row0));
-        // the next tile's rows (past row_end the loads are clamped like a short tile's, and their result is never used)
-        load_tile(xv, row0 + 32);
-        float mB[2], sB[2], mv[2][4];
-        // step (p, rb): the pair of blocks (2p, 2p + 1) on row block rb.  Issue the pair that is selected on next -- the
-        // same blocks on row block 1, or the next pair (mod 8: the next tile's first) on row block 0 -- read the A
-        // fragments of the next pair once both row blocks of this one are issued, then select on this step's 8 values
+        float mB, sB, mv[8];
+        // step b: issue block b + 1 (mod 8: the next tile's first, which then runs under the trip's second tile or the
+        // merge) into the other accumulator set, read the A fragments of block b + 2, then select on block b's 16 values
 #pragma unroll
-        for (int p = 0; p < 8; ++p) {
+        for (int b = 0; b < 8; ++b) {
+            load_a((b + 1) & 7, af);
+            // the next tile's rows (past row_end the loads are clamped like a short tile's, and their result is never
+            // used): loaded and converted in the middle of the tile, between the merges
+            if (b == 1) load_tile(xv, row0 + 32);
+            if (b == 5) split(xv, bnext, ownn);                         // the loads have landed by now
+            screen(af, b < 7 ? bop : bnext, acc[(b + 1) & 1]);
+            // The raw values go straight into inline assembly, and the compiler inserts the wait states between a
+            // matrix instruction and a vector read of its result only in front of instructions of its own.  Nothing
+            // crosses this fence, so a block issued in one step is read a whole step's selection (21 vector
+            // instructions, 20 in a tile's first) and the next block's issue later, however the steps are scheduled
+            // inside (tools/mfma_read_distance.py checks the compiled kernel)
+            __builtin_amdgcn_sched_barrier(0);
+            const f32x16 d = acc[b & 1];
+            // block side: the raw minimum of each half-block (registers 0..7 and 8..15), keyed by its number in 4 bits
+            const float b0 = vmin3(vmin3(d[0], d[1], d[2]), vmin3(d[3], d[4], d[5]), vmin(d[6], d[7]));
+            const float b1 = vmin3(vmin3(d[8], d[9], d[10]), vmin3(d[11], d[12], d[13]), vmin(d[14], d[15]));
+            const float k0 = __uint_as_float((__float_as_uint(b0) & kHalfMask) | (unsigned)(2 * b));
+            const float k1 = __uint_as_float((__float_as_uint(b1) & kHalfMask) | (unsigned)(2 * b + 1));
+            // column side: the raw minimum of every column (register & 7) over the half-blocks
+            if (b == 0) {
+                mB = vmin(k0, k1);
+                sB = vmax(k0, k1);
 #pragma unroll
-            for (int rb = 0; rb < 2; ++rb) {
-                if (rb == 0) {
-                    screen2(af, bop[1], acc[1]);
-                    load_a((2 * p + 2) & 15, af[0]);
-                    load_a((2 * p + 3) & 15, af[1]);
-                    if (p == 4) split(xv, bnext, ownn);                 // the loads have landed by now
-                } else {
-                    screen2(af, p < 7 ? bop[0] : bnext[0], acc[0]);     // under the trip's second tile, or the merge
-                }
-                // The raw values go straight into inline assembly, and the compiler inserts the wait states between a
-                // matrix instruction and a vector read of its result only in front of instructions of its own.  Nothing
-                // crosses this fence, so a pair issued in one step is read a whole step's selection (26 vector
-                // instructions, 13 in a tile's first two) later, however the steps are scheduled inside
-                // (tools/mfma_read_distance.py checks the compiled kernel)
-                __builtin_amdgcn_sched_barrier(0);
-                const f32x4 d0 = acc[rb][0], d1 = acc[rb][1];
-                // block side: the block's raw minimum, keyed by the block number in 4 bits
-                const float b0 = vmin3(d0[0], d0[1], vmin(d0[2], d0[3])), b1 = vmin3(d1[0], d1[1], vmin(d1[2], d1[3]));
-                const float k0 = __uint_as_float((__float_as_uint(b0) & kBlockMask) | (unsigned)(2 * p));
-                const float k1 = __uint_as_float((__float_as_uint(b1) & kBlockMask) | (unsigned)(2 * p + 1));
-                // column side: the raw minimum of every v over the blocks
-                if (p == 0) {
-                    mB[rb] = vmin(k0, k1);
-                    sB[rb] = vmax(k0, k1);
+                for (int c = 0; c < 8; ++c) mv[c] = vmin(d[c], d[8 + c]);
+            } else {
+                keep2(mB, sB, k0, k1);
 #pragma unroll
-                    for (int v = 0; v < 4; ++v) mv[rb][v] = vmin(d0[v], d1[v]);
-                } else {
-                    keep2(mB[rb], sB[rb], k0, k1);
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) fold2(mv[rb][v], d0[v], d1[v]);
-                }
+                for (int c = 0; c < 8; ++c) fold2(mv[c], d[c], d[8 + c]);
             }
         }
-        // end of tile: the smallest value is the smallest block minimum and the smallest column minimum at once, which
-        // names its block and its v; every other value lies in another column or in another block
+        // end of tile: the smallest value is the smallest half-block minimum and the smallest column minimum at once,
+        // which names its half-block and its column; every other value lies in another column or in another half-block
+        float kv[8];
 #pragma unroll
-        for (int rb = 0; rb < 2; ++rb) {
-            float mA = vmin(mv[rb][0], mv[rb][1]), sA = vmax(mv[rb][0], mv[rb][1]);
-            keep2(mA, sA, mv[rb][2], mv[rb][3]);
-            unsigned vs = mv[rb][1] == mA ? 1u : 0u;                    // a tie between columns makes sk = mA: any of them
-            vs = mv[rb][2] == mA ? 2u : vs;
-            vs = mv[rb][3] == mA ? 3u : vs;
-            const unsigned mb = __float_as_uint(mB[rb]);
-            mk[rb] = __uint_as_float((mb & kKeyMask) | (((mb & 15u) << 2) | vs));
-            sk[rb] = vmin(sA, sB[rb]);
-        }
+        for (int c = 0; c < 8; ++c) kv[c] = __uint_as_float((__float_as_uint(mv[c]) & kColMask) | (unsigned)c);
+        float mA = vmin(kv[0], kv[1]), sA = vmax(kv[0], kv[1]);
+        keep2(mA, sA, kv[2], kv[3]);
+        keep2(mA, sA, kv[4], kv[5]);
+        keep2(mA, sA, kv[6], kv[7]);
+        const unsigned mb = __float_as_uint(mB);
+        mk = __uint_as_float((mb & kKey7Mask) | (((mb & 15u) << 3) | (__float_as_uint(mA) & 7u)));
+        sk = vmin(sA, sB);
     };
     u32x4_t bop2[2];
-    float own2[2], ownn[2] = {0.f, 0.f};
-    float mk[2], sk[2], mk2[2], sk2[2];
+    float own2, ownn = 0.f;
+    float mk, sk, mk2, sk2;
     for (int64_t row0 = row_begin, tile_idx = 0; row0 < row_end; row0 += 64, tile_idx += 2) {
         const unsigned long long st_a = a.stamps ? __builtin_amdgcn_s_memtime() : 0;
         tile(row0, bop, bop2, own2, mk, sk);
@@ -545,40 +552,37 @@ __device__ __forceinline__ void encode_mfma16_screen(const EncodeArgs& a)
         // for rows of the next wave; their keys are set here and their rows are masked by row_end below.
         const bool two = row0 + 32 < row_end;                            // wave-uniform
         if (two) tile(row0 + 32, bop2, bop, ownn, mk2, sk2);
-        else mk2[0] = mk2[1] = sk2[0] = sk2[1] = __builtin_inff();
-        // ---- merge, once per trip: transpose (lane group q) x (row block b) so that lane 16 b + i16 holds the four
-        // lane-group values of row row0 + 16 b + i16 -- the row's offset in the trip is the lane number -- then decide
-        // the row in that one lane; store the decided rows, record the others
-        float mq[4] = {mk[0], mk[1], mk2[0], mk2[1]}, sq[4] = {sk[0], sk[1], sk2[0], sk2[1]};
-        float u[4] = {own[0], own[1], own2[0], own2[1]};
-        transpose_groups(mq);
-        transpose_groups(sq);
-        transpose_groups(u);
-        const float xx = sc2 * ((u[0] + u[1]) + (u[2] + u[3]));
-        const float lo01 = vmin(mq[0], mq[1]), hi01 = vmax(mq[0], mq[1]);
-        const float lo23 = vmin(mq[2], mq[3]), hi23 = vmax(mq[2], mq[3]);
-        const float M = vmin(lo01, lo23);
-        const float S2 = vmin(vmin(sq[0], sq[1]), vmin(sq[2], sq[3]));   // smallest second key of a lane group
-        const float S = vmin(vmin(vmax(lo01, lo23), vmin(hi01, hi23)), S2);
+        else mk2 = sk2 = __builtin_inff();
+        // ---- merge, once per trip: one half exchange per quantity brings both halves of row row0 + 32 t + n32 into
+        // lane 32 t + n32 -- the row's offset in the trip is the lane number -- then decide the row in that one lane;
+        // store the decided rows, record the others
+        const auto xm = __builtin_amdgcn_permlane32_swap(__float_as_uint(mk), __float_as_uint(mk2), false, false);
+        const auto xs = __builtin_amdgcn_permlane32_swap(__float_as_uint(sk), __float_as_uint(sk2), false, false);
+        const auto xu = __builtin_amdgcn_permlane32_swap(__float_as_uint(own), __float_as_uint(own2), false, false);
+        const float m0 = __uint_as_float(xm[0]), m1 = __uint_as_float(xm[1]);   // the keys of half 0 and half 1
+        const float xx = sc2 * (__uint_as_float(xu[0]) + __uint_as_float(xu[1]));
+        const float M = vmin(m0, m1);
+        const float S2 = vmin(__uint_as_float(xs[0]), __uint_as_float(xs[1]));   // smaller second key of the two halves
+        const float S = vmin(vmax(m0, m1), S2);
         const float tau = M + (kScreenRel * (xx + maxcct) + kScreenAbs);
         const bool valid = lane < (int)(row_end - row0 < 64 ? row_end - row0 : 64);   // scalar bound
         const bool in_range = valid && cb_ok && xx < kScreenMaxXX;       // the f16 operands are exact enough
         const bool plain = in_range && __builtin_fabsf(M) > kScreenTiny;
         const bool one = plain && S > tau;                               // a single candidate
         if (one) {
-            // the lane group that holds M: only one does, since a tie between two would make S = M
+            // the half that holds M: only one does, since a tie between the two would make S = M
             const unsigned Mb = __float_as_uint(M);
-            const unsigned qw = Mb == __float_as_uint(lo01) ? (Mb == __float_as_uint(mq[0]) ? 0u : 1u)
-                                                            : (Mb == __float_as_uint(mq[2]) ? 2u : 3u);
-            const unsigned kb = Mb & 63u;
+            const unsigned hw = Mb == __float_as_uint(m0) ? 0u : 1u;
             char* ob = reinterpret_cast<char*>(reinterpret_cast<IdxT*>(a.out) + (row0 * a.o_rs + m));   // scalar
-            unsigned oo = ooff;
+            unsigned os = ors;
+            asm volatile("" : "+s"(os));                                 // lane * o_rs once per trip, not a register held
+            unsigned oo = (unsigned)lane * os;
             asm volatile("" : "+v"(oo));                                 // as in load_rows
-            *reinterpret_cast<IdxT*>(ob + oo) = (IdxT)(16 * (kb >> 2) + 4 * qw + (kb & 3));
+            *reinterpret_cast<IdxT*>(ob + oo) = (IdxT)screen_key_centroid(Mb & 127u, hw);
         }
-        // few-candidate rows go to the wave's list (encode_rows_few): every lane group's second value is above tau, so
-        // the candidates are the mq[g] <= tau.  None of them may be tiny (index bits in the subnormal range): they lie
-        // in [M, tau], which is clear of [-kScreenTiny, kScreenTiny] when tau is below it or M above it; a row this
+        // few-candidate rows go to the wave's list (encode_rows_few): the second value of both halves is above tau, so
+        // the candidates are the keys m0, m1 <= tau.  None of them may be tiny (index bits in the subnormal range): they
+        // lie in [M, tau], which is clear of [-kScreenTiny, kScreenTiny] when tau is below it or M above it; a row this
         // holds back only takes the other path.
         const bool few = plain && !one && S2 > tau && (tau < -kScreenTiny || M > kScreenTiny);
         const unsigned long long fewm = __builtin_amdgcn_ballot_w64(few);
@@ -587,12 +591,9 @@ __device__ __forceinline__ void encode_mfma16_screen(const EncodeArgs& a)
         // wave and few_w, past the list's end, is not used again)
         const int pos = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(fewm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)fewm, 0u));
         const bool listed = few && pos < few_room;
-        if (listed) {                                                   // skipped when no lane has one
-            uint2* const en = few_w + kScreenFewWords * pos;
-            en[0] = make_uint2(__float_as_uint(mq[0]), __float_as_uint(mq[1]));
-            en[1] = make_uint2(__float_as_uint(mq[2]), __float_as_uint(mq[3]));
-            en[2] = make_uint2(__float_as_uint(tau), (unsigned)(row0 - row_begin) + (unsigned)lane);
-        }
+        if (listed)                                                     // skipped when no lane has one
+            *reinterpret_cast<u32x4_t*>(few_w + kScreenFewWords * pos) =
+                (u32x4_t){__float_as_uint(m0), __float_as_uint(m1), __float_as_uint(tau), (unsigned)(row0 - row_begin) + (unsigned)lane};
         const int few_k = __builtin_popcountll(fewm);                   // scalar
         few_w += kScreenFewWords * few_k;
         few_room -= few_k;
@@ -613,8 +614,8 @@ __device__ __forceinline__ void encode_mfma16_screen(const EncodeArgs& a)
         record(need_s[wave], flagged, need);
         record(cand_s[wave], flagged_c, cand);
         if (a.stamps) {
-            // the rows with two to four candidates, at most one per lane group (every lane group's second key is above
-            // tau), which round 6 resolved in the loop
+            // the rows with at most one candidate per half (the second key of both halves is above tau): one or two
+            // candidates, which the list takes; the other rows off the screen keep the candidate or the exact path
             const int nfew = __builtin_popcountll(__builtin_amdgcn_ballot_w64(plain && !one && S2 > tau));
             const int off = __builtin_popcountll(need | __builtin_amdgcn_ballot_w64(in_range && !one));
             st_rows += (unsigned long long)nfew | ((unsigned long long)(off - nfew) << 32);
@@ -622,8 +623,7 @@ __device__ __forceinline__ void encode_mfma16_screen(const EncodeArgs& a)
             st_tiles += two ? 2 : 1;
             st_steps += __builtin_amdgcn_s_memtime() - st_a;
         }
-        own[0] = ownn[0];
-        own[1] = ownn[1];
+        own = ownn;
     }
     const unsigned long long st_p0 = a.stamps ? __builtin_amdgcn_s_memtime() : 0;
     // ---- rows the screen does not decide (nothing is live here): the listed few-candidate rows one per lane, the others

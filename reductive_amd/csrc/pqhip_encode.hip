@@ -322,13 +322,13 @@ static int32_t launch_mfma(pqhip_codebook* cb, int slot, const EncodePlan& p, co
     PQCHK(stamps.begin(diag().enc_stamp && p.kind >= 2, (size_t)grid.x * 4 * stamp_words, io.st));
     a.stamps = stamps.ptr();
     PQCHK(launched(launch_encode_mfma(p.kind, cb->T, cb->DP, p.vec, c.code_bytes, a, grid, io.st, diag().lds_pad), p.kernel));
-    // k_encode_mfma16 (kind 3) leaves row counts in word 2: of the rows the screen does not decide, those with two to four
-    // candidates, one per lane group (round 6 resolved them in the loop), and all others (both zero in its FP32 body);
+    // k_encode_mfma16 (kind 3) leaves row counts in word 2: of the rows the screen does not decide, those with at most
+    // one candidate per lane half (two at most: the rows encode_rows_few can take), and all others (both zero in its FP32 body);
     // kinds 0 and 2 leave the seam cycles there.  The screen body adds the
     // image-staging cycles as a sixth word, the few-candidate rows that found their wave's list full as a seventh,
     // the cycles after the loop as an eighth, and of those the cycles in encode_rows_few and in encode_rows_cand_f16
     // as a ninth and a tenth.
-    if (p.kind == 3) return stamps.report5(io.st, "encode", "steps", "2-4-candidate / other off-screen", true, stamp_words);
+    if (p.kind == 3) return stamps.report5(io.st, "encode", "steps", "one-per-half / other off-screen", true, stamp_words);
     return stamps.report5(io.st, "encode", "steps", "seam");
 }
 
