@@ -734,6 +734,65 @@ int32_t pqhip_flat_search_lists_f32_dev(pqhip_codebook *cb, int32_t device_slot,
                                         float *d_val, int64_t val_row_stride, int64_t *d_idx, int64_t idx_row_stride, void *stream);
 
 /*
+ * Exact range search over resident vectors: EVERY row whose true squared distance to query q is <= d_threshold[q]
+ * (metric 0) resp. whose inner product with it is >= d_threshold[q] (metric 1), over ALL rows of d_vectors
+ * (pqhip_flat_range_f32_dev) or over the rows of the lists the query probes (pqhip_flat_range_lists_f32_dev), as CSR.  It
+ * is the exact counterpart of the ADC range searches: the ground truth of their recall, the radius question for a
+ * collection kept as raw vectors, and the only way to true values for a radius query (re-ranking stops at 1,024
+ * candidates).  Every clause is that of an existing call, taken over unchanged.  d_vectors, vec_bytes, d_queries, d and cb
+ * are those of pqhip_flat_search_f32_dev (f32 or IEEE f16 converted exactly, d <= 16384; the quantizer of cb is not read).
+ * Value of a row: the value pqhip_rerank_f32_dev defines, operation for operation -- the 64 lane chains from +0, then the
+ * fixed tree, no contraction.  Predicate: that of pqhip_adc_range_f32_dev -- metric 0: v <= thr[q] as an IEEE comparison,
+ * metric 1: v >= thr[q]; a NaN on either side never qualifies; +Inf resp. -Inf matches every non-NaN row.  The value is
+ * stored bit for bit; nothing is ordered by value, so there is no key.  The chains start at +0, so a value is never -0:
+ * every returned value equals, bit for bit, what pqhip_flat_search_f32_dev returns for that row.
+ * Output, order and capacity: d_lims [n_queries + 1] int64, d_val (f32) and d_idx (int64) flat arrays of `capacity`
+ * entries, with exactly the capacity protocol of the ADC range calls: d_lims always holds the true counts, only slots
+ * < capacity are written and nothing past them is touched, capacity == 0 is a count call (d_val / d_idx may be NULL).
+ * Exhaustive call: the rows of query q in ascending row index.  List call: in the order of the concatenation of the probed
+ * lists -- probe slot first, then position; d_idx holds positions in d_vectors; a list named twice returns its rows twice.
+ * The result is a function of the inputs alone: it does not depend on the grid, the workgroups per query or the queries
+ * per pass (options "flat_range_wgs", "flat_range_wgs_per_query" force the grids).
+ * Mask and probes: d_allow is NULL or the mask words of the flat searches, in row order for the exhaustive call and in
+ * POSITION order for the list call; a disallowed row is not loaded (a NaN in it changes nothing).  d_list_off, d_probes,
+ * -1 padding, bad ids, clamped and inverted ranges and the range flag are exactly those of pqhip_flat_search_lists_f32_dev
+ * (the same plan kernel reads them).  No byte outside [d_vectors, last row + d elements) is read.
+ * Status codes, in the precedence EINVAL, ENODEV, EUNSUPPORTED, ESHAPE -- the union of the checks of
+ * pqhip_flat_search_f32_dev resp. pqhip_flat_search_lists_f32_dev and of the ADC range calls, without k:
+ *   null cb, d < 1, n_queries < 0, n_rows < 0, capacity < 0, metric not 0 / 1 (list call: n_lists < 0, n_probe < 1):
+ *   PQHIP_EINVAL;
+ *   vec_bytes not 2 / 4, d > 16384 (list call: n_rows > 2^32 - 2 or n_probe >= 2^24): PQHIP_EUNSUPPORTED;
+ *   with n_queries > 0, a null d_lims, d_threshold or d_queries, null outputs with capacity > 0, a null d_vectors with
+ *   n_rows > 0 (list call: a null d_list_off or d_probes): PQHIP_EINVAL;
+ *   q_row_stride < d, vec_row_stride < d (n_rows > 0) (list call: probes_row_stride < n_probe): PQHIP_ESHAPE.
+ * n_queries == 0 launches nothing and writes nothing; n_rows == 0 (list call: or n_lists == 0) writes all-zero lims.
+ * Asynchronous on `stream`.  Two passes with a prefix scan between them, as for the ADC range calls: the count pass streams
+ * the rows -- once for the 4 queries of a pass while d <= 9216, else one query per pass; the list call one query per
+ * workgroup set -- and leaves, beside the partial counts, a bitmap of the hits in the codebook's scratch (one bit per row
+ * and query of the pass, n_rows / 8 bytes per query; the list call sizes it for every row probed once); the fill pass loads
+ * only the rows that hit, recomputes their values (the same arithmetic on the same bytes: the same bits) and stores them.  A
+ * selective radius therefore costs one stream of the matrix plus its hits; a radius that admits every row costs two.  A
+ * count call launches no fill.  Queries of the list call are processed in chunks that keep plan, counts and bitmap within
+ * 512 MB of scratch.  Results are not sorted by value: sort on the caller's side.
+ */
+int32_t pqhip_flat_range_f32_dev(pqhip_codebook *cb, int32_t device_slot,
+                                 const float *d_queries, int64_t n_queries, int64_t q_row_stride,
+                                 const void *d_vectors, int32_t vec_bytes, int64_t n_rows, int64_t d, int64_t vec_row_stride,
+                                 const uint32_t *d_allow /* ceil(n_rows / 32) words or NULL */,
+                                 int32_t metric /* 0 = squared L2, 1 = inner product */,
+                                 const float *d_threshold /* [n_queries] */, int64_t *d_lims, float *d_val, int64_t *d_idx,
+                                 int64_t capacity, void *stream);
+int32_t pqhip_flat_range_lists_f32_dev(pqhip_codebook *cb, int32_t device_slot,
+                                       const float *d_queries, int64_t n_queries, int64_t q_row_stride,
+                                       const void *d_vectors, int32_t vec_bytes, int64_t n_rows, int64_t d, int64_t vec_row_stride,
+                                       const uint32_t *d_allow /* ceil(n_rows / 32) words in POSITION order, or NULL */,
+                                       const int64_t *d_list_off, int64_t n_lists,
+                                       const int64_t *d_probes, int32_t n_probe, int64_t probes_row_stride,
+                                       int32_t metric /* 0 = squared L2, 1 = inner product */,
+                                       const float *d_threshold /* [n_queries] */, int64_t *d_lims, float *d_val, int64_t *d_idx,
+                                       int64_t capacity, void *stream);
+
+/*
  * Merge of two list-ordered row arrays: the primitive under growing a partitioned matrix (rows added to an index, two
  * indexes over the same lists joined).  d_a is [n_a] rows of row_bytes bytes in list order under d_off_a [n_lists + 1]
  * (list l = rows off_a[l] .. off_a[l + 1] - 1), d_b likewise [n_b] rows under d_off_b; d_out is [n_a + n_b] rows.  For
@@ -1071,6 +1130,11 @@ int32_t pqhip_set_rotation_variant(int32_t variant);
  *   "flat_search_wgs"      producer workgroups of pqhip_flat_search_f32_dev (0 = one per CU; at most 65536; rows per workgroup
  *                          stay a multiple of 1,024; the result does not depend on it)
  *   "flat_lists_wgs_per_query"  workgroups that share one query of pqhip_flat_search_lists_f32_dev (0 = chosen from the
+ *                          expected probed bytes; at most 4096; the result does not depend on it)
+ *   "flat_range_wgs"       producer workgroups of pqhip_flat_range_f32_dev (0 = one per CU; at most 16384, so that the
+ *                          one-workgroup prefix scan of a pass of 4 queries sums at most 2^20 counts; rows per workgroup
+ *                          stay a multiple of 1,024; the result does not depend on it)
+ *   "flat_range_wgs_per_query"  workgroups that share one query of pqhip_flat_range_lists_f32_dev (0 = chosen from the
  *                          expected probed bytes; at most 4096; the result does not depend on it)
  *   "cross_product_exact" 0 = X^T.R of the OPQ training step / pqhip_at_dot_b_f32_dev as a plain split-K product:
  *                          within 1e-5 relative of the exact rule-2 result, no per-block partial matrices (default 1)

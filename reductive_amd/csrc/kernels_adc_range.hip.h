@@ -218,7 +218,7 @@ __global__ __launch_bounds__(1024) void k_adc_range_lists_u8(const uint8_t* __re
 // of the queries before this launch; the host zeroes lims[0] of a call).  len = nq units: lims[q] receives the prefix at
 // the first unit of query q and lims[nq] the running total -- the lims[0] of the next launch.  1,024 counts per trip
 // with a carry, as k_adc_lists_plan sums its segments.
-__global__ __launch_bounds__(1024) void k_adc_range_scan(int64_t* __restrict__ part, int64_t units, int64_t nq,
+inline __global__ __launch_bounds__(1024) void k_adc_range_scan(int64_t* __restrict__ part, int64_t units, int64_t nq,
                                                          int64_t* __restrict__ lims)
 {
     __shared__ long long wsum[16];

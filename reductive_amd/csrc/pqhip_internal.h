@@ -107,6 +107,8 @@ struct Options {
     std::atomic<int64_t> topk_merge_wgs{0};         // merge of search results: workgroups, queries taken grid-stride (0: one per query)
     std::atomic<int64_t> flat_search_wgs{0};        // exact search over resident vectors: producer workgroups (0: chosen from the shape)
     std::atomic<int64_t> flat_lists_wgs_per_query{0};   // exact search in probed lists: workgroups per query (0: chosen from the probed bytes)
+    std::atomic<int64_t> flat_range_wgs{0};         // exact range search over resident vectors: producer workgroups (0: one per CU)
+    std::atomic<int64_t> flat_range_wgs_per_query{0};   // exact range search in probed lists: workgroups per query (0: chosen from the probed bytes)
 };
 
 struct Diag {

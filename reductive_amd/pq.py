@@ -1388,6 +1388,99 @@ class Pq:
             _marshal.check_range(cb, slot, sp)
         return (val[0], idx[0]) if single else (val, idx)
 
+    # ---- exact range search over resident vectors: every row within a radius, by true distance ---------------------------
+    def _flat_range(self, queries, vectors, threshold, ip, allow, capacity, stream, check, lists=None):
+        """Both exact range searches -> (lims, val, idx): queries, vectors and mask marshalled as for flat_search_device,
+        the threshold and the capacity protocol as for _adc_range (one call with `capacity` entries, default 1 << 20, one
+        read of lims[-1] -- the only synchronisation -- and, if the result is larger, one more call of exactly its
+        size).  lists: (list_off, probes) for the list form."""
+        import torch
+        for t, what in ((queries, "queries"), (vectors, "vectors")):
+            if not hasattr(t, "is_cuda"):
+                raise PanicError("%s must be a torch tensor" % what)
+        if queries.dtype != torch.float32 or queries.dim() not in (1, 2):
+            raise PanicError("queries must be float32 [d] or [nq, d]")
+        if vectors.dtype not in (torch.float32, torch.float16) or vectors.dim() != 2:
+            raise PanicError("vectors must be float32 or float16 [N, d]")
+        q2 = queries[None] if queries.dim() == 1 else queries
+        nq, d = q2.shape
+        N = vectors.shape[0]
+        if d < 1 or vectors.shape[1] != d:
+            raise PanicError("Query and vector length mismatch")
+        if d > 16384:
+            raise PanicError("vectors of at most 16384 elements are searched, got %d" % d)
+        tensors = (queries, vectors)
+        names = "queries, vectors"
+        if lists is not None:
+            if N > (1 << 32) - 2:
+                raise PanicError("at most 2^32 - 2 rows are searched in lists")
+            list_off, probes = lists
+            pr, n_lists, n_probe, p_rs = _marshal.vector_lists_arg(list_off, probes, nq)
+            tensors += (list_off, probes)
+            names += ", list_off, probes"
+        allow = _marshal.vector_mask_words(allow, N)
+        if allow is not None:
+            tensors += (allow,)
+        if not all(t.is_cuda for t in tensors):
+            raise PanicError("%s and allow must be CUDA tensors" % names)
+        if any(t.device != vectors.device for t in tensors):
+            raise PanicError("%s and allow must live on one device" % names)
+        if q2.stride(1) != 1:
+            q2 = q2.contiguous()
+        if N > 0 and vectors.stride(1) != 1:
+            vectors = vectors.contiguous()
+        if allow is not None:
+            allow = _marshal.stand_in(allow, allow.shape[0], vectors.device)   # a mask stays a mask (N = 0 reads no word)
+        dev = vectors.device
+        thr = _marshal.threshold_arg(threshold, nq, dev)
+        cap = (1 << 20) if capacity is None else int(capacity)
+        if cap < 0:
+            raise PanicError("capacity must not be negative")
+        own_stream = stream is None
+        cb, slot, sp = _marshal.launch(self, vectors, stream)
+        head = (cb, slot, q2.data_ptr(), nq, row_stride(q2, nq, d), ptr_or_none(vectors, N), vectors.element_size(), N, d,
+                row_stride(vectors, N, d), None if allow is None else allow.data_ptr())
+        name = "pqhip_flat_range_f32_dev"
+        if lists is not None:
+            head += (list_off.data_ptr(), n_lists, pr.data_ptr(), n_probe, p_rs)
+            name = "pqhip_flat_range_lists_f32_dev"
+        lims = torch.empty(nq + 1, dtype=torch.int64, device=dev)
+        while True:
+            val = torch.empty(cap, dtype=torch.float32, device=dev)
+            idx = torch.empty(cap, dtype=torch.int64, device=dev)
+            _marshal.run(name, *head, 1 if ip else 0, thr.data_ptr(), lims.data_ptr(), ptr_or_none(val, cap), ptr_or_none(idx, cap),
+                         cap, sp)
+            if not own_stream:
+                torch.cuda.ExternalStream(stream, device=dev).synchronize()
+            total = int(lims[-1])
+            if total <= cap:
+                break
+            cap = total             # the second call always suffices
+        if check:
+            _marshal.check_range(cb, slot, sp)
+        return lims, val[:total], idx[:total]
+
+    def flat_range_device(self, queries, vectors, threshold, ip=False, allow=None, capacity=None, stream=None, check=False):
+        """EVERY row of `vectors` whose exact squared distance to the query is <= threshold (ip=True: whose inner product
+        is >= threshold): queries, vectors and allow as for flat_search_device, threshold a scalar or one value per query
+        (float, numpy or tensor) -> (lims, val, idx): CSR, lims CUDA int64 [nq + 1] ([2] for one query), the rows of query
+        q at val[lims[q]:lims[q + 1]] / idx[..] in ascending row index, val the value flat_search_device returns for the
+        row, bit for bit (pqhip_flat_range_f32_dev).  A NaN value never qualifies; threshold +Inf (ip: -Inf) returns
+        every non-NaN row.  capacity: entries allocated for the first call (default 1 << 20); if the result is larger
+        the call is repeated once with exactly its size -- lims[-1] is read in between, the one synchronisation;
+        capacity=0 counts first.  A disallowed row is not read.  There is no range flag to raise; check=True only
+        synchronises."""
+        return self._flat_range(queries, vectors, threshold, ip, allow, capacity, stream, check)
+
+    def flat_range_lists_device(self, queries, vectors, list_off, probes, threshold, ip=False, allow=None, capacity=None,
+                                stream=None, check=False):
+        """flat_range_device restricted, per query, to the rows of the probed lists (vectors in list order, list_off,
+        probes and allow in position order as for flat_search_lists_device) -> (lims, val, idx); idx are positions in
+        vectors and the rows of a query come in the order of the concatenation of its probed lists: probe slot first,
+        then position; a list named twice returns its rows twice (pqhip_flat_range_lists_f32_dev).  check=True
+        synchronises and reports a list id or an offset out of range (they are skipped resp. clamped either way)."""
+        return self._flat_range(queries, vectors, threshold, ip, allow, capacity, stream, check, lists=(list_off, probes))
+
     # ---- growing a partitioned matrix: merge of two list-ordered arrays ------------------------------------------------
     def merge_lists_device(self, list_off_a, a, list_off_b, b, out=None, stream=None, check=False):
         """a, b: CUDA tensors of one dtype, [n_a] / [n_b] or [n_a, c] / [n_b, c], contiguous, their rows in list order

@@ -285,6 +285,29 @@ class _Refine:
         as exact_nearest()."""
         return self._exact(True, queries, k, allow)
 
+    def _exact_range(self, ip, queries, threshold, allow, sort):
+        import torch
+        if self.vectors is None:
+            raise PanicError("refine needs the original vectors: call attach_vectors first")
+        q = _on_device(queries, self.vectors.device, torch.float32, np.float32)
+        lims, val, rows = self.pq.flat_range_device(q, self.vectors, threshold, ip=ip, allow=self._exact_words(allow))
+        if sort:
+            val, rows = sort_ranges(lims, val, rows, ip)
+        return lims, val, rows
+
+    def exact_within(self, queries, radius, allow=None, sort=False):
+        """The true answer of within(): EVERY attached vector whose exact squared distance to the query is <= radius (a
+        scalar or one value per query) -> (lims, dist, idx), CSR over the queries in ascending original row number
+        (Pq.flat_range_device); sort=True: ascending in distance, ties in row order.  The codes are not read: this is
+        what the recall of within() is measured against, and the one way to true distances for a radius query (refine=
+        stops at 1,024 candidates).  allow: as for exact_nearest()."""
+        return self._exact_range(False, queries, radius, allow, sort)
+
+    def exact_similar_above(self, queries, threshold, allow=None, sort=False):
+        """Every attached vector whose exact inner product with the query is >= threshold -> (lims, score, idx), as
+        exact_within(); sort=True: descending in score."""
+        return self._exact_range(True, queries, threshold, allow, sort)
+
 
 class RowFilter:
     """The set of rows a search may return, packed for one matrix: `words` is the device mask of the searches' `allow=`
@@ -1167,7 +1190,8 @@ class FlatMatrix(_Refine, _Filter, _Compact):
     """Rows kept as they are, f32 or f16, and searched exactly: no quantizer, no codes.  Every search is the exhaustive
     top-k by the true squared distance or inner product (Pq.flat_search_device), so rows are searchable the moment
     they are added -- the delta of a MatrixGroup before it is encoded -- and a small collection needs no training.  Its
-    values are those `refine=` returns on the other classes.  `vectors` is the [N, d] device tensor; `pq` is a
+    values are those `refine=` returns on the other classes.  within() / similar_above() return every row inside a
+    radius by the same values (Pq.flat_range_device).  `vectors` is the [N, d] device tensor; `pq` is a
     one-centroid placeholder of width d that only lends its device slot and scratch to the calls."""
 
     def __init__(self, vectors, device="cuda:0", dtype=None, ctx=None):
@@ -1209,6 +1233,28 @@ class FlatMatrix(_Refine, _Filter, _Compact):
         """the k rows of largest exact inner product, largest first -> (score, idx); use_norms is accepted and ignored
         (the rows are stored unscaled), refine and allow as for nearest()."""
         return self._topk(True, queries, k, refine, allow)
+
+    def _range(self, ip, queries, threshold, allow, sort):
+        import torch
+        q = _on_device(queries, self.vectors.device, torch.float32, np.float32)
+        lims, val, rows = self.pq.flat_range_device(q, self.vectors, threshold, ip=ip, allow=self._allow_words(allow))
+        if sort:
+            val, rows = sort_ranges(lims, val, rows, ip)
+        return lims, val, rows
+
+    def within(self, queries, radius, allow=None, sort=False):
+        """EVERY row whose exact squared distance to the query is <= radius (a scalar or one value per query) -> (lims,
+        dist, idx): CSR over the queries, lims int64 [nq + 1] ([2] for one query), the rows of query q at
+        lims[q]:lims[q + 1] in ascending row number, dist the value nearest() returns for the row (Pq.flat_range_device;
+        the result is allocated to its size, after one read of the count).  sort=True: each query's rows ascending in
+        distance instead, ties in row order (sort_ranges).  allow: as for nearest()."""
+        return self._range(False, queries, radius, allow, sort)
+
+    def similar_above(self, queries, threshold, use_norms=True, allow=None, sort=False):
+        """Every row whose exact inner product with the query is >= threshold (a scalar or one value per query) ->
+        (lims, score, idx), CSR as for within(); sort=True: each query's rows descending in score, ties in row order.
+        use_norms is accepted and ignored, as in most_similar()."""
+        return self._range(True, queries, threshold, allow, sort)
 
     def embeddings(self, rows):
         """the stored rows `rows` as float32 [len(rows), d]"""
@@ -1330,6 +1376,30 @@ class PartitionedFlatMatrix(_ListLayout, _Filter, _Compact):
         unscaled), the rest as for nearest().  The lists are chosen by distance to the centroids, as for nearest()."""
         return self._topk(True, queries, k, nprobe, refine, allow)
 
+    def _range(self, ip, queries, threshold, nprobe, allow, sort):
+        import torch
+        q = _on_device(queries, self.rows.device, torch.float32, np.float32)
+        lims, val, pos = self.pq.flat_range_lists_device(q, self.rows, self.list_off, self.probes(q, nprobe), threshold, ip=ip,
+                                                         allow=self._allow_words(allow))
+        rows = self._original_rows(pos)
+        if sort:
+            val, rows = sort_ranges(lims, val, rows, ip)
+        return lims, val, rows
+
+    def within(self, queries, radius, nprobe, allow=None, sort=False):
+        """EVERY row of the nprobe nearest lists whose exact squared distance to the query is <= radius (a scalar or one
+        value per query) -> (lims, dist, idx), CSR over the queries; idx are original row numbers and the rows of a query
+        come list by list in probe order, inside a list in its stored order (Pq.flat_range_lists_device).  The values
+        are FlatMatrix.within()'s: with nprobe = n_lists the result is the same set.  sort=True: ascending in distance,
+        ties in that order.  allow: as for nearest()."""
+        return self._range(False, queries, radius, nprobe, allow, sort)
+
+    def similar_above(self, queries, threshold, nprobe, use_norms=True, allow=None, sort=False):
+        """Every row of the nprobe nearest lists whose exact inner product with the query is >= threshold -> (lims,
+        score, idx), as within(); sort=True: descending in score.  use_norms is accepted and ignored, as in
+        most_similar()."""
+        return self._range(True, queries, threshold, nprobe, allow, sort)
+
     def embeddings(self, rows):
         """the stored rows of the original row numbers `rows` as float32 [len(rows), d]"""
         import torch
@@ -1415,7 +1485,8 @@ class MatrixGroup:
 
     A FlatMatrix part (rows that are not encoded: a fresh delta) contributes its exact values to a top-k search and to
     the shortlist of refine=R, and re-ranks its members against its own rows, which gives the same numbers; a range
-    search of a group with a flat part raises PanicError.  A PartitionedFlatMatrix part (a delta grown large enough to be
+    search of a group with a flat part raises PanicError (the flat classes have within() / similar_above() of their own;
+    joining them in here is a follow-up, because it changes what a group does today).  A PartitionedFlatMatrix part (a delta grown large enough to be
     worth lists) does the same over the lists that `nprobe` names.
 
     add, compact, remove, the *_among searches, persistence and any folding of a small part into a large one stay with
@@ -1566,6 +1637,8 @@ class MatrixGroup:
         return self._topk(True, queries, k, nprobe, use_norms, refine, allow)
 
     def _range(self, ip, queries, threshold, nprobe, use_norms, allow, sort):
+        """A group with a flat part still raises: FlatMatrix / PartitionedFlatMatrix have within() / similar_above() now,
+        but serving them here changes what the group does today and is left to a follow-up."""
         import torch
         if any(isinstance(part, (FlatMatrix, PartitionedFlatMatrix)) for part in self.parts):
             raise PanicError("a range search over the raw vectors of a FlatMatrix part is not served")

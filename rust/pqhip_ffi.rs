@@ -184,6 +184,21 @@ extern "C" {
         vec_row_stride: i64, d_list_off: *const i64, n_lists: i64, d_probes: *const i64, n_probe: i32,
         probes_row_stride: i64, d_allow: *const u32, metric: i32, k: i32, d_val: *mut f32, val_row_stride: i64,
         d_idx: *mut i64, idx_row_stride: i64, stream: *mut c_void) -> i32;
+    // exact range search over resident f32 / f16 vectors: every row with value <= threshold[q] (metric 0) resp. >=
+    // threshold[q] (metric 1) by the value of pqhip_rerank_f32_dev, as CSR (d_lims [n_queries + 1]; d_val / d_idx of
+    // `capacity` entries, capacity 0 = count only, the capacity protocol of the ADC range calls), rows ascending; option
+    // "flat_range_wgs" forces the grid, on which the result does not depend
+    pub fn pqhip_flat_range_f32_dev(cb: *mut pqhip_codebook, device_slot: i32, d_queries: *const f32, n_queries: i64,
+        q_row_stride: i64, d_vectors: *const c_void, vec_bytes: i32, n_rows: i64, d: i64, vec_row_stride: i64,
+        d_allow: *const u32, metric: i32, d_threshold: *const f32, d_lims: *mut i64, d_val: *mut f32, d_idx: *mut i64,
+        capacity: i64, stream: *mut c_void) -> i32;
+    // the call above restricted, per query, to the rows of the probed lists, in the order of their concatenation (d_idx
+    // holds positions; d_allow in POSITION order or NULL); option "flat_range_wgs_per_query" forces the workgroups per query
+    pub fn pqhip_flat_range_lists_f32_dev(cb: *mut pqhip_codebook, device_slot: i32, d_queries: *const f32,
+        n_queries: i64, q_row_stride: i64, d_vectors: *const c_void, vec_bytes: i32, n_rows: i64, d: i64,
+        vec_row_stride: i64, d_allow: *const u32, d_list_off: *const i64, n_lists: i64, d_probes: *const i64,
+        n_probe: i32, probes_row_stride: i64, metric: i32, d_threshold: *const f32, d_lims: *mut i64, d_val: *mut f32,
+        d_idx: *mut i64, capacity: i64, stream: *mut c_void) -> i32;
     // merge of two list-ordered row arrays: list l of d_out = list l of d_a, then list l of d_b (rows of row_bytes bytes,
     // any alignment); the offsets are validated on the device (invalid: nothing written, the stream's range flag raised);
     // d_off_out NULL or [n_lists + 1]; option "lists_merge_wgs" forces the grid
