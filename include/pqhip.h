@@ -793,6 +793,72 @@ int32_t pqhip_flat_range_lists_f32_dev(pqhip_codebook *cb, int32_t device_slot,
                                        int64_t capacity, void *stream);
 
 /*
+ * Exact search among given rows: the exact top-k (pqhip_flat_among_f32_dev) and the exact range result
+ * (pqhip_flat_range_among_f32_dev) of every query over the rows that a list of candidate ids names, by the true squared
+ * distance or inner product to resident f32 / f16 vectors -- "rank exactly these rows" and "which of these rows lie
+ * within the radius" with true values: the (lims, idx) of a range search over codes as they are, a tenant's rows, a
+ * graph's neighbour lists, a shortlist of any length from another index.  Every clause is that of an existing call, taken
+ * over unchanged.  d_vectors, vec_bytes, d_queries, d and cb are those of pqhip_flat_search_f32_dev (f32 or IEEE f16
+ * converted exactly, d <= 16384; the quantizer of cb is not read).
+ * Candidates: exactly those of pqhip_adc_among_f32_dev.  The places of query q are d_ids[lims[q] .. lims[q + 1]), with
+ * d_lims == NULL every query takes d_ids[0 .. n_ids); C_q is the set of their entries that lie in [0, n_rows).  -1 is
+ * padding and is skipped; any other value outside the range is skipped and raises the stream's range flag
+ * (pqhip_check_codes_dev -> PQHIP_ECODE_RANGE); no address is formed for it.  An id named twice is a caller error and may
+ * be returned twice (the wording of pqhip_rerank_f32_dev).  Ids need not be sorted.  d_lims is device memory and is not
+ * trusted: both ends are clamped to [0, n_ids] and an inverted range is empty; both cases raise the flag.  No byte outside
+ * d_ids[0 .. n_ids) is read.  A row that is not named is not loaded (a NaN in it changes nothing); no byte outside
+ * [d_vectors, last row + d elements) is read.
+ * Value of a row: exactly that of pqhip_rerank_f32_dev, operation for operation -- the 64 lane chains from +0, then the
+ * fixed tree, no contraction, f16 converted exactly.  It is therefore, bit for bit, the value the flat searches return
+ * for that row.
+ * Top-k call.  Row q of d_val / d_idx receives the first min(k, |C_q|) members of C_q ordered by (key(value), row id),
+ * resp. (key(-score), row id) for the inner product; key, the canonical NaN, zero as +0 and the padding (-1 with +Inf /
+ * -Inf) are exactly those of pqhip_flat_search_f32_dev.  The order is strict, so the result depends on neither the order
+ * of the ids, nor the grid, nor the chunking.  Hence for distinct in-range ids the result equals, bit for bit, that of
+ * pqhip_flat_search_f32_dev with the mask of C_q, run for that query alone, and with at most 1,024 ids per query that of
+ * pqhip_rerank_f32_dev on the same candidates.
+ * Range call.  The predicate is exactly that of pqhip_flat_range_f32_dev: metric 0: v <= thr[q] as an IEEE comparison,
+ * metric 1: v >= thr[q]; a NaN on either side never qualifies.  The output of query q is the SUB-SEQUENCE OF ITS PLACES
+ * THAT QUALIFY, IN THE ORDER IN WHICH THEY WERE NAMED: d_idx holds the id as named, d_val its value bit for bit, and a
+ * row named twice is returned twice.  The capacity protocol is exactly that of the other range calls: d_out_lims
+ * [n_queries + 1] always holds the true counts, only slots < capacity are written and nothing past them is touched,
+ * capacity == 0 is a count call (d_val / d_idx may be NULL).  The result is a function of the inputs alone.  Hence with
+ * d_ids = 0 .. n_rows - 1 shared it equals pqhip_flat_range_f32_dev without a mask; with ascending distinct ids the masked
+ * call with the mask of C_q; and fed the (lims, idx) of any range call at a threshold that admits a superset it returns
+ * the exact range result restricted to that superset.
+ * Status codes, in the precedence EINVAL, ENODEV, EUNSUPPORTED, null pointers, ESHAPE -- the union of the checks of
+ * pqhip_flat_search_lists_f32_dev resp. pqhip_flat_range_lists_f32_dev and of pqhip_adc_among_f32_dev:
+ *   null cb, d < 1, n_queries < 0, n_rows < 0, n_ids < 0, metric not 0 / 1 (top-k: k < 1; range: capacity < 0):
+ *   PQHIP_EINVAL;  then PQHIP_ENODEV;
+ *   vec_bytes not 2 / 4, d > 16384, n_rows > 2^32 - 2 (top-k: k > 1024): PQHIP_EUNSUPPORTED;
+ *   with n_queries > 0, a null d_queries, d_ids == NULL with n_ids > 0, a null d_vectors with n_rows > 0 (top-k: a null
+ *   output; range: a null d_out_lims or d_threshold, null outputs with capacity > 0): PQHIP_EINVAL;
+ *   q_row_stride < d, vec_row_stride < d (n_rows > 0) (top-k: an output stride below k): PQHIP_ESHAPE.
+ * n_queries == 0 launches nothing and writes nothing.  n_ids == 0 or n_rows == 0 writes the padding resp. all-zero lims;
+ * with n_rows == 0 every id other than -1 raises the flag.  Anything not served is PQHIP_EUNSUPPORTED, never another path.
+ * Both calls are asynchronous on `stream`.  One query per workgroup set, also for a shared list; the workgroups that share
+ * a query are chosen from the mean number of ids per query (n_ids / n_queries, n_ids with d_lims == NULL) and the row
+ * bytes by the rule of pqhip_flat_search_lists_f32_dev (options "flat_among_wgs_per_query",
+ * "flat_range_among_wgs_per_query" force the number).  The range call makes two passes with a prefix scan between them:
+ * the count pass leaves a bitmap of the hits in scratch and the fill pass loads only the rows that hit; a count call
+ * launches no fill.  Scratch comes from the codebook, the caller allocates only the outputs; queries are processed in
+ * chunks that keep partial lists resp. counts and bitmaps within 512 MB.
+ */
+int32_t pqhip_flat_among_f32_dev(pqhip_codebook *cb, int32_t device_slot,
+                                 const float *d_queries, int64_t n_queries, int64_t q_row_stride,
+                                 const void *d_vectors, int32_t vec_bytes, int64_t n_rows, int64_t d, int64_t vec_row_stride,
+                                 const int64_t *d_lims /* [n_queries + 1] or NULL */, const int64_t *d_ids, int64_t n_ids,
+                                 int32_t metric /* 0 = squared L2, 1 = inner product */, int32_t k,
+                                 float *d_val, int64_t val_row_stride, int64_t *d_idx, int64_t idx_row_stride, void *stream);
+int32_t pqhip_flat_range_among_f32_dev(pqhip_codebook *cb, int32_t device_slot,
+                                       const float *d_queries, int64_t n_queries, int64_t q_row_stride,
+                                       const void *d_vectors, int32_t vec_bytes, int64_t n_rows, int64_t d, int64_t vec_row_stride,
+                                       const int64_t *d_lims /* [n_queries + 1] or NULL */, const int64_t *d_ids, int64_t n_ids,
+                                       int32_t metric /* 0 = squared L2, 1 = inner product */,
+                                       const float *d_threshold /* [n_queries] */, int64_t *d_out_lims, float *d_val,
+                                       int64_t *d_idx, int64_t capacity, void *stream);
+
+/*
  * Merge of two list-ordered row arrays: the primitive under growing a partitioned matrix (rows added to an index, two
  * indexes over the same lists joined).  d_a is [n_a] rows of row_bytes bytes in list order under d_off_a [n_lists + 1]
  * (list l = rows off_a[l] .. off_a[l + 1] - 1), d_b likewise [n_b] rows under d_off_b; d_out is [n_a + n_b] rows.  For
@@ -1136,6 +1202,9 @@ int32_t pqhip_set_rotation_variant(int32_t variant);
  *                          stay a multiple of 1,024; the result does not depend on it)
  *   "flat_range_wgs_per_query"  workgroups that share one query of pqhip_flat_range_lists_f32_dev (0 = chosen from the
  *                          expected probed bytes; at most 4096; the result does not depend on it)
+ *   "flat_among_wgs_per_query"  workgroups that share one query of pqhip_flat_among_f32_dev (0 = chosen from the mean
+ *                          number of ids per query and the row bytes; at most 4096; the result does not depend on it)
+ *   "flat_range_among_wgs_per_query"  the same for pqhip_flat_range_among_f32_dev
  *   "cross_product_exact" 0 = X^T.R of the OPQ training step / pqhip_at_dot_b_f32_dev as a plain split-K product:
  *                          within 1e-5 relative of the exact rule-2 result, no per-block partial matrices (default 1)
  *   "cross_product_group_bytes"  workspace of partial matrices per launch group (0 = 4 GiB)

@@ -5,7 +5,7 @@
 // first use, rerank_elem / rerank_step, flat_reduce_tile: kernels_flat_search.hip.h; the plan, slices and segment walk
 // of the list searches: kernels_adc.hip.h) with the consumer of the ADC range searches (range_emit, range_uniform,
 // k_adc_range_scan and the count / scan / fill sequence of kernels_adc_range.hip.h).
-// (Included from exactly one translation unit, pqhip_flat_range.hip.)
+// (Instantiated by pqhip_flat_range.hip; kernels_flat_among.hip.h takes flat_range_tile and flat_range_mask16 from here.)
 //
 // Units and order.  The producer unit is a WAVE with a contiguous sub-range of its workgroup's rows (a multiple of 64, so
 // mask words and tiles never straddle units) -- not the interleaved tiles of the top-k kernels.  Units ascend with rows

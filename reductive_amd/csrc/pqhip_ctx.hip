@@ -364,7 +364,9 @@ int32_t pqhip_ctx_set_option(pqhip_ctx* ctx, const char* name, int64_t value)
         {"adc_search_wgs", &o.adc_search_wgs},         {"adc_among_wgs_per_query", &o.adc_among_wgs_per_query},
         {"rows_compact_wgs", &o.rows_compact_wgs},     {"topk_merge_wgs", &o.topk_merge_wgs},
         {"flat_search_wgs", &o.flat_search_wgs},       {"flat_lists_wgs_per_query", &o.flat_lists_wgs_per_query},
-        {"flat_range_wgs", &o.flat_range_wgs},         {"flat_range_wgs_per_query", &o.flat_range_wgs_per_query}};
+        {"flat_range_wgs", &o.flat_range_wgs},         {"flat_range_wgs_per_query", &o.flat_range_wgs_per_query},
+        {"flat_among_wgs_per_query", &o.flat_among_wgs_per_query},
+        {"flat_range_among_wgs_per_query", &o.flat_range_among_wgs_per_query}};
     for (auto& t : table)
         if (std::strcmp(t.n, name) == 0) { t.v->store(value, std::memory_order_relaxed); return PQHIP_OK; }
     return PQHIP_EINVAL;

@@ -109,6 +109,8 @@ struct Options {
     std::atomic<int64_t> flat_lists_wgs_per_query{0};   // exact search in probed lists: workgroups per query (0: chosen from the probed bytes)
     std::atomic<int64_t> flat_range_wgs{0};         // exact range search over resident vectors: producer workgroups (0: one per CU)
     std::atomic<int64_t> flat_range_wgs_per_query{0};   // exact range search in probed lists: workgroups per query (0: chosen from the probed bytes)
+    std::atomic<int64_t> flat_among_wgs_per_query{0};   // exact search among given rows: workgroups per query (0: chosen from the named bytes)
+    std::atomic<int64_t> flat_range_among_wgs_per_query{0};   // exact range search among given rows: workgroups per query (0: as above)
 };
 
 struct Diag {

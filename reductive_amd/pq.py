@@ -1481,6 +1481,103 @@ class Pq:
         synchronises and reports a list id or an offset out of range (they are skipped resp. clamped either way)."""
         return self._flat_range(queries, vectors, threshold, ip, allow, capacity, stream, check, lists=(list_off, probes))
 
+    # ---- exact search among given rows: top-k and range over per-query candidate id lists, by true distance ---------------
+    def _flat_among_args(self, queries, vectors, ids, lims):
+        """What both exact candidate calls check and marshal: queries and vectors as for flat_search_device, ids and
+        lims as for adc_among_device -> (single, q2, vectors, nq, d, N, n_ids)."""
+        import torch
+        for t, what in ((queries, "queries"), (vectors, "vectors")):
+            if not hasattr(t, "is_cuda"):
+                raise PanicError("%s must be a torch tensor" % what)
+        if queries.dtype != torch.float32 or queries.dim() not in (1, 2):
+            raise PanicError("queries must be float32 [d] or [nq, d]")
+        if vectors.dtype not in (torch.float32, torch.float16) or vectors.dim() != 2:
+            raise PanicError("vectors must be float32 or float16 [N, d]")
+        single = queries.dim() == 1
+        q2 = queries[None] if single else queries
+        nq, d = q2.shape
+        N = vectors.shape[0]
+        if d < 1 or vectors.shape[1] != d:
+            raise PanicError("Query and vector length mismatch")
+        if d > 16384:
+            raise PanicError("vectors of at most 16384 elements are searched, got %d" % d)
+        if N > (1 << 32) - 2:
+            raise PanicError("at most 2^32 - 2 rows are searched among candidates")
+
+        def vector(t, text):
+            if not (hasattr(t, "is_cuda") and t.dtype == torch.int64 and t.dim() == 1 and t.is_contiguous()):
+                raise PanicError(text)
+
+        vector(ids, "candidate ids must be one contiguous int64 vector, shared or cut per query by lims")
+        if lims is not None:
+            vector(lims, "lims must be a contiguous int64 vector")
+            if lims.shape[0] != nq + 1:
+                raise PanicError("lims must hold one offset per query and the end (%d)" % (nq + 1))
+        given = [t for t in (queries, vectors, ids, lims) if t is not None]
+        if not all(t.is_cuda and t.device == vectors.device for t in given):
+            raise PanicError("the exact candidate search expects CUDA tensors on one device")
+        if q2.stride(1) != 1:
+            q2 = q2.contiguous()
+        if N > 0 and vectors.stride(1) != 1:
+            vectors = vectors.contiguous()
+        return single, q2, vectors, nq, d, N, ids.shape[0]
+
+    def flat_among_device(self, queries, vectors, ids, k, lims=None, ip=False, stream=None, check=False):
+        """flat_search_device among given rows: queries CUDA float32 [d] or [nq, d]; vectors CUDA float32 or float16
+        [N, d]; ids CUDA int64 [n_ids] names the candidates -- of every query (lims None), or ids[lims[q] : lims[q + 1]]
+        of query q (lims CUDA int64 [nq + 1], as a range search returns it) -> (value, idx), CUDA float32 and int64
+        [nq, k] ([k] for one query): the first k candidates by (exact squared distance, row), ip=True by (descending inner
+        product, row); past the last candidate index -1 and +Inf (ip: -Inf).  Any number of ids per query.  -1 is
+        padding; any other id outside [0, N) is skipped and, like a bad lims, raises the range flag (check=True); an id
+        named twice may come back twice.  A row that is not named is not read.  For distinct ids the result is
+        flat_search_device's with the mask of the candidates, bit for bit, and rerank_device's where that call takes the
+        candidates (pqhip_flat_among_f32_dev).  The quantizer of self is not used."""
+        import torch
+        single, q2, vectors, nq, d, N, n_ids = self._flat_among_args(queries, vectors, ids, lims)
+        k = int(k)
+        if not 1 <= k <= 1024:
+            raise PanicError("k must be between 1 and 1024, was %d" % k)
+        val = torch.empty((nq, k), dtype=torch.float32, device=vectors.device)
+        idx = torch.empty((nq, k), dtype=torch.int64, device=vectors.device)
+        cb, slot, sp = _marshal.launch(self, vectors, stream)
+        _marshal.run("pqhip_flat_among_f32_dev", cb, slot, q2.data_ptr(), nq, row_stride(q2, nq, d),
+                     ptr_or_none(vectors, N), vectors.element_size(), N, d, row_stride(vectors, N, d),
+                     ptr_or_none(lims), ptr_or_none(ids, n_ids), n_ids, 1 if ip else 0, k, val.data_ptr(), k, idx.data_ptr(), k, sp)
+        if check:
+            _marshal.check_range(cb, slot, sp)
+        return (val[0], idx[0]) if single else (val, idx)
+
+    def flat_range_among_device(self, queries, vectors, ids, threshold, lims=None, ip=False, stream=None, check=False):
+        """flat_range_device among given rows (queries, vectors, ids and lims as for flat_among_device; threshold a scalar
+        or one value per query) -> (lims, val, idx): CSR, the output lims CUDA int64 [nq + 1] ([2] for one query); the
+        entries of query q are those of its candidates whose exact squared distance is <= threshold (ip=True: whose
+        inner product is >= threshold), IN THE ORDER IN WHICH THEY WERE NAMED, val the value flat_search_device returns
+        for the row, bit for bit, idx the id as named; a row named twice is returned twice
+        (pqhip_flat_range_among_f32_dev).  A NaN value never qualifies.  Fed the (lims, idx) of a range search over
+        codes at a larger radius it returns the exact range result among those rows.  The result is allocated to its
+        size: one count call, one read of the total -- the one synchronisation -- then the call that fills.  -1 is
+        padding; any other id outside [0, N) is skipped and, like a bad lims, raises the range flag (check=True)."""
+        import torch
+        _, q2, vectors, nq, d, N, n_ids = self._flat_among_args(queries, vectors, ids, lims)
+        dev = vectors.device
+        thr = _marshal.threshold_arg(threshold, nq, dev)
+        own_stream = stream is None
+        cb, slot, sp = _marshal.launch(self, vectors, stream)
+        head = (cb, slot, q2.data_ptr(), nq, row_stride(q2, nq, d), ptr_or_none(vectors, N), vectors.element_size(), N, d,
+                row_stride(vectors, N, d), ptr_or_none(lims), ptr_or_none(ids, n_ids), n_ids, 1 if ip else 0, thr.data_ptr())
+        out_lims = torch.empty(nq + 1, dtype=torch.int64, device=dev)
+        _marshal.run("pqhip_flat_range_among_f32_dev", *head, out_lims.data_ptr(), None, None, 0, sp)
+        if not own_stream:
+            torch.cuda.ExternalStream(stream, device=dev).synchronize()
+        total = int(out_lims[-1])
+        val = torch.empty(total, dtype=torch.float32, device=dev)
+        idx = torch.empty(total, dtype=torch.int64, device=dev)
+        if total > 0:
+            _marshal.run("pqhip_flat_range_among_f32_dev", *head, out_lims.data_ptr(), val.data_ptr(), idx.data_ptr(), total, sp)
+        if check:
+            _marshal.check_range(cb, slot, sp)
+        return out_lims, val, idx
+
     # ---- growing a partitioned matrix: merge of two list-ordered arrays ------------------------------------------------
     def merge_lists_device(self, list_off_a, a, list_off_b, b, out=None, stream=None, check=False):
         """a, b: CUDA tensors of one dtype, [n_a] / [n_b] or [n_a, c] / [n_b, c], contiguous, their rows in list order

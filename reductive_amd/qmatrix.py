@@ -308,6 +308,57 @@ class _Refine:
         exact_within(); sort=True: descending in score."""
         return self._exact_range(True, queries, threshold, allow, sort)
 
+    def _exact_among(self, ip, queries, rows, k):
+        import torch
+        if self.vectors is None:
+            raise PanicError("refine needs the original vectors: call attach_vectors first")
+        lims, rows = _Among._among_rows(self, rows)
+        q = _on_device(queries, self.vectors.device, torch.float32, np.float32)
+        return self.pq.flat_among_device(q, self.vectors, rows, k, lims=lims, ip=ip)
+
+    def exact_nearest_among(self, queries, rows, k):
+        """exact_nearest() among the rows that `rows` names and no others -- what nearest_among() takes: a vector of
+        ORIGINAL row numbers shared by all queries, or the pair (lims, rows) that within() / similar_above() return ->
+        (dist, idx) [k] or [nq, k]: the k nearest of them by their exact squared distance to the attached vectors, in
+        original row numbers on every class, ties to the smaller row, index -1 and +Inf past the last
+        (Pq.flat_among_device).  Any number of rows per query: this is the re-ranking of a shortlist longer than the 1,024
+        candidates of refine=, e.g. m.exact_nearest_among(q, m.within(q, r)[::2], k).  -1 is padding, any other number
+        outside [0, N) is skipped; a row named twice may come back twice.  For distinct rows the result is
+        exact_nearest(queries, k, allow=<flags of the rows>) at the cost of the named rows alone."""
+        return self._exact_among(False, queries, rows, k)
+
+    def exact_most_similar_among(self, queries, rows, k):
+        """exact_most_similar() among the rows that `rows` names -> (score, idx), largest first, as
+        exact_nearest_among()."""
+        return self._exact_among(True, queries, rows, k)
+
+    def _exact_range_among(self, ip, queries, rows, threshold, sort):
+        import torch
+        if self.vectors is None:
+            raise PanicError("refine needs the original vectors: call attach_vectors first")
+        lims, rows = _Among._among_rows(self, rows)
+        q = _on_device(queries, self.vectors.device, torch.float32, np.float32)
+        lims, val, rows = self.pq.flat_range_among_device(q, self.vectors, rows, threshold, lims=lims, ip=ip)
+        if sort:
+            val, rows = sort_ranges(lims, val, rows, ip)
+        return lims, val, rows
+
+    def exact_within_among(self, queries, rows, radius, sort=False):
+        """exact_within() among the rows that `rows` names (as for exact_nearest_among) -> (lims, dist, idx): of every
+        query's rows those whose exact squared distance is <= radius (a scalar or one value per query), in the order in
+        which they were named, in original row numbers on every class (Pq.flat_range_among_device); sort=True: ascending
+        in distance.  It verifies a radius query over the codes against the stored vectors at the cost of the rows
+        that query returned:
+            m.exact_within_among(q, m.within(q, r + slack)[::2], r)
+        is exact_within(q, r) restricted to the rows within(q, r + slack) found.  A row named twice is returned twice."""
+        return self._exact_range_among(False, queries, rows, radius, sort)
+
+    def exact_similar_above_among(self, queries, rows, threshold, sort=False):
+        """exact_similar_above() among the rows that `rows` names -> (lims, score, idx), as exact_within_among():
+            m.exact_similar_above_among(q, m.similar_above(q, t - slack)[::2], t)
+        sort=True: descending in score."""
+        return self._exact_range_among(True, queries, rows, threshold, sort)
+
 
 class RowFilter:
     """The set of rows a search may return, packed for one matrix: `words` is the device mask of the searches' `allow=`
@@ -1256,6 +1307,29 @@ class FlatMatrix(_Refine, _Filter, _Compact):
         use_norms is accepted and ignored, as in most_similar()."""
         return self._range(True, queries, threshold, allow, sort)
 
+    def nearest_among(self, queries, rows, k):
+        """nearest() among the rows that `rows` names and no others: a vector of row numbers shared by all queries, or the
+        pair (lims, rows) -- the rows of query q are rows[lims[q]:lims[q + 1]], what within() returns -> (dist, idx) [k]
+        or [nq, k], ties to the smaller row, index -1 and +Inf past the last (Pq.flat_among_device).  -1 is padding, any
+        other number outside [0, N) is skipped; a row named twice may come back twice.  For distinct rows the result is
+        nearest(queries, k, allow=<flags of the rows>) at the cost of the named rows alone."""
+        return self._exact_among(False, queries, rows, k)
+
+    def most_similar_among(self, queries, rows, k):
+        """most_similar() among the rows that `rows` names (as for nearest_among) -> (score, idx), largest first."""
+        return self._exact_among(True, queries, rows, k)
+
+    def within_among(self, queries, rows, radius, sort=False):
+        """within() among the rows that `rows` names (as for nearest_among) -> (lims, dist, idx): of every query's rows
+        those whose exact squared distance is <= radius, in the order in which they were named
+        (Pq.flat_range_among_device); sort=True: ascending in distance.  A row named twice is returned twice."""
+        return self._exact_range_among(False, queries, rows, radius, sort)
+
+    def similar_above_among(self, queries, rows, threshold, sort=False):
+        """similar_above() among the rows that `rows` names -> (lims, score, idx), as within_among(); sort=True:
+        descending in score."""
+        return self._exact_range_among(True, queries, rows, threshold, sort)
+
     def embeddings(self, rows):
         """the stored rows `rows` as float32 [len(rows), d]"""
         import torch
@@ -1399,6 +1473,50 @@ class PartitionedFlatMatrix(_ListLayout, _Filter, _Compact):
         score, idx), as within(); sort=True: descending in score.  use_norms is accepted and ignored, as in
         most_similar()."""
         return self._range(True, queries, threshold, nprobe, allow, sort)
+
+    def _among(self, ip, queries, rows, k):
+        import torch
+        lims, rows = _Among._among_rows(self, rows)
+        q = _on_device(queries, self.rows.device, torch.float32, np.float32)
+        val, pos = self.pq.flat_among_device(q, self.rows, self._among_ids(rows), k, lims=lims, ip=ip)
+        return val, self._original_rows(pos)
+
+    def nearest_among(self, queries, rows, k):
+        """nearest() among the rows that `rows` names and no others, whatever their lists: a vector of ORIGINAL row
+        numbers shared by all queries, or the pair (lims, rows) that within() returns -> (dist, idx) [k] or [nq, k] in
+        original row numbers, index -1 and +Inf past the last (Pq.flat_among_device).  The rows are mapped to positions
+        and back; like the quantized partitioned classes this one breaks ties by POSITION in list order, not by row
+        number.  -1 is padding, any other number outside [0, N) is skipped; a row named twice may come back twice.
+        For distinct rows the result is nearest(queries, k, n_lists, allow=<flags of the rows>) at the cost of the named
+        rows alone."""
+        return self._among(False, queries, rows, k)
+
+    def most_similar_among(self, queries, rows, k):
+        """most_similar() among the rows that `rows` names (as for nearest_among, ties by position) -> (score, idx),
+        largest first."""
+        return self._among(True, queries, rows, k)
+
+    def _range_among(self, ip, queries, rows, threshold, sort):
+        import torch
+        lims, rows = _Among._among_rows(self, rows)
+        q = _on_device(queries, self.rows.device, torch.float32, np.float32)
+        lims, val, pos = self.pq.flat_range_among_device(q, self.rows, self._among_ids(rows), threshold, lims=lims, ip=ip)
+        rows = self._original_rows(pos)
+        if sort:
+            val, rows = sort_ranges(lims, val, rows, ip)
+        return lims, val, rows
+
+    def within_among(self, queries, rows, radius, sort=False):
+        """within() among the rows that `rows` names (as for nearest_among), whatever their lists -> (lims, dist, idx): of
+        every query's rows those whose exact squared distance is <= radius, in the order in which they were named, in
+        original row numbers (Pq.flat_range_among_device); sort=True: ascending in distance, ties in that order.  A row
+        named twice is returned twice."""
+        return self._range_among(False, queries, rows, radius, sort)
+
+    def similar_above_among(self, queries, rows, threshold, sort=False):
+        """similar_above() among the rows that `rows` names -> (lims, score, idx), as within_among(); sort=True:
+        descending in score."""
+        return self._range_among(True, queries, rows, threshold, sort)
 
     def embeddings(self, rows):
         """the stored rows of the original row numbers `rows` as float32 [len(rows), d]"""

@@ -199,6 +199,21 @@ extern "C" {
         vec_row_stride: i64, d_allow: *const u32, d_list_off: *const i64, n_lists: i64, d_probes: *const i64,
         n_probe: i32, probes_row_stride: i64, metric: i32, d_threshold: *const f32, d_lims: *mut i64, d_val: *mut f32,
         d_idx: *mut i64, capacity: i64, stream: *mut c_void) -> i32;
+    // exact search among given rows: the top-k of the rows that d_ids[lims[q] .. lims[q + 1]) names (d_lims NULL: d_ids
+    // [0 .. n_ids) for every query) by the value of pqhip_rerank_f32_dev, any number of ids per query; -1 pads, other ids
+    // outside [0, n_rows) and bad lims are skipped resp. clamped and raise the range flag; for distinct ids the result is
+    // pqhip_flat_search_f32_dev's with the mask of the candidates; option "flat_among_wgs_per_query" forces the grid
+    pub fn pqhip_flat_among_f32_dev(cb: *mut pqhip_codebook, device_slot: i32, d_queries: *const f32, n_queries: i64,
+        q_row_stride: i64, d_vectors: *const c_void, vec_bytes: i32, n_rows: i64, d: i64, vec_row_stride: i64,
+        d_lims: *const i64, d_ids: *const i64, n_ids: i64, metric: i32, k: i32, d_val: *mut f32, val_row_stride: i64,
+        d_idx: *mut i64, idx_row_stride: i64, stream: *mut c_void) -> i32;
+    // the range form: of every query's places those with value <= threshold[q] (metric 0) resp. >= threshold[q] (metric
+    // 1), in the order in which they were named, as CSR with the capacity protocol of the other range calls (d_out_lims
+    // [n_queries + 1]; capacity 0 = count only); option "flat_range_among_wgs_per_query" forces the grid
+    pub fn pqhip_flat_range_among_f32_dev(cb: *mut pqhip_codebook, device_slot: i32, d_queries: *const f32,
+        n_queries: i64, q_row_stride: i64, d_vectors: *const c_void, vec_bytes: i32, n_rows: i64, d: i64,
+        vec_row_stride: i64, d_lims: *const i64, d_ids: *const i64, n_ids: i64, metric: i32, d_threshold: *const f32,
+        d_out_lims: *mut i64, d_val: *mut f32, d_idx: *mut i64, capacity: i64, stream: *mut c_void) -> i32;
     // merge of two list-ordered row arrays: list l of d_out = list l of d_a, then list l of d_b (rows of row_bytes bytes,
     // any alignment); the offsets are validated on the device (invalid: nothing written, the stream's range flag raised);
     // d_off_out NULL or [n_lists + 1]; option "lists_merge_wgs" forces the grid
