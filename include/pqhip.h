@@ -859,6 +859,49 @@ int32_t pqhip_flat_range_among_f32_dev(pqhip_codebook *cb, int32_t device_slot,
                                        int64_t *d_idx, int64_t capacity, void *stream);
 
 /*
+ * Conservative range screen over resident vectors on the matrix cores: for a BATCH of queries, per query a superset of
+ * what pqhip_flat_range_f32_dev returns at the same thresholds, as ascending row ids (CSR, no values).  It is the first
+ * stage of the exact searches for query batches: screen, then resolve the candidates exactly with
+ * pqhip_flat_range_among_f32_dev / pqhip_flat_among_f32_dev, whose results are those of the exhaustive calls bit for bit.
+ * One stream of the matrix serves up to 64 queries.  Arguments: those of pqhip_flat_range_f32_dev without d_val, and
+ * x_exp: every row element is multiplied by 2^x_exp (exact) before it is rounded to f16 -- choose it so that the largest
+ * |element| of the matrix lands below 2^15 (and well above 2^-14).  The quantizer of cb is not read.
+ * Contract.  Let R_q be the ids pqhip_flat_range_f32_dev returns for query q at d_threshold[q] (same vectors, mask and
+ * metric; values as pqhip_rerank_f32_dev defines them), O_q the ids of this call, A the allowed rows.
+ *   Sound, unconditionally: R_q is a subset of O_q, O_q of A.  A row is left out only when the kernel has proved that its
+ *   exact value misses the threshold; whatever the proof does not cover is returned -- a non-finite element in the row or
+ *   the query, a scaled row element that overflows f16, a NaN or an infinity out of the matrix instruction, a NaN
+ *   threshold, |x_exp| > 40, a query whose largest |element| is outside [2^-40, 2^40) and not zero.
+ *   Tight on regular rows (finite elements, every scaled element below 2^15, ||x||^2 within f32, a finite query that the
+ *   proof covers, d <= 2048): a regular row is returned only if its exact value v satisfies v <= thr + slack (metric 0)
+ *   resp. v >= thr - slack / 2 (metric 1), slack = 2^-8 (||x||^2 + ||q||^2) + 2^-12 2^-x_exp ||q||_1 + 2^-99.  The
+ *   bound behind it is derived in DESIGN.md section 5c; its constants are kFlatScreenRel, kFlatScreenAbsX and
+ *   kFlatScreenAbs of kernels_flat_screen.hip.h.
+ * Output, order and capacity: d_lims [n_queries + 1] int64 and d_idx (int64) of `capacity` entries; the ids of a query
+ * ascend; the capacity protocol is exactly that of the range calls (true counts always, only slots < capacity written,
+ * capacity == 0 a count call with d_idx NULL).  The count pass leaves the hit bitmap in the codebook's scratch (4 bytes
+ * per tile of 32 rows and query slot of a pass); the fill pass turns bitmaps into ids and does not read the matrix.
+ * A function of the inputs alone: every (row, query) product sum is one chain of v_mfma_f32_32x32x16_f16 in a fixed k
+ * order; the result depends neither on the grid (option "flat_screen_wgs") nor on how queries are grouped into passes.
+ * Memory: no byte outside [d_vectors, last row + d elements) is read; rows may start at any multiple of the element
+ * size (16-, 8- and 4-byte loads are used only when base and row stride are multiples of that size); a disallowed row is not loaded.
+ * vec_bytes 2: the f16 rows are used as they are, x_exp is still applied.
+ * Status codes, in the precedence of the range call: null cb, d < 1, n_queries < 0, n_rows < 0, capacity < 0, metric not
+ * 0 / 1: PQHIP_EINVAL; vec_bytes not 2 / 4, d > 2048: PQHIP_EUNSUPPORTED; with n_queries > 0 a null d_lims, d_threshold or
+ * d_queries, a null d_idx with capacity > 0, a null d_vectors with n_rows > 0: PQHIP_EINVAL; q_row_stride < d,
+ * vec_row_stride < d (n_rows > 0): PQHIP_ESHAPE.  n_queries == 0 launches nothing; n_rows == 0 writes all-zero lims.
+ * Asynchronous on `stream`; per pass of 64 queries (32 while d > 1024): a prep kernel (the f16 query image with one
+ * power-of-two scale per query), the count pass, the prefix scan of the range calls, the fill pass (none for a count call).
+ */
+int32_t pqhip_flat_screen_f32_dev(pqhip_codebook *cb, int32_t device_slot,
+                                  const float *d_queries, int64_t n_queries, int64_t q_row_stride,
+                                  const void *d_vectors, int32_t vec_bytes, int64_t n_rows, int64_t d, int64_t vec_row_stride,
+                                  const uint32_t *d_allow /* ceil(n_rows / 32) words or NULL */,
+                                  int32_t metric /* 0 = squared L2, 1 = inner product */, int32_t x_exp,
+                                  const float *d_threshold /* [n_queries] */, int64_t *d_lims, int64_t *d_idx,
+                                  int64_t capacity, void *stream);
+
+/*
  * Merge of two list-ordered row arrays: the primitive under growing a partitioned matrix (rows added to an index, two
  * indexes over the same lists joined).  d_a is [n_a] rows of row_bytes bytes in list order under d_off_a [n_lists + 1]
  * (list l = rows off_a[l] .. off_a[l + 1] - 1), d_b likewise [n_b] rows under d_off_b; d_out is [n_a + n_b] rows.  For
@@ -1205,6 +1248,9 @@ int32_t pqhip_set_rotation_variant(int32_t variant);
  *   "flat_among_wgs_per_query"  workgroups that share one query of pqhip_flat_among_f32_dev (0 = chosen from the mean
  *                          number of ids per query and the row bytes; at most 4096; the result does not depend on it)
  *   "flat_range_among_wgs_per_query"  the same for pqhip_flat_range_among_f32_dev
+ *   "flat_screen_wgs"      producer workgroups of pqhip_flat_screen_f32_dev (0 = two per CU; at most 2048, so that the
+ *                          prefix scan of a pass of 64 queries sums at most 2^20 counts; rows per workgroup stay a
+ *                          multiple of 256; the result does not depend on it)
  *   "cross_product_exact" 0 = X^T.R of the OPQ training step / pqhip_at_dot_b_f32_dev as a plain split-K product:
  *                          within 1e-5 relative of the exact rule-2 result, no per-block partial matrices (default 1)
  *   "cross_product_group_bytes"  workspace of partial matrices per launch group (0 = 4 GiB)

@@ -110,6 +110,8 @@ def _signatures():
                                            vp, i64, vp, i64, vp]),
         "pqhip_flat_range_among_f32_dev": (i32, [vp, i32, vp, i64, i64, vp, i32, i64, i64, i64, vp, vp, i64, i32,
                                                  vp, vp, vp, vp, i64, vp]),
+        "pqhip_flat_screen_f32_dev": (i32, [vp, i32, vp, i64, i64, vp, i32, i64, i64, i64, vp, i32, i32,
+                                            vp, vp, vp, i64, vp]),
         "pqhip_lists_merge_dev": (i32, [vp, i32, vp, i64, vp, i64, i64, i64, vp, vp, vp, vp, vp]),
         "pqhip_rows_compact_dev": (i32, [vp, i32, vp, i64, i64, vp, vp, i64, vp, i64, vp, vp, vp, vp]),
         "pqhip_topk_merge_f32_dev": (i32, [vp, i32, vp, i64, i64, vp, i64, i64, i64, i64, i32, vp, i32, i32,

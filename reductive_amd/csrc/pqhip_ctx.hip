@@ -366,7 +366,8 @@ int32_t pqhip_ctx_set_option(pqhip_ctx* ctx, const char* name, int64_t value)
         {"flat_search_wgs", &o.flat_search_wgs},       {"flat_lists_wgs_per_query", &o.flat_lists_wgs_per_query},
         {"flat_range_wgs", &o.flat_range_wgs},         {"flat_range_wgs_per_query", &o.flat_range_wgs_per_query},
         {"flat_among_wgs_per_query", &o.flat_among_wgs_per_query},
-        {"flat_range_among_wgs_per_query", &o.flat_range_among_wgs_per_query}};
+        {"flat_range_among_wgs_per_query", &o.flat_range_among_wgs_per_query},
+        {"flat_screen_wgs", &o.flat_screen_wgs}};
     for (auto& t : table)
         if (std::strcmp(t.n, name) == 0) { t.v->store(value, std::memory_order_relaxed); return PQHIP_OK; }
     return PQHIP_EINVAL;

@@ -111,6 +111,7 @@ struct Options {
     std::atomic<int64_t> flat_range_wgs_per_query{0};   // exact range search in probed lists: workgroups per query (0: chosen from the probed bytes)
     std::atomic<int64_t> flat_among_wgs_per_query{0};   // exact search among given rows: workgroups per query (0: chosen from the named bytes)
     std::atomic<int64_t> flat_range_among_wgs_per_query{0};   // exact range search among given rows: workgroups per query (0: as above)
+    std::atomic<int64_t> flat_screen_wgs{0};        // range screen over resident vectors: producer workgroups (0: two per CU)
 };
 
 struct Diag {

@@ -447,6 +447,65 @@ def unpack_codes4(packed, n_subquantizers):
     return out[0] if single else out
 
 
+# ---- exact search for query batches: the pure rules of Pq.flat_search_batch_device ------------------------------------
+FLAT_SCREEN_MAX_D = 2048                 # pqhip_flat_screen_f32_dev serves d <= 2048
+FLAT_SCREEN_MAX_EXP = 40                 # |x_exp| the screen's proof covers
+FLAT_SCREEN_ELEMENT_TOP = 13             # the largest scaled |element| lands in [2^13, 2^14): a factor 2 below the 2^15 of the contract
+FLAT_BATCH_FALLBACK_FRACTION = 1.0 / 16  # candidates of a chunk beyond this share of n nq: the plain call
+FLAT_BATCH_CHUNK = 256                   # queries per screen call of the batch search
+
+
+def flat_screen_x_exp(max_abs):
+    """x_exp for a matrix whose largest |element| is max_abs: 2^x_exp max_abs in [2^13, 2^14), clamped to +-40; 0 for a
+    zero, NaN or infinite maximum (the screen is sound under any x_exp; this choice keeps it tight)."""
+    m = float(max_abs)
+    if not (m > 0.0) or m == float("inf"):
+        return 0
+    import math
+    e = FLAT_SCREEN_ELEMENT_TOP - (math.frexp(m)[1] - 1)        # frexp: m = f 2^e, f in [0.5, 1)
+    return max(-FLAT_SCREEN_MAX_EXP, min(FLAT_SCREEN_MAX_EXP, e))
+
+
+def flat_batch_sample(n, k):
+    """(S, t): the sample of the batch search is rows 0, t, 2 t, .. -- about S = 2 sqrt(n k) of them (at least 4 k, at
+    most n), which balances the sample's cost (nq S rows) against the resolve's (about nq n k / S rows)."""
+    import math
+    n, k = int(n), int(k)
+    if n <= 0:
+        return 0, 1
+    S = min(n, max(4 * k, int(math.ceil(2.0 * math.sqrt(float(n) * k)))))
+    t = max(1, n // S)
+    return (n + t - 1) // t, t
+
+
+def flat_batch_capacity(n, nq, k, S):
+    """ids allocated for one screen call of the batch search: the fallback limit -- a larger result falls back anyway,
+    so the call is never repeated."""
+    return int(FLAT_BATCH_FALLBACK_FRACTION * n * nq) + 1
+
+
+def flat_batch_falls_back(total, n, nq):
+    """a chunk of nq queries with `total` candidates takes the plain call when they exceed the stated share of n nq"""
+    return total > FLAT_BATCH_FALLBACK_FRACTION * n * nq
+
+
+def _matrix_max_abs(vectors):
+    """largest finite |element| of a CUDA matrix as a float (two reductions without a temporary and one
+    synchronisation; a matrix with NaN or infinite elements is reduced again in row chunks over its finite elements)"""
+    import torch
+    if vectors.numel() == 0:
+        return 0.0
+    lo, hi = torch.aminmax(vectors)
+    m = max(-float(lo), float(hi))
+    if m == m and m != float("inf"):
+        return m
+    m = 0.0
+    for r0 in range(0, vectors.shape[0], 1 << 18):
+        a = vectors[r0:r0 + (1 << 18)].abs()
+        m = max(m, float(torch.where(torch.isfinite(a), a, torch.zeros_like(a)).max()))
+    return m
+
+
 class Pq:
     """Product quantizer (Jegou et al., 2011) -- mirror of `reductive::pq::Pq<f32>`."""
 
@@ -1577,6 +1636,152 @@ class Pq:
         if check:
             _marshal.check_range(cb, slot, sp)
         return out_lims, val, idx
+
+    # ---- exact search for query batches: f16 matrix-core screen, exact resolve -----------------------------------------------
+    def _flat_screen_args(self, queries, vectors, allow):
+        """What the screen and its compositions check and marshal (queries, vectors and mask as for flat_range_device,
+        d <= FLAT_SCREEN_MAX_D) -> (single, q2, vectors, allow, nq, d, N)."""
+        import torch
+        for t, what in ((queries, "queries"), (vectors, "vectors")):
+            if not hasattr(t, "is_cuda"):
+                raise PanicError("%s must be a torch tensor" % what)
+        if queries.dtype != torch.float32 or queries.dim() not in (1, 2):
+            raise PanicError("queries must be float32 [d] or [nq, d]")
+        if vectors.dtype not in (torch.float32, torch.float16) or vectors.dim() != 2:
+            raise PanicError("vectors must be float32 or float16 [N, d]")
+        single = queries.dim() == 1
+        q2 = queries[None] if single else queries
+        nq, d = q2.shape
+        N = vectors.shape[0]
+        if d < 1 or vectors.shape[1] != d:
+            raise PanicError("Query and vector length mismatch")
+        if d > FLAT_SCREEN_MAX_D:
+            raise PanicError("the matrix-core screen serves vectors of at most %d elements, got %d" % (FLAT_SCREEN_MAX_D, d))
+        allow = _marshal.vector_mask_words(allow, N)
+        tensors = (queries, vectors) + (() if allow is None else (allow,))
+        if not all(t.is_cuda for t in tensors):
+            raise PanicError("queries, vectors and allow must be CUDA tensors")
+        if any(t.device != vectors.device for t in tensors):
+            raise PanicError("queries, vectors and allow must live on one device")
+        if q2.stride(1) != 1:
+            q2 = q2.contiguous()
+        if N > 0 and vectors.stride(1) != 1:
+            vectors = vectors.contiguous()
+        if allow is not None:
+            allow = _marshal.stand_in(allow, allow.shape[0], vectors.device)
+        return single, q2, vectors, allow, nq, d, N
+
+    def _flat_screen(self, queries, vectors, threshold, ip, allow, x_exp, cap, stream, retry):
+        """One screen call with `cap` entries and, if retry and the result is larger, one more of exactly its size
+        -> (lims, idx[:min(total, cap)], total); lims[-1] is read in between, the one synchronisation."""
+        import torch
+        _, q2, vectors, allow, nq, d, N = self._flat_screen_args(queries, vectors, allow)
+        dev = vectors.device
+        thr = _marshal.threshold_arg(threshold, nq, dev)
+        cap = int(cap)
+        if cap < 0:
+            raise PanicError("capacity must not be negative")
+        x_exp = int(x_exp)
+        if not -(1 << 31) <= x_exp < (1 << 31):
+            raise PanicError("x_exp must fit 32 bits")
+        own_stream = stream is None
+        cb, slot, sp = _marshal.launch(self, vectors, stream)
+        head = (cb, slot, q2.data_ptr(), nq, row_stride(q2, nq, d), ptr_or_none(vectors, N), vectors.element_size(), N, d,
+                row_stride(vectors, N, d), None if allow is None else allow.data_ptr(), 1 if ip else 0, x_exp, thr.data_ptr())
+        lims = torch.empty(nq + 1, dtype=torch.int64, device=dev)
+        while True:
+            idx = torch.empty(cap, dtype=torch.int64, device=dev)
+            _marshal.run("pqhip_flat_screen_f32_dev", *head, lims.data_ptr(), ptr_or_none(idx, cap), cap, sp)
+            if not own_stream:
+                torch.cuda.ExternalStream(stream, device=dev).synchronize()
+            total = int(lims[-1])
+            if total <= cap or not retry:
+                break
+            cap = total             # the second call always suffices
+        return lims, idx[:min(total, cap)], total
+
+    def flat_screen_device(self, queries, vectors, threshold, ip=False, allow=None, x_exp=0, capacity=None, stream=None,
+                           check=False):
+        """Conservative range screen on the matrix cores (pqhip_flat_screen_f32_dev): queries, vectors, allow and
+        threshold as for flat_range_device (d <= 2048) -> (lims, idx): CSR, lims CUDA int64 [nq + 1], the ids of query q at
+        idx[lims[q]:lims[q + 1]] in ascending order -- a SUPERSET of what flat_range_device returns at the same
+        thresholds, within the allowed rows: a row is left out only when its exact value provably misses the threshold,
+        and a regular row is returned only within the slack the header states.  x_exp: every row element is multiplied
+        by 2^x_exp before it is rounded to f16 (flat_screen_x_exp chooses it from the largest |element|).  The capacity
+        protocol is flat_range_device's: one call with `capacity` entries (default 1 << 20), one read of lims[-1] -- the
+        one synchronisation -- and one more call of exactly its size if the result is larger; capacity=0 counts first.
+        There is no range flag to raise; check=True only synchronises."""
+        lims, idx, _ = self._flat_screen(queries, vectors, threshold, ip, allow, x_exp, (1 << 20) if capacity is None else capacity,
+                                         stream, True)
+        if check:
+            import torch
+            torch.cuda.synchronize(vectors.device)
+        return lims, idx
+
+    def flat_range_batch_device(self, queries, vectors, threshold, ip=False, allow=None, x_exp=None, capacity=None,
+                                stream=None, check=False):
+        """flat_range_device for a batch of queries: the matrix-core screen at the thresholds (flat_screen_device), then
+        flat_range_among_device over its ids -> (lims, val, idx), bit for bit what flat_range_device returns: the screen
+        returns a superset of the result in ascending row order, and the candidate call applies the same predicate to
+        the same values in the order named.  x_exp None: chosen from the largest |element| of vectors
+        (flat_screen_x_exp; one reduction over the matrix -- pass it when it is known).  d <= 2048."""
+        if x_exp is None:
+            x_exp = flat_screen_x_exp(_matrix_max_abs(vectors))
+        lims, ids = self.flat_screen_device(queries, vectors, threshold, ip=ip, allow=allow, x_exp=x_exp, capacity=capacity,
+                                            stream=stream)
+        return self.flat_range_among_device(queries, vectors, ids, threshold, lims=lims, ip=ip, stream=stream, check=check)
+
+    def flat_search_batch_device(self, queries, vectors, k, ip=False, allow=None, x_exp=None, stream=None, check=False,
+                                 stats=None):
+        """flat_search_device for a batch of queries, bit for bit in values and ids, at about one stream of the matrix
+        per 64 queries instead of one per 4 (d <= 2048).  Sample: every t-th row (flat_batch_sample; -1 where the mask
+        disallows it) through flat_among_device; T_q, its k-th value, is a valid threshold whatever the sample -- k rows
+        have a value at or below it, so every member of the true top-k has.  Screen at T_q (flat_screen_device): a
+        superset of those rows.  Resolve: flat_among_device over the screen's ids, which is the masked search on a
+        superset of its result.  A query whose sample holds fewer than k numbers, and a chunk of queries whose
+        candidates exceed FLAT_BATCH_FALLBACK_FRACTION of n nq (flat_batch_falls_back), take flat_search_device.
+        stats: a dict that receives the candidate total, the queries that fell back and the sample size."""
+        import torch
+        k = int(k)
+        if not 1 <= k <= 1024:
+            raise PanicError("k must be between 1 and 1024, was %d" % k)
+        single, q2, vectors, allow, nq, d, N = self._flat_screen_args(queries, vectors, allow)
+        dev = vectors.device
+        if N == 0 or nq == 0:
+            return self.flat_search_device(queries, vectors, k, ip=ip, allow=allow, stream=stream, check=check)
+        if x_exp is None:
+            x_exp = flat_screen_x_exp(_matrix_max_abs(vectors))
+        S, t = flat_batch_sample(N, k)
+        ids = torch.arange(0, N, t, dtype=torch.int64, device=dev)
+        if allow is not None:
+            bit = (allow[ids >> 5] >> (ids & 31).to(torch.int32)) & 1
+            ids = torch.where(bit != 0, ids, torch.full_like(ids, -1))
+        sval, sidx = self.flat_among_device(q2, vectors, ids, k, ip=ip, stream=stream)
+        T = sval[:, k - 1]
+        thin = (sidx[:, k - 1] < 0) | torch.isnan(T)
+        nothing = float("inf") if ip else float("-inf")          # a thin query screens nothing and takes the plain call
+        thr = torch.where(thin, torch.full_like(T, nothing), T)
+        val = torch.empty((nq, k), dtype=torch.float32, device=dev)
+        idx = torch.empty((nq, k), dtype=torch.int64, device=dev)
+        plain = thin.clone()
+        total_all = 0
+        for q0 in range(0, nq, FLAT_BATCH_CHUNK):
+            q1 = min(nq, q0 + FLAT_BATCH_CHUNK)
+            cap = flat_batch_capacity(N, q1 - q0, k, S)
+            lims, cand, total = self._flat_screen(q2[q0:q1], vectors, thr[q0:q1], ip, allow, x_exp, cap, stream, False)
+            total_all += total
+            if flat_batch_falls_back(total, N, q1 - q0):
+                plain[q0:q1] = True
+                continue
+            val[q0:q1], idx[q0:q1] = self.flat_among_device(q2[q0:q1], vectors, cand, k, lims=lims, ip=ip, stream=stream)
+        rows = torch.nonzero(plain).reshape(-1)
+        if rows.shape[0] > 0:
+            val[rows], idx[rows] = self.flat_search_device(q2[rows], vectors, k, ip=ip, allow=allow, stream=stream)
+        if stats is not None:
+            stats.update(candidates=total_all, fallback_queries=int(rows.shape[0]), sample=int(ids.shape[0]), x_exp=int(x_exp))
+        if check:
+            torch.cuda.synchronize(dev)
+        return (val[0], idx[0]) if single else (val, idx)
 
     # ---- growing a partitioned matrix: merge of two list-ordered arrays ------------------------------------------------
     def merge_lists_device(self, list_off_a, a, list_off_b, b, out=None, stream=None, check=False):

@@ -24,6 +24,7 @@ import struct
 
 import numpy as np
 
+from . import pq as _pq
 from .pq import Pq, PanicError
 
 CHUNK_QUANTIZED_ARRAY = 4
@@ -265,48 +266,76 @@ class _Refine:
             raise PanicError("allow must be a bool array with one flag per row (%d)" % len(self))
         return self.pq.pack_row_mask_device(allow.view(torch.uint8))
 
-    def _exact(self, ip, queries, k, allow):
+    _max_abs = None           # (key of the vectors it was taken from, their largest |element|)
+
+    def _screen_x_exp(self):
+        """x_exp of the matrix-core screen for `vectors` (pq.flat_screen_x_exp of their largest |element|, which is
+        reduced once and kept until the tensor is replaced or written)"""
+        v = self.vectors
+        key = (v.data_ptr(), tuple(v.shape), v.dtype, v._version)
+        if self._max_abs is None or self._max_abs[0] != key:
+            self._max_abs = (key, _pq._matrix_max_abs(v))
+        return _pq.flat_screen_x_exp(self._max_abs[1])
+
+    def _screens(self, screen):
+        """screen=True takes the batch route where the screen serves the width; wider vectors keep the plain call"""
+        return bool(screen) and self.vectors.shape[1] <= _pq.FLAT_SCREEN_MAX_D
+
+    def _flat_topk(self, q, k, ip, words, screen):
+        if self._screens(screen):
+            return self.pq.flat_search_batch_device(q, self.vectors, k, ip=ip, allow=words, x_exp=self._screen_x_exp())
+        return self.pq.flat_search_device(q, self.vectors, k, ip=ip, allow=words)
+
+    def _flat_range(self, q, threshold, ip, words, screen):
+        if self._screens(screen):
+            return self.pq.flat_range_batch_device(q, self.vectors, threshold, ip=ip, allow=words, x_exp=self._screen_x_exp())
+        return self.pq.flat_range_device(q, self.vectors, threshold, ip=ip, allow=words)
+
+    def _exact(self, ip, queries, k, allow, screen=False):
         import torch
         if self.vectors is None:
             raise PanicError("refine needs the original vectors: call attach_vectors first")
         q = _on_device(queries, self.vectors.device, torch.float32, np.float32)
-        return self.pq.flat_search_device(q, self.vectors, k, ip=ip, allow=self._exact_words(allow))
+        return self._flat_topk(q, k, ip, self._exact_words(allow), screen)
 
-    def exact_nearest(self, queries, k, allow=None):
+    def exact_nearest(self, queries, k, allow=None, screen=False):
         """The true k nearest rows: the exhaustive top-k of ALL attached vectors by their exact squared distance
         (Pq.flat_search_device), in original row numbers, ties to the smaller row -> (dist, idx) [k] or [nq, k].  The
         codes are not read: this is the ground truth the quantized searches are measured against, and dist are the
         values refine= returns.  allow: None, bool flags [N] in original row order, or (QuantizedMatrix) a RowFilter of
-        this matrix; a partitioned matrix's RowFilter is in position order and is refused."""
-        return self._exact(False, queries, k, allow)
+        this matrix; a partitioned matrix's RowFilter is in position order and is refused.  screen=True: the route for
+        query batches (Pq.flat_search_batch_device: matrix-core screen, exact resolve), the same result bit for bit;
+        vectors wider than 2,048 elements keep the plain call."""
+        return self._exact(False, queries, k, allow, screen)
 
-    def exact_most_similar(self, queries, k, allow=None):
+    def exact_most_similar(self, queries, k, allow=None, screen=False):
         """The true k rows of largest inner product with the attached vectors as they are, largest first -> (score, idx),
         as exact_nearest()."""
-        return self._exact(True, queries, k, allow)
+        return self._exact(True, queries, k, allow, screen)
 
-    def _exact_range(self, ip, queries, threshold, allow, sort):
+    def _exact_range(self, ip, queries, threshold, allow, sort, screen=False):
         import torch
         if self.vectors is None:
             raise PanicError("refine needs the original vectors: call attach_vectors first")
         q = _on_device(queries, self.vectors.device, torch.float32, np.float32)
-        lims, val, rows = self.pq.flat_range_device(q, self.vectors, threshold, ip=ip, allow=self._exact_words(allow))
+        lims, val, rows = self._flat_range(q, threshold, ip, self._exact_words(allow), screen)
         if sort:
             val, rows = sort_ranges(lims, val, rows, ip)
         return lims, val, rows
 
-    def exact_within(self, queries, radius, allow=None, sort=False):
+    def exact_within(self, queries, radius, allow=None, sort=False, screen=False):
         """The true answer of within(): EVERY attached vector whose exact squared distance to the query is <= radius (a
         scalar or one value per query) -> (lims, dist, idx), CSR over the queries in ascending original row number
         (Pq.flat_range_device); sort=True: ascending in distance, ties in row order.  The codes are not read: this is
         what the recall of within() is measured against, and the one way to true distances for a radius query (refine=
-        stops at 1,024 candidates).  allow: as for exact_nearest()."""
-        return self._exact_range(False, queries, radius, allow, sort)
+        stops at 1,024 candidates).  allow: as for exact_nearest().  screen=True: the route for query batches
+        (Pq.flat_range_batch_device), the same result bit for bit."""
+        return self._exact_range(False, queries, radius, allow, sort, screen)
 
-    def exact_similar_above(self, queries, threshold, allow=None, sort=False):
+    def exact_similar_above(self, queries, threshold, allow=None, sort=False, screen=False):
         """Every attached vector whose exact inner product with the query is >= threshold -> (lims, score, idx), as
         exact_within(); sort=True: descending in score."""
-        return self._exact_range(True, queries, threshold, allow, sort)
+        return self._exact_range(True, queries, threshold, allow, sort, screen)
 
     def _exact_among(self, ip, queries, rows, k):
         import torch
@@ -1267,45 +1296,47 @@ class FlatMatrix(_Refine, _Filter, _Compact):
     def attach_vectors(self, vectors, dtype=None):
         raise PanicError("a FlatMatrix holds its vectors already")
 
-    def _topk(self, ip, queries, k, refine, allow):
+    def _topk(self, ip, queries, k, refine, allow, screen=False):
         import torch
         if refine is not None:
             self._check_refine(k, refine)       # the estimate is exact already: refine changes nothing
         q = _on_device(queries, self.vectors.device, torch.float32, np.float32)
-        return self.pq.flat_search_device(q, self.vectors, k, ip=ip, allow=self._allow_words(allow))
+        return self._flat_topk(q, k, ip, self._allow_words(allow), screen)
 
-    def nearest(self, queries, k, refine=None, allow=None):
+    def nearest(self, queries, k, refine=None, allow=None, screen=False):
         """the k rows of smallest exact squared distance, ties to the smaller row -> (dist, idx) [k] or [nq, k]; index -1
         and +Inf past the last (allowed) row.  refine is accepted and changes nothing; allow: None, a RowFilter of this
-        matrix or a bool array [N]."""
-        return self._topk(False, queries, k, refine, allow)
+        matrix or a bool array [N].  screen=True: the route for query batches (Pq.flat_search_batch_device: matrix-core
+        screen, exact resolve), the same result bit for bit; vectors wider than 2,048 elements keep the plain call."""
+        return self._topk(False, queries, k, refine, allow, screen)
 
-    def most_similar(self, queries, k, use_norms=True, refine=None, allow=None):
+    def most_similar(self, queries, k, use_norms=True, refine=None, allow=None, screen=False):
         """the k rows of largest exact inner product, largest first -> (score, idx); use_norms is accepted and ignored
         (the rows are stored unscaled), refine and allow as for nearest()."""
-        return self._topk(True, queries, k, refine, allow)
+        return self._topk(True, queries, k, refine, allow, screen)
 
-    def _range(self, ip, queries, threshold, allow, sort):
+    def _range(self, ip, queries, threshold, allow, sort, screen=False):
         import torch
         q = _on_device(queries, self.vectors.device, torch.float32, np.float32)
-        lims, val, rows = self.pq.flat_range_device(q, self.vectors, threshold, ip=ip, allow=self._allow_words(allow))
+        lims, val, rows = self._flat_range(q, threshold, ip, self._allow_words(allow), screen)
         if sort:
             val, rows = sort_ranges(lims, val, rows, ip)
         return lims, val, rows
 
-    def within(self, queries, radius, allow=None, sort=False):
+    def within(self, queries, radius, allow=None, sort=False, screen=False):
         """EVERY row whose exact squared distance to the query is <= radius (a scalar or one value per query) -> (lims,
         dist, idx): CSR over the queries, lims int64 [nq + 1] ([2] for one query), the rows of query q at
         lims[q]:lims[q + 1] in ascending row number, dist the value nearest() returns for the row (Pq.flat_range_device;
         the result is allocated to its size, after one read of the count).  sort=True: each query's rows ascending in
-        distance instead, ties in row order (sort_ranges).  allow: as for nearest()."""
-        return self._range(False, queries, radius, allow, sort)
+        distance instead, ties in row order (sort_ranges).  allow: as for nearest().  screen=True: the route for query
+        batches (Pq.flat_range_batch_device), the same result bit for bit."""
+        return self._range(False, queries, radius, allow, sort, screen)
 
-    def similar_above(self, queries, threshold, use_norms=True, allow=None, sort=False):
+    def similar_above(self, queries, threshold, use_norms=True, allow=None, sort=False, screen=False):
         """Every row whose exact inner product with the query is >= threshold (a scalar or one value per query) ->
         (lims, score, idx), CSR as for within(); sort=True: each query's rows descending in score, ties in row order.
-        use_norms is accepted and ignored, as in most_similar()."""
-        return self._range(True, queries, threshold, allow, sort)
+        use_norms is accepted and ignored, as in most_similar(); screen as for within()."""
+        return self._range(True, queries, threshold, allow, sort, screen)
 
     def nearest_among(self, queries, rows, k):
         """nearest() among the rows that `rows` names and no others: a vector of row numbers shared by all queries, or the

@@ -214,6 +214,15 @@ extern "C" {
         n_queries: i64, q_row_stride: i64, d_vectors: *const c_void, vec_bytes: i32, n_rows: i64, d: i64,
         vec_row_stride: i64, d_lims: *const i64, d_ids: *const i64, n_ids: i64, metric: i32, d_threshold: *const f32,
         d_out_lims: *mut i64, d_val: *mut f32, d_idx: *mut i64, capacity: i64, stream: *mut c_void) -> i32;
+    // conservative range screen on the matrix cores for query batches: per query a superset of what
+    // pqhip_flat_range_f32_dev returns at d_threshold, as ascending ids (CSR without values; the capacity protocol of the
+    // range calls); a row is left out only when its exact value provably misses the threshold; every row element is
+    // multiplied by 2^x_exp before it is rounded to f16; d <= 2048; option "flat_screen_wgs" forces the grid, on which the
+    // result does not depend
+    pub fn pqhip_flat_screen_f32_dev(cb: *mut pqhip_codebook, device_slot: i32, d_queries: *const f32, n_queries: i64,
+        q_row_stride: i64, d_vectors: *const c_void, vec_bytes: i32, n_rows: i64, d: i64, vec_row_stride: i64,
+        d_allow: *const u32, metric: i32, x_exp: i32, d_threshold: *const f32, d_lims: *mut i64, d_idx: *mut i64,
+        capacity: i64, stream: *mut c_void) -> i32;
     // merge of two list-ordered row arrays: list l of d_out = list l of d_a, then list l of d_b (rows of row_bytes bytes,
     // any alignment); the offsets are validated on the device (invalid: nothing written, the stream's range flag raised);
     // d_off_out NULL or [n_lists + 1]; option "lists_merge_wgs" forces the grid
