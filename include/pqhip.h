@@ -902,6 +902,42 @@ int32_t pqhip_flat_screen_f32_dev(pqhip_codebook *cb, int32_t device_slot,
                                   int64_t capacity, void *stream);
 
 /*
+ * The range screen of pqhip_flat_screen_f32_dev in PROBED LISTS: for a batch of queries, per query a superset of what
+ * pqhip_flat_range_lists_f32_dev returns at the same thresholds, as positions (CSR, no values) -- the first stage of the
+ * exact list searches for query batches (resolve with pqhip_flat_range_among_f32_dev / pqhip_flat_among_f32_dev).  The work
+ * is list-major: the probe table of a chunk of queries is inverted on the device, and a list that several queries probe
+ * is streamed once per group of up to 64 of them (32 while d > 1024).  Arguments: those of
+ * pqhip_flat_range_lists_f32_dev without d_val, and x_exp as in pqhip_flat_screen_f32_dev.
+ * Contract.  R_q: the positions pqhip_flat_range_lists_f32_dev returns for query q at d_threshold[q]; S_q: the allowed
+ * rows of q's probed lists; O_q: this call's output.  Sound, unconditionally: R_q within O_q within S_q.  Tight: a
+ * regular row is returned only within the slack stated at pqhip_flat_screen_f32_dev -- every (row, query) screening value
+ * is the same single chain with the same constants, so the bound of DESIGN.md section 5c holds unchanged (section 5d).
+ * Whatever the proof does not cover is returned.  d <= 2048.
+ * Order and capacity: d_lims [n_queries + 1], d_idx positions; within a query probe slot first, then ascending position
+ * -- the order of pqhip_flat_range_lists_f32_dev; a list named twice returns its rows twice.  The capacity protocol is
+ * that of the range calls (true counts always, only slots < capacity written, capacity == 0 a count call with d_idx NULL).
+ * Probes and offsets: -1 is padding; any other id outside [0, n_lists) is skipped and raises the stream's range flag;
+ * list ranges are clamped to [0, n_rows], inverted ranges are empty, both raise the flag.  No byte outside [d_vectors,
+ * last row + d elements) is read, and no byte of a disallowed or unprobed row.
+ * A function of the inputs alone: the result depends neither on the grid ("flat_screen_lists_wgs"), nor on how a
+ * list's rows are cut into units ("flat_screen_lists_unit_rows"), nor on how queries are grouped into groups or chunks
+ * ("flat_screen_lists_chunk_queries").  The only atomics are integer counts and cursors.
+ * Status codes: the union of pqhip_flat_range_lists_f32_dev's and the screen's, in the precedence PQHIP_EINVAL (null cb,
+ * negative counts, d < 1, n_probe < 1, metric not 0 / 1), PQHIP_ENODEV, PQHIP_EUNSUPPORTED (vec_bytes not 2 / 4,
+ * d > 2048, n_rows > 2^32 - 2, n_probe > 2^20), then with n_queries > 0 the null pointers (PQHIP_EINVAL) and the strides
+ * (PQHIP_ESHAPE).  n_queries == 0 launches nothing; n_rows == 0 or n_lists == 0 writes all-zero lims.
+ */
+int32_t pqhip_flat_screen_lists_f32_dev(pqhip_codebook *cb, int32_t device_slot,
+                                        const float *d_queries, int64_t n_queries, int64_t q_row_stride,
+                                        const void *d_vectors, int32_t vec_bytes, int64_t n_rows, int64_t d, int64_t vec_row_stride,
+                                        const uint32_t *d_allow /* position order, or NULL */,
+                                        const int64_t *d_list_off /* [n_lists + 1] */, int64_t n_lists,
+                                        const int64_t *d_probes, int32_t n_probe, int64_t probes_row_stride,
+                                        int32_t metric /* 0 = squared L2, 1 = inner product */, int32_t x_exp,
+                                        const float *d_threshold /* [n_queries] */, int64_t *d_lims, int64_t *d_idx,
+                                        int64_t capacity, void *stream);
+
+/*
  * Merge of two list-ordered row arrays: the primitive under growing a partitioned matrix (rows added to an index, two
  * indexes over the same lists joined).  d_a is [n_a] rows of row_bytes bytes in list order under d_off_a [n_lists + 1]
  * (list l = rows off_a[l] .. off_a[l + 1] - 1), d_b likewise [n_b] rows under d_off_b; d_out is [n_a + n_b] rows.  For
@@ -1251,6 +1287,10 @@ int32_t pqhip_set_rotation_variant(int32_t variant);
  *   "flat_screen_wgs"      producer workgroups of pqhip_flat_screen_f32_dev (0 = two per CU; at most 2048, so that the
  *                          prefix scan of a pass of 64 queries sums at most 2^20 counts; rows per workgroup stay a
  *                          multiple of 256; the result does not depend on it)
+ *   "flat_screen_lists_wgs"  workgroups of pqhip_flat_screen_lists_f32_dev that stride over its units (0 = four per CU)
+ *   "flat_screen_lists_unit_rows"  rows of a unit of that call, rounded up to a multiple of 32 (0 = 1024)
+ *   "flat_screen_lists_chunk_queries"  queries of a chunk of that call (0 = from the scratch bound; at most 2^20 / n_probe);
+ *                          the result depends on none of the three
  *   "cross_product_exact" 0 = X^T.R of the OPQ training step / pqhip_at_dot_b_f32_dev as a plain split-K product:
  *                          within 1e-5 relative of the exact rule-2 result, no per-block partial matrices (default 1)
  *   "cross_product_group_bytes"  workspace of partial matrices per launch group (0 = 4 GiB)

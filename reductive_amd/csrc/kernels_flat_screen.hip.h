@@ -75,7 +75,7 @@ __device__ __forceinline__ float flat_screen_round_up(double t)
 
 // The image row and the (s, tau) pair of one query slot per workgroup; slots >= nq_pass are padding (zeros, tau = NaN).
 // The three sums are reduced by a fixed tree over the 256 threads' partials (thread t owns j = t, t + 256, ..).
-__global__ __launch_bounds__(kFsPrepThreads) void k_flat_screen_prep(const float* __restrict__ queries, int64_t q_rs, int nq_pass,
+inline __global__ __launch_bounds__(kFsPrepThreads) void k_flat_screen_prep(const float* __restrict__ queries, int64_t q_rs, int nq_pass,
                                                                      int d, int ldq, const float* __restrict__ thr, int ip,
                                                                      int x_exp, unsigned short* __restrict__ img,
                                                                      float* __restrict__ prm /* [slots][2] */)
@@ -303,7 +303,7 @@ __global__ __launch_bounds__(64 * kFsWaves) void k_flat_screen(const T* __restri
 
 // The fill pass: the decomposition of the count pass, lane = query of the pass (qp = 32 or 64 per tile), the unit's
 // tiles in ascending order, a word's bits in ascending order.  part: the first slot of every (query, unit), absolute.
-__global__ __launch_bounds__(64 * kFsWaves) void k_flat_screen_fill(const uint32_t* __restrict__ hits, int qp, int nq_pass,
+inline __global__ __launch_bounds__(64 * kFsWaves) void k_flat_screen_fill(const uint32_t* __restrict__ hits, int qp, int nq_pass,
                                                                     int64_t n, int64_t rows_per_wg,
                                                                     const int64_t* __restrict__ part, int64_t capacity,
                                                                     int64_t* __restrict__ out_i)

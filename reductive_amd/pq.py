@@ -489,6 +489,37 @@ def flat_batch_falls_back(total, n, nq):
     return total > FLAT_BATCH_FALLBACK_FRACTION * n * nq
 
 
+FLAT_LISTS_BATCH_FALLBACK_FRACTION = 1.0 / 8   # candidates of a chunk beyond this share of its expected probed rows: the plain call
+FLAT_LISTS_BATCH_CHUNK = 1024            # queries per screen call of the batch list search
+
+
+def flat_lists_batch_sample(n_rows, n_lists, n_probe, k):
+    """s: the probe slots whose rows are the sample of the batch list search -- the first s lists of every query, the
+    nearest ones.  With equally long lists a slot holds n_rows / n_lists rows; s slots should hold about
+    2 sqrt(P k) of the P = n_rows min(n_probe, n_lists) / n_lists probed rows (the balance of flat_batch_sample), at
+    least 4 k.  1 <= s <= n_probe."""
+    import math
+    n_rows, n_lists, n_probe, k = int(n_rows), int(n_lists), int(n_probe), int(k)
+    if n_probe <= 1 or n_rows <= 0 or n_lists <= 0:
+        return max(1, min(1, n_probe))
+    per_list = float(n_rows) / n_lists
+    probed = per_list * min(n_probe, n_lists)
+    want = max(4.0 * k, 2.0 * math.sqrt(probed * k))
+    return max(1, min(n_probe, int(math.ceil(want / per_list))))
+
+
+def flat_lists_batch_fraction():
+    """the share of a chunk's expected probed rows beyond which its candidates take the plain call, in (0, 1]"""
+    return FLAT_LISTS_BATCH_FALLBACK_FRACTION
+
+
+def flat_lists_batch_falls_back(total, n_rows, n_lists, n_probe, nq):
+    """a chunk of nq queries with `total` candidates takes the plain call when they exceed the stated share of the rows
+    it is expected to probe, nq n_rows min(n_probe, n_lists) / n_lists"""
+    expected = float(nq) * n_rows * min(int(n_probe), int(n_lists)) / max(int(n_lists), 1)
+    return total > flat_lists_batch_fraction() * expected
+
+
 def _matrix_max_abs(vectors):
     """largest finite |element| of a CUDA matrix as a float (two reductions without a temporary and one
     synchronisation; a matrix with NaN or infinite elements is reduced again in row chunks over its finite elements)"""
@@ -1781,6 +1812,126 @@ class Pq:
             stats.update(candidates=total_all, fallback_queries=int(rows.shape[0]), sample=int(ids.shape[0]), x_exp=int(x_exp))
         if check:
             torch.cuda.synchronize(dev)
+        return (val[0], idx[0]) if single else (val, idx)
+
+    # ---- exact search in probed lists for query batches: f16 matrix-core screen per list, exact resolve ------------------
+    def _flat_screen_lists(self, queries, vectors, list_off, probes, threshold, ip, allow, x_exp, cap, stream, retry):
+        """One list screen call with `cap` entries and, if retry and the result is larger, one more of exactly its size
+        -> (lims, idx[:min(total, cap)], total, launch); lims[-1] is read in between, the one synchronisation."""
+        import torch
+        _, q2, vectors, allow, nq, d, N = self._flat_screen_args(queries, vectors, allow)
+        if N > (1 << 32) - 2:
+            raise PanicError("at most 2^32 - 2 rows are searched in lists")
+        pr, n_lists, n_probe, p_rs = _marshal.vector_lists_arg(list_off, probes, nq)
+        if not (list_off.is_cuda and probes.is_cuda and list_off.device == vectors.device and probes.device == vectors.device):
+            raise PanicError("queries, vectors, list_off, probes and allow must be CUDA tensors on one device")
+        dev = vectors.device
+        thr = _marshal.threshold_arg(threshold, nq, dev)
+        cap = int(cap)
+        if cap < 0:
+            raise PanicError("capacity must not be negative")
+        x_exp = int(x_exp)
+        if not -(1 << 31) <= x_exp < (1 << 31):
+            raise PanicError("x_exp must fit 32 bits")
+        own_stream = stream is None
+        cb, slot, sp = _marshal.launch(self, vectors, stream)
+        head = (cb, slot, q2.data_ptr(), nq, row_stride(q2, nq, d), ptr_or_none(vectors, N), vectors.element_size(), N, d,
+                row_stride(vectors, N, d), None if allow is None else allow.data_ptr(), list_off.data_ptr(), n_lists,
+                pr.data_ptr(), n_probe, p_rs, 1 if ip else 0, x_exp, thr.data_ptr())
+        lims = torch.empty(nq + 1, dtype=torch.int64, device=dev)
+        while True:
+            idx = torch.empty(cap, dtype=torch.int64, device=dev)
+            _marshal.run("pqhip_flat_screen_lists_f32_dev", *head, lims.data_ptr(), ptr_or_none(idx, cap), cap, sp)
+            if not own_stream:
+                torch.cuda.ExternalStream(stream, device=dev).synchronize()
+            total = int(lims[-1])
+            if total <= cap or not retry:
+                break
+            cap = total             # the second call always suffices
+        return lims, idx[:min(total, cap)], total, (cb, slot, sp)
+
+    def flat_screen_lists_device(self, queries, vectors, list_off, probes, threshold, ip=False, allow=None, x_exp=0,
+                                 capacity=None, stream=None, check=False):
+        """flat_screen_device in probed lists (pqhip_flat_screen_lists_f32_dev): queries, vectors, list_off, probes,
+        allow and threshold as for flat_range_lists_device (d <= 2048) -> (lims, idx): CSR of positions, per query a
+        SUPERSET of what flat_range_lists_device returns at the same thresholds, within the allowed rows of the probed
+        lists and in that call's order -- probe slot first, then position; a list named twice returns its rows twice.
+        A regular row is returned only within the slack the header states.  x_exp and the capacity protocol as for
+        flat_screen_device.  check=True synchronises and reports a list id or an offset out of range (they are skipped
+        resp. clamped either way)."""
+        lims, idx, _, launch = self._flat_screen_lists(queries, vectors, list_off, probes, threshold, ip, allow, x_exp,
+                                                       (1 << 20) if capacity is None else capacity, stream, True)
+        if check:
+            _marshal.check_range(*launch)
+        return lims, idx
+
+    def flat_range_lists_batch_device(self, queries, vectors, list_off, probes, threshold, ip=False, allow=None, x_exp=None,
+                                      capacity=None, stream=None, check=False):
+        """flat_range_lists_device for a batch of queries: the list screen at the thresholds (flat_screen_lists_device),
+        then flat_range_among_device over its positions -> (lims, val, idx), bit for bit what flat_range_lists_device
+        returns: the screen names a superset of the result in that call's order, and the candidate call applies the same
+        predicate to the same values in the order named.  x_exp None: chosen from the largest |element| of vectors.
+        d <= 2048."""
+        if x_exp is None:
+            x_exp = flat_screen_x_exp(_matrix_max_abs(vectors))
+        lims, ids = self.flat_screen_lists_device(queries, vectors, list_off, probes, threshold, ip=ip, allow=allow, x_exp=x_exp,
+                                                  capacity=capacity, stream=stream, check=check)
+        return self.flat_range_among_device(queries, vectors, ids, threshold, lims=lims, ip=ip, stream=stream, check=check)
+
+    def flat_search_lists_batch_device(self, queries, vectors, list_off, probes, k, ip=False, allow=None, x_exp=None,
+                                       stream=None, check=False, stats=None):
+        """flat_search_lists_device for a batch of queries, bit for bit in values and positions (d <= 2048).  Sample:
+        flat_search_lists_device over the first s probe slots only (flat_lists_batch_sample); T_q, its k-th value, is
+        the k-th best of a subset of the query's probed rows and therefore a valid threshold.  Screen at T_q
+        (flat_screen_lists_device): a superset of the rows at or below it, probed list by probed list.  Resolve:
+        flat_among_device over the candidates, whose order (value, position) is the list search's.  A query whose sample
+        holds fewer than k rows, and a chunk of queries whose candidates exceed flat_lists_batch_fraction() of its
+        expected probed rows (flat_lists_batch_falls_back), take flat_search_lists_device.  A list that a query names
+        twice is a candidate twice, so such a query takes the plain call too.  stats: a dict that receives the candidate
+        total, the queries that fell back and the sample slots."""
+        import torch
+        k = int(k)
+        if not 1 <= k <= 1024:
+            raise PanicError("k must be between 1 and 1024, was %d" % k)
+        single, q2, vectors, allow, nq, d, N = self._flat_screen_args(queries, vectors, allow)
+        pr, n_lists, n_probe, p_rs = _marshal.vector_lists_arg(list_off, probes, nq)
+        plain_call = lambda q, p: self.flat_search_lists_device(q, vectors, list_off, p, k, ip=ip, allow=allow, stream=stream)
+        pr2 = probes[None] if probes.dim() == 1 else probes
+        if N == 0 or nq == 0 or n_lists == 0:
+            return self.flat_search_lists_device(queries, vectors, list_off, probes, k, ip=ip, allow=allow, stream=stream, check=check)
+        dev = vectors.device
+        if x_exp is None:
+            x_exp = flat_screen_x_exp(_matrix_max_abs(vectors))
+        s = flat_lists_batch_sample(N, n_lists, n_probe, k)
+        sval, sidx = plain_call(q2, pr2[:, :s].contiguous())
+        T = sval[:, k - 1]
+        srt = torch.sort(pr2, dim=1).values                         # a list named twice: its rows would be candidates twice
+        twice = ((srt[:, 1:] == srt[:, :-1]) & (srt[:, 1:] >= 0)).any(dim=1)
+        thin = (sidx[:, k - 1] < 0) | torch.isnan(T) | twice
+        nothing = float("inf") if ip else float("-inf")          # a thin query screens nothing and takes the plain call
+        thr = torch.where(thin, torch.full_like(T, nothing), T)
+        val = torch.empty((nq, k), dtype=torch.float32, device=dev)
+        idx = torch.empty((nq, k), dtype=torch.int64, device=dev)
+        plain = thin.clone()
+        total_all = 0
+        for q0 in range(0, nq, FLAT_LISTS_BATCH_CHUNK):
+            q1 = min(nq, q0 + FLAT_LISTS_BATCH_CHUNK)
+            cap = int(flat_lists_batch_fraction() * (q1 - q0) * N * min(n_probe, n_lists) / n_lists) + 1
+            lims, cand, total, _ = self._flat_screen_lists(q2[q0:q1], vectors, list_off, pr2[q0:q1], thr[q0:q1], ip, allow, x_exp,
+                                                           cap, stream, False)
+            total_all += total
+            if total > cap or flat_lists_batch_falls_back(total, N, n_lists, n_probe, q1 - q0):
+                plain[q0:q1] = True
+                continue
+            val[q0:q1], idx[q0:q1] = self.flat_among_device(q2[q0:q1], vectors, cand, k, lims=lims, ip=ip, stream=stream)
+        rows = torch.nonzero(plain).reshape(-1)
+        if rows.shape[0] > 0:
+            val[rows], idx[rows] = plain_call(q2[rows], pr2[rows])
+        if stats is not None:
+            stats.update(candidates=total_all, fallback_queries=int(rows.shape[0]), sample_slots=int(s), x_exp=int(x_exp))
+        if check:
+            cb, slot, sp = _marshal.launch(self, vectors, stream)
+            _marshal.check_range(cb, slot, sp)
         return (val[0], idx[0]) if single else (val, idx)
 
     # ---- growing a partitioned matrix: merge of two list-ordered arrays ------------------------------------------------

@@ -1459,51 +1459,75 @@ class PartitionedFlatMatrix(_ListLayout, _Filter, _Compact):
         val, pos = self.pq.rerank_device(queries, self.rows, self._among_ids(rows), k, ip=ip)
         return val, self._original_rows(pos)
 
-    def _topk(self, ip, queries, k, nprobe, refine, allow):
+    def _screen_x_exp(self):
+        """x_exp of the matrix-core screen for the stored rows, computed once (growth and compaction return new matrices)"""
+        v = self.rows
+        key = (v.data_ptr(), tuple(v.shape), v.dtype, v._version)
+        cached = getattr(self, "_max_abs", None)
+        if cached is None or cached[0] != key:
+            self._max_abs = (key, _pq._matrix_max_abs(v))
+        return _pq.flat_screen_x_exp(self._max_abs[1])
+
+    def _screens(self, screen):
+        """screen=True takes the batch route where the screen serves the width; wider rows keep the plain call"""
+        return bool(screen) and self.rows.shape[1] <= _pq.FLAT_SCREEN_MAX_D
+
+    def _topk(self, ip, queries, k, nprobe, refine, allow, screen=False):
         import torch
         if refine is not None:
             self._check_refine(k, refine)       # the values are exact already: refine changes nothing
         q = _on_device(queries, self.rows.device, torch.float32, np.float32)
-        val, pos = self.pq.flat_search_lists_device(q, self.rows, self.list_off, self.probes(q, nprobe), k, ip=ip,
-                                                    allow=self._allow_words(allow))
+        if self._screens(screen):
+            val, pos = self.pq.flat_search_lists_batch_device(q, self.rows, self.list_off, self.probes(q, nprobe), k, ip=ip,
+                                                              allow=self._allow_words(allow), x_exp=self._screen_x_exp())
+        else:
+            val, pos = self.pq.flat_search_lists_device(q, self.rows, self.list_off, self.probes(q, nprobe), k, ip=ip,
+                                                        allow=self._allow_words(allow))
         return val, self._original_rows(pos)
 
-    def nearest(self, queries, k, nprobe, refine=None, allow=None):
+    def nearest(self, queries, k, nprobe, refine=None, allow=None, screen=False):
         """the k rows of smallest exact squared distance among the rows of the nprobe nearest lists, ties to the smaller
         position in list order -> (dist, idx) [k] or [nq, k]; idx are original row numbers, -1 past the last probed
         (allowed) row (distance +Inf).  refine is accepted and changes nothing; allow: None, a RowFilter of this matrix
-        or a bool array [N] in ORIGINAL row order (Pq.flat_search_lists_device)."""
-        return self._topk(False, queries, k, nprobe, refine, allow)
+        or a bool array [N] in ORIGINAL row order (Pq.flat_search_lists_device).  screen=True: the route for query
+        batches (Pq.flat_search_lists_batch_device: matrix-core screen per list, exact resolve), the same result bit for
+        bit; rows wider than 2,048 elements keep the plain call."""
+        return self._topk(False, queries, k, nprobe, refine, allow, screen)
 
-    def most_similar(self, queries, k, nprobe, use_norms=True, refine=None, allow=None):
+    def most_similar(self, queries, k, nprobe, use_norms=True, refine=None, allow=None, screen=False):
         """the k rows of largest exact inner product among the rows of the nprobe nearest lists, largest first ->
         (score, idx), -1 and -Inf past the last probed row; use_norms is accepted and ignored (the rows are stored
         unscaled), the rest as for nearest().  The lists are chosen by distance to the centroids, as for nearest()."""
-        return self._topk(True, queries, k, nprobe, refine, allow)
+        return self._topk(True, queries, k, nprobe, refine, allow, screen)
 
-    def _range(self, ip, queries, threshold, nprobe, allow, sort):
+    def _range(self, ip, queries, threshold, nprobe, allow, sort, screen=False):
         import torch
         q = _on_device(queries, self.rows.device, torch.float32, np.float32)
-        lims, val, pos = self.pq.flat_range_lists_device(q, self.rows, self.list_off, self.probes(q, nprobe), threshold, ip=ip,
-                                                         allow=self._allow_words(allow))
+        if self._screens(screen):
+            lims, val, pos = self.pq.flat_range_lists_batch_device(q, self.rows, self.list_off, self.probes(q, nprobe), threshold,
+                                                                   ip=ip, allow=self._allow_words(allow), x_exp=self._screen_x_exp())
+        else:
+            lims, val, pos = self.pq.flat_range_lists_device(q, self.rows, self.list_off, self.probes(q, nprobe), threshold, ip=ip,
+                                                             allow=self._allow_words(allow))
         rows = self._original_rows(pos)
         if sort:
             val, rows = sort_ranges(lims, val, rows, ip)
         return lims, val, rows
 
-    def within(self, queries, radius, nprobe, allow=None, sort=False):
+    def within(self, queries, radius, nprobe, allow=None, sort=False, screen=False):
         """EVERY row of the nprobe nearest lists whose exact squared distance to the query is <= radius (a scalar or one
         value per query) -> (lims, dist, idx), CSR over the queries; idx are original row numbers and the rows of a query
         come list by list in probe order, inside a list in its stored order (Pq.flat_range_lists_device).  The values
         are FlatMatrix.within()'s: with nprobe = n_lists the result is the same set.  sort=True: ascending in distance,
-        ties in that order.  allow: as for nearest()."""
-        return self._range(False, queries, radius, nprobe, allow, sort)
+        ties in that order.  allow: as for nearest().  screen=True: the route for query batches
+        (Pq.flat_range_lists_batch_device), the same result bit for bit."""
+        return self._range(False, queries, radius, nprobe, allow, sort, screen)
 
-    def similar_above(self, queries, threshold, nprobe, use_norms=True, allow=None, sort=False):
+    def similar_above(self, queries, threshold, nprobe, use_norms=True, allow=None, sort=False, screen=False):
         """Every row of the nprobe nearest lists whose exact inner product with the query is >= threshold -> (lims,
         score, idx), as within(); sort=True: descending in score.  use_norms is accepted and ignored, as in
-        most_similar()."""
-        return self._range(True, queries, threshold, nprobe, allow, sort)
+        most_similar(); screen as for within()."""
+        return self._range(True, queries, threshold, nprobe, allow, sort, screen)
 
     def _among(self, ip, queries, rows, k):
         import torch
