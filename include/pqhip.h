@@ -902,6 +902,53 @@ int32_t pqhip_flat_screen_f32_dev(pqhip_codebook *cb, int32_t device_slot,
                                   int64_t capacity, void *stream);
 
 /*
+ * Conservative range screen over resident u8 CODES with u8 table images: for a BATCH of queries, per query a superset of
+ * what pqhip_adc_range_f32_dev (ip 0: value <= threshold) resp. pqhip_adc_ip_range_f32_dev (ip 1: value >= threshold, the
+ * value fl(sum * scale) with d_scales) returns at the same thresholds, as ascending row ids (CSR, no values).  It is the
+ * first stage of the ADC search for query batches: screen, then resolve the candidates exactly with
+ * pqhip_adc_among_f32_dev / pqhip_adc_ip_among_f32_dev.  Arguments: those of the two range calls without d_val, and the
+ * ip flag in front of d_scales (which must be NULL for ip 0).
+ * Per query a prep kernel derives from the f32 tables a step s, a u8 image u[m][k] = min(255, floor((t - lo_m) / s))
+ * (lo_m the least entry of subquantizer m; the inner product uses the negated tables) and an integer limit; the screen
+ * kernel sums the bytes of a row's codes -- exact integer sums, packed u16 -- for up to 32 queries per stream of the codes
+ * (the most of 32 / 16 / 8 / 4 whose images fit the 160 KB of LDS).
+ * Contract.  Let R_q be the ids the range call returns for query q at d_threshold[q] (same tables, codes, mask, scales),
+ * O_q the ids of this call, A the allowed rows.
+ *   Sound, unconditionally: R_q is a subset of O_q, O_q of A.  A row is left out only when the integer sum proves that
+ *   its exact f32 value -- the sequential chain over m from +0, as pqhip_adc_scan_f32_dev defines it -- misses the
+ *   threshold; whatever the proof does not cover is returned: a NaN or infinite entry in the query's tables, entries whose
+ *   largest magnitudes sum beyond 2^126, a NaN threshold, a negative, NaN or infinite scale.  (An infinite threshold
+ *   needs no proof: over finite tables -Inf, ip +Inf, returns nothing and the opposite one every allowed row.)
+ *   Tight on regular rows: a row is returned only if its value v satisfies v <= thr + slack (ip 0) resp. v >= thr - slack
+ *   (ip 1 without scales), slack = M s + 2 E + 2^-39 (|thr| + |base|), s = (|thr - base| + E) / 254 at least,
+ *   E = kAdcScreenRel M sum_m max_k |t[m][k]| + kAdcScreenAbs, base the sum of the lo_m.  With scales the comparison is
+ *   made per (row, query) in f32 on an upper bound of v widened by 2^-22, and s spans the sums from thr / max scale up.
+ *   The bound is derived in DESIGN.md section 5e; its constants are kAdcScreen* of kernels_adc_screen.hip.h.
+ * Output, order and capacity: d_lims [n_queries + 1] int64 and d_idx (int64) of `capacity` entries; the ids of a query
+ * ascend; the capacity protocol is exactly that of the range calls (true counts always, only slots < capacity written,
+ * capacity == 0 a count call with d_idx NULL).  The count pass leaves the hit bitmap in the codebook's scratch (8 bytes
+ * per 64 rows and query slot of a pass); the fill pass turns bitmaps into ids and does not read the codes.
+ * A function of the inputs alone: the result depends neither on the grid (option "adc_screen_wgs") nor on how queries
+ * are grouped into passes.  Memory: the row fetch of the searches (no byte outside the code matrix is read, rows at any
+ * address); a disallowed row is not loaded.  A code >= K raises the range flag (pqhip_check_codes_dev) and reads entry 0.
+ * Status codes, in the precedence of the range call: null cb, n_queries < 0, n_rows < 0, capacity < 0, ip not 0 / 1,
+ * d_scales with ip 0: PQHIP_EINVAL; code_bytes not 1, M > 100 (the row fetch of the searches; the sums themselves
+ * hold for M <= 257), a quantizer of which four images do not fit the LDS: PQHIP_EUNSUPPORTED -- callers take the plain
+ * call; with n_queries > 0 a null d_lims or d_threshold, a null d_idx with capacity > 0, null d_tables or d_codes with
+ * n_rows > 0: PQHIP_EINVAL; codes_row_stride < M: PQHIP_ESHAPE.  n_queries == 0 launches nothing; n_rows == 0 writes
+ * all-zero lims.  Asynchronous on `stream`; per pass: the prep kernel, the count pass, the prefix scan of the range
+ * calls, the fill pass (none for a count call); with d_scales one reduction over them in front.
+ */
+int32_t pqhip_adc_screen_f32_dev(pqhip_codebook *cb, int32_t device_slot,
+                                 const float *d_tables /* [n_queries][M][K] */, int64_t n_queries,
+                                 const void *d_codes, int32_t code_bytes, int64_t n_rows, int64_t codes_row_stride,
+                                 const uint32_t *d_allow /* ceil(n_rows / 32) words or NULL */,
+                                 int32_t ip /* 0 = distance tables, 1 = inner-product tables */,
+                                 const float *d_scales /* ip 1: [n_rows] or NULL */,
+                                 const float *d_threshold /* [n_queries] */, int64_t *d_lims, int64_t *d_idx,
+                                 int64_t capacity, void *stream);
+
+/*
  * The range screen of pqhip_flat_screen_f32_dev in PROBED LISTS: for a batch of queries, per query a superset of what
  * pqhip_flat_range_lists_f32_dev returns at the same thresholds, as positions (CSR, no values) -- the first stage of the
  * exact list searches for query batches (resolve with pqhip_flat_range_among_f32_dev / pqhip_flat_among_f32_dev).  The work
@@ -1291,6 +1338,9 @@ int32_t pqhip_set_rotation_variant(int32_t variant);
  *   "flat_screen_lists_unit_rows"  rows of a unit of that call, rounded up to a multiple of 32 (0 = 1024)
  *   "flat_screen_lists_chunk_queries"  queries of a chunk of that call (0 = from the scratch bound; at most 2^20 / n_probe);
  *                          the result depends on none of the three
+ *   "adc_screen_wgs"       producer workgroups of pqhip_adc_screen_f32_dev (0 = one per CU; at most 2048, so that the
+ *                          prefix scan of a pass of 32 queries sums at most 2^20 counts; rows per workgroup stay a
+ *                          multiple of 1,024; the result does not depend on it)
  *   "cross_product_exact" 0 = X^T.R of the OPQ training step / pqhip_at_dot_b_f32_dev as a plain split-K product:
  *                          within 1e-5 relative of the exact rule-2 result, no per-block partial matrices (default 1)
  *   "cross_product_group_bytes"  workspace of partial matrices per launch group (0 = 4 GiB)

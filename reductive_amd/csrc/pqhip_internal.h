@@ -113,6 +113,7 @@ struct Options {
     std::atomic<int64_t> flat_among_wgs_per_query{0};   // exact search among given rows: workgroups per query (0: chosen from the named bytes)
     std::atomic<int64_t> flat_range_among_wgs_per_query{0};   // exact range search among given rows: workgroups per query (0: as above)
     std::atomic<int64_t> flat_screen_wgs{0};        // range screen over resident vectors: producer workgroups (0: two per CU)
+    std::atomic<int64_t> adc_screen_wgs{0};         // range screen over resident codes: producer workgroups (0: one per CU)
     std::atomic<int64_t> flat_screen_lists_wgs{0};  // range screen in probed lists: workgroups that stride over the units (0: four per CU)
     std::atomic<int64_t> flat_screen_lists_unit_rows{0};      // ... rows of a unit, a multiple of 32 (0: 1,024)
     std::atomic<int64_t> flat_screen_lists_chunk_queries{0};  // ... queries of a chunk (0: from the scratch bound)

@@ -1284,6 +1284,143 @@ class Pq:
         score with its sign (pqhip_adc_ip_range_f32_dev).  Threshold -Inf returns every non-NaN row."""
         return self._adc_range(True, codes, tables, threshold, scales, stream, check, allow, capacity)
 
+    # ---- ADC search for query batches: u8 table screen, exact resolve ------------------------------------------------
+    def _adc_screen_args(self, codes, tables, ip, scales, allow):
+        """What the screen and its composition check and marshal (codes, tables, scales and mask as for the range calls)
+        -> (codes, n, row stride, nq, the mask argument)."""
+        import torch
+        if not (hasattr(codes, "is_cuda") and codes.dtype == torch.uint8 and codes.dim() == 2):
+            raise PanicError("codes must be a uint8 [n, n_subquantizers] tensor (4-byte and packed codes are not served)")
+        if not (hasattr(tables, "is_cuda") and tables.dtype == torch.float32 and tables.dim() in (2, 3) and tables.is_contiguous()):
+            raise PanicError("lookup tables must be a contiguous float32 tensor")
+        if scales is not None and not ip:
+            raise PanicError("scales belong to the inner-product form")
+        M, K = self.quantized_len(), self.n_quantizer_centroids()
+        W = _marshal.code_width(codes, M)
+        _, nq = _marshal.tables_arg(tables, M, K)
+        if not (codes.is_cuda and tables.is_cuda and tables.device == codes.device):
+            raise PanicError("codes and tables must be CUDA tensors on one device")
+        codes, n, c_rs = _marshal.codes_arg(codes, W)
+        _marshal.per_row_arg(scales, n, "scales")
+        allow = _marshal.vector_mask_words(allow, n)
+        if allow is not None and not allow.is_cuda:
+            raise PanicError("the row mask must be a CUDA tensor")
+        return codes, n, c_rs, nq, _marshal.mask_arg(allow, codes, True)
+
+    def _adc_screen(self, codes, tables, threshold, ip, scales, allow, cap, stream, retry):
+        """One screen call with `cap` entries and, if retry and the result is larger, one more of exactly its size
+        -> (lims, idx[:min(total, cap)], total, launch); lims[-1] is read in between, the one synchronisation."""
+        import torch
+        codes, n, c_rs, nq, mask = self._adc_screen_args(codes, tables, ip, scales, allow)
+        dev = codes.device
+        thr = _marshal.threshold_arg(threshold, nq, dev)
+        cap = int(cap)
+        if cap < 0:
+            raise PanicError("capacity must not be negative")
+        own_stream = stream is None
+        cb, slot, sp = _marshal.launch(self, codes, stream)
+        head = _marshal.search_head(cb, slot, tables, nq, codes, n, c_rs, False, mask, last=(1 if ip else 0, ptr_or_none(scales)))
+        lims = torch.empty(nq + 1, dtype=torch.int64, device=dev)
+        while True:
+            idx = torch.empty(cap, dtype=torch.int64, device=dev)
+            _marshal.run("pqhip_adc_screen_f32_dev", *head, thr.data_ptr(), lims.data_ptr(), ptr_or_none(idx, cap), cap, sp)
+            if not own_stream:
+                torch.cuda.ExternalStream(stream, device=dev).synchronize()
+            total = int(lims[-1])
+            if total <= cap or not retry:
+                break
+            cap = total             # the second call always suffices
+        return lims, idx[:min(total, cap)], total, (cb, slot, sp)
+
+    def adc_screen_device(self, codes, tables, threshold, ip=False, scales=None, allow=None, capacity=None, stream=None,
+                          check=False):
+        """Conservative range screen over resident u8 codes (pqhip_adc_screen_f32_dev): codes, tables, threshold, scales
+        and allow as for adc_range_device (ip=False) resp. adc_ip_range_device (ip=True) -> (lims, idx): CSR, lims CUDA
+        int64 [nq + 1], the ids of query q at idx[lims[q]:lims[q + 1]] in ascending order -- a SUPERSET of what the range
+        call returns at the same thresholds, within the allowed rows: a row is left out only when an exact integer sum
+        over a u8 image of the tables proves that its f32 value misses the threshold, and a regular row is returned only
+        within the slack the header states.  Up to 32 queries share one stream of the codes.  The capacity protocol is
+        adc_range_device's: one call with `capacity` entries (default 1 << 20), one read of lims[-1] -- the one
+        synchronisation -- and one more call of exactly its size if the result is larger; capacity=0 counts first.
+        A quantizer whose images do not fit the LDS raises PqHipError (PQHIP_EUNSUPPORTED).  check=True synchronises
+        and reports a code >= K."""
+        lims, idx, _, (cb, slot, sp) = self._adc_screen(codes, tables, threshold, ip, scales, allow,
+                                                        (1 << 20) if capacity is None else capacity, stream, True)
+        if check:
+            _marshal.check_range(cb, slot, sp)
+        return lims, idx
+
+    def adc_search_batch_device(self, codes, tables, k, ip=False, scales=None, allow=None, stream=None, check=False,
+                                stats=None):
+        """adc_search_device (ip=False) resp. adc_ip_search_device (ip=True) for a batch of queries, bit for bit in
+        values and ids, at one stream of the codes per up to 32 queries.  Sample: every t-th row (flat_batch_sample; -1
+        where the mask disallows it) through adc_among_device / adc_ip_among_device; T_q, its k-th value, is a valid
+        threshold whatever the sample -- k rows have a value at or below (ip: at or above) it, so every member of the
+        true top-k has.  Screen at T_q (adc_screen_device): a superset of those rows.  Resolve: the candidate call over
+        the screen's ids, which is the masked search on a superset of its result.  A query whose sample holds fewer
+        than k numbers, a chunk of queries whose candidates exceed FLAT_BATCH_FALLBACK_FRACTION of n nq
+        (flat_batch_falls_back) and a quantizer the screen does not serve (PQHIP_EUNSUPPORTED) take the plain call.
+        stats: a dict that receives the candidate total, the queries that fell back and the sample size."""
+        import torch
+        k = int(k)
+        if not 1 <= k <= 1024:
+            raise PanicError("k must be between 1 and 1024, was %d" % k)
+        self._adc_screen_args(codes, tables, ip, scales, allow)   # before the mask is indexed for the sample
+        kw = {"scales": scales} if ip else {}
+        among = self.adc_ip_among_device if ip else self.adc_among_device
+        plain_call = self.adc_ip_search_device if ip else self.adc_search_device
+        single = tables.dim() == 2
+        t3 = tables[None] if single else tables
+        nq, N = t3.shape[0], codes.shape[0]
+        dev = codes.device
+        if N == 0 or nq == 0:
+            return plain_call(codes, tables, k, stream=stream, check=check, allow=allow, **kw)
+        S, t = flat_batch_sample(N, k)
+        ids = torch.arange(0, N, t, dtype=torch.int64, device=dev)
+        if allow is not None:
+            bit = (allow[ids >> 5] >> (ids & 31).to(torch.int32)) & 1
+            ids = torch.where(bit != 0, ids, torch.full_like(ids, -1))
+        try:
+            sval, sidx = among(codes, t3, ids, k, stream=stream, **kw)
+        except _lib.PqHipError as e:
+            if e.status != _lib.EUNSUPPORTED:
+                raise
+            if stats is not None:                                # the candidate call does not serve this quantizer
+                stats.update(candidates=0, fallback_queries=nq, sample=0)
+            return plain_call(codes, tables, k, stream=stream, check=check, allow=allow, **kw)
+        T = sval[:, k - 1]
+        thin = (sidx[:, k - 1] < 0) | torch.isnan(T)
+        nothing = float("inf") if ip else float("-inf")          # a thin query takes the plain call
+        thr = torch.where(thin, torch.full_like(T, nothing), T)
+        val = torch.empty((nq, k), dtype=torch.float32, device=dev)
+        idx = torch.empty((nq, k), dtype=torch.int64, device=dev)
+        plain = thin.clone()
+        total_all = 0
+        for q0 in range(0, nq, FLAT_BATCH_CHUNK):
+            q1 = min(nq, q0 + FLAT_BATCH_CHUNK)
+            cap = flat_batch_capacity(N, q1 - q0, k, S)
+            try:
+                lims, cand, total, _ = self._adc_screen(codes, t3[q0:q1], thr[q0:q1], ip, scales, allow, cap, stream, False)
+            except _lib.PqHipError as e:
+                if e.status != _lib.EUNSUPPORTED:
+                    raise
+                plain[:] = True                                  # the screen does not serve this quantizer
+                break
+            total_all += total
+            if flat_batch_falls_back(total, N, q1 - q0):
+                plain[q0:q1] = True
+                continue
+            val[q0:q1], idx[q0:q1] = among(codes, t3[q0:q1], cand, k, lims=lims, stream=stream, **kw)
+        rows = torch.nonzero(plain).reshape(-1)
+        if rows.shape[0] > 0:
+            val[rows], idx[rows] = plain_call(codes, t3[rows].contiguous(), k, stream=stream, allow=allow, **kw)
+        if stats is not None:
+            stats.update(candidates=total_all, fallback_queries=int(rows.shape[0]), sample=int(ids.shape[0]))
+        if check:
+            cb, slot, sp = _marshal.launch(self, codes, stream)
+            _marshal.check_range(cb, slot, sp)
+        return (val[0], idx[0]) if single else (val, idx)
+
     def adc_range_lists_device(self, codes, tables, list_off, probes, threshold, stream=None, check=False, allow=None,
                                capacity=None):
         """adc_range_device restricted, per query, to the rows of the probed lists (list_off, probes as for

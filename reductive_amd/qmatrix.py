@@ -675,21 +675,36 @@ class QuantizedMatrix(_Refine, _Filter, _Packed4, _Search, _Among, _Compact):
             fn = pq.adc_range_device if ranged else pq.adc_search_device
         return fn, self._tables(ip, queries), ()
 
-    def nearest(self, queries, k, refine=None, allow=None):
+    def _topk_screened(self, ip, queries, k, use_norms, refine, allow):
+        """_topk by the route for query batches (Pq.adc_search_batch_device); the shortlist R replaces k"""
+        self._unpacked_only("most_similar(screen=True)" if ip else "nearest(screen=True)")
+        R = k if refine is None else self._check_refine(k, refine)
+        kw = {"scales": self.norms if use_norms else None} if ip else {}
+        val, rows = self.pq.adc_search_batch_device(self.codes, self._tables(ip, queries), R, ip=ip,
+                                                    allow=self._allow_words(allow), **kw)
+        return (val, rows) if refine is None else self._refined(queries, rows, k, ip)
+
+    def nearest(self, queries, k, refine=None, allow=None, screen=False):
         """the k rows of smallest asymmetric squared distance (adc_search_device over all rows), ties to the smaller
         row -> (dist, idx) [k] or [nq, k].  refine=R (k <= R <= 1024, vectors attached): the R nearest rows by that
         estimate are re-ranked by their exact squared distance to the attached vectors (Pq.rerank_device) on the
         device; dist are then the exact distances.  allow: None, a RowFilter of this matrix (row_filter) or a bool
         array [N] packed on the spot -- only allowed rows are ranked, exactly as if the others were not stored (index
-        -1 past the last allowed row); with refine= the shortlist holds allowed rows only."""
+        -1 past the last allowed row); with refine= the shortlist holds allowed rows only.  screen=True: the route for
+        query batches (Pq.adc_search_batch_device: u8 table screen, exact resolve), the same result bit for bit; not
+        served on a packed matrix."""
+        if screen:
+            return self._topk_screened(False, queries, k, True, refine, allow)
         return self._topk(False, queries, k, None, True, refine, allow)
 
-    def most_similar(self, queries, k, use_norms=True, refine=None, allow=None):
+    def most_similar(self, queries, k, use_norms=True, refine=None, allow=None, screen=False):
         """the k rows of largest inner product with what embeddings() returns (the stored vectors, unscaled, with
         use_norms=False or without norms), largest first, ties to the smaller row -> (score, idx) [k] or [nq, k].
         refine=R (k <= R <= 1024, vectors attached): the R most similar rows by that estimate are re-ranked by their
         exact inner product with the attached vectors as they are; use_norms then only affects the candidate stage.
-        allow: as for nearest()."""
+        allow: as for nearest(); screen: as for nearest()."""
+        if screen:
+            return self._topk_screened(True, queries, k, use_norms, refine, allow)
         return self._topk(True, queries, k, None, use_norms, refine, allow)
 
     def within(self, queries, radius, allow=None, sort=False):

@@ -223,6 +223,16 @@ extern "C" {
         q_row_stride: i64, d_vectors: *const c_void, vec_bytes: i32, n_rows: i64, d: i64, vec_row_stride: i64,
         d_allow: *const u32, metric: i32, x_exp: i32, d_threshold: *const f32, d_lims: *mut i64, d_idx: *mut i64,
         capacity: i64, stream: *mut c_void) -> i32;
+    // conservative range screen over resident u8 codes with u8 table images, for query batches: per query a superset of
+    // what pqhip_adc_range_f32_dev (ip 0) resp. pqhip_adc_ip_range_f32_dev (ip 1, d_scales or null) returns at
+    // d_threshold, as ascending ids (CSR without values; the capacity protocol of the range calls); a row is left out only
+    // when an exact integer sum proves that its f32 value misses the threshold; up to 32 queries per stream of the codes;
+    // PQHIP_EUNSUPPORTED where four images do not fit the LDS; option "adc_screen_wgs" forces the grid, on which the
+    // result does not depend
+    pub fn pqhip_adc_screen_f32_dev(cb: *mut pqhip_codebook, device_slot: i32, d_tables: *const f32, n_queries: i64,
+        d_codes: *const c_void, code_bytes: i32, n_rows: i64, codes_row_stride: i64, d_allow: *const u32, ip: i32,
+        d_scales: *const f32, d_threshold: *const f32, d_lims: *mut i64, d_idx: *mut i64, capacity: i64,
+        stream: *mut c_void) -> i32;
     // the same screen in probed lists: per query a superset of what pqhip_flat_range_lists_f32_dev returns, as positions
     // in that call's order (probe slot first, then position); list-major on the device, d <= 2048
     pub fn pqhip_flat_screen_lists_f32_dev(cb: *mut pqhip_codebook, device_slot: i32, d_queries: *const f32, n_queries: i64,
