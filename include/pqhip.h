@@ -985,6 +985,48 @@ int32_t pqhip_flat_screen_lists_f32_dev(pqhip_codebook *cb, int32_t device_slot,
                                         int64_t capacity, void *stream);
 
 /*
+ * The u8 table screen of pqhip_adc_screen_f32_dev in PROBED LISTS: for a batch of queries, per query a superset of what
+ * pqhip_adc_range_lists_f32_dev (ip 0) resp. pqhip_adc_ip_range_lists_f32_dev (ip 1, with the same d_scales) returns at
+ * the same thresholds, as positions (CSR, no values) -- the first stage of the ADC list searches for query batches
+ * (resolve with pqhip_adc_among_f32_dev / pqhip_adc_ip_among_f32_dev).  The work is list-major: the probe table of a
+ * chunk of queries is inverted on the device, and a list that several queries probe is streamed once per group of up to
+ * 32 of them (the most of 32 / 16 / 8 / 4 whose images fit the 160 KB of LDS).  Arguments: those of
+ * pqhip_adc_ip_range_lists_f32_dev without d_val, and the ip flag in front of d_scales (which must be NULL for ip 0).
+ * Contract.  R_q: the positions the range call returns for query q at d_threshold[q]; S_q: the allowed rows of q's
+ * probed lists; O_q: this call's output.  Sound, unconditionally: R_q within O_q within S_q.  Tight: a regular row is
+ * returned only within the slack stated at pqhip_adc_screen_f32_dev -- the image, the limit and the step of a query
+ * depend on its tables, its threshold and the call-wide largest scale alone, and the sum of a (row, query) is an exact
+ * integer, so the bound of DESIGN.md section 5e holds unchanged (section 5f).  Whatever the proof does not cover is
+ * returned: a NaN or infinite table entry, magnitudes that sum beyond 2^126, a NaN threshold, a negative, NaN or
+ * infinite scale.
+ * Order and capacity: d_lims [n_queries + 1], d_idx positions; within a query probe slot first, then ascending position
+ * -- the order of the list range calls; a list named twice returns its rows twice.  The capacity protocol is that of the
+ * range calls (true counts always, only slots < capacity written, capacity == 0 a count call with d_idx NULL).
+ * Probes and offsets: -1 is padding; any other id outside [0, n_lists) is skipped and raises the stream's range flag;
+ * list ranges are clamped to [0, n_codes], inverted ranges are empty, both raise the flag.  No byte of an unprobed or
+ * disallowed row is loaded and no byte outside the code matrix; a code >= K in a row that is read reads entry 0 and
+ * raises the flag.
+ * A function of the inputs alone: the result depends neither on the grid ("adc_screen_lists_wgs"), nor on how a list's
+ * rows are cut into units ("adc_screen_lists_unit_rows"), nor on how queries fall into groups or chunks
+ * ("adc_screen_lists_chunk_queries").  The only atomics are integer counts and cursors.
+ * Status codes, in the precedence of pqhip_flat_screen_lists_f32_dev: PQHIP_EINVAL (null cb, negative counts,
+ * n_probe < 1, ip not 0 / 1, d_scales with ip 0), PQHIP_ENODEV, PQHIP_EUNSUPPORTED (code_bytes not 1, M > 100, a
+ * quantizer of which four images do not fit the LDS, n_codes > 2^32 - 2, n_probe > 2^20), then with n_queries > 0 the
+ * null pointers (PQHIP_EINVAL) and the strides (PQHIP_ESHAPE).  n_queries == 0 launches nothing; n_codes == 0 or
+ * n_lists == 0 writes all-zero lims.
+ */
+int32_t pqhip_adc_screen_lists_f32_dev(pqhip_codebook *cb, int32_t device_slot,
+                                       const float *d_tables /* [n_queries][M][K] */, int64_t n_queries,
+                                       const void *d_codes, int32_t code_bytes, int64_t n_codes, int64_t codes_row_stride,
+                                       const uint32_t *d_allow /* position order, or NULL */,
+                                       const int64_t *d_list_off /* [n_lists + 1] */, int64_t n_lists,
+                                       const int64_t *d_probes, int32_t n_probe, int64_t probes_row_stride,
+                                       int32_t ip /* 0 = distance tables, 1 = inner-product tables */,
+                                       const float *d_scales /* ip 1: [n_codes] or NULL */,
+                                       const float *d_threshold /* [n_queries] */, int64_t *d_lims, int64_t *d_idx,
+                                       int64_t capacity, void *stream);
+
+/*
  * Merge of two list-ordered row arrays: the primitive under growing a partitioned matrix (rows added to an index, two
  * indexes over the same lists joined).  d_a is [n_a] rows of row_bytes bytes in list order under d_off_a [n_lists + 1]
  * (list l = rows off_a[l] .. off_a[l + 1] - 1), d_b likewise [n_b] rows under d_off_b; d_out is [n_a + n_b] rows.  For
@@ -1341,6 +1383,10 @@ int32_t pqhip_set_rotation_variant(int32_t variant);
  *   "adc_screen_wgs"       producer workgroups of pqhip_adc_screen_f32_dev (0 = one per CU; at most 2048, so that the
  *                          prefix scan of a pass of 32 queries sums at most 2^20 counts; rows per workgroup stay a
  *                          multiple of 1,024; the result does not depend on it)
+ *   "adc_screen_lists_wgs"  workgroups of pqhip_adc_screen_lists_f32_dev that stride over its units (0 = one per CU)
+ *   "adc_screen_lists_unit_rows"  rows of a unit of that call, rounded up to a multiple of 64 (0 = 16384)
+ *   "adc_screen_lists_chunk_queries"  queries of a chunk of that call (0 = from the scratch bound; at most 2^20 / n_probe);
+ *                          the result depends on none of the three
  *   "cross_product_exact" 0 = X^T.R of the OPQ training step / pqhip_at_dot_b_f32_dev as a plain split-K product:
  *                          within 1e-5 relative of the exact rule-2 result, no per-block partial matrices (default 1)
  *   "cross_product_group_bytes"  workspace of partial matrices per launch group (0 = 4 GiB)

@@ -96,22 +96,21 @@ inline __global__ __launch_bounds__(256) void k_adc_screen_scale_max(const float
     if ((threadIdx.x & 63) == 0 && m) atomicMax(out, m);
 }
 
-// The image column and the parameters of one query slot per workgroup; slots >= nq_pass are padding (zeros, nothing
-// returned).  Wave w takes the subquantizers w, w + 4, ..; minima and maxima do not depend on the order.  The sums over
-// m are one thread's, in ascending m.  img [M][K][NQ] bytes, prm [NQ].
-inline __global__ __launch_bounds__(kAsPrepThreads) void k_adc_screen_prep(const float* __restrict__ tables, int nq_pass, int M, int K, int NQ,
-                                                                    const float* __restrict__ thr, int ip, int scaled,
-                                                                    const unsigned* __restrict__ cmax_bits,
-                                                                    uint8_t* __restrict__ img, AdcScreenPrm* __restrict__ prm)
+// The image and the parameters of one query slot, by one workgroup of kAsPrepThreads: the body of both prep kernels, so
+// that a query has the same image and parameters wherever it is screened.  A slot that is not `real` is padding (zeros,
+// nothing returned; tq and thr are then not dereferenced).  Wave w takes the subquantizers w, w + 4, ..; minima and
+// maxima do not depend on the order.  The sums over m are one thread's, in ascending m.  Entry i = m K + k goes to
+// dst[i dst_stride].
+__device__ __forceinline__ void adc_screen_prep_slot(const float* __restrict__ tq, bool real, int M, int K, const float* __restrict__ thr,
+                                                     int ip, int scaled, const unsigned* __restrict__ cmax_bits,
+                                                     uint8_t* __restrict__ dst, size_t dst_stride, AdcScreenPrm* __restrict__ prm)
 {
     __shared__ float s_lo[kAdcScreenMaxM], s_hi[kAdcScreenMaxM], s_am[kAdcScreenMaxM];
     __shared__ int s_bad, s_live;
     __shared__ double s_step;
-    const int slot = blockIdx.x, t = threadIdx.x, wave = t >> 6, lane = t & 63;
-    const bool real = slot < nq_pass;
+    const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
     const float sg = ip ? -1.f : 1.f;
     const float inf = __builtin_inff();
-    const float* tq = tables + (size_t)slot * M * K;                // dereferenced only for a real slot
     if (t == 0) { s_bad = 0; s_live = 0; s_step = 1.0; }
     __syncthreads();
     if (real) {
@@ -139,7 +138,7 @@ inline __global__ __launch_bounds__(kAsPrepThreads) void k_adc_screen_prep(const
     }
     __syncthreads();
     if (t == 0) {
-        AdcScreenPrm p{-1, 0.f, 0.f, real ? thr[slot] : 0.f};
+        AdcScreenPrm p{-1, 0.f, 0.f, real ? *thr : 0.f};
         if (real) {
             p.ulim = kAdcScreenKeepAll;
             double sum = 0.0, absum = 0.0, A = 0.0, spread = 0.0;
@@ -186,7 +185,7 @@ inline __global__ __launch_bounds__(kAsPrepThreads) void k_adc_screen_prep(const
                 }
             }
         }
-        prm[slot] = p;
+        *prm = p;
     }
     __syncthreads();
     const bool live = s_live != 0;
@@ -200,8 +199,20 @@ inline __global__ __launch_bounds__(kAsPrepThreads) void k_adc_screen_prep(const
             const double qv = x / step * (1.0 - kAdcScreenF64);
             u = qv >= 255.0 ? (uint8_t)255 : (uint8_t)(int)qv;
         }
-        img[(size_t)i * NQ + slot] = u;
+        dst[(size_t)i * dst_stride] = u;
     }
+}
+
+// One query slot per workgroup, into the image of a pass: img [M][K][NQ] bytes, interleaved by query, prm [NQ]; slots
+// >= nq_pass are padding.
+inline __global__ __launch_bounds__(kAsPrepThreads) void k_adc_screen_prep(const float* __restrict__ tables, int nq_pass, int M, int K, int NQ,
+                                                                    const float* __restrict__ thr, int ip, int scaled,
+                                                                    const unsigned* __restrict__ cmax_bits,
+                                                                    uint8_t* __restrict__ img, AdcScreenPrm* __restrict__ prm)
+{
+    const int slot = blockIdx.x;
+    adc_screen_prep_slot(tables + (size_t)slot * M * K, slot < nq_pass, M, K, thr + slot, ip, scaled, cmax_bits, img + slot, (size_t)NQ,
+                         prm + slot);
 }
 
 template <int ND>
@@ -219,6 +230,64 @@ __device__ __forceinline__ void adc_screen_entry(const uint8_t* p, unsigned (&d)
     } else {
         d[0] = *reinterpret_cast<const unsigned*>(p);
     }
+}
+
+// The integer sums of one row (fetched by adc_fetch_row, shift sh = a & 3) against the interleaved image lm [M][K][4 ND]
+// in LDS, KQ = 4 ND K: per dword j of an entry the packed u16 sums of its bytes 0, 2 (even[j]) and 1, 3 (odd[j]).  A code
+// >= K sets `bad` and reads entry 0.  The count passes of the exhaustive and of the list screen share it.
+template <int NV, int ND>
+__device__ __forceinline__ void adc_screen_row_sums(const unsigned (&w)[NV + 1], unsigned sh, const uint8_t* lm, int M, int K, int KQ,
+                                                    bool& bad, unsigned (&even)[ND], unsigned (&odd)[ND])
+{
+    as_u16x2 acc_a[ND], acc_h[ND];
+#pragma unroll
+    for (int j = 0; j < ND; ++j) { acc_a[j] = (as_u16x2){0, 0}; acc_h[j] = (as_u16x2){0, 0}; }
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+        const unsigned v = __builtin_amdgcn_alignbyte(w[k + 1], w[k], sh);   // bytes 4k .. 4k+3 of the row
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            if (4 * k + e < M) {
+                unsigned c = (v >> (8 * e)) & 0xffu;
+                if (c >= (unsigned)K) { bad = true; c = 0; }
+                unsigned d[ND];
+                adc_screen_entry<ND>(lm + c * (4 * ND), d);
+#pragma unroll
+                for (int j = 0; j < ND; ++j) {
+                    const as_u16x2 x = __builtin_bit_cast(as_u16x2, d[j]);
+                    acc_a[j] += x;
+                    acc_h[j] += x >> (as_u16x2){8, 8};
+                }
+                lm += KQ;
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < ND; ++j) {
+        even[j] = __builtin_bit_cast(unsigned, (as_u16x2)(acc_a[j] - (acc_h[j] << (as_u16x2){8, 8})));
+        odd[j] = __builtin_bit_cast(unsigned, acc_h[j]);
+    }
+}
+
+// U of query slot q (a constant after unrolling) from the packed sums
+template <int ND>
+__device__ __forceinline__ int adc_screen_sum_of(const unsigned (&even)[ND], const unsigned (&odd)[ND], int q)
+{
+    const unsigned pair = (q & 1) ? odd[q >> 2] : even[q >> 2];
+    return (int)((q & 2) ? pair >> 16 : pair & 0xffffu);
+}
+
+// Is a row with integer sum U and scale sc returned for the query of p?  (p is wave-uniform.)
+__device__ __forceinline__ bool adc_screen_keep(int U, const AdcScreenPrm& p, float sc)
+{
+    bool keep = U <= p.ulim;
+    if (p.ulim == kAdcScreenPerRow) {
+        const float wv = __builtin_fmaf(-p.s, (float)U, p.b);
+        const float wu = fadd(__builtin_fmaf(__builtin_fabsf(wv), 0x1p-22f, wv), 0x1p-100f);
+        const float pv = fmul(wu, sc);
+        keep = !(sc >= 0.f && sc < __builtin_inff() && pv < p.thr);   // NaN anywhere: not proved, returned
+    }
+    return keep;
 }
 
 // The count pass, NQ query slots per pass.  Workgroup b owns rows [b rows_per_wg, (b + 1) rows_per_wg) (rows_per_wg a
@@ -257,7 +326,6 @@ __global__ __launch_bounds__(1024) void k_adc_screen_u8(const uint8_t* __restric
     const uintptr_t lo = reinterpret_cast<uintptr_t>(codes);
     const uintptr_t hi = lo + (uintptr_t)((n - 1) * c_rs + M);      // one past the last code byte
     const int KQ = K * NQ;
-    const float inf = __builtin_inff();
     int64_t cnt = 0;                                                // lane q < nq_pass: the unit's hits of query q
     bool bad = false;
     for (int64_t b0 = row_begin; b0 < row_end; b0 += 64) {          // wave-uniform: the ballots are wave-wide
@@ -273,50 +341,12 @@ __global__ __launch_bounds__(1024) void k_adc_screen_u8(const uint8_t* __restric
             const uintptr_t a = lo + (uintptr_t)(row * c_rs);
             unsigned w[NW];
             adc_fetch_row<NW>(a, lo, hi, M, w);
-            const unsigned sh = (unsigned)(a & 3);
-            as_u16x2 acc_a[ND], acc_h[ND];
-#pragma unroll
-            for (int j = 0; j < ND; ++j) { acc_a[j] = (as_u16x2){0, 0}; acc_h[j] = (as_u16x2){0, 0}; }
-            const uint8_t* lm = lds_u;
-#pragma unroll
-            for (int k = 0; k < NV; ++k) {
-                const unsigned v = __builtin_amdgcn_alignbyte(w[k + 1], w[k], sh);   // bytes 4k .. 4k+3 of the row
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    if (4 * k + e < M) {
-                        unsigned c = (v >> (8 * e)) & 0xffu;
-                        if (c >= (unsigned)K) { bad = true; c = 0; }
-                        unsigned d[ND];
-                        adc_screen_entry<ND>(lm + c * NQ, d);
-#pragma unroll
-                        for (int j = 0; j < ND; ++j) {
-                            const as_u16x2 x = __builtin_bit_cast(as_u16x2, d[j]);
-                            acc_a[j] += x;
-                            acc_h[j] += x >> (as_u16x2){8, 8};
-                        }
-                        lm += KQ;
-                    }
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < ND; ++j) {
-                even[j] = __builtin_bit_cast(unsigned, (as_u16x2)(acc_a[j] - (acc_h[j] << (as_u16x2){8, 8})));
-                odd[j] = __builtin_bit_cast(unsigned, acc_h[j]);
-            }
+            adc_screen_row_sums<NV, ND>(w, (unsigned)(a & 3), lds_u, M, K, KQ, bad, even, odd);
         }
         unsigned long long mine = 0ull;                             // lane q: the hit word of query q
 #pragma unroll
         for (int q = 0; q < NQ; ++q) {
-            const unsigned pair = (q & 1) ? odd[q >> 2] : even[q >> 2];
-            const int U = (int)((q & 2) ? pair >> 16 : pair & 0xffffu);
-            const AdcScreenPrm p = prm[q];
-            bool keep = U <= p.ulim;
-            if (p.ulim == kAdcScreenPerRow) {                       // wave-uniform
-                const float wv = __builtin_fmaf(-p.s, (float)U, p.b);
-                const float wu = fadd(__builtin_fmaf(__builtin_fabsf(wv), 0x1p-22f, wv), 0x1p-100f);
-                const float pv = fmul(wu, sc);
-                keep = !(sc >= 0.f && sc < inf && pv < p.thr);      // NaN anywhere: not proved, returned
-            }
+            const bool keep = adc_screen_keep(adc_screen_sum_of<ND>(even, odd, q), prm[q], sc);
             const unsigned long long bl = __ballot(valid && keep && q < nq_pass);
             if (lane == q) mine = bl;
         }

@@ -45,6 +45,17 @@ namespace pqhip {
 constexpr int kFslPlanThreads = 256;
 constexpr int64_t kFslMaxEntries = 1 << 20;     // (query, slot) entries of a chunk: what one scan launch sums
 
+// Hit words of one query of a chunk (host): twice what a query probes when the lists are equally long -- n_rows
+// min(n_probe, n_lists) / n_lists rows in tiles of 32, one partial tile per slot -- and never more than n_probe whole
+// matrices.  The budget of a chunk is the sum over its queries: what a query leaves, another may take.
+inline int64_t fsl_words_per_query(int64_t n_rows, int64_t n_lists, int64_t n_probe)
+{
+    const double frac = (double)(n_probe < n_lists ? n_probe : n_lists) / (double)n_lists;
+    const int64_t expected = (int64_t)((double)n_rows * frac / kFsTile) + 1 + n_probe;
+    const int64_t most = n_probe * (n_rows / kFsTile + 1);
+    return 2 * expected < most ? 2 * expected : most;
+}
+
 // list l as the list calls read it: clamped to [0, n], an inverted range empty; bad: the flag is due
 struct FslRange {
     int64_t lo, hi;
@@ -58,7 +69,7 @@ __device__ __forceinline__ FslRange fsl_list_range(const int64_t* __restrict__ l
     return {cl, ch > cl ? ch : cl, cl != lo || ch != hi || hi < lo};
 }
 
-__global__ __launch_bounds__(kFslPlanThreads) void k_fsl_pairs(const int64_t* __restrict__ list_off, int64_t n_lists,
+inline __global__ __launch_bounds__(kFslPlanThreads) void k_fsl_pairs(const int64_t* __restrict__ list_off, int64_t n_lists,
                                                                const int64_t* __restrict__ probes, int n_probe, int64_t p_rs,
                                                                int64_t n, int64_t nq, unsigned* __restrict__ lcnt,
                                                                int64_t* __restrict__ tiles, int64_t* __restrict__ cnt,
@@ -88,7 +99,7 @@ __global__ __launch_bounds__(kFslPlanThreads) void k_fsl_pairs(const int64_t* __
 
 // pair_off [n_lists + 1], unit_off [n_lists + 1]: exclusive prefixes of the lists' pairs and units, 1,024 lists per trip
 // with a carry (the scan of k_adc_range_scan, two sums at once).  A list has pairs only if it has rows.
-__global__ __launch_bounds__(1024) void k_fsl_units(const int64_t* __restrict__ list_off, int64_t n_lists, int64_t n,
+inline __global__ __launch_bounds__(1024) void k_fsl_units(const int64_t* __restrict__ list_off, int64_t n_lists, int64_t n,
                                                     const unsigned* __restrict__ lcnt, int qg, int64_t unit_rows,
                                                     unsigned* __restrict__ pair_off, int64_t* __restrict__ unit_off)
 {
@@ -135,7 +146,7 @@ __global__ __launch_bounds__(1024) void k_fsl_units(const int64_t* __restrict__ 
 }
 
 // tiles[e] > 0 marks the pairs (k_fsl_pairs; the tile scan runs after this kernel)
-__global__ __launch_bounds__(kFslPlanThreads) void k_fsl_scatter(const int64_t* __restrict__ probes, int n_probe, int64_t p_rs,
+inline __global__ __launch_bounds__(kFslPlanThreads) void k_fsl_scatter(const int64_t* __restrict__ probes, int n_probe, int64_t p_rs,
                                                                  int64_t nq, const int64_t* __restrict__ tiles,
                                                                  const unsigned* __restrict__ pair_off,
                                                                  unsigned* __restrict__ cursor, unsigned* __restrict__ pairs)

@@ -370,6 +370,9 @@ int32_t pqhip_ctx_set_option(pqhip_ctx* ctx, const char* name, int64_t value)
         {"flat_screen_wgs", &o.flat_screen_wgs},       {"flat_screen_lists_wgs", &o.flat_screen_lists_wgs},
         {"flat_screen_lists_unit_rows", &o.flat_screen_lists_unit_rows},
         {"flat_screen_lists_chunk_queries", &o.flat_screen_lists_chunk_queries},
+        {"adc_screen_lists_wgs", &o.adc_screen_lists_wgs},
+        {"adc_screen_lists_unit_rows", &o.adc_screen_lists_unit_rows},
+        {"adc_screen_lists_chunk_queries", &o.adc_screen_lists_chunk_queries},
         {"adc_screen_wgs", &o.adc_screen_wgs}};
     for (auto& t : table)
         if (std::strcmp(t.n, name) == 0) { t.v->store(value, std::memory_order_relaxed); return PQHIP_OK; }

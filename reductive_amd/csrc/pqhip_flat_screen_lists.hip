@@ -84,17 +84,6 @@ static int32_t launch_flat_screen_lists_fill_t(const FlatScreenListsLaunch& a)
     return PQHIP_OK;
 }
 
-// Hit words of one query of a chunk: twice what a query probes when the lists are equally long -- n_rows
-// min(n_probe, n_lists) / n_lists rows in tiles of 32, one partial tile per slot -- and never more than n_probe whole
-// matrices.  The budget of a chunk is the sum over its queries: what a query leaves, another may take.
-static int64_t flat_screen_lists_words_per_query(int64_t n_rows, int64_t n_lists, int64_t n_probe)
-{
-    const double frac = (double)std::min<int64_t>(n_probe, n_lists) / (double)n_lists;
-    const int64_t expected = (int64_t)((double)n_rows * frac / kFsTile) + 1 + n_probe;
-    const int64_t most = n_probe * (n_rows / kFsTile + 1);
-    return std::min<int64_t>(2 * expected, most);
-}
-
 }  // namespace pqh
 
 using namespace pqh;
@@ -138,7 +127,7 @@ int32_t pqhip_flat_screen_lists_f32_dev(pqhip_codebook* cb, int32_t slot, const 
     // per list: lcnt, cursor, pair_off (+1), unit_off (+1); per query: image row, (s, tau), the dummy lims of the tile
     // scan, per entry cnt, hoff and the pair; the hit words
     const size_t lists_bytes = (size_t)round_up((n_lists + 1) * 20, 256);
-    const int64_t words_q = flat_screen_lists_words_per_query(n_rows, n_lists, n_probe);
+    const int64_t words_q = fsl_words_per_query(n_rows, n_lists, n_probe);
     const size_t per_q = (size_t)ldq * 2 + 8 + 8 + (size_t)n_probe * 20 + (size_t)words_q * 4;
     const size_t room = kListsScratchBytes > lists_bytes + 4096 ? kListsScratchBytes - lists_bytes - 4096 : 0;
     const int64_t forced_chunk = opt.flat_screen_lists_chunk_queries.load(std::memory_order_relaxed);

@@ -13,6 +13,7 @@
 //     pqhip_adc_among.hip ADC search among given rows: top-k over per-query candidate id lists
 //     pqhip_adc_range.hip ADC range search: every row within a radius, as CSR
 //     pqhip_flat_screen_lists.hip  matrix-core range screen in probed lists (query batches of the exact list searches)
+//     pqhip_adc_screen_lists.hip  u8 table screen over codes in probed lists (query batches of the ADC list searches)
 //     pqhip_rerank.hip    exact re-ranking of search candidates against resident vectors
 //     pqhip_lists_merge.hip  merge of two list-ordered row arrays (growing a partitioned matrix)
 //     pqhip_lists_layout.hip  building a partitioned index: layout of the lists, residuals, query-free row terms
@@ -117,6 +118,9 @@ struct Options {
     std::atomic<int64_t> flat_screen_lists_wgs{0};  // range screen in probed lists: workgroups that stride over the units (0: four per CU)
     std::atomic<int64_t> flat_screen_lists_unit_rows{0};      // ... rows of a unit, a multiple of 32 (0: 1,024)
     std::atomic<int64_t> flat_screen_lists_chunk_queries{0};  // ... queries of a chunk (0: from the scratch bound)
+    std::atomic<int64_t> adc_screen_lists_wgs{0};   // code screen in probed lists: workgroups that stride over the units (0: one per CU)
+    std::atomic<int64_t> adc_screen_lists_unit_rows{0};       // ... rows of a unit, a multiple of 64 (0: 16,384)
+    std::atomic<int64_t> adc_screen_lists_chunk_queries{0};   // ... queries of a chunk (0: from the scratch bound)
 };
 
 struct Diag {

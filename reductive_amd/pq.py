@@ -1421,6 +1421,120 @@ class Pq:
             _marshal.check_range(cb, slot, sp)
         return (val[0], idx[0]) if single else (val, idx)
 
+    # ---- ADC search in probed lists for query batches: u8 table screen per list, exact resolve ---------------------------
+    def _adc_screen_lists(self, codes, tables, list_off, probes, threshold, ip, scales, allow, cap, stream, retry):
+        """One list screen call with `cap` entries and, if retry and the result is larger, one more of exactly its size
+        -> (lims, idx[:min(total, cap)], total, launch); lims[-1] is read in between, the one synchronisation."""
+        import torch
+        codes, n, c_rs, nq, mask = self._adc_screen_args(codes, tables, ip, scales, allow)
+        if n > (1 << 32) - 2:
+            raise PanicError("at most 2^32 - 2 rows are searched in lists")
+        pr, _, n_probe, p_rs = _marshal.vector_lists_arg(list_off, probes, nq)
+        dev = codes.device
+        if not (list_off.is_cuda and probes.is_cuda and list_off.device == dev and probes.device == dev):
+            raise PanicError("codes, tables, list_off, probes and allow must be CUDA tensors on one device")
+        thr = _marshal.threshold_arg(threshold, nq, dev)
+        cap = int(cap)
+        if cap < 0:
+            raise PanicError("capacity must not be negative")
+        own_stream = stream is None
+        cb, slot, sp = _marshal.launch(self, codes, stream)
+        head = _marshal.search_head(cb, slot, tables, nq, codes, n, c_rs, False, mask, (list_off, pr, n_probe, p_rs),
+                                    last=(1 if ip else 0, ptr_or_none(scales)))
+        lims = torch.empty(nq + 1, dtype=torch.int64, device=dev)
+        while True:
+            idx = torch.empty(cap, dtype=torch.int64, device=dev)
+            _marshal.run("pqhip_adc_screen_lists_f32_dev", *head, thr.data_ptr(), lims.data_ptr(), ptr_or_none(idx, cap), cap, sp)
+            if not own_stream:
+                torch.cuda.ExternalStream(stream, device=dev).synchronize()
+            total = int(lims[-1])
+            if total <= cap or not retry:
+                break
+            cap = total             # the second call always suffices
+        return lims, idx[:min(total, cap)], total, (cb, slot, sp)
+
+    def adc_screen_lists_device(self, codes, tables, list_off, probes, threshold, ip=False, scales=None, allow=None,
+                                capacity=None, stream=None, check=False):
+        """adc_screen_device in probed lists (pqhip_adc_screen_lists_f32_dev): codes, tables, list_off, probes, threshold,
+        scales and allow as for adc_range_lists_device (ip=False) resp. adc_ip_range_lists_device (ip=True) -> (lims,
+        idx): CSR of positions, per query a SUPERSET of what the list range call returns at the same thresholds, within
+        the allowed rows of the probed lists and in that call's order -- probe slot first, then position; a list named
+        twice returns its rows twice.  A regular row is returned only within the slack the header states.  Up to 32
+        queries that probe a list share one stream of its codes.  The capacity protocol is adc_screen_device's.
+        check=True synchronises and reports a code >= K, a list id or an offset out of range (the latter are skipped
+        resp. clamped either way)."""
+        lims, idx, _, launch = self._adc_screen_lists(codes, tables, list_off, probes, threshold, ip, scales, allow,
+                                                      (1 << 20) if capacity is None else capacity, stream, True)
+        if check:
+            _marshal.check_range(*launch)
+        return lims, idx
+
+    def adc_search_lists_batch_device(self, codes, tables, list_off, probes, k, ip=False, scales=None, allow=None,
+                                      stream=None, check=False, stats=None):
+        """adc_search_lists_device (ip=False) resp. adc_ip_search_lists_device (ip=True) for a batch of queries, bit for
+        bit in values and positions.  Sample: the plain list search over the first s probe slots only
+        (flat_lists_batch_sample); T_q, its k-th value, is the k-th best of a subset of the query's probed rows and
+        therefore a valid threshold.  Screen at T_q (adc_screen_lists_device): a superset of the rows at or below (ip:
+        at or above) it, probed list by probed list.  Resolve: adc_among_device / adc_ip_among_device over the
+        candidates, whose order (value, position) is the list search's.  A query whose sample holds fewer than k rows, a
+        query that names a list twice (its rows would be candidates twice), a chunk of queries whose candidates exceed
+        flat_lists_batch_fraction() of its expected probed rows (flat_lists_batch_falls_back) and a quantizer that
+        either stage does not serve (PQHIP_EUNSUPPORTED) take the plain call.  stats: a dict that receives the
+        candidate total, the queries that fell back and the sample slots."""
+        import torch
+        k = int(k)
+        if not 1 <= k <= 1024:
+            raise PanicError("k must be between 1 and 1024, was %d" % k)
+        _, N, _, nq, _ = self._adc_screen_args(codes, tables, ip, scales, allow)
+        _, n_lists, n_probe, _ = _marshal.vector_lists_arg(list_off, probes, nq)
+        kw = {"scales": scales} if ip else {}
+        among = self.adc_ip_among_device if ip else self.adc_among_device
+        lists_call = self.adc_ip_search_lists_device if ip else self.adc_search_lists_device
+        plain_call = lambda t, p: lists_call(codes, t, list_off, p, k, stream=stream, allow=allow, **kw)
+        if N == 0 or nq == 0 or n_lists == 0:
+            return lists_call(codes, tables, list_off, probes, k, stream=stream, check=check, allow=allow, **kw)
+        single = tables.dim() == 2
+        t3 = tables[None] if single else tables
+        pr2 = probes[None] if probes.dim() == 1 else probes
+        dev = codes.device
+        s = flat_lists_batch_sample(N, n_lists, n_probe, k)
+        sval, sidx = plain_call(t3, pr2[:, :s].contiguous())
+        T = sval[:, k - 1]
+        srt = torch.sort(pr2, dim=1).values                         # a list named twice: its rows would be candidates twice
+        twice = ((srt[:, 1:] == srt[:, :-1]) & (srt[:, 1:] >= 0)).any(dim=1)
+        thin = (sidx[:, k - 1] < 0) | torch.isnan(T) | twice
+        nothing = float("inf") if ip else float("-inf")          # a thin query screens nothing and takes the plain call
+        thr = torch.where(thin, torch.full_like(T, nothing), T)
+        val = torch.empty((nq, k), dtype=torch.float32, device=dev)
+        idx = torch.empty((nq, k), dtype=torch.int64, device=dev)
+        plain = thin.clone()
+        total_all = 0
+        for q0 in range(0, nq, FLAT_LISTS_BATCH_CHUNK):
+            q1 = min(nq, q0 + FLAT_LISTS_BATCH_CHUNK)
+            cap = int(flat_lists_batch_fraction() * (q1 - q0) * N * min(n_probe, n_lists) / n_lists) + 1
+            try:
+                lims, cand, total, _ = self._adc_screen_lists(codes, t3[q0:q1], list_off, pr2[q0:q1], thr[q0:q1], ip, scales,
+                                                              allow, cap, stream, False)
+                total_all += total
+                if total > cap or flat_lists_batch_falls_back(total, N, n_lists, n_probe, q1 - q0):
+                    plain[q0:q1] = True
+                    continue
+                val[q0:q1], idx[q0:q1] = among(codes, t3[q0:q1], cand, k, lims=lims, stream=stream, **kw)
+            except _lib.PqHipError as e:
+                if e.status != _lib.EUNSUPPORTED:
+                    raise
+                plain[:] = True                                  # a stage does not serve this quantizer
+                break
+        rows = torch.nonzero(plain).reshape(-1)
+        if rows.shape[0] > 0:
+            val[rows], idx[rows] = plain_call(t3[rows].contiguous(), pr2[rows])
+        if stats is not None:
+            stats.update(candidates=total_all, fallback_queries=int(rows.shape[0]), sample_slots=int(s))
+        if check:
+            cb, slot, sp = _marshal.launch(self, codes, stream)
+            _marshal.check_range(cb, slot, sp)
+        return (val[0], idx[0]) if single else (val, idx)
+
     def adc_range_lists_device(self, codes, tables, list_off, probes, threshold, stream=None, check=False, allow=None,
                                capacity=None):
         """adc_range_device restricted, per query, to the rows of the probed lists (list_off, probes as for

@@ -1113,20 +1113,37 @@ class PartitionedMatrix(_Lists):
             fn = pq.adc_range_lists_device if ranged else pq.adc_search_lists_device
         return fn, self._tables(ip, queries), (self.list_off, self.probes(queries, nprobe))
 
-    def nearest(self, queries, k, nprobe, refine=None, allow=None):
+    def _topk_screened(self, ip, queries, k, nprobe, use_norms, refine, allow):
+        """_topk by the route for query batches (Pq.adc_search_lists_batch_device); the shortlist R replaces k"""
+        self._unpacked_only("most_similar(screen=True)" if ip else "nearest(screen=True)")
+        R = k if refine is None else self._check_refine(k, refine)
+        kw = {"scales": self.norms if use_norms else None} if ip else {}
+        val, pos = self.pq.adc_search_lists_batch_device(self.codes, self._tables(ip, queries), self.list_off,
+                                                         self.probes(queries, nprobe), R, ip=ip,
+                                                         allow=self._allow_words(allow), **kw)
+        rows = self._original_rows(pos)
+        return (val, rows) if refine is None else self._refined(queries, rows, k, ip)
+
+    def nearest(self, queries, k, nprobe, refine=None, allow=None, screen=False):
         """the k rows of smallest asymmetric squared distance among the rows of the nprobe nearest lists, ties to the
         smaller position in list order -> (dist, idx) [k] or [nq, k]; idx are original row numbers, -1 past the last
         probed row (distance +Inf).  refine=R (k <= R <= 1024, vectors attached): the R first rows of that search are
         re-ranked by their exact squared distance to the attached vectors (Pq.rerank_device), ties to the smaller
         original row number; dist are then the exact distances.  allow: None, a RowFilter of this matrix or a bool array
-        [N] in ORIGINAL row order -- only allowed rows of the probed lists are ranked, as if the others were not stored."""
+        [N] in ORIGINAL row order -- only allowed rows of the probed lists are ranked, as if the others were not stored.
+        screen=True: the route for query batches (Pq.adc_search_lists_batch_device: u8 table screen per list, exact
+        resolve), the same result bit for bit; not served on a packed matrix."""
+        if screen:
+            return self._topk_screened(False, queries, k, nprobe, True, refine, allow)
         return self._topk(False, queries, k, nprobe, True, refine, allow)
 
-    def most_similar(self, queries, k, nprobe, use_norms=True, refine=None, allow=None):
+    def most_similar(self, queries, k, nprobe, use_norms=True, refine=None, allow=None, screen=False):
         """QuantizedMatrix.most_similar among the rows of the nprobe nearest lists -> (score, idx), idx original row
         numbers, -1 past the last probed row (score -Inf).  refine=R: the R first rows are re-ranked by their exact
         inner product with the attached vectors as they are; use_norms then only affects the candidate stage.
-        allow: as for nearest()."""
+        allow: as for nearest(); screen: as for nearest()."""
+        if screen:
+            return self._topk_screened(True, queries, k, nprobe, use_norms, refine, allow)
         return self._topk(True, queries, k, nprobe, use_norms, refine, allow)
 
     def within(self, queries, radius, nprobe, allow=None, sort=False):
