@@ -949,6 +949,60 @@ int32_t pqhip_adc_screen_f32_dev(pqhip_codebook *cb, int32_t device_slot,
                                  int64_t capacity, void *stream);
 
 /*
+ * pqhip_adc_screen_f32_dev with a 16-BIT table image: the same arguments (16, same order and meaning), the same output, a
+ * finer image and so a tighter screen -- the call for large M, where the u8 image returns too many rows (at M = 48 a row
+ * may lie 19 % of thr - base beyond the threshold there, 3.5 % here).  An entry of the image is a u16 of at most
+ * L = floor(65,535 / M) levels, so a row's integer sum U <= M L <= 65,535 is summed as packed u16 with one packed add per
+ * pair of queries and never wraps.  Two bytes per entry: 16, 8 or 4 queries share one stream of the codes (the most whose
+ * images fit the 160 KB of LDS), half of the u8 screen's.
+ * Contract.  Let R_q be the ids pqhip_adc_range_f32_dev (ip 0: value <= threshold) resp. pqhip_adc_ip_range_f32_dev (ip 1:
+ * value >= threshold, the value fl(sum * scale) with the same d_scales) returns for query q at d_threshold[q] (same
+ * tables, codes, mask), O_q the ids of this call, A the allowed rows.
+ *   Output: d_lims [n_queries + 1] int64 (CSR) and d_idx (int64) of `capacity` entries; R_q is a subset of O_q, O_q of
+ *   A; the ids of a query ascend.
+ *   Capacity protocol, that of the range calls: true counts always, only slots < capacity written (a valid prefix when
+ *   d_idx is short), capacity == 0 a count call with d_idx NULL.
+ *   Masks: a disallowed row is never loaded; the row fetch is that of the searches (no byte outside the code matrix is
+ *   read, rows at any address, any stride >= M).
+ *   Range flag: a code >= K reads entry 0 and raises the range flag (pqhip_check_codes_dev).
+ *   Independence: a function of the inputs alone -- the result depends neither on the grid (option "adc_screen_wgs",
+ *   shared with pqhip_adc_screen_f32_dev), nor on the passes, nor on how the queries are split over calls.
+ *   Preparation, per query, in f64 (t' = t, thr' = thr for ip 0; the negated tables and threshold for ip 1):
+ *     lo_m = min_k t'[m][k], a_m = max_k |t[m][k]|, base = sum_m lo_m - kAdcScreenF64 sum_m |lo_m|,
+ *     E = kAdcScreenRel M sum_m a_m + kAdcScreenAbs, num = thr' + E - base + kAdcScreenF64 (|thr'| + |base|),
+ *     s = max(num / (L - 1), kAdcScreenMinStep),
+ *     u[m][k] = min(L, floor((t'[m][k] - lo_m) / s (1 - kAdcScreenF64))),
+ *     U_lim = min(65,535, floor(num / s (1 + kAdcScreenF64))), and -1 when num <= 0.
+ *   With d_scales: B = E - base (rounded up to f32), s32 = s rounded down, num the span of the sums from thr / c_max
+ *   (c_max the largest finite scale) up, and the f32 epilogue of pqhip_adc_screen_f32_dev per (row, query): the row is
+ *   provably outside iff its scale c is finite, c >= 0 and fl(w c) < thr for the widened upper bound w of B - s32 U.
+ *   Soundness: lo_m + s u[m][k] <= t'[m][k] in the reals, saturated or not, so base + s U is at most the row's real sum
+ *   and U > U_lim proves that the row's f32 chain -- the sequential chain over m from +0, as pqhip_adc_scan_f32_dev
+ *   defines it -- misses the threshold.  Every other allowed row is returned.
+ *   Tightness: a regular row is returned only while v' <= thr' + M s + 2 E + 2^-39 (|thr'| + |base|).
+ *   Keep-all: whatever the proof does not cover returns every allowed row -- a NaN or infinite entry in the query's
+ *   tables, sum_m a_m > 2^126, a NaN threshold; a row with a negative, NaN or infinite scale is returned.  (An infinite
+ *   threshold needs no proof: over finite tables -Inf, ip +Inf, returns nothing and the opposite one every allowed row.)
+ *   The bound is derived in DESIGN.md section 5g from that of section 5e; the constants are kAdcScreen* of
+ *   kernels_adc_screen.hip.h, L is adc_screen16_levels of kernels_adc_screen16.hip.h.
+ * Status codes and their precedence are those of pqhip_adc_screen_f32_dev: null cb, n_queries < 0, n_rows < 0,
+ * capacity < 0, ip not 0 / 1, d_scales with ip 0: PQHIP_EINVAL; a bad device_slot: PQHIP_ENODEV; code_bytes not 1,
+ * M > 100, a quantizer of which four 16-bit images do not fit the LDS (M K above 20,472): PQHIP_EUNSUPPORTED -- callers
+ * take the plain call; with n_queries > 0 a null d_lims or d_threshold, a null d_idx with capacity > 0, null d_tables or
+ * d_codes with n_rows > 0: PQHIP_EINVAL; codes_row_stride < M: PQHIP_ESHAPE.  n_queries == 0 launches nothing;
+ * n_rows == 0 writes all-zero lims.  Asynchronous on `stream`; per pass: the prep kernel, the count pass, the prefix scan
+ * of the range calls, the fill pass (none for a count call); with d_scales one reduction over them in front.
+ */
+int32_t pqhip_adc_screen16_f32_dev(pqhip_codebook *cb, int32_t device_slot,
+                                   const float *d_tables /* [n_queries][M][K] */, int64_t n_queries,
+                                   const void *d_codes, int32_t code_bytes, int64_t n_rows, int64_t codes_row_stride,
+                                   const uint32_t *d_allow /* ceil(n_rows / 32) words or NULL */,
+                                   int32_t ip /* 0 = distance tables, 1 = inner-product tables */,
+                                   const float *d_scales /* ip 1: [n_rows] or NULL */,
+                                   const float *d_threshold /* [n_queries] */, int64_t *d_lims, int64_t *d_idx,
+                                   int64_t capacity, void *stream);
+
+/*
  * The range screen of pqhip_flat_screen_f32_dev in PROBED LISTS: for a batch of queries, per query a superset of what
  * pqhip_flat_range_lists_f32_dev returns at the same thresholds, as positions (CSR, no values) -- the first stage of the
  * exact list searches for query batches (resolve with pqhip_flat_range_among_f32_dev / pqhip_flat_among_f32_dev).  The work
@@ -1380,7 +1434,7 @@ int32_t pqhip_set_rotation_variant(int32_t variant);
  *   "flat_screen_lists_unit_rows"  rows of a unit of that call, rounded up to a multiple of 32 (0 = 1024)
  *   "flat_screen_lists_chunk_queries"  queries of a chunk of that call (0 = from the scratch bound; at most 2^20 / n_probe);
  *                          the result depends on none of the three
- *   "adc_screen_wgs"       producer workgroups of pqhip_adc_screen_f32_dev (0 = one per CU; at most 2048, so that the
+ *   "adc_screen_wgs"       producer workgroups of pqhip_adc_screen_f32_dev and pqhip_adc_screen16_f32_dev (0 = one per CU; at most 2048, so that the
  *                          prefix scan of a pass of 32 queries sums at most 2^20 counts; rows per workgroup stay a
  *                          multiple of 1,024; the result does not depend on it)
  *   "adc_screen_lists_wgs"  workgroups of pqhip_adc_screen_lists_f32_dev that stride over its units (0 = one per CU)

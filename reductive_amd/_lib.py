@@ -115,6 +115,7 @@ def _signatures():
         "pqhip_flat_screen_lists_f32_dev": (i32, [vp, i32, vp, i64, i64, vp, i32, i64, i64, i64, vp, vp, i64, vp, i32, i64,
                                                   i32, i32, vp, vp, vp, i64, vp]),
         "pqhip_adc_screen_f32_dev": (i32, [vp, i32, vp, i64, vp, i32, i64, i64, vp, i32, vp, vp, vp, vp, i64, vp]),
+        "pqhip_adc_screen16_f32_dev": (i32, [vp, i32, vp, i64, vp, i32, i64, i64, vp, i32, vp, vp, vp, vp, i64, vp]),
         "pqhip_adc_screen_lists_f32_dev": (i32, [vp, i32, vp, i64, vp, i32, i64, i64, vp, vp, i64, vp, i32, i64, i32, vp,
                                                  vp, vp, vp, i64, vp]),
         "pqhip_lists_merge_dev": (i32, [vp, i32, vp, i64, vp, i64, i64, i64, vp, vp, vp, vp, vp]),

@@ -100,11 +100,15 @@ inline __global__ __launch_bounds__(256) void k_adc_screen_scale_max(const float
 // that a query has the same image and parameters wherever it is screened.  A slot that is not `real` is padding (zeros,
 // nothing returned; tq and thr are then not dereferenced).  Wave w takes the subquantizers w, w + 4, ..; minima and
 // maxima do not depend on the order.  The sums over m are one thread's, in ascending m.  Entry i = m K + k goes to
-// dst[i dst_stride].
+// dst[i dst_stride].  ET is the entry type and `levels` the value an entry saturates at, one step more than the steps
+// num is cut into: uint8_t with kAdcScreenSteps + 1 = 255 here, uint16_t with floor(65,535 / M) in
+// kernels_adc_screen16.hip.h; the arithmetic is the same expression for both.
+template <typename ET>
 __device__ __forceinline__ void adc_screen_prep_slot(const float* __restrict__ tq, bool real, int M, int K, const float* __restrict__ thr,
-                                                     int ip, int scaled, const unsigned* __restrict__ cmax_bits,
-                                                     uint8_t* __restrict__ dst, size_t dst_stride, AdcScreenPrm* __restrict__ prm)
+                                                     int ip, int scaled, const unsigned* __restrict__ cmax_bits, int levels,
+                                                     ET* __restrict__ dst, size_t dst_stride, AdcScreenPrm* __restrict__ prm)
 {
+    const double steps = (double)(levels - 1), sat = (double)levels;
     __shared__ float s_lo[kAdcScreenMaxM], s_hi[kAdcScreenMaxM], s_am[kAdcScreenMaxM];
     __shared__ int s_bad, s_live;
     __shared__ double s_step;
@@ -162,7 +166,7 @@ __device__ __forceinline__ void adc_screen_prep_slot(const float* __restrict__ t
                     if (!(num > 0.0)) {
                         p.ulim = -1;                                // thr' + E < base: no row can qualify
                     } else {
-                        const double step = num / (double)kAdcScreenSteps > kAdcScreenMinStep ? num / (double)kAdcScreenSteps : kAdcScreenMinStep;
+                        const double step = num / steps > kAdcScreenMinStep ? num / steps : kAdcScreenMinStep;
                         const double lim = __builtin_floor(num / step * (1.0 + kAdcScreenF64));
                         p.ulim = lim < (double)kAdcScreenKeepAll ? (int)lim : kAdcScreenKeepAll;
                         s_step = step;
@@ -176,7 +180,7 @@ __device__ __forceinline__ void adc_screen_prep_slot(const float* __restrict__ t
                         const double span = B - (double)p.thr / (double)cmax * (1.0 - 0x1p-20);
                         num = span < num ? span : num;
                     }
-                    const double step = num / (double)kAdcScreenSteps > kAdcScreenMinStep ? num / (double)kAdcScreenSteps : kAdcScreenMinStep;
+                    const double step = num / steps > kAdcScreenMinStep ? num / steps : kAdcScreenMinStep;
                     p.ulim = kAdcScreenPerRow;
                     p.b = adc_screen_f32_up(B);
                     p.s = adc_screen_f32_down(step);
@@ -192,12 +196,12 @@ __device__ __forceinline__ void adc_screen_prep_slot(const float* __restrict__ t
     const double step = s_step;
     const int MK = M * K;
     for (int i = t; i < MK; i += kAsPrepThreads) {
-        uint8_t u = 0;
+        ET u = 0;
         if (live) {
             const int m = i / K;
             const double x = (double)(sg * tq[i]) - (double)s_lo[m];
             const double qv = x / step * (1.0 - kAdcScreenF64);
-            u = qv >= 255.0 ? (uint8_t)255 : (uint8_t)(int)qv;
+            u = qv >= sat ? (ET)levels : (ET)(int)qv;
         }
         dst[(size_t)i * dst_stride] = u;
     }
@@ -211,8 +215,8 @@ inline __global__ __launch_bounds__(kAsPrepThreads) void k_adc_screen_prep(const
                                                                     uint8_t* __restrict__ img, AdcScreenPrm* __restrict__ prm)
 {
     const int slot = blockIdx.x;
-    adc_screen_prep_slot(tables + (size_t)slot * M * K, slot < nq_pass, M, K, thr + slot, ip, scaled, cmax_bits, img + slot, (size_t)NQ,
-                         prm + slot);
+    adc_screen_prep_slot(tables + (size_t)slot * M * K, slot < nq_pass, M, K, thr + slot, ip, scaled, cmax_bits, kAdcScreenSteps + 1,
+                         img + slot, (size_t)NQ, prm + slot);
 }
 
 template <int ND>

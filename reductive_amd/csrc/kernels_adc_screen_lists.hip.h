@@ -53,7 +53,8 @@ inline __global__ __launch_bounds__(kAsPrepThreads) void k_adc_screen_lists_prep
                                                                           AdcScreenPrm* __restrict__ prm)
 {
     const int64_t q = blockIdx.x;
-    adc_screen_prep_slot(tables + (size_t)q * M * K, true, M, K, thr + q, ip, scaled, cmax_bits, imgq + q * pitch, (size_t)1, prm + q);
+    adc_screen_prep_slot(tables + (size_t)q * M * K, true, M, K, thr + q, ip, scaled, cmax_bits, kAdcScreenSteps + 1,
+                         imgq + q * pitch, (size_t)1, prm + q);
 }
 
 // rows a, b, c, d of 4 bytes each -> their columns: o[i] = (a_i, b_i, c_i, d_i), 8 v_perm_b32

@@ -1307,9 +1307,17 @@ class Pq:
             raise PanicError("the row mask must be a CUDA tensor")
         return codes, n, c_rs, nq, _marshal.mask_arg(allow, codes, True)
 
-    def _adc_screen(self, codes, tables, threshold, ip, scales, allow, cap, stream, retry):
-        """One screen call with `cap` entries and, if retry and the result is larger, one more of exactly its size
-        -> (lims, idx[:min(total, cap)], total, launch); lims[-1] is read in between, the one synchronisation."""
+    @staticmethod
+    def _adc_screen_entry(image_bits):
+        """the screen's entry point by the width of its table image: 8 or 16 bits per entry"""
+        if image_bits not in (8, 16):
+            raise PanicError("image_bits must be 8 or 16, was %r" % (image_bits,))
+        return "pqhip_adc_screen_f32_dev" if image_bits == 8 else "pqhip_adc_screen16_f32_dev"
+
+    def _adc_screen(self, codes, tables, threshold, ip, scales, allow, cap, stream, retry, entry="pqhip_adc_screen_f32_dev"):
+        """One screen call (the entry point `entry`) with `cap` entries and, if retry and the result is larger, one more of
+        exactly its size -> (lims, idx[:min(total, cap)], total, launch); lims[-1] is read in between, the one
+        synchronisation."""
         import torch
         codes, n, c_rs, nq, mask = self._adc_screen_args(codes, tables, ip, scales, allow)
         dev = codes.device
@@ -1323,7 +1331,7 @@ class Pq:
         lims = torch.empty(nq + 1, dtype=torch.int64, device=dev)
         while True:
             idx = torch.empty(cap, dtype=torch.int64, device=dev)
-            _marshal.run("pqhip_adc_screen_f32_dev", *head, thr.data_ptr(), lims.data_ptr(), ptr_or_none(idx, cap), cap, sp)
+            _marshal.run(entry, *head, thr.data_ptr(), lims.data_ptr(), ptr_or_none(idx, cap), cap, sp)
             if not own_stream:
                 torch.cuda.ExternalStream(stream, device=dev).synchronize()
             total = int(lims[-1])
@@ -1333,7 +1341,7 @@ class Pq:
         return lims, idx[:min(total, cap)], total, (cb, slot, sp)
 
     def adc_screen_device(self, codes, tables, threshold, ip=False, scales=None, allow=None, capacity=None, stream=None,
-                          check=False):
+                          check=False, image_bits=8):
         """Conservative range screen over resident u8 codes (pqhip_adc_screen_f32_dev): codes, tables, threshold, scales
         and allow as for adc_range_device (ip=False) resp. adc_ip_range_device (ip=True) -> (lims, idx): CSR, lims CUDA
         int64 [nq + 1], the ids of query q at idx[lims[q]:lims[q + 1]] in ascending order -- a SUPERSET of what the range
@@ -1343,15 +1351,18 @@ class Pq:
         adc_range_device's: one call with `capacity` entries (default 1 << 20), one read of lims[-1] -- the one
         synchronisation -- and one more call of exactly its size if the result is larger; capacity=0 counts first.
         A quantizer whose images do not fit the LDS raises PqHipError (PQHIP_EUNSUPPORTED).  check=True synchronises
-        and reports a code >= K."""
+        and reports a code >= K.  image_bits=16: the 16-bit image (pqhip_adc_screen16_f32_dev) of floor(65,535 / M)
+        levels per entry -- the same contract with a slack of M / (floor(65,535 / M) - 1) of thr - base instead of
+        M / 254, at 16 / 8 / 4 queries per stream of the codes; any other value but 8 is refused."""
+        entry = self._adc_screen_entry(image_bits)
         lims, idx, _, (cb, slot, sp) = self._adc_screen(codes, tables, threshold, ip, scales, allow,
-                                                        (1 << 20) if capacity is None else capacity, stream, True)
+                                                        (1 << 20) if capacity is None else capacity, stream, True, entry)
         if check:
             _marshal.check_range(cb, slot, sp)
         return lims, idx
 
     def adc_search_batch_device(self, codes, tables, k, ip=False, scales=None, allow=None, stream=None, check=False,
-                                stats=None):
+                                stats=None, image_bits=8):
         """adc_search_device (ip=False) resp. adc_ip_search_device (ip=True) for a batch of queries, bit for bit in
         values and ids, at one stream of the codes per up to 32 queries.  Sample: every t-th row (flat_batch_sample; -1
         where the mask disallows it) through adc_among_device / adc_ip_among_device; T_q, its k-th value, is a valid
@@ -1360,11 +1371,14 @@ class Pq:
         the screen's ids, which is the masked search on a superset of its result.  A query whose sample holds fewer
         than k numbers, a chunk of queries whose candidates exceed FLAT_BATCH_FALLBACK_FRACTION of n nq
         (flat_batch_falls_back) and a quantizer the screen does not serve (PQHIP_EUNSUPPORTED) take the plain call.
-        stats: a dict that receives the candidate total, the queries that fell back and the sample size."""
+        stats: a dict that receives the candidate total, the queries that fell back and the sample size.
+        image_bits=16 screens with the 16-bit image (adc_screen_device): the same sample, chunks, capacity, fallback rule
+        and resolve, so the same result; fewer candidates at large M, half the queries per stream of the codes."""
         import torch
         k = int(k)
         if not 1 <= k <= 1024:
             raise PanicError("k must be between 1 and 1024, was %d" % k)
+        entry = self._adc_screen_entry(image_bits)
         self._adc_screen_args(codes, tables, ip, scales, allow)   # before the mask is indexed for the sample
         kw = {"scales": scales} if ip else {}
         among = self.adc_ip_among_device if ip else self.adc_among_device
@@ -1400,7 +1414,7 @@ class Pq:
             q1 = min(nq, q0 + FLAT_BATCH_CHUNK)
             cap = flat_batch_capacity(N, q1 - q0, k, S)
             try:
-                lims, cand, total, _ = self._adc_screen(codes, t3[q0:q1], thr[q0:q1], ip, scales, allow, cap, stream, False)
+                lims, cand, total, _ = self._adc_screen(codes, t3[q0:q1], thr[q0:q1], ip, scales, allow, cap, stream, False, entry)
             except _lib.PqHipError as e:
                 if e.status != _lib.EUNSUPPORTED:
                     raise

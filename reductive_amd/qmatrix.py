@@ -675,13 +675,14 @@ class QuantizedMatrix(_Refine, _Filter, _Packed4, _Search, _Among, _Compact):
             fn = pq.adc_range_device if ranged else pq.adc_search_device
         return fn, self._tables(ip, queries), ()
 
-    def _topk_screened(self, ip, queries, k, use_norms, refine, allow):
-        """_topk by the route for query batches (Pq.adc_search_batch_device); the shortlist R replaces k"""
+    def _topk_screened(self, ip, queries, k, use_norms, refine, allow, screen):
+        """_topk by the route for query batches (Pq.adc_search_batch_device); the shortlist R replaces k; screen "u16"
+        takes the 16-bit image, any other true value the u8 image"""
         self._unpacked_only("most_similar(screen=True)" if ip else "nearest(screen=True)")
         R = k if refine is None else self._check_refine(k, refine)
         kw = {"scales": self.norms if use_norms else None} if ip else {}
         val, rows = self.pq.adc_search_batch_device(self.codes, self._tables(ip, queries), R, ip=ip,
-                                                    allow=self._allow_words(allow), **kw)
+                                                    allow=self._allow_words(allow), image_bits=16 if screen == "u16" else 8, **kw)
         return (val, rows) if refine is None else self._refined(queries, rows, k, ip)
 
     def nearest(self, queries, k, refine=None, allow=None, screen=False):
@@ -692,9 +693,10 @@ class QuantizedMatrix(_Refine, _Filter, _Packed4, _Search, _Among, _Compact):
         array [N] packed on the spot -- only allowed rows are ranked, exactly as if the others were not stored (index
         -1 past the last allowed row); with refine= the shortlist holds allowed rows only.  screen=True: the route for
         query batches (Pq.adc_search_batch_device: u8 table screen, exact resolve), the same result bit for bit; not
-        served on a packed matrix."""
+        served on a packed matrix.  screen="u16": that route with the 16-bit table image, the one for many subquantizers
+        and shortlists of 100 and more."""
         if screen:
-            return self._topk_screened(False, queries, k, True, refine, allow)
+            return self._topk_screened(False, queries, k, True, refine, allow, screen)
         return self._topk(False, queries, k, None, True, refine, allow)
 
     def most_similar(self, queries, k, use_norms=True, refine=None, allow=None, screen=False):
@@ -704,7 +706,7 @@ class QuantizedMatrix(_Refine, _Filter, _Packed4, _Search, _Among, _Compact):
         exact inner product with the attached vectors as they are; use_norms then only affects the candidate stage.
         allow: as for nearest(); screen: as for nearest()."""
         if screen:
-            return self._topk_screened(True, queries, k, use_norms, refine, allow)
+            return self._topk_screened(True, queries, k, use_norms, refine, allow, screen)
         return self._topk(True, queries, k, None, use_norms, refine, allow)
 
     def within(self, queries, radius, allow=None, sort=False):

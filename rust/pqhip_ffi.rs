@@ -233,6 +233,14 @@ extern "C" {
         d_codes: *const c_void, code_bytes: i32, n_rows: i64, codes_row_stride: i64, d_allow: *const u32, ip: i32,
         d_scales: *const f32, d_threshold: *const f32, d_lims: *mut i64, d_idx: *mut i64, capacity: i64,
         stream: *mut c_void) -> i32;
+    // pqhip_adc_screen_f32_dev with a 16-bit table image of floor(65,535 / M) levels per entry: the same arguments and
+    // output, a returned row at most M / (L - 1) of thr - base beyond the threshold (3.5 % at M = 48 against 19 %); 16, 8
+    // or 4 queries per stream of the codes; PQHIP_EUNSUPPORTED where four 16-bit images do not fit the LDS; the grid option
+    // is "adc_screen_wgs"
+    pub fn pqhip_adc_screen16_f32_dev(cb: *mut pqhip_codebook, device_slot: i32, d_tables: *const f32, n_queries: i64,
+        d_codes: *const c_void, code_bytes: i32, n_rows: i64, codes_row_stride: i64, d_allow: *const u32, ip: i32,
+        d_scales: *const f32, d_threshold: *const f32, d_lims: *mut i64, d_idx: *mut i64, capacity: i64,
+        stream: *mut c_void) -> i32;
     // the same screen in probed lists: per query a superset of what pqhip_flat_range_lists_f32_dev returns, as positions
     // in that call's order (probe slot first, then position); list-major on the device, d <= 2048
     pub fn pqhip_flat_screen_lists_f32_dev(cb: *mut pqhip_codebook, device_slot: i32, d_queries: *const f32, n_queries: i64,
