@@ -1081,6 +1081,68 @@ int32_t pqhip_adc_screen_lists_f32_dev(pqhip_codebook *cb, int32_t device_slot,
                                        int64_t capacity, void *stream);
 
 /*
+ * The u8 table screen of pqhip_adc_screen_lists_f32_dev over RESIDUAL codes (IVFADC with residual encoding): for a batch
+ * of queries, per query a superset of what pqhip_adc_range_lists_residual_f32_dev (ip 0) resp.
+ * pqhip_adc_ip_range_lists_residual_f32_dev (ip 1, with the same d_scales) returns at the same thresholds, as positions
+ * (CSR, no values) in that call's order -- the first stage of the residual list searches for query batches (resolve with
+ * the residual form of pqhip_adc_among_f32_dev / pqhip_adc_ip_among_f32_dev).  Arguments: those of
+ * pqhip_adc_screen_lists_f32_dev with d_probe_bias, bias_row_stride and d_row_terms where
+ * pqhip_adc_range_lists_residual_f32_dev has them.  d_tables are the INNER-PRODUCT tables in both forms; d_row_terms is
+ * required for ip 0 and must be NULL for ip 1; d_scales must be NULL for ip 0.  Only u8 table images over one-byte codes:
+ * a 16-bit image and 4-bit packed codes are not served.
+ * Values.  With s the f32 chain of a row over the query's table, bias = d_probe_bias[q][p] of the slot through which the
+ * row is reached: dist = fl(fl(bias + term[i]) - fl(s + s)), score = fl(fl(bias + s) * scale[i]) (fl(bias + s) without
+ * d_scales).  The bias belongs to the (query, slot) pair and the term to the row, so the screen decides per (row, pair).
+ * Screening value.  The image of a query is that of pqhip_adc_screen_f32_dev for the negated table in its scaled form: an
+ * exact integer sum U of a row gives w = fl(B - s32 U), widened by 2^-22 |w| + 2^-100, with w >= s whether an entry
+ * saturates or not.  Every operation of the two formulas is a single rounded f32 operation and
+ * therefore monotone, so fl(fl(bias + term) - fl(w + w)) <= dist and, for a finite scale >= 0, fl(fl(bias + w) * scale) >=
+ * score.  A row is left out iff that bound strictly misses the threshold.
+ * Contract.  R_q: the positions the residual range call returns for query q at d_threshold[q]; S_q: the allowed rows of
+ * q's probed lists; O_q: this call's output.  Sound, unconditionally: R_q within O_q within S_q.  Whatever the proof does
+ * not cover is returned: a NaN or infinite table entry, magnitudes that sum beyond 2^126, a NaN threshold, a NaN bias or
+ * term, a negative, NaN or infinite scale (ip 1: every row of a query whose threshold is -Inf; ip 0 screens a threshold
+ * of -Inf at the least finite f32).
+ * The step of a query's image is (B - floor) / 254, floor being the least chain value that can still qualify:
+ * (min_p bias[q][p] + min_i term[i] - thr) / 2 for ip 0, thr / c_max - max_p bias[q][p] for ip 1 (c_max the largest finite
+ * scale, 1 without scales; with scales only for thr >= 2^-100), over the query's valid slots and ALL rows of the call
+ * (one reduction in front of the passes, NaN passed over), lowered by 2^-19 of the magnitudes involved; never more than
+ * the whole span of the sums.  Tight: a regular row is returned only while, with G = M step + 2 E (E of section 5e) +
+ * 2^-39 (|thr| + |base|) + 2^-22 (|B| + 255 step),
+ *     dist - thr <= 2 G + 2^-20 (|fl(bias + term)| + 2 |s| + 2 G)     resp.
+ *     thr - score <= (G + 2^-20 (|bias| + |s| + G)) scale             (scale = 1 without d_scales).
+ * Everything else is exactly as in pqhip_adc_screen_lists_f32_dev: order (probe slot first, then ascending position; a
+ * list named twice returns its rows twice), the capacity protocol, probes and offsets (-1 padding, ids out of range
+ * skipped and flagged, ranges clamped, inverted ranges empty), the row mask, the range flag, "no byte of an unprobed or
+ * disallowed row's codes is loaded" (the bias of a skipped probe and the term or scale of a disallowed row enter no
+ * decision about a row; the call-wide reductions read every term resp. scale and steer the step alone), and the result
+ * is a function of the inputs alone: it depends neither on the grid ("adc_screen_lists_wgs"), nor on how a list's rows
+ * are cut into units ("adc_screen_lists_unit_rows"), nor on how queries fall into groups or chunks
+ * ("adc_screen_lists_chunk_queries") -- the same three options govern this call.  The count pass stages per slot an
+ * integer limit and skips the f32 epilogue of a wave step in which no row is at or under it; the limit is the largest
+ * sum at which the epilogue itself, with the call-wide least term resp. largest scale, does not prove a row outside, so
+ * it changes no result.
+ * Status codes, in the precedence of pqhip_adc_screen_lists_f32_dev: PQHIP_EINVAL (null cb, negative counts,
+ * n_probe < 1, ip not 0 / 1, d_scales with ip 0, d_row_terms with ip 1), PQHIP_ENODEV, PQHIP_EUNSUPPORTED (code_bytes
+ * not 1, M > 100, a quantizer of which four images do not fit the LDS, n_codes > 2^32 - 2, n_probe > 2^20), then with
+ * n_queries > 0 the null pointers (PQHIP_EINVAL; also a null d_probe_bias, a null d_row_terms with ip 0) and the strides
+ * (PQHIP_ESHAPE; also bias_row_stride < n_probe).  n_queries == 0 launches nothing; n_codes == 0 or n_lists == 0 writes
+ * all-zero lims.
+ */
+int32_t pqhip_adc_screen_lists_residual_f32_dev(pqhip_codebook *cb, int32_t device_slot,
+                                                const float *d_tables /* [n_queries][M][K], inner-product tables */,
+                                                int64_t n_queries, const void *d_codes, int32_t code_bytes, int64_t n_codes,
+                                                int64_t codes_row_stride, const uint32_t *d_allow /* position order, or NULL */,
+                                                const int64_t *d_list_off /* [n_lists + 1] */, int64_t n_lists,
+                                                const int64_t *d_probes, int32_t n_probe, int64_t probes_row_stride,
+                                                const float *d_probe_bias, int64_t bias_row_stride,
+                                                const float *d_row_terms /* ip 0: [n_codes]; ip 1: NULL */,
+                                                int32_t ip /* 0 = distances, 1 = inner products */,
+                                                const float *d_scales /* ip 1: [n_codes] or NULL */,
+                                                const float *d_threshold /* [n_queries] */, int64_t *d_lims, int64_t *d_idx,
+                                                int64_t capacity, void *stream);
+
+/*
  * Merge of two list-ordered row arrays: the primitive under growing a partitioned matrix (rows added to an index, two
  * indexes over the same lists joined).  d_a is [n_a] rows of row_bytes bytes in list order under d_off_a [n_lists + 1]
  * (list l = rows off_a[l] .. off_a[l + 1] - 1), d_b likewise [n_b] rows under d_off_b; d_out is [n_a + n_b] rows.  For

@@ -103,10 +103,14 @@ inline __global__ __launch_bounds__(256) void k_adc_screen_scale_max(const float
 // dst[i dst_stride].  ET is the entry type and `levels` the value an entry saturates at, one step more than the steps
 // num is cut into: uint8_t with kAdcScreenSteps + 1 = 255 here, uint16_t with floor(65,535 / M) in
 // kernels_adc_screen16.hip.h; the arithmetic is the same expression for both.
+// floor_sum (scaled mode only): null, or the least chain value that can still qualify, which ends the step's span in
+// the place of thr / c_max (kernels_adc_screen_lists_residual.hip.h); cmax_bits is then not read.  -Inf
+// or NaN: no floor, the step spans all sums.
 template <typename ET>
 __device__ __forceinline__ void adc_screen_prep_slot(const float* __restrict__ tq, bool real, int M, int K, const float* __restrict__ thr,
                                                      int ip, int scaled, const unsigned* __restrict__ cmax_bits, int levels,
-                                                     ET* __restrict__ dst, size_t dst_stride, AdcScreenPrm* __restrict__ prm)
+                                                     ET* __restrict__ dst, size_t dst_stride, AdcScreenPrm* __restrict__ prm,
+                                                     const double* floor_sum = nullptr)
 {
     const double steps = (double)(levels - 1), sat = (double)levels;
     __shared__ float s_lo[kAdcScreenMaxM], s_hi[kAdcScreenMaxM], s_am[kAdcScreenMaxM];
@@ -174,10 +178,17 @@ __device__ __forceinline__ void adc_screen_prep_slot(const float* __restrict__ t
                     }
                 } else {
                     const double B = (E - base) + kAdcScreenF64 * __builtin_fabs(base);
-                    const float cmax = __uint_as_float(*cmax_bits);
                     double num = spread + 2.0 * E;                  // the whole span of the sums
-                    if (p.thr > 0.f && cmax > 0.f) {                // fl(v c) >= thr needs v >= thr / c_max (1 - 2^-23)
-                        const double span = B - (double)p.thr / (double)cmax * (1.0 - 0x1p-20);
+                    double least = -(double)inf;                    // the sums below it cannot qualify
+                    if (floor_sum) {
+                        least = *floor_sum;
+                    } else {
+                        const float cmax = __uint_as_float(*cmax_bits);
+                        if (p.thr > 0.f && cmax > 0.f)              // fl(v c) >= thr needs v >= thr / c_max (1 - 2^-23)
+                            least = (double)p.thr / (double)cmax * (1.0 - 0x1p-20);
+                    }
+                    if (least > -(double)inf) {
+                        const double span = B - least;
                         num = span < num ? span : num;
                     }
                     const double step = num / steps > kAdcScreenMinStep ? num / steps : kAdcScreenMinStep;
@@ -281,13 +292,20 @@ __device__ __forceinline__ int adc_screen_sum_of(const unsigned (&even)[ND], con
     return (int)((q & 2) ? pair >> 16 : pair & 0xffffu);
 }
 
+// The f32 upper bound of the chain of a row with integer sum U: B - s32 U by one fma, widened by 2^-22 |w| + 2^-100.
+// Non-increasing in U.
+__device__ __forceinline__ float adc_screen_chain_bound(int U, const AdcScreenPrm& p)
+{
+    const float wv = __builtin_fmaf(-p.s, (float)U, p.b);
+    return fadd(__builtin_fmaf(__builtin_fabsf(wv), 0x1p-22f, wv), 0x1p-100f);
+}
+
 // Is a row with integer sum U and scale sc returned for the query of p?  (p is wave-uniform.)
 __device__ __forceinline__ bool adc_screen_keep(int U, const AdcScreenPrm& p, float sc)
 {
     bool keep = U <= p.ulim;
     if (p.ulim == kAdcScreenPerRow) {
-        const float wv = __builtin_fmaf(-p.s, (float)U, p.b);
-        const float wu = fadd(__builtin_fmaf(__builtin_fabsf(wv), 0x1p-22f, wv), 0x1p-100f);
+        const float wu = adc_screen_chain_bound(U, p);
         const float pv = fmul(wu, sc);
         keep = !(sc >= 0.f && sc < __builtin_inff() && pv < p.thr);   // NaN anywhere: not proved, returned
     }

@@ -224,6 +224,33 @@ __global__ __launch_bounds__(1024) void k_adc_screen_lists(
     if (bad) atomicOr(err, 1);
 }
 
+// The stored hit words of one pair into positions, by one wave: 64 words per trip, a wave prefix of their popcounts.
+// run: the pair's first slot.  Both list screens' fill passes walk their words with it.
+__device__ __forceinline__ void adc_screen_lists_emit_words(const uint32_t* __restrict__ hits, int64_t hb, int64_t list_tiles, int64_t lo,
+                                                            int64_t run, int64_t capacity, int64_t* __restrict__ out_i, int lane)
+{
+    for (int64_t t0 = 0; t0 < list_tiles; t0 += 64) {
+        const int64_t t = t0 + lane;
+        unsigned w = t < list_tiles ? hits[hb + t] : 0u;
+        const int pc = __popc(w);
+        int incl = pc;
+#pragma unroll
+        for (int s = 1; s < 64; s <<= 1) {
+            const int o = __shfl_up(incl, s);
+            if (lane >= s) incl += o;
+        }
+        int64_t slot = run + (int64_t)(incl - pc);
+        const int64_t base = lo + t * kFsTile;
+        while (w) {
+            const int b = __builtin_ctz(w);
+            w &= w - 1;
+            if (slot < capacity) out_i[slot] = base + b;
+            ++slot;
+        }
+        run += (int64_t)__shfl(incl, 63);
+    }
+}
+
 // The fill pass: one wave per entry e, entries taken grid-stride.  first [entries]: the scanned counts.
 inline __global__ __launch_bounds__(64 * kRangeWaves) void k_adc_screen_lists_fill(
     const uint8_t* __restrict__ codes, int64_t n, int64_t c_rs, const uint32_t* __restrict__ allow, const float* __restrict__ scales,
@@ -243,26 +270,7 @@ inline __global__ __launch_bounds__(64 * kRangeWaves) void k_adc_screen_lists_fi
         const int64_t hb = hoff[e];
         int64_t run = first[e];
         if (hb + list_tiles <= budget) {
-            for (int64_t t0 = 0; t0 < list_tiles; t0 += 64) {
-                const int64_t t = t0 + lane;
-                unsigned w = t < list_tiles ? hits[hb + t] : 0u;
-                const int pc = __popc(w);
-                int incl = pc;
-#pragma unroll
-                for (int s = 1; s < 64; s <<= 1) {
-                    const int o = __shfl_up(incl, s);
-                    if (lane >= s) incl += o;
-                }
-                int64_t slot = run + (int64_t)(incl - pc);
-                const int64_t base = r.lo + t * kFsTile;
-                while (w) {
-                    const int b = __builtin_ctz(w);
-                    w &= w - 1;
-                    if (slot < capacity) out_i[slot] = base + b;
-                    ++slot;
-                }
-                run += (int64_t)__shfl(incl, 63);
-            }
+            adc_screen_lists_emit_words(hits, hb, list_tiles, r.lo, run, capacity, out_i, lane);
         } else {                                                    // no stored words: form them again, this query alone
             const AdcScreenPrm p = prm_g[q];
             const uint8_t* iq = imgq + q * pitch;

@@ -14,6 +14,7 @@
 //     pqhip_adc_range.hip ADC range search: every row within a radius, as CSR
 //     pqhip_flat_screen_lists.hip  matrix-core range screen in probed lists (query batches of the exact list searches)
 //     pqhip_adc_screen_lists.hip  u8 table screen over codes in probed lists (query batches of the ADC list searches)
+//     pqhip_adc_screen_lists_residual.hip  the same screen over residual codes: a bound per (row, probe slot) from bias and row term
 //     pqhip_adc_screen16.hip  16-bit table screen over resident codes (query batches at large M; policy: adc_screen_launch.h)
 //     pqhip_rerank.hip    exact re-ranking of search candidates against resident vectors
 //     pqhip_lists_merge.hip  merge of two list-ordered row arrays (growing a partitioned matrix)

@@ -1549,6 +1549,150 @@ class Pq:
             _marshal.check_range(cb, slot, sp)
         return (val[0], idx[0]) if single else (val, idx)
 
+    # ---- the same over residual codes: the screen decides per (row, probe slot), the resolve reads a bias per list ---------
+    def _adc_screen_lists_residual(self, codes, ip_tables, list_off, probes, probe_bias, row_terms, threshold, ip, scales,
+                                   allow, cap, stream, retry):
+        """_adc_screen_lists over residual codes (pqhip_adc_screen_lists_residual_f32_dev), the same capacity handling"""
+        import torch
+        if probe_bias is None or not hasattr(probe_bias, "is_cuda"):
+            raise PanicError("the residual screen needs a probe bias")
+        if ip and row_terms is not None:
+            raise PanicError("row terms belong to the distance form")
+        if not ip and row_terms is None:
+            raise PanicError("the residual distance screen needs the row terms")
+        cap = int(cap)
+        if cap < 0:
+            raise PanicError("capacity must not be negative")
+        codes, n, c_rs, nq, mask = self._adc_screen_args(codes, ip_tables, ip, scales, allow)
+        if n > (1 << 32) - 2:
+            raise PanicError("at most 2^32 - 2 rows are searched in lists")
+        pr, _, n_probe, p_rs = _marshal.vector_lists_arg(list_off, probes, nq)
+        dev = codes.device
+        given = [t for t in (list_off, probes, probe_bias, row_terms) if t is not None]
+        if not all(hasattr(t, "is_cuda") and t.is_cuda and t.device == dev for t in given):
+            raise PanicError("codes, tables, list_off, probes, probe_bias, row_terms and allow must be CUDA tensors on one device")
+        bias = _marshal.bias_arg(probe_bias, nq, n_probe)
+        _marshal.per_row_arg(row_terms, n, "row_terms")
+        thr = _marshal.threshold_arg(threshold, nq, dev)
+        own_stream = stream is None
+        cb, slot, sp = _marshal.launch(self, codes, stream)
+        rt = None if ip else _marshal.stand_in(row_terms, n, dev)   # the C call wants an address even without a row to read
+        head = _marshal.search_head(cb, slot, ip_tables, nq, codes, n, c_rs, False, mask, (list_off, pr, n_probe, p_rs), bias,
+                                    last=(ptr_or_none(rt), 1 if ip else 0, ptr_or_none(scales)))
+        lims = torch.empty(nq + 1, dtype=torch.int64, device=dev)
+        while True:
+            idx = torch.empty(cap, dtype=torch.int64, device=dev)
+            _marshal.run("pqhip_adc_screen_lists_residual_f32_dev", *head, thr.data_ptr(), lims.data_ptr(), ptr_or_none(idx, cap),
+                         cap, sp)
+            if not own_stream:
+                torch.cuda.ExternalStream(stream, device=dev).synchronize()
+            total = int(lims[-1])
+            if total <= cap or not retry:
+                break
+            cap = total             # the second call always suffices
+        return lims, idx[:min(total, cap)], total, (cb, slot, sp)
+
+    def adc_screen_lists_residual_device(self, codes, ip_tables, list_off, probes, probe_bias, row_terms, threshold, ip=False,
+                                         scales=None, allow=None, capacity=None, stream=None, check=False):
+        """adc_screen_lists_device over residual codes (pqhip_adc_screen_lists_residual_f32_dev): the arguments of
+        adc_range_lists_residual_device (ip=False) resp. adc_ip_range_lists_residual_device (ip=True, row_terms None)
+        -> (lims, idx): CSR of positions, per query a SUPERSET of what that range call returns at the same thresholds,
+        within the allowed rows of the probed lists and in its order.  A row is left out only when an f32 bound formed
+        from its exact integer sum over a u8 image of the table, the bias of its probe slot and its term resp. scale
+        proves that its value misses the threshold; a regular row is returned only within the slack the header states.
+        Up to 32 queries that probe a list share one stream of its codes.  Capacity and check as for
+        adc_screen_lists_device.  Only u8 codes: packed rows are not served."""
+        lims, idx, _, launch = self._adc_screen_lists_residual(codes, ip_tables, list_off, probes, probe_bias, row_terms,
+                                                               threshold, ip, scales, allow,
+                                                               (1 << 20) if capacity is None else capacity, stream, True)
+        if check:
+            _marshal.check_range(*launch)
+        return lims, idx
+
+    def adc_search_lists_residual_batch_device(self, codes, ip_tables, list_off, probes, probe_bias, row_terms, row_list, k,
+                                               ip=False, scales=None, allow=None, stream=None, check=False, stats=None):
+        """adc_search_lists_residual_device (ip=False) resp. adc_ip_search_lists_residual_device (ip=True, row_terms
+        None) for a batch of queries, bit for bit in values and positions: the sample / screen / resolve of
+        adc_search_lists_batch_device with the same rules and fallbacks.  Sample: the plain residual list search over
+        the first slots.  Screen: adc_screen_lists_residual_device at the sample's k-th value.  Resolve: the residual
+        form of adc_among_device / adc_ip_among_device; row_list CUDA int64 [n] names the list of every position, and the
+        [queries, n_lists] bias it reads is built per chunk by scattering the GIVEN probe_bias through probes (valid
+        slots only), so every candidate sees the bias of its slot bit for bit."""
+        import torch
+        k = int(k)
+        if not 1 <= k <= 1024:
+            raise PanicError("k must be between 1 and 1024, was %d" % k)
+        if probe_bias is None or (not ip and row_terms is None) or row_list is None:
+            raise PanicError("the residual batch search needs the probe bias, the list of every row and, for distances, the row terms")
+        if ip and row_terms is not None:
+            raise PanicError("row terms belong to the distance form")
+        _, N, _, nq, _ = self._adc_screen_args(codes, ip_tables, ip, scales, allow)
+        _, n_lists, n_probe, _ = _marshal.vector_lists_arg(list_off, probes, nq)
+        if ip:
+            kw, akw = {"scales": scales}, {"scales": scales}
+            among = self.adc_ip_among_device
+            plain_call = lambda t, p, b: self.adc_ip_search_lists_residual_device(codes, t, list_off, p, b, k, stream=stream,
+                                                                                  allow=allow, **kw)
+        else:
+            kw, akw = {}, {"row_terms": row_terms}
+            among = self.adc_among_device
+            plain_call = lambda t, p, b: self.adc_search_lists_residual_device(codes, t, list_off, p, b, row_terms, k,
+                                                                               stream=stream, allow=allow)
+        single = ip_tables.dim() == 2
+        t3 = ip_tables[None] if single else ip_tables
+        pr2 = probes[None] if probes.dim() == 1 else probes
+        pb2 = probe_bias[None] if probe_bias.dim() == 1 else probe_bias
+        dev = codes.device
+
+        def finish(val, idx):
+            if check:
+                cb, slot, sp = _marshal.launch(self, codes, stream)
+                _marshal.check_range(cb, slot, sp)
+            return (val[0], idx[0]) if single else (val, idx)
+
+        if N == 0 or nq == 0 or n_lists == 0:
+            return finish(*plain_call(t3, pr2, pb2))
+        s = flat_lists_batch_sample(N, n_lists, n_probe, k)
+        sval, sidx = plain_call(t3, pr2[:, :s].contiguous(), pb2[:, :s].contiguous())
+        T = sval[:, k - 1]
+        srt = torch.sort(pr2, dim=1).values                         # a list named twice: its rows would be candidates twice
+        twice = ((srt[:, 1:] == srt[:, :-1]) & (srt[:, 1:] >= 0)).any(dim=1)
+        thin = (sidx[:, k - 1] < 0) | torch.isnan(T) | twice
+        nothing = float("inf") if ip else float("-inf")          # a thin query screens nothing and takes the plain call
+        thr = torch.where(thin, torch.full_like(T, nothing), T)
+        val = torch.empty((nq, k), dtype=torch.float32, device=dev)
+        idx = torch.empty((nq, k), dtype=torch.int64, device=dev)
+        plain = thin.clone()
+        total_all = 0
+        for q0 in range(0, nq, FLAT_LISTS_BATCH_CHUNK):
+            q1 = min(nq, q0 + FLAT_LISTS_BATCH_CHUNK)
+            cap = int(flat_lists_batch_fraction() * (q1 - q0) * N * min(n_probe, n_lists) / n_lists) + 1
+            try:
+                lims, cand, total, _ = self._adc_screen_lists_residual(codes, t3[q0:q1], list_off, pr2[q0:q1], pb2[q0:q1], row_terms,
+                                                                       thr[q0:q1], ip, scales, allow, cap, stream, False)
+                total_all += total
+                if total > cap or flat_lists_batch_falls_back(total, N, n_lists, n_probe, q1 - q0):
+                    plain[q0:q1] = True
+                    continue
+                # the bias of every list of a query: the given bias of the slot that names it; a pad or a bad id goes to a
+                # spare column, so it never overwrites a list
+                p, b = pr2[q0:q1], pb2[q0:q1]
+                col = torch.where((p >= 0) & (p < n_lists), p, torch.full_like(p, n_lists))
+                lb = torch.zeros((q1 - q0, n_lists + 1), dtype=torch.float32, device=dev).scatter_(1, col, b)[:, :n_lists]
+                val[q0:q1], idx[q0:q1] = among(codes, t3[q0:q1], cand, k, lims=lims, row_list=row_list, list_bias=lb,
+                                               stream=stream, **akw)
+            except _lib.PqHipError as e:
+                if e.status != _lib.EUNSUPPORTED:
+                    raise
+                plain[:] = True                                  # a stage does not serve this quantizer
+                break
+        rows = torch.nonzero(plain).reshape(-1)
+        if rows.shape[0] > 0:
+            val[rows], idx[rows] = plain_call(t3[rows].contiguous(), pr2[rows], pb2[rows])
+        if stats is not None:
+            stats.update(candidates=total_all, fallback_queries=int(rows.shape[0]), sample_slots=int(s))
+        return finish(val, idx)
+
     def adc_range_lists_device(self, codes, tables, list_off, probes, threshold, stream=None, check=False, allow=None,
                                capacity=None):
         """adc_range_device restricted, per query, to the rows of the probed lists (list_off, probes as for

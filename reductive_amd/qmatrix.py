@@ -1217,14 +1217,30 @@ class ResidualPartitionedMatrix(_Lists):
             fn = pq.adc_range_lists_residual_device if ranged else pq.adc_search_lists_residual_device
         return fn, pq.adc_ip_tables_device(queries), (self.list_off, pr, bias) + (() if ip else (self.row_terms,))
 
-    def nearest(self, queries, k, nprobe, refine=None, allow=None):
+    def _topk_screened(self, ip, queries, k, nprobe, use_norms, refine, allow):
+        """_topk by the route for query batches (Pq.adc_search_lists_residual_batch_device); the shortlist R replaces k"""
+        self._unpacked_only("most_similar(screen=True)" if ip else "nearest(screen=True)")
+        R = k if refine is None else self._check_refine(k, refine)
+        pr, bias = self._probes_and_ips(queries, nprobe) if ip else self._probes_and_dists(queries, nprobe)
+        kw = {"scales": self.norms if use_norms else None} if ip else {}
+        val, pos = self.pq.adc_search_lists_residual_batch_device(self.codes, self.pq.adc_ip_tables_device(queries), self.list_off,
+                                                                  pr, bias, None if ip else self.row_terms, self.lists, R, ip=ip,
+                                                                  allow=self._allow_words(allow), **kw)
+        rows = self._original_rows(pos)
+        return (val, rows) if refine is None else self._refined(queries, rows, k, ip)
+
+    def nearest(self, queries, k, nprobe, refine=None, allow=None, screen=False):
         """the k rows of smallest dist = fl(fl(bias + row_term) - fl(s + s)) among the rows of the nprobe nearest lists:
         s the row sum over the query's inner-product table, bias the coarse distance of the row's list as
         coarse.adc_search_device returns it beside the probed ids (the coarse table row when more than 1,024 lists are
         all probed) -> (dist, idx) [k] or [nq, k]; idx are original row numbers, -1 past the last probed row (+Inf).
         refine=R (k <= R <= 1024, vectors attached): the R first rows of that search are re-ranked by their exact
         squared distance to the attached vectors (Pq.rerank_device); dist are then the exact distances.  allow: as for
-        PartitionedMatrix.nearest."""
+        PartitionedMatrix.nearest.  screen=True: the route for query batches
+        (Pq.adc_search_lists_residual_batch_device: u8 table screen per list with list and row terms, exact resolve), the
+        same result bit for bit; not served on a packed matrix."""
+        if screen:
+            return self._topk_screened(False, queries, k, nprobe, True, refine, allow)
         return self._topk(False, queries, k, nprobe, True, refine, allow)
 
     def _probes_and_ips(self, queries, nprobe):
@@ -1236,12 +1252,15 @@ class ResidualPartitionedMatrix(_Lists):
         ipt = ipt[0] if queries.dim() == 1 else ipt[:, 0, :]
         return pr, torch.gather(ipt, -1, pr.clamp(min=0)).contiguous()
 
-    def most_similar(self, queries, k, nprobe, use_norms=True, refine=None, allow=None):
+    def most_similar(self, queries, k, nprobe, use_norms=True, refine=None, allow=None, screen=False):
         """the k rows of largest score = fl(fl(bias + s) * norm) (fl(bias + s) with use_norms=False or without norms)
         among the rows of the nprobe nearest lists, bias the entry of coarse.adc_ip_tables_device(queries)[:, 0, :] at
         the row's list, i.e. <q, c_l> -> (score, idx), idx original row numbers, -1 past the last probed row (-Inf).
         refine=R: the R first rows are re-ranked by their exact inner product with the attached vectors as they are;
-        use_norms then only affects the candidate stage.  allow: as for PartitionedMatrix.nearest."""
+        use_norms then only affects the candidate stage.  allow: as for PartitionedMatrix.nearest; screen: as for
+        nearest()."""
+        if screen:
+            return self._topk_screened(True, queries, k, nprobe, use_norms, refine, allow)
         return self._topk(True, queries, k, nprobe, use_norms, refine, allow)
 
     def within(self, queries, radius, nprobe, allow=None, sort=False):
