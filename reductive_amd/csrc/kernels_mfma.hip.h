@@ -56,7 +56,7 @@ struct EncodeArgs {
     // that found the list full, cycles after the loop}
     unsigned long long* stamps = nullptr;
     // the screen body of k_encode_mfma16 only: the f16 codebook images in LDS order, [M][16,384 bytes], and behind them
-    // the 16-byte headers [M] with the bits of max cc (k_build_screen_image)
+    // the 16-byte headers [M] with the bits of max cc and the threshold's two coefficients (k_build_screen_image)
     const unsigned* screen_img = nullptr;
 };
 

@@ -7,7 +7,8 @@
 //     A operand (centroid):  [-2 c~ (20) | cc~_hi | cc~_lo | 0 | 0 ...]      (a padding centroid: [0 ... | 0 | 0 | 65504 | 0 ...])
 //     B operand (row):       [   x~ (20) |    1   |    1   | 65504 | 0 ...]
 // xx is the same for every centroid of a row and is left out.  |A(c) - s^2 (D(c) - xx)| <= E_r for every c, D the CANON-F32
-// distance, with E_r = kScreenRel / 2 * (xx~ + max cc~) + kScreenAbs / 2 (the proof and its terms: DESIGN.md §5).
+// distance, with E_r = (a xx~ + b) / 2 less a key's perturbation, a and b the codebook's threshold coefficients (kScreenRelX
+// below; at most kScreenRel and kScreenRel max cc~ + kScreenAbs; the proof and its terms: DESIGN.md §5, rounds 7 and 13).
 // The loop screens on v_mfma_f32_32x32x16_f16 (round 12): a block is 32 centroids x the tile's 32 rows, its 32 k
 // positions are two instructions chained through the accumulator, and an instruction holds the vector issue as long as a
 // 16x16x32 one for four times the values.  The chain adds the second instruction's products to the first's sum: one
@@ -55,10 +56,18 @@
 namespace pqhip {
 
 // the screen's constants, on the scaled values (xx~ = s^2 xx, max cc~ = s^2 max cc, M): accept a row when
-// S > M + kScreenRel * (xx~ + max cc~) + kScreenAbs and |M| > kScreenTiny
+// S > M + (a xx~ + b) and |M| > kScreenTiny, where a <= kScreenRel and b <= kScreenRel max cc~ + kScreenAbs
 constexpr float kScreenRel = 0x1.2p-9f;   // >= 2 E_r + 2 key perturbation: (132.6 + 4.04) 2^-16 needed, 144 2^-16 taken
 constexpr float kScreenAbs = 0x1p-100f;   // flushed f32 subnormal products and partial sums
 constexpr float kScreenTiny = 0x1p-100f;  // keeps the index bits of M out of the subnormal range
+// The threshold per codebook (round 13): S > M + (a xx~ + b) with a = kScreenRelX + (1 + 2^-11) delta / sqrt(max cc~),
+// b = a max cc~ + kScreenAbs, delta the largest || fl16(-2 s c) - (-2 s c) || of the codebook's centroids, measured by
+// k_build_screen_image.  kScreenRel charges that error at its worst case 2 u || s c || = 64 of its 144 units; kScreenRelX is
+// the rest, 80 units: the rows' rounding 64, the bound's other terms 4.6, two key perturbations 2 kScreenKeyUnits, and
+// the 7.3 units of slack that kScreenRel keeps for the f32 rounding of the threshold.  a and b never exceed the
+// kScreenRel values: a codebook rounded at the worst case screens with the round-7 threshold.
+constexpr float kScreenRelX = 0x1.4p-10f;
+constexpr float kScreenKeyUnits = 0x1.04p1f;   // a 7-bit key moves a value by < 2.02 2^-16 (xx~ + max cc~)
 // the scale: s^2 max cc in [2^kScreenScaleLo, 2^(kScreenScaleLo + 2)); rows with xx~ >= kScreenMaxXX take the exact path
 // (then every |x~_k| < 2^15 and no f16 operand overflows); codebooks with max cc outside [2^-100, 2^100) do too
 constexpr int kScreenScaleLo = 12;
@@ -75,8 +84,8 @@ template <int T, int DP> constexpr bool mfma16_screens() { return mfma16_screen_
 
 // The f16 codebook image of the screen, built once per codebook by k_build_screen_image (kernels_prep.hip.h) and copied
 // into LDS by every workgroup: per subquantizer kScreenImageBytes in LDS order (256 rows of 32 f16, chunk j of row r at
-// chunk j ^ ((r >> 2) & 3), padding rows included), and behind the M images one 16-byte header per subquantizer whose
-// first word holds the bits of max cc.
+// chunk j ^ ((r >> 2) & 3), padding rows included), and behind the M images one 16-byte header per subquantizer: the bits
+// of max cc, then the threshold's coefficients a and b.
 constexpr int kScreenImageBytes = 256 * 32 * 2;
 constexpr int kScreenHeaderBytes = 16;
 constexpr size_t screen_image_bytes(int64_t M) { return (size_t)M * (kScreenImageBytes + kScreenHeaderBytes); }
@@ -165,7 +174,7 @@ template <typename IdxT>
 __device__ __forceinline__ void encode_rows_cand_f16(const float* x, int64_t x_rs, void* out, int64_t o_rs, const float* cbk,
                                                   const float* ccn, int K, int k_pad, int dsub, int64_t n, int m,
                                                   int64_t row_begin, const unsigned short* img, const unsigned* tiles,
-                                                  unsigned long long flagged_c, float sc, float maxcct)
+                                                  unsigned long long flagged_c, float sc, float thr_a, float thr_b)
 {
     constexpr int DP = 20, kRow = 32;
     const int lane = threadIdx.x & 63;
@@ -234,7 +243,7 @@ __device__ __forceinline__ void encode_rows_cand_f16(const float* x, int64_t x_r
         gather_groups(mn, mq);
         // (a lane with no row tests against NaN: no candidate, and no branch around the tests for the compiler to sink
         // them into, behind all sixteen blocks)
-        const float tau = rv ? fminf(fminf(mq[0], mq[1]), fminf(mq[2], mq[3])) + (kScreenRel * (xxs + maxcct) + kScreenAbs)
+        const float tau = rv ? fminf(fminf(mq[0], mq[1]), fminf(mq[2], mq[3])) + fmaf(thr_a, xxs, thr_b)
                              : __builtin_nanf("");
         const PQHIP_LDS_AS unsigned short* arow2 = arow;
         asm volatile("" : "+v"(arow2) : "v"(tau));                     // (and not before tau is there to test against)
@@ -372,19 +381,19 @@ __device__ __forceinline__ void encode_mfma16_screen(const EncodeArgs& a)
 
     const unsigned long long st_s0 = a.stamps ? __builtin_amdgcn_s_memtime() : 0;
     // the subquantizer's image, as k_build_screen_image left it: thread t copies the 16-byte chunks t, t + 256, t + 512 and
-    // t + 768; max cc comes from the header with one wave-uniform load
-    unsigned maxcc_bits = 0u;
+    // t + 768; max cc and the threshold's coefficients come from the header with one wave-uniform load
+    u32x4_t hdr = {0u, 0u, 0u, 0u};
     if (wg_active) {
         const u32x4_t* src = reinterpret_cast<const u32x4_t*>(a.screen_img) + (int64_t)m * (kScreenImageBytes / 16) + threadIdx.x;
         u32x4_t* dst = reinterpret_cast<u32x4_t*>(img_s) + threadIdx.x;
         u32x4_t ch[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) ch[j] = src[256 * j];
-        maxcc_bits = a.screen_img[(int64_t)a.M * (kScreenImageBytes / 4) + m * (kScreenHeaderBytes / 4)];
+        hdr = *reinterpret_cast<const u32x4_t*>(a.screen_img + (int64_t)a.M * (kScreenImageBytes / 4) + m * (kScreenHeaderBytes / 4));
 #pragma unroll
         for (int j = 0; j < 4; ++j) dst[256 * j] = ch[j];
     }
-    const float maxcc = __uint_as_float(maxcc_bits);
+    const float maxcc = __uint_as_float(hdr[0]);
     const ScreenScale scale = screen_scale(maxcc);
     const bool cc_range = scale.cc_range;
     const float sc = scale.sc, sc2 = scale.sc2;
@@ -399,6 +408,10 @@ __device__ __forceinline__ void encode_mfma16_screen(const EncodeArgs& a)
     const bool near_rows = (uint64_t)a.x_rs < (1ull << 24) && (uint64_t)a.o_rs < (1ull << 24);   // wave-uniform
     const bool cb_ok = !bad_codebook && cc_range && near_rows;            // wave-uniform
     const float maxcct = sc2 * maxcc;                                    // max cc~, exact
+    // the threshold M + (thr_a xx~ + thr_b): the codebook's measured coefficients, never above the round-7 ones (fminf
+    // drops a NaN word)
+    const float thr_a = fminf(__uint_as_float(hdr[1]), kScreenRel);
+    const float thr_b = fminf(__uint_as_float(hdr[2]), kScreenRel * maxcct + kScreenAbs);
 
     // x chunks of lane (n32, h): x[8h .. 8h + 7] for the first k step and one chunk of 4 floats for the second, x[16 .. 19]
     // in half 0; half 1 carries zeros there and reads x[8 .. 11] again, inside the sub-vector, to multiply it by zero
@@ -564,7 +577,7 @@ __device__ __forceinline__ void encode_mfma16_screen(const EncodeArgs& a)
         const float M = vmin(m0, m1);
         const float S2 = vmin(__uint_as_float(xs[0]), __uint_as_float(xs[1]));   // smaller second key of the two halves
         const float S = vmin(vmax(m0, m1), S2);
-        const float tau = M + (kScreenRel * (xx + maxcct) + kScreenAbs);
+        const float tau = M + fmaf(thr_a, xx, thr_b);
         const bool valid = lane < (int)(row_end - row0 < 64 ? row_end - row0 : 64);   // scalar bound
         const bool in_range = valid && cb_ok && xx < kScreenMaxXX;       // the f16 operands are exact enough
         const bool plain = in_range && __builtin_fabsf(M) > kScreenTiny;
@@ -634,7 +647,7 @@ __device__ __forceinline__ void encode_mfma16_screen(const EncodeArgs& a)
     const unsigned long long st_p1 = a.stamps ? __builtin_amdgcn_s_memtime() : 0;
     if (flagged_c)                                                      // wave-uniform
         encode_rows_cand_f16<IdxT>(a.x, a.x_rs, a.out, a.o_rs, a.cb, a.cc, a.K, a.k_pad, a.dsub, a.n, m, row_begin,
-                                   img_s, cand_s[wave], flagged_c, sc, sc2 * maxcc);
+                                   img_s, cand_s[wave], flagged_c, sc, thr_a, thr_b);
     const unsigned long long st_p2 = a.stamps ? __builtin_amdgcn_s_memtime() : 0;
     // ---- rows outside the f16 range or under a bad codebook: every centroid exactly
     while (flagged) {                                                   // wave-uniform

@@ -68,15 +68,21 @@ __global__ void k_check_norms(const float* __restrict__ cc, int M, int K, int k_
 // The f16 image of the screen body of k_encode_mfma16 (kernels_mfma16_screen.hip.h: the operand rows, the swizzle and the
 // scale), one workgroup of 256 threads per subquantizer, one thread per image row: the largest real ||c||^2 first (bits
 // order = value order for cc >= +0; a NaN norm comes out above +inf), then the scale and the row.  K <= 256 = k_pad,
-// dsub = 20.  img: [M][256 rows][32 f16] in LDS order, then the headers [M][4 words], word 0 the bits of max cc.
+// dsub = 20.  img: [M][256 rows][32 f16] in LDS order, then the headers [M][4 words]: word 0 the bits of max cc, words 1 and
+// 2 the threshold's coefficients a and b (kScreenRelX in kernels_mfma16_screen.hip.h).  They come
+// from delta, the largest 2-norm over the real centroids of the rounding error fl16(-2 s c) - (-2 s c): the difference of
+// the two f32 values is exact, its squares are summed in double, and every later step is rounded up or carries the
+// factor 1 + 2^-20, so a and b are upper bounds.  An operand below f16's normal range counts with the error of its
+// subnormal rounding here; that the matrix core may flush it is charged to the rows' half of the bound as before.
 __global__ __launch_bounds__(256) void k_build_screen_image(const float* __restrict__ cb, const float* __restrict__ cc, int M, int K,
                                                             int k_pad, unsigned* __restrict__ img)
 {
     constexpr int DP = 20;
     constexpr int kRow = 32;
     __shared__ unsigned maxcc_s;
+    __shared__ unsigned long long err2_s;                            // bits of the largest squared error norm (>= +0: bits order)
     const int m = blockIdx.x;
-    if (threadIdx.x == 0) maxcc_s = 0u;
+    if (threadIdx.x == 0) { maxcc_s = 0u; err2_s = 0ull; }
     __syncthreads();
     const int c = threadIdx.x;
     const float ccv = cc[(int64_t)m * k_pad + c];
@@ -91,6 +97,14 @@ __global__ __launch_bounds__(256) void k_build_screen_image(const float* __restr
         const float m2s = -2.f * sc;
 #pragma unroll
         for (int j = 0; j < DP / 2; ++j) w[j] = pk_f16(m2s * cp[2 * j], m2s * cp[2 * j + 1]);   // RNE(-2 s c)
+        double e2 = 0.0;
+#pragma unroll
+        for (int k = 0; k < DP; ++k) {
+            const float v = m2s * cp[k];
+            const double e = (double)((float)(_Float16)v - v);
+            e2 += e * e;
+        }
+        if (scale.cc_range) atomicMax(&err2_s, (unsigned long long)__double_as_longlong(e2));
         const float cct = sc2 * ccv;                                 // exact, < 2^14
         const unsigned hp = pk_f16(cct, 0.f);
         w[10] = pk_f16(cct, cct - f16_lo(hp));                       // cct - hi is exact
@@ -107,9 +121,21 @@ __global__ __launch_bounds__(256) void k_build_screen_image(const float* __restr
     const int swz = (c >> 2) & 3;
 #pragma unroll
     for (int j = 0; j < 4; ++j) dst[j ^ swz] = (u32x4_t){w[4 * j], w[4 * j + 1], w[4 * j + 2], w[4 * j + 3]};
-    if (c == 0)
+    __syncthreads();
+    if (c == 0) {
+        // the round-7 threshold, and the measured one when both of its coefficients are below it
+        const float maxcct = sc2 * maxcc;
+        float a = kScreenRel, b = kScreenRel * maxcct + kScreenAbs;
+        if (scale.cc_range) {
+            auto up = [](double v) { const float f = (float)v; return (double)f >= v ? f : __uint_as_float(__float_as_uint(f) + 1u); };   // v > 0
+            const double delta = sqrt(__longlong_as_double((long long)err2_s));
+            const float am = up((double)kScreenRelX + ((1.0 + 0x1p-11) * (1.0 + 0x1p-20)) * delta / sqrt((double)maxcct));
+            const float bm = up((double)am * (double)maxcct + (double)kScreenAbs);
+            if (am < a && bm < b) { a = am; b = bm; }
+        }
         *reinterpret_cast<u32x4_t*>(img + (int64_t)M * (kScreenImageBytes / 4) + m * (kScreenHeaderBytes / 4)) =
-            (u32x4_t){__float_as_uint(maxcc), 0u, 0u, 0u};
+            (u32x4_t){__float_as_uint(maxcc), __float_as_uint(a), __float_as_uint(b), 0u};
+    }
 }
 
 // fragp[p][s][lane = (i, h)] = A[i][2 s + h] of pair p (see the header); ccp[p][hh][r] = ||c_{2p+hh}[r]||^2
