@@ -1003,6 +1003,34 @@ int32_t pqhip_adc_screen16_f32_dev(pqhip_codebook *cb, int32_t device_slot,
                                    int64_t capacity, void *stream);
 
 /*
+ * pqhip_adc_screen_f32_dev over 4-BIT PACKED rows (pqhip_pack_codes4_dev; K <= 16): the same arguments (16, same order
+ * and meaning) with d_codes the packed rows -- ceil(M / 2) bytes each, codes_row_stride >= ceil(M / 2) bytes, any address
+ * and any stride, code_bytes 1 -- and the same output.  With K <= 16 the integer sum of a row is a matrix product,
+ * U[row][q] = onehot(row) . IMG[q], and is taken on the i8 matrix cores (v_mfma_i32_32x32x32_i8: two subquantizers for
+ * 32 rows x 32 queries per instruction, exact in int32); up to 64 queries share one stream of the codes (32 for M > 64).
+ * Definition: d_lims and d_idx are bit for bit what pqhip_adc_screen_f32_dev returns on the unpacked codes with the same
+ * tables, thresholds, ip, scales, mask and capacity -- the same per-query image and parameters, the same predicate
+ * (U <= U_lim, or the f32 epilogue of the scaled form, operation for operation), the same ascending ids and capacity
+ * protocol; the result depends neither on the grid (option "adc_screen_wgs") nor on how queries are grouped into passes.
+ * Nibbles: a nibble >= K in an allowed row raises the range flag (pqhip_check_codes_dev) and selects an image entry of 0,
+ * so the row can only become more likely to be returned (pqhip_adc_screen_f32_dev reads entry 0 of the subquantizer
+ * there: under the flag the two may differ).  The pad nibble of an odd M is ignored whatever it holds.  A disallowed row
+ * and a row past n_rows are never loaded; no byte outside the code matrix is read.
+ * Status codes as for pqhip_adc_screen_f32_dev, with: K > 16, M > 100 (kAdcScreenMaxM), code_bytes not 1:
+ * PQHIP_EUNSUPPORTED; codes_row_stride < ceil(M / 2): PQHIP_ESHAPE.  Per pass: the prep kernel, the count pass, the prefix
+ * scan of the range calls, the fill pass per 32 queries (none for a count call); with d_scales one reduction in front.
+ */
+int32_t pqhip_adc_screen_packed4_f32_dev(pqhip_codebook *cb, int32_t device_slot,
+                                         const float *d_tables /* [n_queries][M][K] */, int64_t n_queries,
+                                         const void *d_codes /* packed rows */, int32_t code_bytes, int64_t n_rows,
+                                         int64_t codes_row_stride,
+                                         const uint32_t *d_allow /* ceil(n_rows / 32) words or NULL */,
+                                         int32_t ip /* 0 = distance tables, 1 = inner-product tables */,
+                                         const float *d_scales /* ip 1: [n_rows] or NULL */,
+                                         const float *d_threshold /* [n_queries] */, int64_t *d_lims, int64_t *d_idx,
+                                         int64_t capacity, void *stream);
+
+/*
  * The range screen of pqhip_flat_screen_f32_dev in PROBED LISTS: for a batch of queries, per query a superset of what
  * pqhip_flat_range_lists_f32_dev returns at the same thresholds, as positions (CSR, no values) -- the first stage of the
  * exact list searches for query batches (resolve with pqhip_flat_range_among_f32_dev / pqhip_flat_among_f32_dev).  The work
@@ -1496,8 +1524,8 @@ int32_t pqhip_set_rotation_variant(int32_t variant);
  *   "flat_screen_lists_unit_rows"  rows of a unit of that call, rounded up to a multiple of 32 (0 = 1024)
  *   "flat_screen_lists_chunk_queries"  queries of a chunk of that call (0 = from the scratch bound; at most 2^20 / n_probe);
  *                          the result depends on none of the three
- *   "adc_screen_wgs"       producer workgroups of pqhip_adc_screen_f32_dev and pqhip_adc_screen16_f32_dev (0 = one per CU; at most 2048, so that the
- *                          prefix scan of a pass of 32 queries sums at most 2^20 counts; rows per workgroup stay a
+ *   "adc_screen_wgs"       producer workgroups of pqhip_adc_screen_f32_dev and pqhip_adc_screen16_f32_dev, and of pqhip_adc_screen_packed4_f32_dev (0 = one per CU; at most 2048: the
+ *                          prefix scan of a pass then sums at most 2^20 counts per 32 queries, 2^21 for a packed pass of 64; rows per workgroup stay a
  *                          multiple of 1,024; the result does not depend on it)
  *   "adc_screen_lists_wgs"  workgroups of pqhip_adc_screen_lists_f32_dev that stride over its units (0 = one per CU)
  *   "adc_screen_lists_unit_rows"  rows of a unit of that call, rounded up to a multiple of 64 (0 = 16384)

@@ -13,7 +13,7 @@ namespace pqh {
 
 using namespace pqhip;
 
-constexpr int64_t kAdcScreenWgsMax = 2048;       // 32,768 units: a pass of 32 queries has 2^20 counts, what one scan launch sums
+constexpr int64_t kAdcScreenWgsMax = 2048;       // 32,768 units: 2^20 counts per 32 queries of a pass for the one scan launch (it loops over any length)
 constexpr size_t kAdcScreenLds = 160 * 1024;
 
 struct AdcScreenLaunch {

@@ -1285,10 +1285,12 @@ class Pq:
         return self._adc_range(True, codes, tables, threshold, scales, stream, check, allow, capacity)
 
     # ---- ADC search for query batches: u8 table screen, exact resolve ------------------------------------------------
-    def _adc_screen_args(self, codes, tables, ip, scales, allow):
-        """What the screen and its composition check and marshal (codes, tables, scales and mask as for the range calls)
-        -> (codes, n, row stride, nq, the mask argument)."""
+    def _adc_screen_args(self, codes, tables, ip, scales, allow, packed4=False):
+        """What the screen and its composition check and marshal (codes, tables, scales and mask as for the range calls;
+        packed4: 4-bit packed rows) -> (codes, n, row stride, nq, the mask argument)."""
         import torch
+        if packed4:
+            self._packed4_served()
         if not (hasattr(codes, "is_cuda") and codes.dtype == torch.uint8 and codes.dim() == 2):
             raise PanicError("codes must be a uint8 [n, n_subquantizers] tensor (4-byte and packed codes are not served)")
         if not (hasattr(tables, "is_cuda") and tables.dtype == torch.float32 and tables.dim() in (2, 3) and tables.is_contiguous()):
@@ -1296,7 +1298,7 @@ class Pq:
         if scales is not None and not ip:
             raise PanicError("scales belong to the inner-product form")
         M, K = self.quantized_len(), self.n_quantizer_centroids()
-        W = _marshal.code_width(codes, M)
+        W = _marshal.code_width(codes, M, packed4)
         _, nq = _marshal.tables_arg(tables, M, K)
         if not (codes.is_cuda and tables.is_cuda and tables.device == codes.device):
             raise PanicError("codes and tables must be CUDA tensors on one device")
@@ -1308,18 +1310,23 @@ class Pq:
         return codes, n, c_rs, nq, _marshal.mask_arg(allow, codes, True)
 
     @staticmethod
-    def _adc_screen_entry(image_bits):
-        """the screen's entry point by the width of its table image: 8 or 16 bits per entry"""
+    def _adc_screen_entry(image_bits, packed4=False):
+        """the screen's entry point by the width of its table image, 8 or 16 bits per entry, and the form of the rows"""
         if image_bits not in (8, 16):
             raise PanicError("image_bits must be 8 or 16, was %r" % (image_bits,))
+        if packed4:
+            if image_bits != 8:
+                raise PanicError("4-bit packed codes are screened with the u8 image only (image_bits=8)")
+            return "pqhip_adc_screen_packed4_f32_dev"
         return "pqhip_adc_screen_f32_dev" if image_bits == 8 else "pqhip_adc_screen16_f32_dev"
 
-    def _adc_screen(self, codes, tables, threshold, ip, scales, allow, cap, stream, retry, entry="pqhip_adc_screen_f32_dev"):
-        """One screen call (the entry point `entry`) with `cap` entries and, if retry and the result is larger, one more of
+    def _adc_screen(self, codes, tables, threshold, ip, scales, allow, cap, stream, retry, entry="pqhip_adc_screen_f32_dev",
+                    packed4=False):
+        """One screen call (the entry point `entry`; packed4: over 4-bit packed rows) with `cap` entries and, if retry and the result is larger, one more of
         exactly its size -> (lims, idx[:min(total, cap)], total, launch); lims[-1] is read in between, the one
         synchronisation."""
         import torch
-        codes, n, c_rs, nq, mask = self._adc_screen_args(codes, tables, ip, scales, allow)
+        codes, n, c_rs, nq, mask = self._adc_screen_args(codes, tables, ip, scales, allow, packed4)
         dev = codes.device
         thr = _marshal.threshold_arg(threshold, nq, dev)
         cap = int(cap)
@@ -1341,7 +1348,7 @@ class Pq:
         return lims, idx[:min(total, cap)], total, (cb, slot, sp)
 
     def adc_screen_device(self, codes, tables, threshold, ip=False, scales=None, allow=None, capacity=None, stream=None,
-                          check=False, image_bits=8):
+                          check=False, image_bits=8, packed4=False):
         """Conservative range screen over resident u8 codes (pqhip_adc_screen_f32_dev): codes, tables, threshold, scales
         and allow as for adc_range_device (ip=False) resp. adc_ip_range_device (ip=True) -> (lims, idx): CSR, lims CUDA
         int64 [nq + 1], the ids of query q at idx[lims[q]:lims[q + 1]] in ascending order -- a SUPERSET of what the range
@@ -1353,16 +1360,20 @@ class Pq:
         A quantizer whose images do not fit the LDS raises PqHipError (PQHIP_EUNSUPPORTED).  check=True synchronises
         and reports a code >= K.  image_bits=16: the 16-bit image (pqhip_adc_screen16_f32_dev) of floor(65,535 / M)
         levels per entry -- the same contract with a slack of M / (floor(65,535 / M) - 1) of thr - base instead of
-        M / 254, at 16 / 8 / 4 queries per stream of the codes; any other value but 8 is refused."""
-        entry = self._adc_screen_entry(image_bits)
+        M / 254, at 16 / 8 / 4 queries per stream of the codes; any other value but 8 is refused.  packed4=True: codes are
+        4-bit packed rows (pack_codes4_device; K <= 16) and the result is bit for bit that of the unpacked codes, the
+        integer sums taken as one-hot products on the i8 matrix cores at up to 64 queries per stream of the codes
+        (pqhip_adc_screen_packed4_f32_dev); a nibble >= K raises the range flag and counts as an image entry of 0, the pad
+        nibble of an odd M is ignored; image_bits=16 is refused."""
+        entry = self._adc_screen_entry(image_bits, packed4)
         lims, idx, _, (cb, slot, sp) = self._adc_screen(codes, tables, threshold, ip, scales, allow,
-                                                        (1 << 20) if capacity is None else capacity, stream, True, entry)
+                                                        (1 << 20) if capacity is None else capacity, stream, True, entry, packed4)
         if check:
             _marshal.check_range(cb, slot, sp)
         return lims, idx
 
     def adc_search_batch_device(self, codes, tables, k, ip=False, scales=None, allow=None, stream=None, check=False,
-                                stats=None, image_bits=8):
+                                stats=None, image_bits=8, packed4=False):
         """adc_search_device (ip=False) resp. adc_ip_search_device (ip=True) for a batch of queries, bit for bit in
         values and ids, at one stream of the codes per up to 32 queries.  Sample: every t-th row (flat_batch_sample; -1
         where the mask disallows it) through adc_among_device / adc_ip_among_device; T_q, its k-th value, is a valid
@@ -1373,12 +1384,16 @@ class Pq:
         (flat_batch_falls_back) and a quantizer the screen does not serve (PQHIP_EUNSUPPORTED) take the plain call.
         stats: a dict that receives the candidate total, the queries that fell back and the sample size.
         image_bits=16 screens with the 16-bit image (adc_screen_device): the same sample, chunks, capacity, fallback rule
-        and resolve, so the same result; fewer candidates at large M, half the queries per stream of the codes."""
+        and resolve, so the same result; fewer candidates at large M, half the queries per stream of the codes.
+        packed4=True: codes are 4-bit packed rows and the result is that of the plain packed search, bit for bit
+        (_adc_search_batch_packed4)."""
         import torch
         k = int(k)
         if not 1 <= k <= 1024:
             raise PanicError("k must be between 1 and 1024, was %d" % k)
-        entry = self._adc_screen_entry(image_bits)
+        entry = self._adc_screen_entry(image_bits, packed4)
+        if packed4:
+            return self._adc_search_batch_packed4(codes, tables, k, ip, scales, allow, stream, check, stats, entry)
         self._adc_screen_args(codes, tables, ip, scales, allow)   # before the mask is indexed for the sample
         kw = {"scales": scales} if ip else {}
         among = self.adc_ip_among_device if ip else self.adc_among_device
@@ -1428,6 +1443,86 @@ class Pq:
         rows = torch.nonzero(plain).reshape(-1)
         if rows.shape[0] > 0:
             val[rows], idx[rows] = plain_call(codes, t3[rows].contiguous(), k, stream=stream, allow=allow, **kw)
+        if stats is not None:
+            stats.update(candidates=total_all, fallback_queries=int(rows.shape[0]), sample=int(ids.shape[0]))
+        if check:
+            cb, slot, sp = _marshal.launch(self, codes, stream)
+            _marshal.check_range(cb, slot, sp)
+        return (val[0], idx[0]) if single else (val, idx)
+
+    def _adc_search_batch_packed4(self, codes, tables, k, ip, scales, allow, stream, check, stats, entry):
+        """adc_search_batch_device over 4-bit packed rows: the same sample, chunks, capacity and fallback rules with the
+        one-hot screen (pqhip_adc_screen_packed4_f32_dev), and the plain packed search wherever the unpacked route takes
+        the plain call.  The candidate call does not read packed rows, so the sample and the screen's ids are gathered
+        and unpacked first (unpack_codes4_device(rows=)) and ranked by PLACE: the candidate call runs over the gathered
+        [total, M] codes with the places 0 .. total - 1 as ids, the screen's lims and the scales gathered by the same
+        ids, and the returned places are mapped back through the id list (-1 stays -1).  Exactness: the screen returns
+        a query's ids ascending, so within a query place order equals row order and the candidate call's (key, row)
+        order is kept; the values are the same f32 chains over the same codes.  In the sample a disallowed row is
+        gathered and unpacked like any other and its place is named -1, so the candidate call skips it: this read of a
+        disallowed row is intended (its codes are in range of the matrix, the unpack raises no flag for a nibble, and a
+        stand-in row would cost a second gather); "never loaded" is the promise of the screen kernel alone."""
+        import torch
+        self._adc_screen_args(codes, tables, ip, scales, allow, True)   # before the mask is indexed for the sample
+        among = self.adc_ip_among_device if ip else self.adc_among_device
+        plain_call = self.adc_ip_search_device if ip else self.adc_search_device
+        kw = {"scales": scales} if ip else {}
+        single = tables.dim() == 2
+        t3 = tables[None] if single else tables
+        nq, N = t3.shape[0], codes.shape[0]
+        dev = codes.device
+        if N == 0 or nq == 0:
+            return plain_call(codes, tables, k, stream=stream, check=check, allow=allow, packed4=True, **kw)
+
+        def among_rows(tb, rows, names, lims=None):
+            """the candidate call over the unpacked rows `rows`, named by `names` -> (values, places)"""
+            sub = self.unpack_codes4_device(codes, rows=rows, stream=stream)
+            kws = {"scales": None if scales is None else scales[rows].contiguous()} if ip else {}
+            return among(sub, tb, names, k, lims=lims, stream=stream, **kws)
+
+        S, t = flat_batch_sample(N, k)
+        ids = torch.arange(0, N, t, dtype=torch.int64, device=dev)
+        names = torch.arange(ids.shape[0], dtype=torch.int64, device=dev)
+        if allow is not None:
+            bit = (allow[ids >> 5] >> (ids & 31).to(torch.int32)) & 1
+            names = torch.where(bit != 0, names, torch.full_like(names, -1))
+        try:
+            sval, sidx = among_rows(t3, ids, names)
+        except _lib.PqHipError as e:
+            if e.status != _lib.EUNSUPPORTED:
+                raise
+            if stats is not None:                                # the candidate call does not serve this quantizer
+                stats.update(candidates=0, fallback_queries=nq, sample=0)
+            return plain_call(codes, tables, k, stream=stream, check=check, allow=allow, packed4=True, **kw)
+        T = sval[:, k - 1]
+        thin = (sidx[:, k - 1] < 0) | torch.isnan(T)
+        nothing = float("inf") if ip else float("-inf")          # a thin query takes the plain call
+        thr = torch.where(thin, torch.full_like(T, nothing), T)
+        val = torch.empty((nq, k), dtype=torch.float32, device=dev)
+        idx = torch.empty((nq, k), dtype=torch.int64, device=dev)
+        plain = thin.clone()
+        total_all = 0
+        for q0 in range(0, nq, FLAT_BATCH_CHUNK):
+            q1 = min(nq, q0 + FLAT_BATCH_CHUNK)
+            cap = flat_batch_capacity(N, q1 - q0, k, S)
+            try:
+                lims, cand, total, _ = self._adc_screen(codes, t3[q0:q1], thr[q0:q1], ip, scales, allow, cap, stream, False, entry, True)
+            except _lib.PqHipError as e:
+                if e.status != _lib.EUNSUPPORTED:
+                    raise
+                plain[:] = True                                  # the screen does not serve this quantizer
+                break
+            total_all += total
+            if flat_batch_falls_back(total, N, q1 - q0):
+                plain[q0:q1] = True
+                continue
+            if total == 0:                                       # only thin queries: the plain call below
+                continue
+            val[q0:q1], place = among_rows(t3[q0:q1], cand, torch.arange(total, dtype=torch.int64, device=dev), lims)
+            idx[q0:q1] = torch.where(place >= 0, cand[place.clamp(min=0)], place)
+        rows = torch.nonzero(plain).reshape(-1)
+        if rows.shape[0] > 0:
+            val[rows], idx[rows] = plain_call(codes, t3[rows].contiguous(), k, stream=stream, allow=allow, packed4=True, **kw)
         if stats is not None:
             stats.update(candidates=total_all, fallback_queries=int(rows.shape[0]), sample=int(ids.shape[0]))
         if check:

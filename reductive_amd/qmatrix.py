@@ -677,10 +677,16 @@ class QuantizedMatrix(_Refine, _Filter, _Packed4, _Search, _Among, _Compact):
 
     def _topk_screened(self, ip, queries, k, use_norms, refine, allow, screen):
         """_topk by the route for query batches (Pq.adc_search_batch_device); the shortlist R replaces k; screen "u16"
-        takes the 16-bit image, any other true value the u8 image"""
-        self._unpacked_only("most_similar(screen=True)" if ip else "nearest(screen=True)")
+        takes the 16-bit image, "onehot" the one-hot screen of a packed matrix, any other true value the u8 image"""
+        onehot = isinstance(screen, str) and screen == "onehot"
+        if onehot and not self.packed4:
+            raise PanicError("screen=\"onehot\" reads 4-bit packed codes: call pack4() first")
+        if not onehot:
+            self._unpacked_only("most_similar(screen=True)" if ip else "nearest(screen=True)")
         R = k if refine is None else self._check_refine(k, refine)
         kw = {"scales": self.norms if use_norms else None} if ip else {}
+        if onehot:
+            kw["packed4"] = True
         val, rows = self.pq.adc_search_batch_device(self.codes, self._tables(ip, queries), R, ip=ip,
                                                     allow=self._allow_words(allow), image_bits=16 if screen == "u16" else 8, **kw)
         return (val, rows) if refine is None else self._refined(queries, rows, k, ip)
@@ -694,7 +700,9 @@ class QuantizedMatrix(_Refine, _Filter, _Packed4, _Search, _Among, _Compact):
         -1 past the last allowed row); with refine= the shortlist holds allowed rows only.  screen=True: the route for
         query batches (Pq.adc_search_batch_device: u8 table screen, exact resolve), the same result bit for bit; not
         served on a packed matrix.  screen="u16": that route with the 16-bit table image, the one for many subquantizers
-        and shortlists of 100 and more."""
+        and shortlists of 100 and more (DESIGN.md §5g).  screen="onehot": the batch route of a PACKED matrix (pack4();
+        Pq.adc_search_batch_device(packed4=True): one-hot screen on the i8 matrix cores), the same result
+        bit for bit; on an unpacked matrix a PanicError."""
         if screen:
             return self._topk_screened(False, queries, k, True, refine, allow, screen)
         return self._topk(False, queries, k, None, True, refine, allow)

@@ -241,6 +241,13 @@ extern "C" {
         d_codes: *const c_void, code_bytes: i32, n_rows: i64, codes_row_stride: i64, d_allow: *const u32, ip: i32,
         d_scales: *const f32, d_threshold: *const f32, d_lims: *mut i64, d_idx: *mut i64, capacity: i64,
         stream: *mut c_void) -> i32;
+    // pqhip_adc_screen_f32_dev over 4-bit packed rows (K <= 16; codes_row_stride >= ceil(M / 2) bytes): bit for bit its
+    // result on the unpacked codes, the integer sums as one-hot products on the i8 matrix cores, up to 64 queries per
+    // stream of the codes; a nibble >= K raises the range flag and counts as an entry of 0, the pad nibble is ignored
+    pub fn pqhip_adc_screen_packed4_f32_dev(cb: *mut pqhip_codebook, device_slot: i32, d_tables: *const f32, n_queries: i64,
+        d_codes: *const c_void, code_bytes: i32, n_rows: i64, codes_row_stride: i64, d_allow: *const u32, ip: i32,
+        d_scales: *const f32, d_threshold: *const f32, d_lims: *mut i64, d_idx: *mut i64, capacity: i64,
+        stream: *mut c_void) -> i32;
     // the same screen in probed lists: per query a superset of what pqhip_flat_range_lists_f32_dev returns, as positions
     // in that call's order (probe slot first, then position); list-major on the device, d <= 2048
     pub fn pqhip_flat_screen_lists_f32_dev(cb: *mut pqhip_codebook, device_slot: i32, d_queries: *const f32, n_queries: i64,
