@@ -1109,6 +1109,39 @@ int32_t pqhip_adc_screen_lists_f32_dev(pqhip_codebook *cb, int32_t device_slot,
                                        int64_t capacity, void *stream);
 
 /*
+ * pqhip_adc_screen_lists_f32_dev over 4-BIT PACKED rows (pqhip_pack_codes4_dev; K <= 16): the same arguments (21, same
+ * order and meaning) with d_codes the packed rows -- ceil(M / 2) bytes each, codes_row_stride >= ceil(M / 2) bytes, any
+ * address and any stride, code_bytes 1 -- and the same output.  The integer sum of a (row, query) is the one-hot product
+ * of pqhip_adc_screen_packed4_f32_dev on the i8 matrix cores (v_mfma_i32_32x32x32_i8, exact in int32); a list that several
+ * queries probe is streamed once per group of up to 64 of them (32 for M > 64).
+ * Definition: d_lims and d_idx are bit for bit what pqhip_adc_screen_lists_f32_dev returns on the unpacked codes with the
+ * same tables, thresholds, ip, scales, mask, lists, probes and capacity -- the same per-query image and parameters, the
+ * same predicate, the same order (probe slot first, then ascending position; a list named twice returns its rows twice)
+ * and the same capacity protocol.  The result depends neither on the grid ("adc_screen_lists_wgs"), nor on how a list's
+ * rows are cut into units ("adc_screen_lists_unit_rows"), nor on how queries fall into groups or chunks
+ * ("adc_screen_lists_chunk_queries"): the same three options govern this call.
+ * Nibbles: a nibble >= K in an allowed row of a probed list raises the range flag and selects an image entry of 0, so the
+ * row can only become more likely to be returned (pqhip_adc_screen_lists_f32_dev reads entry 0 of the subquantizer
+ * there: under the flag the two may differ).  The pad nibble of an odd M is ignored whatever it holds.  A disallowed row,
+ * a row of an unprobed list and a row past a list's end are never loaded; no byte outside the code matrix is read.
+ * Probes and offsets as in pqhip_adc_screen_lists_f32_dev (-1 padding, ids out of range skipped and flagged, ranges
+ * clamped and flagged, inverted ranges empty).  Residual packed lists are not served by any screen.
+ * Status codes as for pqhip_adc_screen_lists_f32_dev, with: K > 16, M > 100, code_bytes not 1: PQHIP_EUNSUPPORTED;
+ * codes_row_stride < ceil(M / 2): PQHIP_ESHAPE.
+ */
+int32_t pqhip_adc_screen_lists_packed4_f32_dev(pqhip_codebook *cb, int32_t device_slot,
+                                               const float *d_tables /* [n_queries][M][K] */, int64_t n_queries,
+                                               const void *d_codes /* packed rows */, int32_t code_bytes, int64_t n_codes,
+                                               int64_t codes_row_stride,
+                                               const uint32_t *d_allow /* position order, or NULL */,
+                                               const int64_t *d_list_off /* [n_lists + 1] */, int64_t n_lists,
+                                               const int64_t *d_probes, int32_t n_probe, int64_t probes_row_stride,
+                                               int32_t ip /* 0 = distance tables, 1 = inner-product tables */,
+                                               const float *d_scales /* ip 1: [n_codes] or NULL */,
+                                               const float *d_threshold /* [n_queries] */, int64_t *d_lims, int64_t *d_idx,
+                                               int64_t capacity, void *stream);
+
+/*
  * The u8 table screen of pqhip_adc_screen_lists_f32_dev over RESIDUAL codes (IVFADC with residual encoding): for a batch
  * of queries, per query a superset of what pqhip_adc_range_lists_residual_f32_dev (ip 0) resp.
  * pqhip_adc_ip_range_lists_residual_f32_dev (ip 1, with the same d_scales) returns at the same thresholds, as positions
@@ -1530,7 +1563,8 @@ int32_t pqhip_set_rotation_variant(int32_t variant);
  *   "adc_screen_lists_wgs"  workgroups of pqhip_adc_screen_lists_f32_dev that stride over its units (0 = one per CU)
  *   "adc_screen_lists_unit_rows"  rows of a unit of that call, rounded up to a multiple of 64 (0 = 16384)
  *   "adc_screen_lists_chunk_queries"  queries of a chunk of that call (0 = from the scratch bound; at most 2^20 / n_probe);
- *                          the result depends on none of the three
+ *                          the result depends on none of the three; they also govern
+ *                          pqhip_adc_screen_lists_residual_f32_dev and pqhip_adc_screen_lists_packed4_f32_dev
  *   "cross_product_exact" 0 = X^T.R of the OPQ training step / pqhip_at_dot_b_f32_dev as a plain split-K product:
  *                          within 1e-5 relative of the exact rule-2 result, no per-block partial matrices (default 1)
  *   "cross_product_group_bytes"  workspace of partial matrices per launch group (0 = 4 GiB)

@@ -119,6 +119,8 @@ def _signatures():
         "pqhip_adc_screen_packed4_f32_dev": (i32, [vp, i32, vp, i64, vp, i32, i64, i64, vp, i32, vp, vp, vp, vp, i64, vp]),
         "pqhip_adc_screen_lists_f32_dev": (i32, [vp, i32, vp, i64, vp, i32, i64, i64, vp, vp, i64, vp, i32, i64, i32, vp,
                                                  vp, vp, vp, i64, vp]),
+        "pqhip_adc_screen_lists_packed4_f32_dev": (i32, [vp, i32, vp, i64, vp, i32, i64, i64, vp, vp, i64, vp, i32, i64, i32,
+                                                         vp, vp, vp, vp, i64, vp]),
         "pqhip_adc_screen_lists_residual_f32_dev": (i32, [vp, i32, vp, i64, vp, i32, i64, i64, vp, vp, i64, vp, i32, i64, vp, i64,
                                                           vp, i32, vp, vp, vp, vp, i64, vp]),
         "pqhip_lists_merge_dev": (i32, [vp, i32, vp, i64, vp, i64, i64, i64, vp, vp, vp, vp, vp]),

@@ -17,6 +17,7 @@
 //     pqhip_adc_screen_lists_residual.hip  the same screen over residual codes: a bound per (row, probe slot) from bias and row term
 //     pqhip_adc_screen16.hip  16-bit table screen over resident codes (query batches at large M; policy: adc_screen_launch.h)
 //     pqhip_adc_screen_packed4.hip  the u8 table screen over 4-bit packed rows: one-hot products on the i8 matrix cores
+//     pqhip_adc_screen_lists_packed4.hip  that one-hot screen over 4-bit packed rows in probed lists
 //     pqhip_rerank.hip    exact re-ranking of search candidates against resident vectors
 //     pqhip_lists_merge.hip  merge of two list-ordered row arrays (growing a partitioned matrix)
 //     pqhip_lists_layout.hip  building a partitioned index: layout of the lists, residuals, query-free row terms

@@ -1531,11 +1531,14 @@ class Pq:
         return (val[0], idx[0]) if single else (val, idx)
 
     # ---- ADC search in probed lists for query batches: u8 table screen per list, exact resolve ---------------------------
-    def _adc_screen_lists(self, codes, tables, list_off, probes, threshold, ip, scales, allow, cap, stream, retry):
+    def _adc_screen_lists(self, codes, tables, list_off, probes, threshold, ip, scales, allow, cap, stream, retry,
+                          packed4=False):
         """One list screen call with `cap` entries and, if retry and the result is larger, one more of exactly its size
-        -> (lims, idx[:min(total, cap)], total, launch); lims[-1] is read in between, the one synchronisation."""
+        -> (lims, idx[:min(total, cap)], total, launch); lims[-1] is read in between, the one synchronisation.
+        packed4: codes are 4-bit packed rows and the call is pqhip_adc_screen_lists_packed4_f32_dev."""
         import torch
-        codes, n, c_rs, nq, mask = self._adc_screen_args(codes, tables, ip, scales, allow)
+        codes, n, c_rs, nq, mask = self._adc_screen_args(codes, tables, ip, scales, allow, packed4)
+        entry = "pqhip_adc_screen_lists_packed4_f32_dev" if packed4 else "pqhip_adc_screen_lists_f32_dev"
         if n > (1 << 32) - 2:
             raise PanicError("at most 2^32 - 2 rows are searched in lists")
         pr, _, n_probe, p_rs = _marshal.vector_lists_arg(list_off, probes, nq)
@@ -1553,7 +1556,7 @@ class Pq:
         lims = torch.empty(nq + 1, dtype=torch.int64, device=dev)
         while True:
             idx = torch.empty(cap, dtype=torch.int64, device=dev)
-            _marshal.run("pqhip_adc_screen_lists_f32_dev", *head, thr.data_ptr(), lims.data_ptr(), ptr_or_none(idx, cap), cap, sp)
+            _marshal.run(entry, *head, thr.data_ptr(), lims.data_ptr(), ptr_or_none(idx, cap), cap, sp)
             if not own_stream:
                 torch.cuda.ExternalStream(stream, device=dev).synchronize()
             total = int(lims[-1])
@@ -1563,7 +1566,7 @@ class Pq:
         return lims, idx[:min(total, cap)], total, (cb, slot, sp)
 
     def adc_screen_lists_device(self, codes, tables, list_off, probes, threshold, ip=False, scales=None, allow=None,
-                                capacity=None, stream=None, check=False):
+                                capacity=None, stream=None, check=False, packed4=False):
         """adc_screen_device in probed lists (pqhip_adc_screen_lists_f32_dev): codes, tables, list_off, probes, threshold,
         scales and allow as for adc_range_lists_device (ip=False) resp. adc_ip_range_lists_device (ip=True) -> (lims,
         idx): CSR of positions, per query a SUPERSET of what the list range call returns at the same thresholds, within
@@ -1571,15 +1574,19 @@ class Pq:
         twice returns its rows twice.  A regular row is returned only within the slack the header states.  Up to 32
         queries that probe a list share one stream of its codes.  The capacity protocol is adc_screen_device's.
         check=True synchronises and reports a code >= K, a list id or an offset out of range (the latter are skipped
-        resp. clamped either way)."""
+        resp. clamped either way).  packed4=True: codes are 4-bit packed rows (pack_codes4_device; K <= 16) and the
+        result is bit for bit that of the unpacked codes, the integer sums taken as one-hot products on the i8 matrix
+        cores at up to 64 queries per stream of a list (32 for M > 64; pqhip_adc_screen_lists_packed4_f32_dev); a nibble
+        >= K in an allowed, probed row raises the range flag and counts as an image entry of 0, the pad nibble of an
+        odd M is ignored.  Residual packed lists are not served."""
         lims, idx, _, launch = self._adc_screen_lists(codes, tables, list_off, probes, threshold, ip, scales, allow,
-                                                      (1 << 20) if capacity is None else capacity, stream, True)
+                                                      (1 << 20) if capacity is None else capacity, stream, True, packed4)
         if check:
             _marshal.check_range(*launch)
         return lims, idx
 
     def adc_search_lists_batch_device(self, codes, tables, list_off, probes, k, ip=False, scales=None, allow=None,
-                                      stream=None, check=False, stats=None):
+                                      stream=None, check=False, stats=None, packed4=False):
         """adc_search_lists_device (ip=False) resp. adc_ip_search_lists_device (ip=True) for a batch of queries, bit for
         bit in values and positions.  Sample: the plain list search over the first s probe slots only
         (flat_lists_batch_sample); T_q, its k-th value, is the k-th best of a subset of the query's probed rows and
@@ -1589,17 +1596,42 @@ class Pq:
         query that names a list twice (its rows would be candidates twice), a chunk of queries whose candidates exceed
         flat_lists_batch_fraction() of its expected probed rows (flat_lists_batch_falls_back) and a quantizer that
         either stage does not serve (PQHIP_EUNSUPPORTED) take the plain call.  stats: a dict that receives the
-        candidate total, the queries that fell back and the sample slots."""
+        candidate total, the queries that fell back and the sample slots.
+        packed4=True: codes are 4-bit packed rows and the result is that of adc_search_lists_device(packed4=True) resp.
+        adc_ip_search_lists_device(packed4=True), bit for bit: the sample is the plain packed list search, the screen is
+        adc_screen_lists_device(packed4=True), and the same thin, twice-named, fallback and PQHIP_EUNSUPPORTED rules
+        lead to the plain packed list search.  The candidate call does not read packed rows, so the resolve is that of
+        _adc_search_batch_packed4: the candidates are gathered and unpacked (unpack_codes4_device(rows=)) and ranked by
+        PLACE, and the places are mapped back.  The list screen returns a query's candidates slot-major, so they are
+        first sorted by position (one sort on the key query * n + position; positions are distinct, a twice-named query
+        having fallen back): place order is then position order and ties break as in the list search.  The sort, the
+        gather and the mapping back are torch operations on torch's CURRENT stream (as in _adc_search_batch_packed4):
+        with packed4=True pass stream=None or make `stream` the current torch stream, or they are not ordered with the
+        library calls."""
         import torch
         k = int(k)
         if not 1 <= k <= 1024:
             raise PanicError("k must be between 1 and 1024, was %d" % k)
-        _, N, _, nq, _ = self._adc_screen_args(codes, tables, ip, scales, allow)
+        _, N, _, nq, _ = self._adc_screen_args(codes, tables, ip, scales, allow, packed4)
         _, n_lists, n_probe, _ = _marshal.vector_lists_arg(list_off, probes, nq)
         kw = {"scales": scales} if ip else {}
+        if packed4:
+            kw["packed4"] = True
         among = self.adc_ip_among_device if ip else self.adc_among_device
         lists_call = self.adc_ip_search_lists_device if ip else self.adc_search_lists_device
         plain_call = lambda t, p: lists_call(codes, t, list_off, p, k, stream=stream, allow=allow, **kw)
+
+        def resolve(tb, cand, lims):
+            """the candidate call over the screen's positions `cand` (CSR by `lims`) -> (values, positions)"""
+            if not packed4:
+                return among(codes, tb, cand, k, lims=lims, stream=stream, **kw)
+            owner = torch.repeat_interleave(torch.arange(tb.shape[0], dtype=torch.int64, device=cand.device), lims[1:] - lims[:-1])
+            cand = (torch.sort(owner * N + cand).values - owner * N).contiguous()
+            sub = self.unpack_codes4_device(codes, rows=cand, stream=stream)
+            kws = {"scales": None if scales is None else scales[cand].contiguous()} if ip else {}
+            v, place = among(sub, tb, torch.arange(cand.shape[0], dtype=torch.int64, device=cand.device), k, lims=lims,
+                             stream=stream, **kws)
+            return v, torch.where(place >= 0, cand[place.clamp(min=0)], place)
         if N == 0 or nq == 0 or n_lists == 0:
             return lists_call(codes, tables, list_off, probes, k, stream=stream, check=check, allow=allow, **kw)
         single = tables.dim() == 2
@@ -1623,12 +1655,14 @@ class Pq:
             cap = int(flat_lists_batch_fraction() * (q1 - q0) * N * min(n_probe, n_lists) / n_lists) + 1
             try:
                 lims, cand, total, _ = self._adc_screen_lists(codes, t3[q0:q1], list_off, pr2[q0:q1], thr[q0:q1], ip, scales,
-                                                              allow, cap, stream, False)
+                                                              allow, cap, stream, False, packed4)
                 total_all += total
                 if total > cap or flat_lists_batch_falls_back(total, N, n_lists, n_probe, q1 - q0):
                     plain[q0:q1] = True
                     continue
-                val[q0:q1], idx[q0:q1] = among(codes, t3[q0:q1], cand, k, lims=lims, stream=stream, **kw)
+                if packed4 and total == 0:                           # only thin queries: the plain call below
+                    continue
+                val[q0:q1], idx[q0:q1] = resolve(t3[q0:q1], cand, lims)
             except _lib.PqHipError as e:
                 if e.status != _lib.EUNSUPPORTED:
                     raise

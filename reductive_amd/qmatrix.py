@@ -1123,11 +1123,18 @@ class PartitionedMatrix(_Lists):
             fn = pq.adc_range_lists_device if ranged else pq.adc_search_lists_device
         return fn, self._tables(ip, queries), (self.list_off, self.probes(queries, nprobe))
 
-    def _topk_screened(self, ip, queries, k, nprobe, use_norms, refine, allow):
-        """_topk by the route for query batches (Pq.adc_search_lists_batch_device); the shortlist R replaces k"""
-        self._unpacked_only("most_similar(screen=True)" if ip else "nearest(screen=True)")
+    def _topk_screened(self, ip, queries, k, nprobe, use_norms, refine, allow, screen=True):
+        """_topk by the route for query batches (Pq.adc_search_lists_batch_device); the shortlist R replaces k; screen
+        "onehot" takes the one-hot screen of a packed matrix, any other true value the u8 image of an unpacked one"""
+        onehot = isinstance(screen, str) and screen == "onehot"
+        if onehot and not self.packed4:
+            raise PanicError("screen=\"onehot\" reads 4-bit packed codes: call pack4() first")
+        if not onehot:
+            self._unpacked_only("most_similar(screen=True)" if ip else "nearest(screen=True)")
         R = k if refine is None else self._check_refine(k, refine)
         kw = {"scales": self.norms if use_norms else None} if ip else {}
+        if onehot:
+            kw["packed4"] = True
         val, pos = self.pq.adc_search_lists_batch_device(self.codes, self._tables(ip, queries), self.list_off,
                                                          self.probes(queries, nprobe), R, ip=ip,
                                                          allow=self._allow_words(allow), **kw)
@@ -1142,9 +1149,11 @@ class PartitionedMatrix(_Lists):
         original row number; dist are then the exact distances.  allow: None, a RowFilter of this matrix or a bool array
         [N] in ORIGINAL row order -- only allowed rows of the probed lists are ranked, as if the others were not stored.
         screen=True: the route for query batches (Pq.adc_search_lists_batch_device: u8 table screen per list, exact
-        resolve), the same result bit for bit; not served on a packed matrix."""
+        resolve), the same result bit for bit; not served on a packed matrix.  screen="onehot": the batch route of a
+        PACKED matrix (pack4(); Pq.adc_search_lists_batch_device(packed4=True): one-hot screen per list on the i8 matrix
+        cores), the same result bit for bit; on an unpacked matrix a PanicError."""
         if screen:
-            return self._topk_screened(False, queries, k, nprobe, True, refine, allow)
+            return self._topk_screened(False, queries, k, nprobe, True, refine, allow, screen)
         return self._topk(False, queries, k, nprobe, True, refine, allow)
 
     def most_similar(self, queries, k, nprobe, use_norms=True, refine=None, allow=None, screen=False):
@@ -1153,7 +1162,7 @@ class PartitionedMatrix(_Lists):
         inner product with the attached vectors as they are; use_norms then only affects the candidate stage.
         allow: as for nearest(); screen: as for nearest()."""
         if screen:
-            return self._topk_screened(True, queries, k, nprobe, use_norms, refine, allow)
+            return self._topk_screened(True, queries, k, nprobe, use_norms, refine, allow, screen)
         return self._topk(True, queries, k, nprobe, use_norms, refine, allow)
 
     def within(self, queries, radius, nprobe, allow=None, sort=False):

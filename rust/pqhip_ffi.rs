@@ -263,6 +263,15 @@ extern "C" {
         d_list_off: *const i64, n_lists: i64, d_probes: *const i64, n_probe: i32, probes_row_stride: i64, ip: i32,
         d_scales: *const f32, d_threshold: *const f32, d_lims: *mut i64, d_idx: *mut i64, capacity: i64,
         stream: *mut c_void) -> i32;
+    // pqhip_adc_screen_lists_f32_dev over 4-bit packed rows (K <= 16; codes_row_stride >= ceil(M / 2) bytes): bit for bit
+    // its result on the unpacked codes, the integer sums as one-hot products on the i8 matrix cores, up to 64 queries of
+    // a list per stream of its codes (32 for M > 64); a nibble >= K raises the range flag and counts as an entry of 0,
+    // the pad nibble is ignored; residual packed lists are not served
+    pub fn pqhip_adc_screen_lists_packed4_f32_dev(cb: *mut pqhip_codebook, device_slot: i32, d_tables: *const f32,
+        n_queries: i64, d_codes: *const c_void, code_bytes: i32, n_codes: i64, codes_row_stride: i64, d_allow: *const u32,
+        d_list_off: *const i64, n_lists: i64, d_probes: *const i64, n_probe: i32, probes_row_stride: i64, ip: i32,
+        d_scales: *const f32, d_threshold: *const f32, d_lims: *mut i64, d_idx: *mut i64, capacity: i64,
+        stream: *mut c_void) -> i32;
     // the same screen over residual codes: a superset of what pqhip_adc_range_lists_residual_f32_dev (ip 0, d_row_terms)
     // resp. pqhip_adc_ip_range_lists_residual_f32_dev (ip 1, d_row_terms null, d_scales or null) returns; the predicate is
     // per (row, probe slot): an f32 bound from the row's integer sum, the slot's bias and the row's term or scale
