@@ -607,6 +607,55 @@ int32_t pqhip_adc_ip_among_f32_dev(pqhip_codebook *cb, int32_t device_slot, cons
                                    void *stream);
 
 /*
+ * ADC range search among given rows: of the rows that the caller names per query, those within a radius resp. at or
+ * above a similarity, as CSR -- the range form of the two calls above, and the resolve stage of a range search for query
+ * batches: fed the (lims, idx) of pqhip_adc_screen_f32_dev, pqhip_adc_screen16_f32_dev or pqhip_adc_screen_lists_f32_dev
+ * at the same thresholds it returns, bit for bit, what pqhip_adc_range_f32_dev / pqhip_adc_ip_range_f32_dev resp. the two
+ * plain list range calls return (the screens name a superset of that result in its order).
+ * Arguments: those of pqhip_adc_among_f32_dev / pqhip_adc_ip_among_f32_dev up to d_row_terms resp. d_scales, then the
+ * thresholds and the CSR outputs of the range calls.  Candidate set, -1 padding, the untrusted d_lims and the range flag
+ * are those calls': ids outside [0, n_codes) are skipped and flagged, both ends of d_lims are clamped, an inverted range
+ * is empty, and no byte outside d_ids[0 .. n_ids) is read.  A row that is not named is not read.
+ * Values: those of pqhip_adc_among_f32_dev, operation for operation -- s; fl(s * scale[i]); residual
+ * fl(fl(b + term[i]) - fl(s + s)) resp. fl(fl(b + s) * scale[i]) -- and a score is NOT negated.  Row i qualifies iff
+ * value <= d_threshold[q] resp. score >= d_threshold[q] as an IEEE comparison: a NaN value or threshold matches nothing.
+ * Result: d_out_lims [n_queries + 1] always receives the true counts as CSR offsets; the entries of query q are its
+ * qualifying places IN THE ORDER IN WHICH THEY WERE NAMED, d_idx the id as named and d_val the value bit for bit (a zero
+ * keeps its sign); an id named twice is returned twice.  Entries are written iff their slot lies below capacity, so what
+ * is written is a valid prefix; capacity == 0 counts only and d_val / d_idx may then be NULL.  The result depends on
+ * neither the workgroups per query nor the query chunks.
+ * Status codes in the precedence of pqhip_adc_among_f32_dev.  PQHIP_EINVAL: cb == NULL, a negative count or capacity;
+ * then PQHIP_ENODEV; then PQHIP_EUNSUPPORTED: code_bytes != 1, more than 100 subquantizers, a table that does not fit
+ * LDS, n_codes > 2^32 - 2.  n_queries == 0 launches nothing.  Then PQHIP_EINVAL: d_out_lims or d_threshold NULL, a NULL
+ * d_val / d_idx with capacity > 0, d_ids == NULL with n_ids > 0, NULL tables or codes with rows to read, only one of
+ * d_row_list / d_list_bias, d_row_terms == NULL in the residual distance call; then PQHIP_ESHAPE: codes_row_stride below
+ * the row length, bias_row_stride < n_lists.  n_ids == 0 or n_codes == 0 writes zero counts.  Anything not served is
+ * PQHIP_EUNSUPPORTED, never another path.
+ * Three launches per chunk of queries, all on the caller's stream: a count pass that also leaves one hit bit per place
+ * in the codebook's scratch, the prefix scan of the range calls, and a fill pass (skipped with capacity == 0) that reads
+ * the bits, so a place that missed costs a bit and not a row.  Workgroups per query: the policy of
+ * pqhip_adc_among_f32_dev; option "adc_among_range_wgs_per_query" forces the number.  With d_lims the bitmap of a query
+ * covers min(n_ids, 4 n_ids / n_queries + 1,024) places, and at most 2^31 places with or without d_lims (256 MB: a
+ * query's bitmap stays within the scratch bound whatever n_ids); the places of a range beyond it are computed twice.
+ */
+int32_t pqhip_adc_among_range_f32_dev(pqhip_codebook *cb, int32_t device_slot, const float *d_tables, int64_t n_queries,
+                                      const void *d_codes, int32_t code_bytes, int64_t n_codes, int64_t codes_row_stride,
+                                      const int64_t *d_lims /* [n_queries + 1] or NULL */, const int64_t *d_ids, int64_t n_ids,
+                                      const int64_t *d_row_list /* [n_codes] or NULL */, int64_t n_lists,
+                                      const float *d_list_bias /* [n_queries][bias_row_stride] or NULL */,
+                                      int64_t bias_row_stride, const float *d_row_terms /* [n_codes]; residual form only */,
+                                      const float *d_threshold /* [n_queries] */, int64_t *d_out_lims, float *d_val,
+                                      int64_t *d_idx, int64_t capacity, void *stream);
+int32_t pqhip_adc_ip_among_range_f32_dev(pqhip_codebook *cb, int32_t device_slot, const float *d_tables, int64_t n_queries,
+                                         const void *d_codes, int32_t code_bytes, int64_t n_codes, int64_t codes_row_stride,
+                                         const int64_t *d_lims /* [n_queries + 1] or NULL */, const int64_t *d_ids,
+                                         int64_t n_ids, const int64_t *d_row_list /* [n_codes] or NULL */, int64_t n_lists,
+                                         const float *d_list_bias /* [n_queries][bias_row_stride] or NULL */,
+                                         int64_t bias_row_stride, const float *d_scales /* [n_codes] or NULL */,
+                                         const float *d_threshold /* [n_queries] */, int64_t *d_out_lims, float *d_val,
+                                         int64_t *d_idx, int64_t capacity, void *stream);
+
+/*
  * Exact re-ranking of search candidates against resident vectors ("IVFADC+R", refine): the stage after an ADC search
  * that replaces the quantizer's estimate by the distance to the stored vector.  For query q, the first n_cand entries of
  * row q of d_cand [n_queries][cand_row_stride] int64 name rows of d_vectors [n_rows][vec_row_stride], vec_bytes = 4 (f32)
@@ -1520,6 +1569,7 @@ int32_t pqhip_set_rotation_variant(int32_t variant);
  *   "adc_lists_wgs_per_query"  workgroups that share one query of the list searches (0 = chosen from the shape; at most 4096)
  *   "adc_among_wgs_per_query"  workgroups that share one query of the searches among given rows (0 = chosen from the
  *                          mean number of ids per query; at most 4096)
+ *   "adc_among_range_wgs_per_query"  the same for the two range searches among given rows
  *   "adc_range_wgs"        producer workgroups of the exhaustive range searches (0 = chosen from the shape; at most 8192,
  *                          so that the one-workgroup prefix scan of a pass sums at most 2^20 counts)
  *   "adc_range_wgs_per_query"  workgroups that share one query of the list range searches (0 = chosen from the shape; at

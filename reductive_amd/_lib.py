@@ -167,6 +167,9 @@ def _signatures():
     # The two searches among given rows: lims, ids, n_ids; row_list, n_lists; list_bias, its row stride; row terms / scales
     for name in ("pqhip_adc_among_f32_dev", "pqhip_adc_ip_among_f32_dev"):
         sig[name] = (i32, [vp, i32, vp, i64, vp, i32, i64, i64, vp, vp, i64, vp, i64, vp, i64, vp] + topk)
+    # their range forms: the same arguments up to the row terms / scales, then the CSR outputs of the range calls
+    for name in ("pqhip_adc_among_range_f32_dev", "pqhip_adc_ip_among_range_f32_dev"):
+        sig[name] = (i32, [vp, i32, vp, i64, vp, i32, i64, i64, vp, vp, i64, vp, i64, vp, i64, vp] + csr)
     return sig
 
 

@@ -362,6 +362,7 @@ int32_t pqhip_ctx_set_option(pqhip_ctx* ctx, const char* name, int64_t value)
         {"adc_range_wgs_per_query", &o.adc_range_wgs_per_query}, {"lists_merge_wgs", &o.lists_merge_wgs},
         {"adc_packed4_wgs", &o.adc_packed4_wgs},       {"lists_layout_wgs", &o.lists_layout_wgs},
         {"adc_search_wgs", &o.adc_search_wgs},         {"adc_among_wgs_per_query", &o.adc_among_wgs_per_query},
+        {"adc_among_range_wgs_per_query", &o.adc_among_range_wgs_per_query},
         {"rows_compact_wgs", &o.rows_compact_wgs},     {"topk_merge_wgs", &o.topk_merge_wgs},
         {"flat_search_wgs", &o.flat_search_wgs},       {"flat_lists_wgs_per_query", &o.flat_lists_wgs_per_query},
         {"flat_range_wgs", &o.flat_range_wgs},         {"flat_range_wgs_per_query", &o.flat_range_wgs_per_query},

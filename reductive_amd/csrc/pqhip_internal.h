@@ -11,6 +11,7 @@
 //     pqhip_adc_packed4.hip  4-bit packed codes: pack / unpack and the searches over packed rows (list producers:
 //                         pqhip_adc_packed4_lists.hip)
 //     pqhip_adc_among.hip ADC search among given rows: top-k over per-query candidate id lists
+//     pqhip_adc_among_range.hip ADC range search among given rows: CSR over per-query candidate id lists
 //     pqhip_adc_range.hip ADC range search: every row within a radius, as CSR
 //     pqhip_flat_screen_lists.hip  matrix-core range screen in probed lists (query batches of the exact list searches)
 //     pqhip_adc_screen_lists.hip  u8 table screen over codes in probed lists (query batches of the ADC list searches)
@@ -109,6 +110,7 @@ struct Options {
     std::atomic<int64_t> adc_search_wgs{0};         // exhaustive u8 / masked / generic searches: producer workgroups (0: chosen from the shape)
     std::atomic<int64_t> lists_layout_wgs{0};       // list layout: workgroups, one row slice each (0: chosen from the size)
     std::atomic<int64_t> adc_among_wgs_per_query{0};   // searches among given rows: workgroups per query (0: chosen from the mean number of ids)
+    std::atomic<int64_t> adc_among_range_wgs_per_query{0};   // range search among given rows: workgroups per query (0: as above)
     std::atomic<int64_t> rows_compact_wgs{0};       // row compaction: workgroups, one row slice each (0: chosen from the size)
     std::atomic<int64_t> topk_merge_wgs{0};         // merge of search results: workgroups, queries taken grid-stride (0: one per query)
     std::atomic<int64_t> flat_search_wgs{0};        // exact search over resident vectors: producer workgroups (0: chosen from the shape)

@@ -1123,11 +1123,13 @@ class Pq:
                                       probe_bias=probe_bias, allow=allow, packed4=packed4)
 
     # ---- ADC search among given rows: exact top-k over per-query candidate id lists ------------------------------------
-    def _adc_among(self, ip, codes, tables, ids, k, lims, row_list, list_bias, extra, what, stream, check):
-        """Both candidate searches; row_list and list_bias given: the residual forms.  extra: the scales (ip) or the row
-        terms, named `what`."""
+    def _adc_among_head(self, ip, codes, tables, ids, k, lims, row_list, list_bias, extra, what):
+        """What the candidate searches and their range forms check and marshal (k None: a range form); row_list and
+        list_bias given: the residual forms; extra: the scales (ip) or the row terms, named `what` -> (single, nq, keep,
+        the arguments of the C call from the tables to the row terms / scales).  keep = (codes, row_list, list_bias,
+        extra) as marshalled -- contiguous copies and stand-ins among them: the arguments are their addresses, so the
+        caller holds keep until its last call is enqueued."""
         import torch
-        name = "pqhip_adc_%samong_f32_dev" % ("ip_" if ip else "")
         M, K = self.quantized_len(), self.n_quantizer_centroids()
 
         def vector(t, dtype, text):
@@ -1145,7 +1147,7 @@ class Pq:
             vector(lims, torch.int64, "lims must be a contiguous int64 vector")
             if lims.shape[0] != nq + 1:
                 raise PanicError("lims must hold one offset per query and the end (%d)" % (nq + 1))
-        if not isinstance(k, int) or k < 1:
+        if k is not None and (not isinstance(k, int) or k < 1):
             raise PanicError("k must be a positive integer")
         n = codes.shape[0]
         if extra is not None:
@@ -1180,16 +1182,47 @@ class Pq:
             if not ip:
                 extra = _marshal.stand_in(extra, n, codes.device)
         n_ids = ids.shape[0]
+        keep = (codes, row_list, lb, extra)
+        return single, nq, keep, (tables.data_ptr(), nq, codes.data_ptr(), codes.element_size(), n, c_rs, ptr_or_none(lims),
+                                  ptr_or_none(ids, n_ids), n_ids, ptr_or_none(row_list), n_lists, ptr_or_none(lb), b_rs,
+                                  ptr_or_none(extra, extra is not None and extra.shape[0]) if (ip or residual) else None)
+
+    def _adc_among(self, ip, codes, tables, ids, k, lims, row_list, list_bias, extra, what, stream, check):
+        """Both candidate searches (arguments: _adc_among_head)."""
+        import torch
+        single, nq, keep, head = self._adc_among_head(ip, codes, tables, ids, k, lims, row_list, list_bias, extra, what)
+        codes = keep[0]
         val = torch.empty((nq, k), dtype=torch.float32, device=codes.device)
         idx = torch.empty((nq, k), dtype=torch.int64, device=codes.device)
         cb, slot, sp = _marshal.launch(self, codes, stream)
-        _marshal.run(name, cb, slot, tables.data_ptr(), nq, codes.data_ptr(), codes.element_size(), n, c_rs, ptr_or_none(lims),
-                     ptr_or_none(ids, n_ids), n_ids, ptr_or_none(row_list), n_lists, ptr_or_none(lb), b_rs,
-                     ptr_or_none(extra, extra is not None and extra.shape[0]) if (ip or residual) else None,
-                     k, val.data_ptr(), k, idx.data_ptr(), k, sp)
+        _marshal.run("pqhip_adc_%samong_f32_dev" % ("ip_" if ip else ""), cb, slot, *head, k, val.data_ptr(), k, idx.data_ptr(), k, sp)
         if check:
             _marshal.check_range(cb, slot, sp)
         return (val[0], idx[0]) if single else (val, idx)
+
+    def _adc_among_range(self, ip, codes, tables, ids, threshold, lims, row_list, list_bias, extra, what, stream, check):
+        """Both range searches among given rows -> (lims, val, idx), allocated to the size of the result: one count call,
+        one read of the total -- the one synchronisation -- then the call that fills, as flat_range_among_device."""
+        import torch
+        _, nq, keep, head = self._adc_among_head(ip, codes, tables, ids, None, lims, row_list, list_bias, extra, what)
+        codes = keep[0]
+        name = "pqhip_adc_%samong_range_f32_dev" % ("ip_" if ip else "")
+        dev = codes.device
+        thr = _marshal.threshold_arg(threshold, nq, dev)
+        own_stream = stream is None
+        cb, slot, sp = _marshal.launch(self, codes, stream)
+        out_lims = torch.empty(nq + 1, dtype=torch.int64, device=dev)
+        _marshal.run(name, cb, slot, *head, thr.data_ptr(), out_lims.data_ptr(), None, None, 0, sp)
+        if not own_stream:
+            torch.cuda.ExternalStream(stream, device=dev).synchronize()
+        total = int(out_lims[-1])
+        val = torch.empty(total, dtype=torch.float32, device=dev)
+        idx = torch.empty(total, dtype=torch.int64, device=dev)
+        if total > 0:
+            _marshal.run(name, cb, slot, *head, thr.data_ptr(), out_lims.data_ptr(), val.data_ptr(), idx.data_ptr(), total, sp)
+        if check:
+            _marshal.check_range(cb, slot, sp)
+        return out_lims, val, idx
 
     def adc_among_device(self, codes, tables, ids, k, lims=None, row_list=None, list_bias=None, row_terms=None,
                          stream=None, check=False):
@@ -1210,6 +1243,27 @@ class Pq:
         scales None or CUDA float32 [n]) -> (score, idx), the first k candidates by (descending score, row).  Residual
         codes: list_bias holds <q, c_l> per list, score = fl(fl(bias + s) * scale) (pqhip_adc_ip_among_f32_dev)."""
         return self._adc_among(True, codes, tables, ids, k, lims, row_list, list_bias, scales, "scales", stream, check)
+
+    def adc_among_range_device(self, codes, tables, ids, threshold, lims=None, row_list=None, list_bias=None, row_terms=None,
+                               stream=None, check=False):
+        """adc_range_device among given rows (codes, tables, ids, lims and the residual inputs as for adc_among_device;
+        threshold a scalar or one value per query) -> (lims, dist, idx): CSR, the output lims CUDA int64 [nq + 1] ([2] for
+        2-D tables); the entries of query q are those of its candidates whose value is <= threshold, IN THE ORDER IN
+        WHICH THEY WERE NAMED, dist the value adc_among_device ranks the row by, bit for bit, idx the id as named; an id
+        named twice is returned twice (pqhip_adc_among_range_f32_dev).  A NaN value or threshold matches nothing.  Fed
+        the (lims, idx) of adc_screen_device at the same thresholds it returns adc_range_device's result.  -1 is padding;
+        any other id outside [0, n) is skipped and, like a bad lims, raises the range flag (check=True).  A row that is
+        not named is not read."""
+        return self._adc_among_range(False, codes, tables, ids, threshold, lims, row_list, list_bias, row_terms, "row_terms",
+                                     stream, check)
+
+    def adc_ip_among_range_device(self, codes, tables, ids, threshold, lims=None, row_list=None, list_bias=None, scales=None,
+                                  stream=None, check=False):
+        """adc_ip_range_device among given rows (arguments as for adc_ip_among_device with the threshold in the place of
+        k) -> (lims, score, idx): the candidates whose score is >= threshold, in the order named, the score as it is
+        (pqhip_adc_ip_among_range_f32_dev)."""
+        return self._adc_among_range(True, codes, tables, ids, threshold, lims, row_list, list_bias, scales, "scales", stream,
+                                     check)
 
     # ---- ADC range search: every row within a radius / at or above a similarity, as CSR ------------------------------
     def _adc_range(self, ip, codes, tables, threshold, scales, stream, check, allow, capacity, lists=None, probe_bias=None,
@@ -1371,6 +1425,32 @@ class Pq:
         if check:
             _marshal.check_range(cb, slot, sp)
         return lims, idx
+
+    def adc_range_batch_device(self, codes, tables, threshold, ip=False, scales=None, allow=None, capacity=None, stream=None,
+                               check=False, image_bits=8):
+        """adc_range_device (ip=False) resp. adc_ip_range_device (ip=True) for a batch of queries: the table screen at the
+        thresholds (adc_screen_device; image_bits 8 or 16), then adc_among_range_device / adc_ip_among_range_device over
+        its ids -> (lims, val, idx), bit for bit what the plain call returns: the screen names a superset of the result
+        in ascending row order within the allowed rows, and the candidate call applies the same predicate to the same
+        values in the order named.  capacity: the entries of the screen's first call.  A quantizer that the screen does
+        not serve (PQHIP_EUNSUPPORTED) takes the plain call.  Packed rows are refused: no packed range call defines
+        their result."""
+        import torch
+        if not (hasattr(codes, "is_cuda") and codes.dtype == torch.uint8 and codes.dim() == 2
+                and codes.shape[1] == self.quantized_len()):
+            raise PanicError("adc_range_batch_device reads uint8 [n, n_subquantizers] codes (4-bit packed rows have no range call)")
+        entry = self._adc_screen_entry(image_bits)
+        kw = {"scales": scales} if ip else {}
+        try:
+            lims, ids, _, _ = self._adc_screen(codes, tables, threshold, ip, scales, allow,
+                                               (1 << 20) if capacity is None else capacity, stream, True, entry)
+        except _lib.PqHipError as e:
+            if e.status != _lib.EUNSUPPORTED:
+                raise
+            plain = self.adc_ip_range_device if ip else self.adc_range_device
+            return plain(codes, tables, threshold, stream=stream, check=check, allow=allow, capacity=capacity, **kw)
+        among = self.adc_ip_among_range_device if ip else self.adc_among_range_device
+        return among(codes, tables, ids, threshold, lims=lims, stream=stream, check=check, **kw)
 
     def adc_search_batch_device(self, codes, tables, k, ip=False, scales=None, allow=None, stream=None, check=False,
                                 stats=None, image_bits=8, packed4=False):
@@ -1584,6 +1664,32 @@ class Pq:
         if check:
             _marshal.check_range(*launch)
         return lims, idx
+
+    def adc_range_lists_batch_device(self, codes, tables, list_off, probes, threshold, ip=False, scales=None, allow=None,
+                                     capacity=None, stream=None, check=False):
+        """adc_range_lists_device (ip=False) resp. adc_ip_range_lists_device (ip=True) for a batch of queries: the list
+        screen at the thresholds (adc_screen_lists_device), then adc_among_range_device / adc_ip_among_range_device over
+        its positions -> (lims, val, idx), bit for bit what the list range call returns: the screen names a superset of
+        the result in that call's order -- probe slot first, then position; the rows of a list named twice twice; a -1
+        probe nothing -- and the candidate call keeps the order named.  A quantizer that the screen does not serve
+        (PQHIP_EUNSUPPORTED) takes the plain call.  Residual and packed lists are not served."""
+        import torch
+        if not (hasattr(codes, "is_cuda") and codes.dtype == torch.uint8 and codes.dim() == 2
+                and codes.shape[1] == self.quantized_len()):
+            raise PanicError("adc_range_lists_batch_device reads uint8 [n, n_subquantizers] codes (4-bit packed rows have no "
+                             "range call)")
+        kw = {"scales": scales} if ip else {}
+        try:
+            lims, ids, _, _ = self._adc_screen_lists(codes, tables, list_off, probes, threshold, ip, scales, allow,
+                                                     (1 << 20) if capacity is None else capacity, stream, True)
+        except _lib.PqHipError as e:
+            if e.status != _lib.EUNSUPPORTED:
+                raise
+            plain = self.adc_ip_range_lists_device if ip else self.adc_range_lists_device
+            return plain(codes, tables, list_off, probes, threshold, stream=stream, check=check, allow=allow,
+                         capacity=capacity, **kw)
+        among = self.adc_ip_among_range_device if ip else self.adc_among_range_device
+        return among(codes, tables, ids, threshold, lims=lims, stream=stream, check=check, **kw)
 
     def adc_search_lists_batch_device(self, codes, tables, list_off, probes, k, ip=False, scales=None, allow=None,
                                       stream=None, check=False, stats=None, packed4=False):

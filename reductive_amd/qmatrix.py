@@ -619,6 +619,35 @@ class _Among:
         """most_similar() among the rows that `rows` names (as for nearest_among) -> (score, idx), largest first."""
         return self._among(True, queries, rows, k, use_norms, refine, check)
 
+    def _among_range(self, ip, queries, rows, threshold, use_norms, sort):
+        self._unpacked_only("similar_above_among" if ip else "within_among")
+        lims, rows = self._among_rows(rows)
+        tables, kw = self._among_terms(ip, queries)
+        if ip:
+            kw["scales"] = self.norms if use_norms else None
+        fn = self.pq.adc_ip_among_range_device if ip else self.pq.adc_among_range_device
+        lims, val, pos = fn(self.codes, tables, self._among_ids(rows), threshold, lims=lims, **kw)
+        rows = self._original_rows(pos)
+        if sort:
+            val, rows = sort_ranges(lims, val, rows, ip)
+        return lims, val, rows
+
+    def within_among(self, queries, rows, radius, sort=False):
+        """within() among the rows that `rows` names and no others (as for nearest_among: a vector of ORIGINAL row numbers
+        shared by all queries, or the pair (lims, rows) of an earlier range search) -> (lims, dist, idx): of every query's
+        rows those whose distance, as nearest_among() values it, is <= radius (a scalar or one value per query), in the
+        order in which they were named, in original row numbers (Pq.adc_among_range_device); sort=True: ascending in
+        distance.  It narrows a range result without another pass over the matrix:
+            m.within_among(q, m.within(q, 2 * r)[::2], r)
+        is within(q, r) restricted to those rows.  -1 is padding, any other number outside [0, N) is skipped; a row named
+        twice is returned twice.  Not served on a packed matrix: unpack4() first."""
+        return self._among_range(False, queries, rows, radius, True, sort)
+
+    def similar_above_among(self, queries, rows, threshold, use_norms=True, sort=False):
+        """similar_above() among the rows that `rows` names -> (lims, score, idx), as within_among()
+        (Pq.adc_ip_among_range_device); sort=True: descending in score."""
+        return self._among_range(True, queries, rows, threshold, use_norms, sort)
+
 
 class QuantizedMatrix(_Refine, _Filter, _Packed4, _Search, _Among, _Compact):
     """Codes (+ norms) resident in HBM next to the device codebook: the lookup, scan and similarity-search consumer."""
@@ -717,20 +746,41 @@ class QuantizedMatrix(_Refine, _Filter, _Packed4, _Search, _Among, _Compact):
             return self._topk_screened(True, queries, k, use_norms, refine, allow, screen)
         return self._topk(True, queries, k, None, use_norms, refine, allow)
 
-    def within(self, queries, radius, allow=None, sort=False):
+    def _range_screened(self, ip, queries, threshold, use_norms, allow, sort, screen):
+        """_range by the route for query batches (Pq.adc_range_batch_device); screen "u16" takes the 16-bit image, any
+        other true value the u8 image"""
+        if self.packed4:
+            raise PanicError("%s(screen=True) does not read 4-bit packed codes: call unpack4() first"
+                             % ("similar_above" if ip else "within"))
+        kw = {"scales": self.norms if use_norms else None} if ip else {}
+        lims, val, rows = self.pq.adc_range_batch_device(self.codes, self._tables(ip, queries), threshold, ip=ip,
+                                                         allow=self._allow_words(allow),
+                                                         image_bits=16 if screen == "u16" else 8, **kw)
+        if sort:
+            val, rows = sort_ranges(lims, val, rows, ip)
+        return lims, val, rows
+
+    def within(self, queries, radius, allow=None, sort=False, screen=False):
         """EVERY row whose asymmetric squared distance to the query is <= radius (a scalar or one value per query) ->
         (lims, dist, idx): CSR over the queries, lims int64 [nq + 1] ([2] for one query), the rows of query q at
         lims[q]:lims[q + 1] in ascending row number (Pq.adc_range_device; the result is allocated to its size, after one
         read of the count).  sort=True: each query's rows ascending in distance instead, ties in row order
         (sort_ranges).  allow: as for nearest().  There is no refine=: re-ranking is defined for at most 1,024
-        candidates per query, and a range result has no such bound.  Not served on a packed matrix: unpack4() first."""
+        candidates per query, and a range result has no such bound.  Not served on a packed matrix: unpack4() first.
+        screen=True: the route for query batches (Pq.adc_range_batch_device: u8 table screen at the radius, exact range
+        call among its candidates), the same result bit for bit; screen="u16": that route with the 16-bit table image
+        (DESIGN.md §5k says which to pass where)."""
+        if screen:
+            return self._range_screened(False, queries, radius, True, allow, sort, screen)
         return self._range(False, queries, radius, None, True, allow, sort)
 
-    def similar_above(self, queries, threshold, use_norms=True, allow=None, sort=False):
+    def similar_above(self, queries, threshold, use_norms=True, allow=None, sort=False, screen=False):
         """Every row whose inner product with the query, as most_similar() scores it, is >= threshold (a scalar or one
         value per query) -> (lims, score, idx), CSR as for within() (Pq.adc_ip_range_device).  sort=True: each query's
         rows descending in score, ties in row order.  No refine=, as for within().  Not served on a packed matrix:
-        unpack4() first."""
+        unpack4() first.  screen: as for within()."""
+        if screen:
+            return self._range_screened(True, queries, threshold, use_norms, allow, sort, screen)
         return self._range(True, queries, threshold, None, use_norms, allow, sort)
 
     def add(self, vectors, norms=None):
@@ -1165,17 +1215,37 @@ class PartitionedMatrix(_Lists):
             return self._topk_screened(True, queries, k, nprobe, use_norms, refine, allow, screen)
         return self._topk(True, queries, k, nprobe, use_norms, refine, allow)
 
-    def within(self, queries, radius, nprobe, allow=None, sort=False):
+    def _range_screened(self, ip, queries, threshold, nprobe, use_norms, allow, sort):
+        """_range by the route for query batches (Pq.adc_range_lists_batch_device)"""
+        if self.packed4:
+            raise PanicError("%s(screen=True) does not read 4-bit packed codes: call unpack4() first"
+                             % ("similar_above" if ip else "within"))
+        kw = {"scales": self.norms if use_norms else None} if ip else {}
+        lims, val, pos = self.pq.adc_range_lists_batch_device(self.codes, self._tables(ip, queries), self.list_off,
+                                                              self.probes(queries, nprobe), threshold, ip=ip,
+                                                              allow=self._allow_words(allow), **kw)
+        rows = self._original_rows(pos)
+        if sort:
+            val, rows = sort_ranges(lims, val, rows, ip)
+        return lims, val, rows
+
+    def within(self, queries, radius, nprobe, allow=None, sort=False, screen=False):
         """QuantizedMatrix.within among the rows of the nprobe nearest lists -> (lims, dist, idx), idx original row
         numbers; the rows of a query come list by list in probe order, inside a list in ascending original row number
         (Pq.adc_range_lists_device).  sort=True: ascending in distance, ties in that order.  No refine=: re-ranking is
-        defined for at most 1,024 candidates per query.  Not served on a packed matrix: unpack4() first."""
+        defined for at most 1,024 candidates per query.  Not served on a packed matrix: unpack4() first.  screen=True:
+        the route for query batches (Pq.adc_range_lists_batch_device: u8 table screen per list at the radius, exact range
+        call among its candidates), the same result bit for bit."""
+        if screen:
+            return self._range_screened(False, queries, radius, nprobe, True, allow, sort)
         return self._range(False, queries, radius, nprobe, True, allow, sort)
 
-    def similar_above(self, queries, threshold, nprobe, use_norms=True, allow=None, sort=False):
+    def similar_above(self, queries, threshold, nprobe, use_norms=True, allow=None, sort=False, screen=False):
         """QuantizedMatrix.similar_above among the rows of the nprobe nearest lists -> (lims, score, idx), idx original
         row numbers, order as for within() (Pq.adc_ip_range_lists_device).  sort=True: descending in score.  Not served
-        on a packed matrix: unpack4() first."""
+        on a packed matrix: unpack4() first.  screen: as for within()."""
+        if screen:
+            return self._range_screened(True, queries, threshold, nprobe, use_norms, allow, sort)
         return self._range(True, queries, threshold, nprobe, use_norms, allow, sort)
 
     def add(self, vectors, norms=None):

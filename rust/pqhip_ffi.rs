@@ -94,6 +94,20 @@ extern "C" {
         d_ids: *const i64, n_ids: i64, d_row_list: *const i64, n_lists: i64, d_list_bias: *const f32,
         bias_row_stride: i64, d_scales: *const f32, k: i32, d_score: *mut f32, score_row_stride: i64,
         d_idx: *mut i64, idx_row_stride: i64, stream: *mut c_void) -> i32;
+    // their range forms: of every query's places those with value <= threshold[q] resp. score >= threshold[q] (scores
+    // as they are, not negated), in the order in which they were named, as CSR with the capacity protocol of the range
+    // calls (d_out_lims [n_queries + 1]; capacity 0 = count only, d_val / d_idx may then be NULL); option
+    // "adc_among_range_wgs_per_query" forces the workgroups that share a query
+    pub fn pqhip_adc_among_range_f32_dev(cb: *mut pqhip_codebook, device_slot: i32, d_tables: *const f32, n_queries: i64,
+        d_codes: *const c_void, code_bytes: i32, n_codes: i64, codes_row_stride: i64, d_lims: *const i64,
+        d_ids: *const i64, n_ids: i64, d_row_list: *const i64, n_lists: i64, d_list_bias: *const f32,
+        bias_row_stride: i64, d_row_terms: *const f32, d_threshold: *const f32, d_out_lims: *mut i64, d_val: *mut f32,
+        d_idx: *mut i64, capacity: i64, stream: *mut c_void) -> i32;
+    pub fn pqhip_adc_ip_among_range_f32_dev(cb: *mut pqhip_codebook, device_slot: i32, d_tables: *const f32, n_queries: i64,
+        d_codes: *const c_void, code_bytes: i32, n_codes: i64, codes_row_stride: i64, d_lims: *const i64,
+        d_ids: *const i64, n_ids: i64, d_row_list: *const i64, n_lists: i64, d_list_bias: *const f32,
+        bias_row_stride: i64, d_scales: *const f32, d_threshold: *const f32, d_out_lims: *mut i64, d_val: *mut f32,
+        d_idx: *mut i64, capacity: i64, stream: *mut c_void) -> i32;
     // the six searches restricted to an allowed set of rows: d_allow holds ceil(n_codes / 32) words in the row order of
     // d_codes, bit i & 31 of word i >> 5 set = row i may be returned; NULL = the unmasked call itself; option
     // "adc_search_wgs" forces the producer workgroups of the two exhaustive calls, as of their unmasked forms
